@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MRI volumes/sec (fwd + bwd + optimizer step) of the 3-D U-Net at 160x192x160 on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): `unet.UNet`(c0=8, 3 encoding blocks,
@@ -12,12 +12,16 @@ Inputs are generated on the device before the timed region.
 `--dtype bf16` (not the default, not the headline) runs the same step inside the bf16 storage region — BASELINE configs[3]'s
 per-GPU share (2 volumes per GPU, batch 16 over 8 GPUs): bf16 activations, fp32 accumulate / parameters / loss.
 
-Prints ONE JSON line on rank 0 (see the driver contract), including
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 (see the driver contract): `value`
+(volumes/s), `ms_per_step` and the configuration.  `--dump-outputs DIR` then also writes what the last timed step handed
+its caller (loss, updated parameters, their gradients, BatchNorm running statistics) as float32 DIR/<name>.npy.
+`--full` adds to the line what the headline does not need:
   roofline     — the dominant kernel (largest share of step time, found over the last two warm-up steps where every operator
                  is bracketed) measured live with stream events inside the timed region: algorithmic FLOP (or bytes) per launch /
                  average launch time against the gfx950 peak;
   cpu_baseline — the CPU oracle (PyTorch restatement of the reference model, kind "port") timed on this box's host
-                 cores on a bounded sample (batch-1 volumes of the same size), rank 0, N == 1 only.
+                 cores on a bounded sample (batch-1 volumes of the same size), rank 0, N == 1 only;
+  secondary    — the other BASELINE configurations, measured after the timed region, N == 1 f32 only.
 """
 import argparse
 import json
@@ -191,6 +195,31 @@ def secondary_benchmarks(device, steps=10, warmup=3):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, flat, loss):
+    """--dump-outputs DIR: what the timed path hands its caller after its last step, one float32 DIR/<name>.npy per array —
+    the step's loss, the flat parameter vector after the AdamW update, the flat gradient that update used (summed over ranks)
+    and the floating-point BatchNorm running statistics.  Inputs and initial weights are seeded, so two builds given the same
+    arguments can be compared array for array.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    arrays = {
+        "loss": loss.detach().float().reshape(1),
+        "params": flat.flat.detach().float(),
+        "grads": flat.grad.detach().float(),
+        "bn_running_stats": torch.cat([b.detach().float().reshape(-1) for b in model.buffers() if b.is_floating_point()]),
+    }
+    total = sum(a.numel() * 4 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy().astype(np.float32))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` (N > 1) without a torchrun environment: this process becomes a pure launcher.  It has not
     imported torch and never touches the GPU (no os.exec of a GPU process either): it starts
@@ -269,9 +298,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the `roofline` object (per-operator event table of "
+                         "the warm-up steps), `cpu_baseline` and `secondary`")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's loss, parameters, gradients and BatchNorm running "
+                         "statistics as float32 DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` object (the other BASELINE configurations, measured after the timed region)")
+                    help="with --full: skip the `secondary` object (the other BASELINE configurations, measured after the "
+                         "timed region)")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32")
     ap.add_argument("--graph", choices=("auto", "on", "off"), default="auto",
                     help="replay forward+backward as one captured hipGraph.  auto = off for f32 (GPU-bound, and the "
@@ -282,6 +318,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # N > 1 and no torchrun environment: become the launcher BEFORE torch is imported or any GPU call is made.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -358,11 +396,13 @@ def main():
     # `roofline` kernel) is bracketed — 2 events per step instead of ~600, whose timestamp packets between the kernels cost the
     # step 1 % (31.1 against 30.8 ms).  With no warm-up step every operator is bracketed in the timed region, as before.
     # Graph replay cannot be bracketed from the host: there the largest layer is timed right after the timed region.
-    table_steps = 0 if graphed else min(2, args.warmup)
+    # All of this is --full only: a plain run brackets nothing, its warm-up and timed steps are the bare step.
+    instrument = args.full and not graphed
+    table_steps = min(2, args.warmup) if instrument else 0
     # two more warm-up steps run bracketed with a timer that is thrown away: the first few hundred timing events of a process make
     # the HIP runtime grow its signal pool once — a 55-77 ms host stall inside whatever call is running (tools/host_gap_probe.py)
     # that must not land in the table the dominant operator is chosen from
-    discard_steps = 0 if graphed else min(2, args.warmup - table_steps)
+    discard_steps = min(2, args.warmup - table_steps) if instrument else 0
     for _ in range(args.warmup - table_steps - discard_steps):
         step()
     if discard_steps:
@@ -386,8 +426,8 @@ def main():
     only = None
     if table:
         only = {max(table.items(), key=lambda kv: kv[1]["ms"])[0]}
-    timer = ops.KernelTimer(only=only) if rank == 0 else None
-    if not graphed:
+    timer = ops.KernelTimer(only=only) if (rank == 0 and args.full) else None
+    if instrument:
         ops.set_timer(timer)
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -395,8 +435,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ops.set_timer(None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, flat, loss)
     probe_steps = args.steps
-    if graphed and rank == 0:
+    if args.full and graphed and rank == 0:
         # kernels inside a replayed graph cannot be bracketed from the host, and an eager re-run is host-bound at bf16
         # speeds: time the three passes of the model's largest conv layer (decoder 48->16 at full resolution, 42 % of the
         # step's FLOPs) back to back between two events on the launch stream instead.
@@ -427,7 +469,8 @@ def main():
         elapsed = tt.item()
     final_loss = loss.item()
 
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         agg = timer.summary()
         dom_tag, dom = max(agg.items(), key=lambda kv: kv[1]["ms"])   # (timed region: the one bracketed operator, or all of them)
         if table:   # the table and the operator's share of a step come from the warm-up steps
@@ -478,6 +521,7 @@ def main():
             sys.stderr.write("  bracketed operators: %.2f ms/step of kernels%s; timed wall %.2f ms/step (eager)\n"
                              % (total_ms / probe_steps, " (warm-up steps, every operator bracketed)" if table else "",
                                 elapsed * 1e3 / args.steps))
+    if rank == 0:
         out = {
             "metric": "MRI volumes/sec (fwd+bwd) 3D U-Net @160x192x160",
             "value": round(world * PER_GPU_BATCH * args.steps / elapsed, 4),
@@ -500,11 +544,12 @@ def main():
                        "global_batch": world * PER_GPU_BATCH, "volume": list(SHAPE),
                        "parallelism": "dp%d" % world, "final_loss": round(final_loss, 6),
                        "launch": "hipGraph(fwd+bwd) + all-reduce + AdamW" if graphed else "eager"},
-            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline and not bf16:
+        if args.full:
+            out["roofline"] = roofline
+        if args.full and world == 1 and not args.no_cpu_baseline and not bf16:
             out["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.no_secondary and not bf16:
+        if args.full and world == 1 and not args.no_secondary and not bf16:
             # the timed region is over and `value` is final: the other configurations run now, on the same device, one by one
             del x, t
             out["secondary"] = secondary_benchmarks(device)

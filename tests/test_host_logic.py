@@ -218,6 +218,35 @@ def test_bench_rank_plan_and_barrier_helper():
     parallel.release_captured_graphs()   # nothing captured: a no-op
 
 
+def test_bench_dump_outputs_writes_the_step_state_as_float32(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the loss, the flat parameters and gradients and the BatchNorm running
+    statistics land as float32 DIR/<name>.npy, value for value."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    torch.manual_seed(0)
+    m = _unet(8)
+    flat = parallel.FlatParams(m)
+    flat.grad.copy_(torch.linspace(-1, 1, flat.grad.numel()))
+    next(t for t in m.modules() if isinstance(t, torch.nn.BatchNorm3d)).running_mean.fill_(0.25)
+    shapes = b.dump_outputs(str(tmp_path / "out"), m, flat, torch.tensor(0.75))
+    assert shapes == {"loss": [1], "params": [246412], "grads": [246412], "bn_running_stats": [shapes["bn_running_stats"][0]]}
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [0.75]
+    assert np.array_equal(got["params"], flat.flat.numpy()) and np.array_equal(got["grads"], flat.grad.numpy())
+    bufs = [t for t in m.buffers() if t.is_floating_point()]
+    assert np.array_equal(got["bn_running_stats"], torch.cat([t.reshape(-1) for t in bufs]).numpy())
+    assert 0.25 in got["bn_running_stats"]
+    assert sum(a.nbytes for a in got.values()) <= b.DUMP_LIMIT_BYTES
+
+
+def test_bench_refuses_zero_steps():
+    res = _run_bench(["--gpus", "1", "--steps", "0", "--launch-check"])
+    assert res.returncode != 0 and "--steps" in res.stderr and not res.stdout.strip()
+
+
 def test_bench_refuses_a_world_size_that_is_not_gpus():
     res = _run_bench(["--gpus", "2", "--launch-check"], env_extra={"WORLD_SIZE": "1"})
     assert res.returncode != 0 and "WORLD_SIZE=1" in res.stderr and not res.stdout.strip()

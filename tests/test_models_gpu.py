@@ -664,7 +664,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MRI3D_BENCH_ONE_GPU_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+           "--master-port", "29547", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -696,6 +696,32 @@ def test_bench_gpus_2_self_launches_two_ranks_on_one_gpu():
     assert len(lines) == 1, res.stdout
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["config"]["global_batch"] == 4 and out["value"] > 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one JSON line with the headline fields and none of
+    the --full objects, `steps` timed steps behind `ms_per_step`, and the last step's loss / parameters / gradients / BatchNorm
+    running statistics as finite float32 arrays (the loss the one the line reports)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "out")], env=env, cwd=root, capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["dtype"] == "f32" and out["unit"] == "volumes/s"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0
+    assert abs(out["value"] - 2 / (out["ms_per_step"] / 1e3)) < 1e-2 * out["value"]
+    assert not {"roofline", "cpu_baseline", "secondary"} & set(out)
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in ("loss", "params", "grads", "bn_running_stats")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["params"].shape == got["grads"].shape == (246412,) and np.abs(got["grads"]).max() > 0
+    assert abs(got["loss"][0] - out["config"]["final_loss"]) < 1e-5
 
 
 # ------------------------------------------------------------------------------------------------ routines capture by default
