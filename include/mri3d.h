@@ -85,8 +85,13 @@ int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, vo
  * (mri3d_conv3d_workspace_bytes).  stat_partials (may be NULL): as in mri3d_conv3d_fwd_stats.
  * mri3d_conv3d_cat_supported(g, split, second_ld, pass) = 1 when the pass is served (3x3x3 / stride 1 / pad 1 on the tiled MFMA
  * kernels, split a multiple of 16, every pointer 16-byte aligned); otherwise concatenate (mri3d_copy_channels) and call the plain
- * entry points. */
+ * entry points.
+ * mri3d_conv3d_fwd_cat_stats_blocks(g, split, second_ld) = the number of blocks of stat_partials mri3d_conv3d_fwd_cat writes for
+ * exactly this geometry, split and second-tensor pitch: the required size of stat_partials is [blocks][g->co][2] doubles.  It may
+ * differ from mri3d_conv3d_fwd_stats_blocks of the same geometry (the second tensor's pitch takes part in the choice of kernel);
+ * 0 = no fused statistics (pass stat_partials = NULL). */
 int32_t mri3d_conv3d_cat_supported(const Mri3dConvGeom* g, int32_t split, int32_t second_ld, int32_t pass);
+int32_t mri3d_conv3d_fwd_cat_stats_blocks(const Mri3dConvGeom* g, int32_t split, int32_t second_ld);
 int mri3d_conv3d_fwd_cat(const Mri3dConvGeom* g, const void* x, const void* x2, int32_t split, int32_t x2_ld, const void* w,
                          const void* bias, void* y, double* stat_partials, void* workspace, size_t ws_bytes,
                          mri3d_stream_t stream);

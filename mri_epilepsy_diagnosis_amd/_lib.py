@@ -59,6 +59,7 @@ SIGNATURES = {
     "mri3d_conv3d_dgrad": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_wgrad": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_cat_supported": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32]),
+    "mri3d_conv3d_fwd_cat_stats_blocks": (c_int32, [POINTER(ConvGeom), c_int32, c_int32]),
     "mri3d_conv3d_fwd_cat": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_dgrad_cat": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, c_int32, c_int32, _P, c_size_t, _P]),
     "mri3d_conv3d_wgrad_cat": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),

@@ -32,7 +32,7 @@ int conv_mfma_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, cons
                     size_t ws_bytes, hipStream_t s);
 int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                     size_t ws_bytes, hipStream_t s);
-int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g);
+int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);
 bool conv_mfma_cat_supported(const Mri3dConvGeom& g, int split, int second_ld, int pass);
 int conv_mfma_fwd_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const float* w, const float* bias,
                       void* y, double* stat_part, void* ws, size_t ws_bytes, hipStream_t s);
@@ -147,6 +147,11 @@ extern "C" int32_t mri3d_conv3d_cat_supported(const Mri3dConvGeom* g, int32_t sp
     return conv_mfma_cat_supported(*g, split, second_ld, pass) ? 1 : 0;
 }
 
+extern "C" int32_t mri3d_conv3d_fwd_cat_stats_blocks(const Mri3dConvGeom* g, int32_t split, int32_t second_ld) {
+    if (!g || split <= 0 || conv_check(g, "conv3d_fwd_cat_stats_blocks", split) != MRI3D_OK) return 0;
+    return conv_mfma_cat_supported(*g, split, second_ld, MRI3D_PASS_FWD) ? conv_mfma_fwd_stat_blocks(*g, split, second_ld) : 0;
+}
+
 extern "C" int mri3d_conv3d_fwd_cat(const Mri3dConvGeom* g, const void* x, const void* x2, int32_t split, int32_t x2_ld,
                                     const void* w, const void* bias, void* y, double* stat_partials, void* workspace,
                                     size_t ws_bytes, mri3d_stream_t stream) {
@@ -155,7 +160,8 @@ extern "C" int mri3d_conv3d_fwd_cat(const Mri3dConvGeom* g, const void* x, const
     MRI3D_REQUIRE(x && x2 && w && y, MRI3D_EINVAL, "conv3d_fwd_cat: null pointer");
     MRI3D_REQUIRE(conv_mfma_cat_supported(*g, split, x2_ld, MRI3D_PASS_FWD) && aligned16(x, y, workspace) && aligned16(x2),
                   MRI3D_ENOTSUP, "conv3d_fwd_cat: geometry / alignment not served (query mri3d_conv3d_cat_supported)");
-    MRI3D_REQUIRE(stat_partials == nullptr || conv_mfma_fwd_stat_blocks(*g) > 0, MRI3D_ENOTSUP, "conv3d_fwd_cat: no fused statistics for this geometry");
+    MRI3D_REQUIRE(stat_partials == nullptr || conv_mfma_fwd_stat_blocks(*g, split, x2_ld) > 0, MRI3D_ENOTSUP,
+                  "conv3d_fwd_cat: no fused statistics for this geometry (query mri3d_conv3d_fwd_cat_stats_blocks)");
     return conv_mfma_fwd_cat(*g, x, x2, split, x2_ld, (const float*)w, (const float*)bias, y, stat_partials, workspace, ws_bytes,
                              static_cast<hipStream_t>(stream));
 }

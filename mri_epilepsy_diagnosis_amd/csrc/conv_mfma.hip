@@ -1045,6 +1045,15 @@ static bool mfma_fwd_plan(const Mri3dConvGeom& g, bool dgrad, MfmaFwdPlan& p) {
 // >= split live in `second` (pitch second_ld); second == nullptr: none
 struct ConvSplit { const void* second; int split, second_ld; };
 
+// The forward / data-gradient dispatcher's one choice between the marching kernel (conv_march.hip) and the kernels of this file.
+// run_mfma_fwd launches what it picks and conv_mfma_fwd_stat_blocks sizes the statistics partials by the same answer, so that the
+// two can never disagree about the grid.  A split operand (sp.split > 0) goes to the marching kernel only with a second-tensor
+// pitch of a multiple of 8 channels; the tiled kernel takes the others.
+static bool fwd_takes_march(const Mri3dConvGeom& g, bool dgrad, bool stats, const ConvSplit& sp) {
+    return !direct_only(g) && conv_march_takes(g, dgrad, stats, false) &&
+           (sp.split <= 0 || (sp.split % 16 == 0 && sp.second_ld % 8 == 0));
+}
+
 static int run_mfma_fwd(const Mri3dConvGeom& g, bool dgrad, const void* in_v, const float* w, const float* bias,
                         void* out_v, void* ws, size_t ws_bytes, hipStream_t s, double* stat_part = nullptr,
                         ConvSplit sp = ConvSplit{nullptr, 0, 0}) {
@@ -1052,8 +1061,7 @@ static int run_mfma_fwd(const Mri3dConvGeom& g, bool dgrad, const void* in_v, co
     DirectPlan dp;
     const bool strided = direct_only(g);
     // the layers the marching kernel is faster on (bf16 tensors on a chip-filling grid): conv_march.hip
-    if (!strided && conv_march_takes(g, dgrad, stat_part != nullptr, false) &&
-        (sp.second == nullptr || (sp.split % 16 == 0 && sp.second_ld % 8 == 0)))
+    if (fwd_takes_march(g, dgrad, stat_part != nullptr, sp))
         return conv_march_run(g, dgrad, false, in_v, w, bias, out_v, ws, ws_bytes, s, stat_part, sp.second, sp.split, sp.second_ld);
     if (strided) {
         MRI3D_REQUIRE(direct_plan(g, dgrad, dp) && stat_part == nullptr, MRI3D_ENOTSUP, "conv3d(mfma): unsupported strided geometry");
@@ -1129,9 +1137,10 @@ int conv_mfma_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const f
     return run_mfma_fwd(g, false, x, w, bias, y, ws, ws_bytes, s);
 }
 
-// number of per-workgroup statistics partials the forward kernel writes for this geometry (0: not served by the MFMA path)
-int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g) {
-    if (!direct_only(g) && conv_march_takes(g, false, true, false)) return conv_march_stat_blocks(g, false);
+// number of per-workgroup statistics partials the forward kernel writes for this geometry (0: not served by the MFMA path);
+// split / second_ld: those of a split operand (conv_mfma_fwd_cat), split 0: one tensor
+int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split, int second_ld) {
+    if (fwd_takes_march(g, false, true, ConvSplit{nullptr, split, second_ld})) return conv_march_stat_blocks(g, false);
     MfmaFwdPlan p;
     if (!mfma_fwd_plan(g, false, p) || p.NTT > 8 || p.narrow) return 0;   // LDS statistics slots for up to 128 output channels
     return p.grid;

@@ -530,8 +530,9 @@ class _Conv3dCatFn(torch.autograd.Function):
         ws = _workspace(L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_FWD), xa.device)
         part = None
         if stats_holder is not None:
-            gq = _conv_geom((xa.shape[0], ca + cb) + tuple(xa.shape[2:]), w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), dtype=_dt(xa))
-            blocks = L.mri3d_conv3d_fwd_stats_blocks(ctypes.byref(gq))     # (a query about the concatenated geometry)
+            # the partials are sized by the query about exactly what is launched: geometry, split and second-tensor pitch (the
+            # pitch takes part in the choice between the marching and the tiled kernel, whose grids differ)
+            blocks = L.mri3d_conv3d_fwd_cat_stats_blocks(ctypes.byref(g), ca, b_ld)
             if blocks > 0:
                 part = torch.empty(blocks * g.co * 2, dtype=torch.float64, device=xa.device)
                 stats_holder.append((part, blocks, bias.detach() if bias is not None else None))

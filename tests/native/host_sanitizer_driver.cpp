@@ -101,8 +101,53 @@ int main() {
                         for (int pass = 0; pass < 3; ++pass) served += mri3d_conv3d_cat_supported(&c, ca, cb, pass);
                         EXPECT(mri3d_conv3d_cat_supported(&c, 0, cb, 0) == 0);          // no first part
                         EXPECT(mri3d_conv3d_cat_supported(&c, ca + cb, cb, 0) == 0);    // no second part
+                        EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(&c, 0, cb) == 0);
+                        EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(&c, ca + cb, cb) == 0);
+                        const int blocks = mri3d_conv3d_fwd_cat_stats_blocks(&c, ca, cb);
+                        EXPECT(blocks >= 0 && (blocks == 0 || mri3d_conv3d_cat_supported(&c, ca, cb, 0) == 1));
+                        // a dense second tensor (pitch = its channel count, a multiple of 8) takes the same kernel as the
+                        // concatenation in one tensor
+                        Mri3dConvGeom whole = c;
+                        whole.x_ld = ca + cb;
+                        if (blocks > 0 && cb % 8 == 0) EXPECT(blocks == mri3d_conv3d_fwd_stats_blocks(&whole));
                     }
         EXPECT(served > 0);
+        // statistics partials of the split forward: the block count must be that of the kernel which runs.  fp32 volumes of >= 4 M
+        // voxels with 16 output channels go to the marching kernel, but only with a second-tensor pitch of a multiple of 8; the
+        // other pitches (20, 28: served, multiples of 4) run the tiled kernel, whose grid is larger (512 against 240 at 160x192x160)
+        int swept = 0;
+        for (int dtype = 0; dtype < 2; ++dtype)
+            for (int n : {1, 2})
+                for (auto& sz : {std::vector<int>{160, 192, 160}, std::vector<int>{128, 128, 256}, std::vector<int>{40, 48, 40}})
+                    for (int cb : {16, 32})
+                        for (int extra : {0, 4, 8, 12}) {
+                            const int ld = cb + extra;
+                            Mri3dConvGeom c = conv(n, sz[0], sz[1], sz[2], 16 + cb, 16, 3, 1, 1, 1, dtype, 0, 0);
+                            c.x_ld = 16;
+                            const int blocks = mri3d_conv3d_fwd_cat_stats_blocks(&c, 16, ld);
+                            const int supported = mri3d_conv3d_cat_supported(&c, 16, ld, 0);
+                            EXPECT((blocks > 0) == (supported == 1));
+                            if (!supported) continue;
+                            ++swept;
+                            Mri3dConvGeom whole = c;
+                            whole.x_ld = 16 + cb;
+                            EXPECT(blocks > 0 && blocks <= 512 + mri3d_conv3d_march_stats_blocks(&whole));
+                            if (ld % 8 == 0) EXPECT(blocks == mri3d_conv3d_fwd_stats_blocks(&whole));
+                        }
+        EXPECT(swept > 20);
+        {   // the case of the overrun: fp32, 1 x (16 + 16) -> 16 at 160x192x160, the second tensor a slice of a 20-channel buffer
+            Mri3dConvGeom c = conv(1, 160, 192, 160, 32, 16, 3, 1, 1, 1, MRI3D_F32, 0, 0);
+            Mri3dConvGeom whole = c;
+            c.x_ld = 16;
+            const int one = mri3d_conv3d_fwd_stats_blocks(&whole);
+            EXPECT(one > 0 && one < 512);                                             // the marching kernel's grid
+            for (int ld : {20, 28}) {
+                EXPECT(mri3d_conv3d_cat_supported(&c, 16, ld, 0) == 1);
+                EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(&c, 16, ld) == 512);         // the tiled kernel's grid
+            }
+            EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(&c, 16, 16) == one && mri3d_conv3d_fwd_cat_stats_blocks(&c, 16, 24) == one);
+            EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(nullptr, 16, 16) == 0);
+        }
         EXPECT(mri3d_conv3d_cat_supported(nullptr, 16, 32, 0) == 0);
         Mri3dConvGeom c = conv(2, 160, 192, 160, 48, 16, 3, 1, 1, 1, 0, 0, 0);
         c.x_ld = 16;

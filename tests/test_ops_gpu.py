@@ -661,7 +661,9 @@ CAT_CASES = [(2, 16, 32, 16, (24, 40, 70), 0, True, True, True), (2, 32, 64, 32,
                                                                        #  prefers the LDS-free kernel and the sums are ordered differently)
              (2, 16, 24, 16, (24, 40, 70), 0, True, False, True),      # 24 trailing channels: not a ci-tile multiple for the fp32 weight gradient
              (1, 8, 16, 16, (24, 40, 70), 0, True, False, False),      # 8 leading channels: the split must be a multiple of 16
-             (1, 16, 32, 16, (6, 7, 9), 0, True, False, True)]         # tiny volume: fp32 runs on the LDS-free kernel (no split support)
+             (1, 16, 32, 16, (6, 7, 9), 0, True, False, True),         # tiny volume: fp32 runs on the LDS-free kernel (no split support)
+             (5, 16, 16, 16, (17, 40, 65), 4, True, True, False)]      # second tensor of pitch 20: fp32 served (16-byte aligned slice),
+                                                                       # bf16 falls back (the slice starts 8 bytes into the voxel)
 
 
 def test_conv3d_cat_between_256_and_512_work_units_stays_on_the_tiled_kernel():
