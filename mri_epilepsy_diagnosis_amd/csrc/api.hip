@@ -1,6 +1,7 @@
 // api.hip — C-ABI entry points that are not tied to one kernel file: version, error string, and the Conv3d
 // dispatcher (generic direct kernels vs. the MFMA implicit-GEMM path for 3x3x3 stride-1 layers).
 #include "common.h"
+#include "conv_backends.h"
 #include <string.h>
 
 namespace mri3d {
@@ -14,53 +15,8 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-// conv_generic.hip
-size_t conv_generic_workspace_bytes(const Mri3dConvGeom& g, int pass);
-// activations (x, y, dy, dx) are in the storage type g.dtype; weights, bias and their gradients are fp32
-int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, void* ws,
-                     size_t ws_bytes, hipStream_t s);
-int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
-                       size_t ws_bytes, hipStream_t s);
-int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
-                       size_t ws_bytes, hipStream_t s);
-// conv_mfma.hip
-bool conv_mfma_supported(const Mri3dConvGeom& g, int pass);
-size_t conv_mfma_workspace_bytes(const Mri3dConvGeom& g, int pass);
-int conv_mfma_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, void* ws,
-                  size_t ws_bytes, hipStream_t s);
-int conv_mfma_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
-                    size_t ws_bytes, hipStream_t s);
-int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
-                    size_t ws_bytes, hipStream_t s);
-int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);
-bool conv_mfma_cat_supported(const Mri3dConvGeom& g, int split, int second_ld, int pass);
-int conv_mfma_fwd_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const float* w, const float* bias,
-                      void* y, double* stat_part, void* ws, size_t ws_bytes, hipStream_t s);
-int conv_mfma_dgrad_cat(const Mri3dConvGeom& g, const void* dy, const float* w, void* dx, void* dx2, int split, int dx2_ld, void* ws,
-                        size_t ws_bytes, hipStream_t s);
-int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
-                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
-int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, double* stat_part,
-                        void* ws, size_t ws_bytes, hipStream_t s);
-
-// conv_march.hip
-bool conv_march_takes(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force);
-int conv_march_stat_blocks(const Mri3dConvGeom& g, bool force);
-int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
-                   void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const void* second, int split, int second_ld);
-
-// conv_pointwise.hip
-bool conv_pointwise_supported(const Mri3dConvGeom& g, int pass);
-size_t conv_pointwise_workspace_bytes(const Mri3dConvGeom& g, int pass);
-int conv_pointwise_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, hipStream_t s);
-int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx,
-                         hipStream_t s);
-int conv_pointwise_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
-                         size_t ws_bytes, hipStream_t s);
-
-// the MFMA kernels move 16-byte pieces: a pitched channel slice whose base is not 16-byte aligned (legal for the generic
-// kernels) must not be routed to them
-
+// (the aligned16 tests of the entry points below: the MFMA kernels move 16-byte pieces, so a pitched channel slice whose base is
+// not 16-byte aligned, legal for the generic kernels, must not be routed to them)
 // first_ci >= 0: the input is split over two tensors (the *_cat entry points) and x_ld is the pitch of the first, which holds
 // first_ci channels
 static int conv_check(const Mri3dConvGeom* g, const char* who, int first_ci = -1) {
@@ -192,12 +148,12 @@ extern "C" int mri3d_conv3d_wgrad_cat(const Mri3dConvGeom* g, const void* x, con
 // the layers it is faster on; these take EVERY geometry it can compute, so that parity tests reach it with small volumes.
 extern "C" int32_t mri3d_conv3d_march_supported(const Mri3dConvGeom* g, int32_t pass) {
     if (!g || (pass != MRI3D_PASS_FWD && pass != MRI3D_PASS_DGRAD) || conv_check(g, "conv3d_march_supported") != MRI3D_OK) return 0;
-    return conv_march_takes(*g, pass == MRI3D_PASS_DGRAD, false, true) ? 1 : 0;
+    return conv_march_needs(*g, pass == MRI3D_PASS_DGRAD, false, true).grid > 0 ? 1 : 0;
 }
 
 extern "C" int32_t mri3d_conv3d_march_stats_blocks(const Mri3dConvGeom* g) {
     if (!g || conv_check(g, "conv3d_march_stats_blocks") != MRI3D_OK) return 0;
-    return conv_march_stat_blocks(*g, true);
+    return conv_march_needs(*g, false, true, true).grid;
 }
 
 extern "C" int mri3d_conv3d_fwd_march(const Mri3dConvGeom* g, const void* x, const void* x2, int32_t split, int32_t x2_ld,
@@ -208,7 +164,7 @@ extern "C" int mri3d_conv3d_fwd_march(const Mri3dConvGeom* g, const void* x, con
     MRI3D_REQUIRE(x && w && y, MRI3D_EINVAL, "conv3d_fwd_march: null pointer");
     MRI3D_REQUIRE(x2 == nullptr || (split > 0 && split < g->ci && x2_ld >= g->ci - split), MRI3D_EINVAL, "conv3d_fwd_march: bad split");
     return conv_march_run(*g, false, true, x, (const float*)w, (const float*)bias, y, workspace, ws_bytes,
-                          static_cast<hipStream_t>(stream), stat_partials, x2, split, x2_ld);
+                          static_cast<hipStream_t>(stream), stat_partials, ConvSplit{x2, split, x2_ld});
 }
 
 extern "C" int mri3d_conv3d_dgrad_march(const Mri3dConvGeom* g, const void* dy, const void* w, void* dx, void* dx2, int32_t split,
@@ -218,7 +174,7 @@ extern "C" int mri3d_conv3d_dgrad_march(const Mri3dConvGeom* g, const void* dy, 
     MRI3D_REQUIRE(dy && w && dx, MRI3D_EINVAL, "conv3d_dgrad_march: null pointer");
     MRI3D_REQUIRE(dx2 == nullptr || (split > 0 && split < g->ci && dx2_ld >= g->ci - split), MRI3D_EINVAL, "conv3d_dgrad_march: bad split");
     return conv_march_run(*g, true, true, dy, (const float*)w, nullptr, dx, workspace, ws_bytes, static_cast<hipStream_t>(stream),
-                          nullptr, dx2, split, dx2_ld);
+                          nullptr, ConvSplit{dx2, split, dx2_ld});
 }
 
 extern "C" int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, void* dw, void* dbias,

@@ -1,0 +1,61 @@
+// conv_backends.h — what the Conv3d kernel files offer each other and the dispatcher in api.hip.  Every file that defines or
+// calls one of these includes this header, so a definition is always compiled against its declaration.
+// Activations (x, y, dy, dx) are in the storage type g.dtype; weights, bias and their gradients are fp32.
+#pragma once
+#include "common.h"
+
+namespace mri3d {
+
+// second tensor of a split operand (conv over cat((x, x2), channels) / its data gradient written to two tensors): channels
+// >= split live in `second` (pitch second_ld); split == 0: one tensor
+struct ConvSplit {
+    const void* second = nullptr;
+    int split = 0, second_ld = 0;
+};
+
+// conv_generic.hip
+size_t conv_generic_workspace_bytes(const Mri3dConvGeom& g, int pass);
+int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, void* ws,
+                     size_t ws_bytes, hipStream_t s);
+int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
+                       size_t ws_bytes, hipStream_t s);
+int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
+                       size_t ws_bytes, hipStream_t s);
+
+// conv_mfma.hip
+bool conv_mfma_supported(const Mri3dConvGeom& g, int pass);
+size_t conv_mfma_workspace_bytes(const Mri3dConvGeom& g, int pass);
+int conv_mfma_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, void* ws,
+                  size_t ws_bytes, hipStream_t s);
+int conv_mfma_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
+                    size_t ws_bytes, hipStream_t s);
+int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
+                    size_t ws_bytes, hipStream_t s);
+int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);
+bool conv_mfma_cat_supported(const Mri3dConvGeom& g, int split, int second_ld, int pass);
+int conv_mfma_fwd_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const float* w, const float* bias,
+                      void* y, double* stat_part, void* ws, size_t ws_bytes, hipStream_t s);
+int conv_mfma_dgrad_cat(const Mri3dConvGeom& g, const void* dy, const float* w, void* dx, void* dx2, int split, int dx2_ld, void* ws,
+                        size_t ws_bytes, hipStream_t s);
+int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
+                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
+int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, double* stat_part,
+                        void* ws, size_t ws_bytes, hipStream_t s);
+
+// conv_march.hip: forward / data gradient marching along d.  `force` = the explicit entry points (every geometry the kernel can
+// compute); otherwise the dispatcher's own choice of the layers where it is the faster kernel.
+struct MarchNeeds { int grid; size_t wp_bytes; };   // workgroups (= statistics partials) and packed-weight image; grid 0: not taken
+MarchNeeds conv_march_needs(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force);
+int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
+                   void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const ConvSplit& sp);
+
+// conv_pointwise.hip
+bool conv_pointwise_supported(const Mri3dConvGeom& g, int pass);
+size_t conv_pointwise_workspace_bytes(const Mri3dConvGeom& g, int pass);
+int conv_pointwise_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, hipStream_t s);
+int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx,
+                         hipStream_t s);
+int conv_pointwise_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
+                         size_t ws_bytes, hipStream_t s);
+
+}  // namespace mri3d

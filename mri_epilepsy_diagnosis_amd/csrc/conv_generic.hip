@@ -6,6 +6,7 @@
 // Roofline: these layers have arithmetic intensity of a few FLOP/byte (separable convs AI~6) and are
 // HBM-bound; the design goal is one coalesced pass over x and y with weights on the scalar path.
 #include "common.h"
+#include "conv_backends.h"
 
 namespace mri3d {
 

@@ -23,6 +23,7 @@
 //
 // Roofline: bf16 layers are bound by HBM bytes; algorithmic bytes per launch = input + output tensors once.
 #include "common.h"
+#include "conv_backends.h"
 #include "mfma_util.h"
 #include <algorithm>
 #include <type_traits>
@@ -672,38 +673,28 @@ bool conv_march_plan(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force,
     return true;
 }
 
-bool conv_march_takes(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force) {
+MarchNeeds conv_march_needs(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force) {
     MarchPlan p;
-    return conv_march_plan(g, dgrad, stats, force, p);
-}
-
-size_t conv_march_workspace_bytes(const Mri3dConvGeom& g, bool dgrad) {
-    MarchPlan p;
-    return conv_march_plan(g, dgrad, false, true, p) ? p.wp_bytes : 0;
-}
-
-int conv_march_stat_blocks(const Mri3dConvGeom& g, bool force) {
-    MarchPlan p;
-    return conv_march_plan(g, false, true, force, p) ? p.grid : 0;
+    return conv_march_plan(g, dgrad, stats, force, p) ? MarchNeeds{p.grid, p.wp_bytes} : MarchNeeds{0, 0};
 }
 
 // second tensor of a split operand: forward, input channels >= split live in `second`; data gradient, output channels >= split
 int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
-                   void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const void* second, int split, int second_ld) {
+                   void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const ConvSplit& sp) {
     MarchPlan p;
     MRI3D_REQUIRE(conv_march_plan(g, dgrad, stat_part != nullptr, force, p), MRI3D_ENOTSUP, "conv3d(march): unsupported geometry");
     MRI3D_REQUIRE(ws && ws_bytes >= p.wp_bytes, MRI3D_EWORKSPACE, "conv3d(march): workspace %zu < %zu", ws_bytes, p.wp_bytes);
-    MRI3D_REQUIRE(aligned16(in_v, out_v, ws) && aligned16(second), MRI3D_EINVAL, "conv3d(march): tensors / workspace must be 16-byte aligned");
+    MRI3D_REQUIRE(aligned16(in_v, out_v, ws) && aligned16(sp.second), MRI3D_EINVAL, "conv3d(march): tensors / workspace must be 16-byte aligned");
     MarchGeom q = p.q;
     const bool bf = g.dtype == MRI3D_BF16;
-    if (second) {
-        MRI3D_REQUIRE(split > 0 && split % 16 == 0 && second_ld % (bf ? 8 : 4) == 0 && second_ld % 4 == 0, MRI3D_ENOTSUP,
+    if (sp.second) {
+        MRI3D_REQUIRE(sp.split > 0 && sp.split % 16 == 0 && sp.second_ld % (bf ? 8 : 4) == 0 && sp.second_ld % 4 == 0, MRI3D_ENOTSUP,
                       "conv3d(march): split must be a multiple of 16");
-        MRI3D_REQUIRE(!(bf && dgrad) || second_ld % 8 == 0, MRI3D_ENOTSUP, "conv3d(march): bf16 output pitch must be a multiple of 8");
-        if (dgrad) q.nsplit = split, q.out2_ld = second_ld;
+        MRI3D_REQUIRE(!(bf && dgrad) || sp.second_ld % 8 == 0, MRI3D_ENOTSUP, "conv3d(march): bf16 output pitch must be a multiple of 8");
+        if (dgrad) q.nsplit = sp.split, q.out2_ld = sp.second_ld;
         else {
-            MRI3D_REQUIRE(split % (bf ? 16 : 8) == 0, MRI3D_ENOTSUP, "conv3d(march): split inside a chunk");
-            q.ksplit = split, q.in2_ld = second_ld;
+            MRI3D_REQUIRE(sp.split % (bf ? 16 : 8) == 0, MRI3D_ENOTSUP, "conv3d(march): split inside a chunk");
+            q.ksplit = sp.split, q.in2_ld = sp.second_ld;
         }
     }
     const int total_el = (int)(p.wp_bytes / (bf ? 2 : 4));
@@ -713,8 +704,8 @@ int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* i
     else
         hipLaunchKernelGGL(pack_w_march_kernel<float>, dim3(std::min(cdiv(total_el, 256), 2048)), dim3(256), 0, s, w,
                            static_cast<float*>(ws), g.co, g.ci, dgrad ? 1 : 0, q.nchunks, q.NTT);
-    const void* x2 = dgrad ? nullptr : second;
-    void* y2 = dgrad ? const_cast<void*>(second) : nullptr;
+    const void* x2 = dgrad ? nullptr : sp.second;
+    void* y2 = dgrad ? const_cast<void*>(sp.second) : nullptr;
 #define MRI3D_MARCH_CASE(STv, BIv)                                                                                      \
     if ((stat_part != nullptr) == STv && (bias != nullptr) == BIv) {                                                    \
         auto k8 = conv_march_kernel<T, STv, BIv>;                                                                       \

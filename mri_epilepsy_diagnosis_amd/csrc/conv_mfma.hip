@@ -19,19 +19,12 @@
 // Roofline: compute-bound for Cin*Cout >= 8*16 (AI 72..270 FLOP/B vs ridge ~20): the bound is the fp32
 // MFMA peak; algorithmic FLOPs = 2 * N*D*H*W * Cin * Cout * 27 per pass.
 #include "common.h"
+#include "conv_backends.h"
 #include "mfma_util.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace mri3d {
-
-// conv_march.hip: forward / data gradient marching along d.  `force` = the explicit entry points (every geometry the kernel can
-// compute); otherwise the dispatcher's own choice of the layers where it is the faster kernel.
-bool conv_march_takes(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force);
-size_t conv_march_workspace_bytes(const Mri3dConvGeom& g, bool dgrad);
-int conv_march_stat_blocks(const Mri3dConvGeom& g, bool force);
-int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
-                   void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const void* second, int split, int second_ld);
 
 constexpr int TD = 4, TH = 8, TW = 16;               // output tile (d, h, w)
 constexpr int HD = TD + 2, HH = TH + 2, HW = TW + 2;  // halo tile
@@ -913,12 +906,10 @@ conv_mfma_direct_kernel(const T* __restrict__ in, const float* __restrict__ wp, 
 }
 
 // ------------------------------------------------------------------ host side
+// Plan of the tiled kernel (conv_mfma_fwd2_kernel): 3x3x3, stride 1, pad 1, dilation 1.
 struct MfmaFwdPlan {
     int CK, NT, NTT, gy, nchunks, tilesD, tilesH, tilesW, ntiles, grid;
-    int small;   // served by the LDS-free kernel (conv_mfma_direct_kernel): 1 = fewer than 256 work units (or narrow / strided), 2 = fewer
-                 // than one per workgroup slot (a preference: split operands and fused statistics stay on the tiled kernel)
-    int narrow;  // ... or when the volume is narrower than a tile row (then also with BatchNorm statistics requested)
-    size_t wp_floats, s_wp_floats, smem, stat_smem;   // packed-weight image of the tiled / the small-volume kernel
+    size_t wp_floats, smem, stat_smem;   // packed-weight image, halo buffers, float64 statistics of the STATS variant
 };
 
 // Plan of the LDS-free kernel (conv_mfma_direct_kernel): 3x3x3, pad 1, dilation 1, one stride s for the three axes.
@@ -926,6 +917,7 @@ struct DirectPlan {
     DirectGeom q;
     int nt, mode, split, units;
     size_t wp_floats;
+    int grid() const { return split ? units : cdiv(units, 4); }
 };
 
 static bool direct_plan(const Mri3dConvGeom& g, bool dgrad, DirectPlan& p) {
@@ -971,10 +963,9 @@ static bool direct_plan(const Mri3dConvGeom& g, bool dgrad, DirectPlan& p) {
 
 template <typename T>
 static void launch_direct(const DirectPlan& p, const T* in, const float* wp, const float* bias, T* out, hipStream_t s) {
-    const int grid = p.split ? p.units : cdiv(p.units, 4);
 #define MRI3D_DIRECT_CASE(NTv, MODEv, SPv)                                                                            \
     if (p.nt == NTv && p.mode == MODEv && p.split == SPv)                                                             \
-        hipLaunchKernelGGL((conv_mfma_direct_kernel<T, NTv, MODEv, (SPv != 0)>), dim3(grid), dim3(256), 0, s, in, wp, bias, out, p.q);
+        hipLaunchKernelGGL((conv_mfma_direct_kernel<T, NTv, MODEv, (SPv != 0)>), dim3(p.grid()), dim3(256), 0, s, in, wp, bias, out, p.q);
 #define MRI3D_DIRECT_NT(MODEv, SPv) MRI3D_DIRECT_CASE(1, MODEv, SPv) MRI3D_DIRECT_CASE(2, MODEv, SPv) MRI3D_DIRECT_CASE(4, MODEv, SPv)
     MRI3D_DIRECT_NT(0, 0)
     MRI3D_DIRECT_NT(0, 1)
@@ -983,9 +974,6 @@ static void launch_direct(const DirectPlan& p, const T* in, const float* wp, con
 #undef MRI3D_DIRECT_NT
 #undef MRI3D_DIRECT_CASE
 }
-
-// strided layers: served by the LDS-free kernel only
-static bool direct_only(const Mri3dConvGeom& g) { return g.sd > 1 || g.sh > 1 || g.sw > 1; }
 
 static bool mfma_fwd_plan(const Mri3dConvGeom& g, bool dgrad, MfmaFwdPlan& p) {
     if (!(g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 1 && g.ph == 1 &&
@@ -1015,98 +1003,135 @@ static bool mfma_fwd_plan(const Mri3dConvGeom& g, bool dgrad, MfmaFwdPlan& p) {
     int64_t st = (int64_t)p.ntiles * p.gy;  // (spatial tile, n-tile block) work units
     if (st > 0x7fffffff) return false;
     p.grid = (int)std::min<int64_t>(st, 512);  // 2 resident workgroups per CU x 256 CUs
-    // Small volumes (fp32): no more work units than workgroup slots — the wave-per-M-tile kernel fills the chip instead.  Its
-    // operands come from L2 / the Infinity Cache, so it is only used while the input is small (<= 32 MB).
-    p.small = 0;
-    p.s_wp_floats = 0;
-    const int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
-    DirectPlan dp;
-#ifndef MRI3D_SMALL_UNITS
-#define MRI3D_SMALL_UNITS 512   // one work unit per workgroup slot or fewer.  Measured (tools/small_units_ab.sh, variants -DMRI3D_SMALL_UNITS=N): 256 -> 512 moves 32 -> 32
-#endif                          // @ 40x48x40 x 2 from 64 to 72 and 64 -> 64 @ 40x48x40 from 68 to 80 TFLOP/s; 1024 loses on 32 -> 64 (85 -> 79)
-    if (!bf && st < MRI3D_SMALL_UNITS && nvox * Kc * 4 <= ((int64_t)32 << 20) && direct_plan(g, dgrad, dp)) {   // bf16 tensors stay on the bf16 MFMA
-        p.small = st < 256 ? 1 : 2;   // 2: a preference only — split operands and fused statistics still take the tiled kernel
-        p.s_wp_floats = dp.wp_floats;
-    }
-    // Volumes at most half a tile row wide (the 8^3 level of the patch CNN, cnn_model.py:104-175, batch 512): a 16-voxel tile row
-    // would be half padding.  The LDS-free kernel's M-tiles are 16 consecutive voxels of the flattened index space (two rows of
-    // eight), nothing is wasted: 64 -> 64 @ 8^3 x 512 forward 61 -> 90, data gradient 65 -> 97 TFLOP/s.  (No fused BatchNorm
-    // statistics there: conv_mfma_fwd_stat_blocks() answers 0 and the statistics pass reads the small output once.)
-    p.narrow = 0;
-    if (!bf && g.wi <= 8 && direct_plan(g, dgrad, dp)) {
-        p.small = 1;
-        p.narrow = 1;
-        p.s_wp_floats = dp.wp_floats;
-    }
     return true;
 }
 
-// second tensor of a split operand (conv over cat((x, x2), channels) / its data gradient written to two tensors): channels
-// >= split live in `second` (pitch second_ld); second == nullptr: none
-struct ConvSplit { const void* second; int split, second_ld; };
+// What the LDS-free kernel is to a geometry; the reasons are rows 1, 3, 5 and 6 of the table on fwd_route.  preferred / few_units:
+// a small volume of 256 work units or more / of fewer; strided: it is the only kernel of this file with a stride.
+enum class DirectUse { no, preferred, few_units, narrow, strided };
 
-// The forward / data-gradient dispatcher's one choice between the marching kernel (conv_march.hip) and the kernels of this file.
-// run_mfma_fwd launches what it picks and conv_mfma_fwd_stat_blocks sizes the statistics partials by the same answer, so that the
-// two can never disagree about the grid.  A split operand (sp.split > 0) goes to the marching kernel only with a second-tensor
-// pitch of a multiple of 8 channels; the tiled kernel takes the others.
-static bool fwd_takes_march(const Mri3dConvGeom& g, bool dgrad, bool stats, const ConvSplit& sp) {
-    return !direct_only(g) && conv_march_takes(g, dgrad, stats, false) &&
-           (sp.split <= 0 || (sp.split % 16 == 0 && sp.second_ld % 8 == 0));
+// `tiled`: the tiled kernel's plan where mfma_fwd_plan accepts, else nullptr.  dp is filled unless the answer is `no`.
+static DirectUse direct_use(const Mri3dConvGeom& g, bool dgrad, const MfmaFwdPlan* tiled, DirectPlan& dp) {
+    if (g.sd > 1 || g.sh > 1 || g.sw > 1) return direct_plan(g, dgrad, dp) ? DirectUse::strided : DirectUse::no;
+    if (g.dtype == MRI3D_BF16 || tiled == nullptr) return DirectUse::no;   // bf16 tensors stay on the bf16 MFMA
+    if (g.wi <= 8) return direct_plan(g, dgrad, dp) ? DirectUse::narrow : DirectUse::no;
+#ifndef MRI3D_SMALL_UNITS
+#define MRI3D_SMALL_UNITS 512   // one work unit per workgroup slot or fewer.  Measured (tools/small_units_ab.sh, variants -DMRI3D_SMALL_UNITS=N): 256 -> 512 moves 32 -> 32
+#endif                          // @ 40x48x40 x 2 from 64 to 72 and 64 -> 64 @ 40x48x40 from 68 to 80 TFLOP/s; 1024 loses on 32 -> 64 (85 -> 79)
+    const int st = tiled->ntiles * tiled->gy;   // (spatial tile, n-tile block) work units of the tiled kernel
+    const int64_t in_bytes = (int64_t)g.n * g.di * g.hi * g.wi * (dgrad ? g.co : g.ci) * 4;
+    if (st >= MRI3D_SMALL_UNITS || in_bytes > ((int64_t)32 << 20) || !direct_plan(g, dgrad, dp)) return DirectUse::no;
+    return st < 256 ? DirectUse::few_units : DirectUse::preferred;
 }
 
+enum class FwdKernel { none, march, direct, tiled, tiled_n8 };   // conv_march_kernel, conv_mfma_direct_kernel, conv_mfma_fwd2_kernel<.., N8>
+
+struct FwdRoute {
+    FwdKernel kernel = FwdKernel::none;   // none: not served
+    int grid = 0;                         // workgroups of the kernel = statistics partials when it fuses the statistics
+    size_t wp_bytes = 0;                  // its packed-weight image at the head of the workspace
+    MfmaFwdPlan tiled{};                  // kernel == tiled / tiled_n8  (the marching kernel keeps its MarchPlan in conv_march.hip)
+    DirectPlan direct{};                  // kernel == direct
+};
+
+// THE forward / data-gradient decision of this file: which kernel runs, on what grid, with how much workspace.  The launch
+// (run_mfma_fwd) and every query (conv_mfma_supported, conv_mfma_cat_supported, conv_mfma_fwd_stat_blocks) read this one answer,
+// so they cannot disagree about the kernel or its grid.  `stats`: BatchNorm statistics fused into the forward; `sp`: a split
+// operand (sp.split > 0).  First matching row wins:
+//
+//   1  any stride > 1                                          direct if direct_plan accepts, no stats and no split; otherwise none
+//   2  mfma_fwd_plan refuses                                   none
+//   3  a split, and row 5's `narrow` or `few units`            none (the LDS-free kernel has no second operand)
+//   4  conv_march.hip takes it by choice, and no split or      march: the layers the marching kernel is faster on (bf16 tensors on
+//      (split % 16 == 0 and second_ld % 8 == 0)                a chip-filling grid); the tiled kernel takes the other pitches
+//   5  fp32, direct_plan accepts, no stats, no split, and      direct
+//      narrow (wi <= 8) or small (see below)
+//   6  stats, and more than 128 output channels or narrow      none: LDS statistics slots for up to 128 channels
+//   7  exactly 8 output channels, no stats                     tiled_n8: the row-paired variant (10 tap groups per chunk)
+//   8  otherwise                                               tiled
+//
+// Small volumes: no more work units than workgroup slots (fewer than MRI3D_SMALL_UNITS) — the wave-per-M-tile kernel fills the chip
+// instead.  Its operands come from L2 / the Infinity Cache, so it is only used while the input is small (<= 32 MB).  With 256 units
+// or more (`preferred`) that is a preference only: split operands and fused statistics still take the tiled kernel.
+// Narrow volumes, at most half a tile row wide (the 8^3 level of the patch CNN, cnn_model.py:104-175, batch 512): a 16-voxel tile row
+// would be half padding.  The LDS-free kernel's M-tiles are 16 consecutive voxels of the flattened index space (two rows of eight),
+// nothing is wasted: 64 -> 64 @ 8^3 x 512 forward 61 -> 90, data gradient 65 -> 97 TFLOP/s.  (No fused BatchNorm statistics there:
+// row 6, and the statistics pass reads the small output once.)
+// Rows 2 and 3 stand before the marching kernel because the dispatcher (api.hip) has always asked conv_mfma_supported /
+// conv_mfma_cat_supported first, which answered by them.
+static FwdRoute fwd_route(const Mri3dConvGeom& g, bool dgrad, bool stats, const ConvSplit& sp) {
+    FwdRoute r;
+    const bool split = sp.split > 0;
+    DirectPlan dp;
+    MfmaFwdPlan p;
+    const bool tiled_ok = mfma_fwd_plan(g, dgrad, p);   // (refuses a stride at once)
+    const DirectUse du = direct_use(g, dgrad, tiled_ok ? &p : nullptr, dp);
+    const auto direct = [&] {
+        r.kernel = FwdKernel::direct, r.grid = dp.grid(), r.wp_bytes = dp.wp_floats * sizeof(float), r.direct = dp;
+        return r;
+    };
+    if (du == DirectUse::strided) return (stats || split) ? r : direct();                                  // 1
+    if (!tiled_ok) return r;                                                                               // 2
+    if (split && (du == DirectUse::few_units || du == DirectUse::narrow)) return r;                        // 3
+    const MarchNeeds march = conv_march_needs(g, dgrad, stats, false);
+    if (march.grid > 0 && (!split || (sp.split % 16 == 0 && sp.second_ld % 8 == 0))) {                     // 4
+        r.kernel = FwdKernel::march, r.grid = march.grid, r.wp_bytes = march.wp_bytes;
+        return r;
+    }
+    if (du != DirectUse::no && !stats && !split) return direct();                                          // 5
+    if (stats && (p.NTT > 8 || du == DirectUse::narrow)) return r;                                         // 6
+    const bool n8 = (dgrad ? g.ci : g.co) == 8 && !stats;                                                  // 7, 8
+    r.kernel = n8 ? FwdKernel::tiled_n8 : FwdKernel::tiled, r.grid = p.grid, r.tiled = p;
+    // n8: 10 x 16-byte fragments x 64 lanes per chunk; both storage types: 256 floats == 512 bf16 per (chunk, tap group, N-tile)
+    r.wp_bytes = (n8 ? (size_t)p.nchunks * 10 * 256 : p.wp_floats) * sizeof(float);
+    return r;
+}
+
+// grid of a weight-packing kernel (grid-stride over the image's elements)
+static dim3 pack_blocks(int elements) { return dim3(std::min(cdiv(elements, 256), 2048)); }
+
+// The workspace must hold the chosen kernel's packed-weight image (callers size it with conv_mfma_workspace_bytes, a maximum over
+// the kernel families, so this is never the stricter of the two).
 static int run_mfma_fwd(const Mri3dConvGeom& g, bool dgrad, const void* in_v, const float* w, const float* bias,
                         void* out_v, void* ws, size_t ws_bytes, hipStream_t s, double* stat_part = nullptr,
-                        ConvSplit sp = ConvSplit{nullptr, 0, 0}) {
-    MfmaFwdPlan p;
-    DirectPlan dp;
-    const bool strided = direct_only(g);
-    // the layers the marching kernel is faster on (bf16 tensors on a chip-filling grid): conv_march.hip
-    if (fwd_takes_march(g, dgrad, stat_part != nullptr, sp))
-        return conv_march_run(g, dgrad, false, in_v, w, bias, out_v, ws, ws_bytes, s, stat_part, sp.second, sp.split, sp.second_ld);
-    if (strided) {
-        MRI3D_REQUIRE(direct_plan(g, dgrad, dp) && stat_part == nullptr, MRI3D_ENOTSUP, "conv3d(mfma): unsupported strided geometry");
-        p.small = 1;
-        p.wp_floats = 0;
-        p.s_wp_floats = dp.wp_floats;
-    } else {
-        MRI3D_REQUIRE(mfma_fwd_plan(g, dgrad, p), MRI3D_ENOTSUP, "conv3d(mfma): unsupported geometry");
-    }
-    const size_t need = std::max(p.wp_floats, p.s_wp_floats) * sizeof(float);
-    MRI3D_REQUIRE(ws && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d(mfma): workspace %zu < %zu", ws_bytes, need);
-    MRI3D_REQUIRE(((reinterpret_cast<uintptr_t>(in_v) | reinterpret_cast<uintptr_t>(out_v) | reinterpret_cast<uintptr_t>(ws)) & 15) == 0,
-                  MRI3D_EINVAL, "conv3d(mfma): input/output/workspace must be 16-byte aligned");
+                        ConvSplit sp = ConvSplit{}) {
+    const FwdRoute r = fwd_route(g, dgrad, stat_part != nullptr, sp);
+    MRI3D_REQUIRE(r.kernel != FwdKernel::none && (sp.second != nullptr) == (sp.split > 0), MRI3D_ENOTSUP,
+                  "conv3d(mfma): geometry, fused statistics or split operand not served");
+    MRI3D_REQUIRE(ws && ws_bytes >= r.wp_bytes, MRI3D_EWORKSPACE, "conv3d(mfma): workspace %zu < %zu", ws_bytes, r.wp_bytes);
+    MRI3D_REQUIRE(aligned16(in_v, out_v, ws), MRI3D_EINVAL, "conv3d(mfma): input/output/workspace must be 16-byte aligned");
     float* wp = static_cast<float*>(ws);
     const int Kc = dgrad ? g.co : g.ci, Nc = dgrad ? g.ci : g.co;
     const int in_ld = dgrad ? g.y_ld : g.x_ld, out_ld = dgrad ? g.x_ld : g.y_ld;
-    int total = (int)p.wp_floats;
-    MRI3D_REQUIRE(sp.second == nullptr || (p.small != 1 && !strided), MRI3D_ENOTSUP, "conv3d(mfma): split operands need the tiled kernel");
-    if (p.small && stat_part == nullptr && sp.second == nullptr) {
-        if (!strided) MRI3D_REQUIRE(direct_plan(g, dgrad, dp), MRI3D_ENOTSUP, "conv3d(mfma): unsupported geometry");
-        const int stotal = (int)dp.wp_floats;
-        hipLaunchKernelGGL(pack_w_mfma_kernel, dim3(std::min(cdiv(stotal, 256), 2048)), dim3(256), 0, s, w, wp, g.co, g.ci,
-                           dgrad ? 1 : 0, 16, dp.q.NTT, cdiv(Kc, 16));
-        MRI3D_DISPATCH_DTYPE(g.dtype, T, { launch_direct<T>(dp, (const T*)in_v, wp, bias, (T*)out_v, s); });
+    const bool bf = g.dtype == MRI3D_BF16;
+    const MfmaFwdPlan& p = r.tiled;
+    const int wp_floats = (int)(r.wp_bytes / sizeof(float));   // fp32 images: elements; the tiled kernels' bf16 images: two elements each
+    switch (r.kernel) {
+    case FwdKernel::none: return MRI3D_ENOTSUP;
+    case FwdKernel::march: return conv_march_run(g, dgrad, false, in_v, w, bias, out_v, ws, ws_bytes, s, stat_part, sp);
+    case FwdKernel::direct:
+        hipLaunchKernelGGL(pack_w_mfma_kernel, pack_blocks(wp_floats), dim3(256), 0, s, w, wp, g.co, g.ci, dgrad ? 1 : 0, 16, r.direct.q.NTT, cdiv(Kc, 16));
+        MRI3D_DISPATCH_DTYPE(g.dtype, T, { launch_direct<T>(r.direct, (const T*)in_v, wp, bias, (T*)out_v, s); });
         return check_launch(dgrad ? "conv3d_dgrad(mfma direct)" : "conv3d_fwd(mfma direct)");
-    }
-    const bool n8 = Nc == 8 && stat_part == nullptr;   // exactly 8 output channels: the row-paired variant (10 groups per chunk)
-    if (n8) {
-        const int ptotal = p.nchunks * 10 * 256;   // 16-byte fragments x 64 lanes, in 4-byte units
-        if (g.dtype == MRI3D_BF16)
-            hipLaunchKernelGGL(pack_w_mfma_n8_kernel<bf16_t>, dim3(std::min(cdiv(2 * ptotal, 256), 2048)), dim3(256), 0, s, w,
-                               reinterpret_cast<bf16_t*>(wp), g.co, g.ci, dgrad ? 1 : 0, p.nchunks);
+    case FwdKernel::tiled_n8:
+        if (bf)
+            hipLaunchKernelGGL(pack_w_mfma_n8_kernel<bf16_t>, pack_blocks(2 * wp_floats), dim3(256), 0, s, w, reinterpret_cast<bf16_t*>(wp), g.co, g.ci,
+                               dgrad ? 1 : 0, p.nchunks);
         else
-            hipLaunchKernelGGL(pack_w_mfma_n8_kernel<float>, dim3(std::min(cdiv(ptotal, 256), 2048)), dim3(256), 0, s, w, wp, g.co,
-                               g.ci, dgrad ? 1 : 0, p.nchunks);
-    } else if (g.dtype == MRI3D_BF16)   // same image size in bytes: 256 floats == 512 bf16 per (chunk, tg, nt)
-        hipLaunchKernelGGL(pack_w_mfma_bf16_kernel, dim3(std::min(cdiv(2 * total, 256), 2048)), dim3(256), 0, s, w,
-                           reinterpret_cast<bf16_t*>(wp), g.co, g.ci, dgrad ? 1 : 0, p.NTT, p.nchunks);
-    else
-        hipLaunchKernelGGL(pack_w_mfma_kernel, dim3(std::min(cdiv(total, 256), 2048)), dim3(256), 0, s, w, wp, g.co, g.ci,
-                           dgrad ? 1 : 0, 8, p.NTT, p.nchunks);
+            hipLaunchKernelGGL(pack_w_mfma_n8_kernel<float>, pack_blocks(wp_floats), dim3(256), 0, s, w, wp, g.co, g.ci, dgrad ? 1 : 0, p.nchunks);
+        break;
+    case FwdKernel::tiled:
+        if (bf)
+            hipLaunchKernelGGL(pack_w_mfma_bf16_kernel, pack_blocks(2 * wp_floats), dim3(256), 0, s, w, reinterpret_cast<bf16_t*>(wp), g.co, g.ci,
+                               dgrad ? 1 : 0, p.NTT, p.nchunks);
+        else
+            hipLaunchKernelGGL(pack_w_mfma_kernel, pack_blocks(wp_floats), dim3(256), 0, s, w, wp, g.co, g.ci, dgrad ? 1 : 0, 8, p.NTT, p.nchunks);
+        break;
+    }
+    const bool n8 = r.kernel == FwdKernel::tiled_n8;
     const int st = p.ntiles * p.gy;
     const size_t smem = p.smem + (stat_part ? p.stat_smem : 0);
     constexpr int kMaxSmem = 2 * kStg * 256 * 16 + 4 * 8 * 16 * 2 * 8;   // two halo buffers + float64 statistics of up to 128 channels
-    MRI3D_REQUIRE(smem <= (size_t)kMaxSmem, MRI3D_ENOTSUP, "conv3d(mfma): too many output channels for fused statistics");
     // forward: the split is on the input (K) side; data gradient: on the output (N) side
     const void* x2 = dgrad ? nullptr : sp.second;
     void* y2 = dgrad ? const_cast<void*>(sp.second) : nullptr;
@@ -1117,7 +1142,7 @@ static int run_mfma_fwd(const Mri3dConvGeom& g, bool dgrad, const void* in_v, co
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                       \
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem);     \
         (void)attr;   /* once per kernel, not per launch */                                                          \
-        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), smem, s, (const T*)in_v, wp, bias, (T*)out_v, g.n, g.di,    \
+        hipLaunchKernelGGL(kern, dim3(r.grid), dim3(256), smem, s, (const T*)in_v, wp, bias, (T*)out_v, g.n, g.di,    \
                            g.hi, g.wi, Kc, in_ld, Nc, out_ld, p.NTT, p.gy, p.tilesD, p.tilesH, p.tilesW, st,         \
                            stat_part, (const T*)x2, x2_ld, ksplit, (T*)y2, y2_ld, nsplit);                           \
     }
@@ -1137,13 +1162,10 @@ int conv_mfma_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const f
     return run_mfma_fwd(g, false, x, w, bias, y, ws, ws_bytes, s);
 }
 
-// number of per-workgroup statistics partials the forward kernel writes for this geometry (0: not served by the MFMA path);
+// number of per-workgroup statistics partials the forward kernel writes for this geometry (0: no fused statistics);
 // split / second_ld: those of a split operand (conv_mfma_fwd_cat), split 0: one tensor
 int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split, int second_ld) {
-    if (fwd_takes_march(g, false, true, ConvSplit{nullptr, split, second_ld})) return conv_march_stat_blocks(g, false);
-    MfmaFwdPlan p;
-    if (!mfma_fwd_plan(g, false, p) || p.NTT > 8 || p.narrow) return 0;   // LDS statistics slots for up to 128 output channels
-    return p.grid;
+    return fwd_route(g, false, true, ConvSplit{nullptr, split, second_ld}).grid;
 }
 
 int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, double* stat_part,
@@ -1157,9 +1179,8 @@ int conv_mfma_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, cons
     return run_mfma_fwd(g, true, dy, w, bias, dx, ws, ws_bytes, s);
 }
 
-// ---- split operands (conv over cat((x, x2), channels)): served by the tiled forward kernel and the transposed-tile weight
-// gradient kernels only; `split` and the second tensor's channel count must be multiples of 16 (bf16 weight gradient: 8 for the
-// second), the second tensor 16-byte aligned with a pitch like the first's
+// ---- split operands (conv over cat((x, x2), channels)): which kernels take them is fwd_route's / mfma_wgrad_plan's answer, what the
+// operand itself must satisfy is in conv_mfma_cat_supported; the second tensor 16-byte aligned with a pitch like the first's
 int conv_mfma_fwd_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const float* w, const float* bias,
                       void* y, double* stat_part, void* ws, size_t ws_bytes, hipStream_t s) {
     return run_mfma_fwd(g, false, x, w, bias, y, ws, ws_bytes, s, stat_part, ConvSplit{x2, split, x2_ld});
@@ -2561,68 +2582,108 @@ wgrad_mfma_reduce_kernel(const float* __restrict__ part, float* __restrict__ dw,
     if (tap < 27 && ci < Ci) dw[((size_t)co * Ci + ci) * 27 + tap] = (float)s;
 }
 
+// The weight-gradient kernels of this file; mfma_wgrad_plan chooses one, and this list with the cascade there is the one
+// description of that choice.
+enum class WgradKernel {
+    cin1,      // conv_mfma_wgrad_kernel<T, 1>: the first layer (Cin = 1: 16 taps per M-tile)
+    wgrad3,    // conv_mfma_wgrad3_kernel: Cin % 8 == 0, register prefetch
+    wgrad4,    // conv_mfma_wgrad4_kernel: Cin % 16 == 0, small double-buffered tile: only for bf16 tensors the bf16 MFMA kernels cannot take
+    bf16,      // conv_mfma_wgrad_bf16_kernel: bf16 tensors, Cin % 8 == 0: a 16-channel ci-tile whose upper half may be empty
+    wgrad6,    // conv_mfma_wgrad6_kernel: fp32, Cin % 16 == 0, transposed tile: 110 / 104 / 102 TFLOP/s on 48->16 / 96->32 / 16->16 against wgrad4's 103 / 90 / 99
+    bf16t      // conv_mfma_wgrad_bf16t_kernel: bf16, marching along d
+};
+
 struct MfmaWgradPlan {
-    int CK, CIT, COB, TG, P, tilesD, tilesH, tilesW, ntiles, v2, mode8, segl;
+    WgradKernel kernel;
+    bool ci8, co8;   // wgrad6 with eight-channel operands: rows / columns 8..15 of a tile repeat the channels for another tap
+    int CK, CIT, COB, TG, P, tilesD, tilesH, tilesW, ntiles, segl;
     size_t part_floats, smem;
+    // the transposed-tile kernels are the only ones with a second operand; wgrad6 needs whole 16-channel chunks in it (the bf16
+    // kernels' 8 follow from Cin % 8 == 0 and split % 16 == 0)
+    bool takes_split() const { return kernel == WgradKernel::wgrad6 || kernel == WgradKernel::bf16 || kernel == WgradKernel::bf16t; }
+    bool second_needs_16_channels() const { return kernel == WgradKernel::wgrad6; }
+    bool needs_16_byte_alignment() const { return kernel == WgradKernel::bf16 || kernel == WgradKernel::bf16t; }
 };
 
 static bool mfma_wgrad_plan(const Mri3dConvGeom& g, MfmaWgradPlan& p) {
     if (!(g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 && g.pd == 1 && g.ph == 1 &&
           g.pw == 1 && g.dd == 1 && g.dh == 1 && g.dw == 1))
         return false;
-    // kernel: 0 = first-layer kernel (Cin = 1: 16 taps per M-tile), 1 = v3 (Cin % 8 == 0, register prefetch),
-    // 2 = v4 (Cin % 16 == 0, small double-buffered tile: only for bf16 tensors the bf16 MFMA kernel cannot take),
-    // 3 = bf16 MFMA (bf16 tensors, Cin % 8 == 0: a 16-channel ci-tile whose upper half may be empty),
-    // 4 = v6 (fp32, Cin % 16 == 0, transposed tile: 110 / 104 / 102 TFLOP/s on 48->16 / 96->32 / 16->16 against v4's 103 / 90 / 99)
-    p.v2 = (g.ci % 8 == 0 && g.co % 4 == 0 && g.y_ld % 4 == 0) ? (g.ci % 16 == 0 ? 2 : 1) : 0;
-    if (g.dtype == MRI3D_BF16 && g.ci % 8 == 0 && g.co % 8 == 0 && g.x_ld % 8 == 0 && g.y_ld % 8 == 0) p.v2 = 3;
-    if (p.v2 == 2 && g.dtype == MRI3D_F32) p.v2 = 4;
-    // v6 with eight-channel operands: 16k -> 8 (dY columns paired over kw) and 8 -> 8 (X rows paired over (kd, kh) as well)
-    p.mode8 = 0;
-    if (g.dtype == MRI3D_F32 && g.co == 8 && g.y_ld % 4 == 0 && g.x_ld % 4 == 0 && (g.ci % 16 == 0 || g.ci == 8)) {
-        p.v2 = 4;
-        p.mode8 = 2 | (g.ci == 8 ? 1 : 0);
-    }
+    const bool bf = g.dtype == MRI3D_BF16, f32 = g.dtype == MRI3D_F32;
+    const bool quads = g.ci % 8 == 0 && g.co % 4 == 0 && g.y_ld % 4 == 0;
+    p.ci8 = p.co8 = false;
+    p.segl = 0;
+    if (bf && g.ci % 8 == 0 && g.co % 8 == 0 && g.x_ld % 8 == 0 && g.y_ld % 8 == 0) {
+        p.kernel = WgradKernel::bf16;
 #ifndef MRI3D_BF16_WGRAD_MARCH_MIN_D
 #define MRI3D_BF16_WGRAD_MARCH_MIN_D 8   // (tuning builds: a huge value keeps every bf16 layer on the tile kernel)
 #endif
-    // bf16, marching along d (conv_mfma_wgrad_bf16t_kernel): when the columns x segments give every workgroup at least three
-    // tasks — segments of 40 planes, or 20 for smaller volumes (each task pays 4 staging-only fill steps; with 10-plane segments
-    // the 32 -> 32 layer at 80x96x80 ran 0.132 ms against the tile kernel's 0.122)
-    p.segl = 0;
-    if (p.v2 == 3 && g.di >= MRI3D_BF16_WGRAD_MARCH_MIN_D) {
-        const int pairs5 = cdiv(g.ci, 16) * cdiv(g.co, 16);
-        const int P5 = std::max(1, 512 / std::max(1, pairs5));
-        const int64_t cols = (int64_t)g.n * cdiv(g.hi, MTH) * cdiv(g.wi, BTW);
-        for (int sl = kMarchSeg; sl >= 20 && p.segl == 0; sl /= 2)
-            if (cols * cdiv(g.di, sl) >= (int64_t)3 * P5) p.segl = sl;
-        if (p.segl) p.v2 = 5;
-    }
-    // (The same structure for fp32 — tools/experiments/wgrad6m_kernel.hip, parity-green — measured no gain: 16 -> 16 1.20 -> 1.25 ms,
-    // 48 -> 16 3.35 -> 3.40 ms, 96 -> 32 1.83 -> 1.81 ms, only 32^3 x 512 patches 2.21 -> 2.03 ms.  The fp32 kernel is MFMA-bound and
-    // at its register limit; fewer staged bytes buy it nothing.)
-    if (p.v2 == 3 || p.v2 == 5) p.CK = 16;
-    else if (p.mode8) p.CK = 16;
-    else if (p.v2 != 0 && g.ci % 16 == 0) p.CK = 16;
-    else if (p.v2 != 0) p.CK = 8;
-    else if (g.ci == 1) {
+        // bf16, marching along d (conv_mfma_wgrad_bf16t_kernel): when the columns x segments give every workgroup at least three
+        // tasks — segments of 40 planes, or 20 for smaller volumes (each task pays 4 staging-only fill steps; with 10-plane segments
+        // the 32 -> 32 layer at 80x96x80 ran 0.132 ms against the tile kernel's 0.122)
+        if (g.di >= MRI3D_BF16_WGRAD_MARCH_MIN_D) {
+            const int pairs5 = cdiv(g.ci, 16) * cdiv(g.co, 16);
+            const int P5 = std::max(1, 512 / std::max(1, pairs5));
+            const int64_t cols = (int64_t)g.n * cdiv(g.hi, MTH) * cdiv(g.wi, BTW);
+            for (int sl = kMarchSeg; sl >= 20 && p.segl == 0; sl /= 2)
+                if (cols * cdiv(g.di, sl) >= (int64_t)3 * P5) p.segl = sl;
+            if (p.segl) p.kernel = WgradKernel::bf16t;
+        }
+        // (The same structure for fp32 — tools/experiments/wgrad6m_kernel.hip, parity-green — measured no gain: 16 -> 16 1.20 -> 1.25 ms,
+        // 48 -> 16 3.35 -> 3.40 ms, 96 -> 32 1.83 -> 1.81 ms, only 32^3 x 512 patches 2.21 -> 2.03 ms.  The fp32 kernel is MFMA-bound and
+        // at its register limit; fewer staged bytes buy it nothing.)
+    } else if (f32 && g.co == 8 && g.y_ld % 4 == 0 && g.x_ld % 4 == 0 && (g.ci % 16 == 0 || g.ci == 8)) {
+        // wgrad6 with eight-channel operands: 16k -> 8 (dY columns paired over kw) and 8 -> 8 (X rows paired over (kd, kh) as well)
+        p.kernel = WgradKernel::wgrad6;
+        p.co8 = true, p.ci8 = g.ci == 8;
+    } else if (quads && g.ci % 16 == 0) {
+        p.kernel = f32 ? WgradKernel::wgrad6 : WgradKernel::wgrad4;
+    } else if (quads) {
+        p.kernel = WgradKernel::wgrad3;
+    } else if (g.ci == 1) {
         // Conv3d(1, 8, 3) and the 1 -> 1 stencil have direct kernels in conv_generic.hip (conv_cin1_wgrad_kernel: 0.25 vs
         // 0.47 ms on 2 x 160x192x160; conv_c1c1_wgrad_kernel); Co = 16 stays here (0.22 vs 0.24 ms on 16 x 64^3)
         if ((g.co == 8 && g.y_ld % 4 == 0) || g.co == 1) return false;
-        p.CK = 1;
+        p.kernel = WgradKernel::cin1;
     } else return false;
+    // per kernel: channels per chunk, tap groups, output tile (tasks = tiles), dynamic LDS without the reduction buffer
+    int td = WTD, th = WTH, tw = WTW;
+    size_t lds = 0;
+    p.CK = 16;
+    p.TG = wg_tap_groups(16);
+    switch (p.kernel) {
+    case WgradKernel::cin1:
+        p.CK = 1, p.TG = wg_tap_groups(1);
+        lds = ((((size_t)WHVOX + 3) & ~(size_t)3) + (size_t)WVOX * 16) * sizeof(float);
+        break;
+    case WgradKernel::wgrad3:
+        p.CK = 8, p.TG = wg_tap_groups(8);
+        lds = ((size_t)((WHVOX * (8 / 4) + 255) / 256) * 256 * 4 + (size_t)WVOX * 16) * sizeof(float);
+        break;
+    case WgradKernel::wgrad4:
+        th = V4TH;
+        lds = ((size_t)2 * V4XBUF + 2 * V4YBUF) * sizeof(float);
+        break;
+    case WgradKernel::bf16:
+        td = BTD, th = BTH, tw = BTW;
+        lds = (size_t)BXS + BYS + BYH;
+        break;
+    case WgradKernel::wgrad6:
+        p.TG = wg6_groups(p.ci8, p.co8);
+        td = BTD, th = BTH, tw = FTW;
+        lds = (size_t)BXS + BYS + BYH;
+        break;
+    case WgradKernel::bf16t:   // tasks = (sample, segment of d, column): tilesD holds the segments
+        td = p.segl, th = MTH, tw = BTW;
+        lds = (size_t)TLDS;
+        break;
+    }
     if (p.CK >= 4 && g.x_ld % 4 != 0) return false;
     p.CIT = cdiv(g.ci, p.CK);
     p.COB = cdiv(g.co, 16);
-    p.TG = p.mode8 ? wg6_groups(p.mode8 & 1, p.mode8 & 2) : wg_tap_groups(p.CK);
-    p.tilesD = cdiv(g.di, p.v2 >= 3 ? BTD : WTD);
-    p.tilesH = cdiv(g.hi, p.v2 >= 3 ? BTH : (p.v2 == 2 ? V4TH : WTH));
-    p.tilesW = cdiv(g.wi, p.v2 == 3 ? BTW : (p.v2 == 4 ? FTW : WTW));
-    if (p.v2 == 5) {   // tasks = (sample, segment of d, column): tilesD holds the segments
-        p.tilesD = cdiv(g.di, p.segl);
-        p.tilesH = cdiv(g.hi, MTH);
-        p.tilesW = cdiv(g.wi, BTW);
-    }
+    p.tilesD = cdiv(g.di, td);
+    p.tilesH = cdiv(g.hi, th);
+    p.tilesW = cdiv(g.wi, tw);
     int64_t nt = (int64_t)g.n * p.tilesD * p.tilesH * p.tilesW;
     if (nt > 0x7fffffff) return false;
     p.ntiles = (int)nt;
@@ -2633,170 +2694,92 @@ static bool mfma_wgrad_plan(const Mri3dConvGeom& g, MfmaWgradPlan& p) {
     if (P > p.ntiles) P = p.ntiles;
     p.P = P;
     p.part_floats = (size_t)P * p.CIT * p.COB * (p.TG + 1) * 256;
-    size_t xs = ((size_t)WHVOX * p.CK + 3) & ~(size_t)3;
-    size_t red = (size_t)(p.TG + 1) * 256;
-    size_t tile_floats = xs + (size_t)WVOX * 16;
-    p.smem = (tile_floats > red ? tile_floats : red) * sizeof(float);
-    if (p.v2 == 1) {
-        size_t xbuf = (size_t)((WHVOX * (p.CK / 4) + 255) / 256) * 256 * 4;
-        p.smem = std::max<size_t>(xbuf + (size_t)WVOX * 16, red) * sizeof(float);
-    } else if (p.v2 == 2) {
-        p.smem = std::max<size_t>((size_t)2 * V4XBUF + 2 * V4YBUF, red) * sizeof(float);
-    } else if (p.v2 == 5) {
-        p.smem = std::max<size_t>((size_t)TLDS, red * sizeof(float));
-    } else if (p.v2 >= 3) {
-        p.smem = std::max<size_t>((size_t)BXS + BYS + BYH, red * sizeof(float));
-    }
+    p.smem = std::max(lds, (size_t)(p.TG + 1) * 256 * sizeof(float));   // the waves' partials are combined through the same LDS
     return true;
 }
 
+// the split operand's own divisibility checks, then: does a kernel take it (fwd_route / mfma_wgrad_plan)
 bool conv_mfma_cat_supported(const Mri3dConvGeom& g, int split, int second_ld, int pass) {
     const bool bf = g.dtype == MRI3D_BF16;
     if (split <= 0 || split >= g.ci || split % 16 != 0 || second_ld % (bf ? 8 : 4) != 0 || second_ld < g.ci - split) return false;
-    if (direct_only(g)) return false;
-    MfmaFwdPlan p;
+    const ConvSplit sp{nullptr, split, second_ld};
     MfmaWgradPlan q;
-    if (pass == MRI3D_PASS_FWD) return mfma_fwd_plan(g, false, p) && p.small != 1 && (g.ci - split) % 8 == 0;
-    if (pass == MRI3D_PASS_DGRAD) return mfma_fwd_plan(g, true, p) && p.small != 1 && (g.ci - split) % 4 == 0;   // N side: 16-channel tiles
-    if (pass == MRI3D_PASS_WGRAD) return mfma_wgrad_plan(g, q) && (q.v2 == 4 ? (g.ci - split) % 16 == 0 : (q.v2 == 3 || q.v2 == 5));
+    if (pass == MRI3D_PASS_FWD) return (g.ci - split) % 8 == 0 && fwd_route(g, false, false, sp).kernel != FwdKernel::none;
+    if (pass == MRI3D_PASS_DGRAD) return (g.ci - split) % 4 == 0 && fwd_route(g, true, false, sp).kernel != FwdKernel::none;   // N side: 16-channel tiles
+    if (pass == MRI3D_PASS_WGRAD) return mfma_wgrad_plan(g, q) && q.takes_split() && (!q.second_needs_16_channels() || (g.ci - split) % 16 == 0);
     return false;
 }
 
 bool conv_mfma_supported(const Mri3dConvGeom& g, int pass) {
-    MfmaFwdPlan p;
     MfmaWgradPlan q;
-    DirectPlan dp;
-    if (pass != MRI3D_PASS_WGRAD && direct_only(g)) return direct_plan(g, pass == MRI3D_PASS_DGRAD, dp);
-    if (pass == MRI3D_PASS_FWD) return mfma_fwd_plan(g, false, p);
-    if (pass == MRI3D_PASS_DGRAD) return mfma_fwd_plan(g, true, p);
-    if (pass == MRI3D_PASS_WGRAD) return mfma_wgrad_plan(g, q);
-    return false;
+    if (pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD) return fwd_route(g, pass == MRI3D_PASS_DGRAD, false, ConvSplit{}).kernel != FwdKernel::none;
+    return pass == MRI3D_PASS_WGRAD && mfma_wgrad_plan(g, q);
 }
 
+// Forward / data gradient: the caller asks before it knows whether statistics or a split operand will be requested, and
+// mri3d_conv3d_{fwd,dgrad}_march is documented to size its workspace with this query too.  So the answer is not the need of one
+// route but the maximum over the kernel families that accept the geometry at all: the tiled kernel's image where mfma_fwd_plan
+// accepts (also for narrow volumes, which no route takes there), the LDS-free kernel's where a direct route exists, and the forced
+// marching plan's.
 size_t conv_mfma_workspace_bytes(const Mri3dConvGeom& g, int pass) {
     MfmaFwdPlan p;
     MfmaWgradPlan q;
     DirectPlan dp;
-    if (pass != MRI3D_PASS_WGRAD && direct_only(g)) return direct_plan(g, pass == MRI3D_PASS_DGRAD, dp) ? dp.wp_floats * sizeof(float) : 0;
-    if (pass == MRI3D_PASS_FWD && mfma_fwd_plan(g, false, p))
-        return std::max(std::max(p.wp_floats, p.s_wp_floats) * sizeof(float), conv_march_workspace_bytes(g, false));
-    if (pass == MRI3D_PASS_DGRAD && mfma_fwd_plan(g, true, p))
-        return std::max(std::max(p.wp_floats, p.s_wp_floats) * sizeof(float), conv_march_workspace_bytes(g, true));
-    if (pass == MRI3D_PASS_WGRAD && mfma_wgrad_plan(g, q)) return q.part_floats * sizeof(float);
-    return 0;
+    if (pass == MRI3D_PASS_WGRAD) return mfma_wgrad_plan(g, q) ? q.part_floats * sizeof(float) : 0;
+    if (!conv_mfma_supported(g, pass)) return 0;
+    const bool dgrad = pass == MRI3D_PASS_DGRAD;
+    size_t bytes = conv_march_needs(g, dgrad, false, true).wp_bytes;
+    const bool tiled_ok = mfma_fwd_plan(g, dgrad, p);
+    if (tiled_ok) bytes = std::max(bytes, p.wp_floats * sizeof(float));
+    if (direct_use(g, dgrad, tiled_ok ? &p : nullptr, dp) != DirectUse::no) bytes = std::max(bytes, dp.wp_floats * sizeof(float));
+    return bytes;
 }
 
-// set a kernel's dynamic-LDS limit once (not per launch)
-#define MRI3D_SET_SMEM_ONCE(kern, bytes)                                                                              \
-    do {                                                                                                              \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                      \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
-        (void)attr_;                                                                                                  \
-    } while (0)
+// One launch for every weight-gradient kernel: the common arguments, then the kernel's own (`tail`).  The kernel's dynamic-LDS
+// limit is set once per kernel (the static of this instantiation), not per launch.
+template <auto kern, typename T, typename... Tail>
+static void launch_wgrad(const MfmaWgradPlan& p, const Mri3dConvGeom& g, const T* x, const T* dy, float* part, hipStream_t s, Tail... tail) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.smem);
+    (void)attr;
+    hipLaunchKernelGGL(kern, dim3(p.P, p.CIT, p.COB), dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co, g.y_ld,
+                       p.tilesD, p.tilesH, p.tilesW, p.ntiles, tail...);
+}
 
+// Calls f with std::true_type / std::false_type for `bias`: the kernel templates reserve the bias accumulator slot in the partial
+// layout (TGA = TG + 1) only with BIAS.
+template <typename F>
+static void with_bias(bool bias, F f) {
+    if (bias) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// `if constexpr` keeps the kernels of the other storage type from being instantiated.  The bias is chosen per kernel, and the
+// cases stand in the order in which the kernels have always been instantiated: that is their order in the code object.
 template <typename T>
-static void launch_mfma_wgrad_cin1(const MfmaWgradPlan& p, const Mri3dConvGeom& g, const T* x, const T* dy,
-                                   float* part, bool bias, hipStream_t s) {
-    dim3 grid(p.P, p.CIT, p.COB);
-    if (bias) {
-        hipLaunchKernelGGL((conv_mfma_wgrad_kernel<T, 1, true>), grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi,
-                           g.ci, g.x_ld, g.co, g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles);
-    } else {
-        hipLaunchKernelGGL((conv_mfma_wgrad_kernel<T, 1, false>), grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi,
-                           g.ci, g.x_ld, g.co, g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles);
+static void run_mfma_wgrad(const MfmaWgradPlan& p, const Mri3dConvGeom& g, const T* x, const T* dy, float* part, bool bias, hipStream_t s,
+                           const ConvSplit& sp) {
+    [[maybe_unused]] const T* x2 = static_cast<const T*>(sp.second);
+    switch (p.kernel) {
+    case WgradKernel::bf16t:
+        if constexpr (sizeof(T) == 2) with_bias(bias, [&](auto B) { launch_wgrad<conv_mfma_wgrad_bf16t_kernel<B.value>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split, p.segl); });
+        break;
+    case WgradKernel::bf16:
+        if constexpr (sizeof(T) == 2) with_bias(bias, [&](auto B) { launch_wgrad<conv_mfma_wgrad_bf16_kernel<B.value>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split); });
+        break;
+    case WgradKernel::wgrad6:
+        if constexpr (sizeof(T) == 4) with_bias(bias, [&](auto B) {
+            if (p.ci8 && p.co8) launch_wgrad<conv_mfma_wgrad6_kernel<B.value, true, true>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split);
+            else if (p.co8) launch_wgrad<conv_mfma_wgrad6_kernel<B.value, false, true>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split);
+            else if (p.ci8) launch_wgrad<conv_mfma_wgrad6_kernel<B.value, true, false>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split);
+            else launch_wgrad<conv_mfma_wgrad6_kernel<B.value, false, false>>(p, g, x, dy, part, s, x2, sp.second_ld, sp.split);
+        });
+        break;
+    case WgradKernel::wgrad4:   // fp32 tensors with Cin % 16 == 0 always take wgrad6
+        if constexpr (sizeof(T) == 2) with_bias(bias, [&](auto B) { launch_wgrad<conv_mfma_wgrad4_kernel<T, B.value>>(p, g, x, dy, part, s); });
+        break;
+    case WgradKernel::wgrad3: with_bias(bias, [&](auto B) { launch_wgrad<conv_mfma_wgrad3_kernel<T, 8, B.value>>(p, g, x, dy, part, s); }); break;
+    case WgradKernel::cin1: with_bias(bias, [&](auto B) { launch_wgrad<conv_mfma_wgrad_kernel<T, 1, B.value>>(p, g, x, dy, part, s); }); break;
     }
-}
-
-template <typename T>
-static void run_mfma_wgrad(const MfmaWgradPlan& p, const Mri3dConvGeom& g, const T* x, const T* dy, float* part, bool bias,
-                           hipStream_t s, ConvSplit sp = ConvSplit{nullptr, 0, 0}) {
-    // the kernel template reserves the bias accumulator slot in the partial layout (TGA = TG + 1) only when BIAS
-    if (p.v2 == 5) {
-        if constexpr (sizeof(T) == 2) {
-            dim3 grid(p.P, p.CIT, p.COB);
-#define MRI3D_WGM(Bv)                                                                                                 \
-    {                                                                                                                 \
-        auto kern = conv_mfma_wgrad_bf16t_kernel<Bv>;                                                                 \
-        MRI3D_SET_SMEM_ONCE(kern, p.smem);                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co,  \
-                           g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles, (const bf16_t*)sp.second, sp.second_ld,    \
-                           sp.split, p.segl);                                                                         \
-    }
-            if (bias) MRI3D_WGM(true) else MRI3D_WGM(false)
-#undef MRI3D_WGM
-        }
-    } else if (p.v2 == 3) {
-        if constexpr (sizeof(T) == 2) {
-            dim3 grid(p.P, p.CIT, p.COB);
-#define MRI3D_WGB(Bv)                                                                                                 \
-    {                                                                                                                 \
-        auto kern = conv_mfma_wgrad_bf16_kernel<Bv>;                                                                  \
-        MRI3D_SET_SMEM_ONCE(kern, p.smem);                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co,  \
-                           g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles, (const bf16_t*)sp.second, sp.second_ld,    \
-                           sp.split);                                                                                 \
-    }
-            if (bias) MRI3D_WGB(true) else MRI3D_WGB(false)
-#undef MRI3D_WGB
-        }
-    } else if (p.v2 == 4) {
-        if constexpr (sizeof(T) == 4) {
-            dim3 grid(p.P, p.CIT, p.COB);
-#define MRI3D_WG6(Bv)                                                                                                 \
-    if (p.mode8 == 3) MRI3D_WG6M(Bv, true, true) else if (p.mode8 == 2) MRI3D_WG6M(Bv, false, true) else if (p.mode8 == 1) MRI3D_WG6M(Bv, true, false) else MRI3D_WG6M(Bv, false, false)
-#define MRI3D_WG6M(Bv, I8, O8)                                                                                        \
-    {                                                                                                                 \
-        auto kern = conv_mfma_wgrad6_kernel<Bv, I8, O8>;                                                              \
-        MRI3D_SET_SMEM_ONCE(kern, p.smem);                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co,  \
-                           g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles, (const float*)sp.second, sp.second_ld,     \
-                           sp.split);                                                                                 \
-    }
-            if (bias) { MRI3D_WG6(true) } else { MRI3D_WG6(false) }
-#undef MRI3D_WG6
-#undef MRI3D_WG6M
-        }
-    } else if (p.v2 == 2) {
-      if constexpr (sizeof(T) == 2) {   // fp32 tensors with Cin % 16 == 0 always take v6
-        dim3 grid(p.P, p.CIT, p.COB);
-#define MRI3D_WG4(Bv)                                                                                                 \
-    {                                                                                                                 \
-        auto kern = conv_mfma_wgrad4_kernel<T, Bv>;                                                                   \
-        MRI3D_SET_SMEM_ONCE(kern, p.smem);                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co,  \
-                           g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles);                                           \
-    }
-        if (bias) MRI3D_WG4(true) else MRI3D_WG4(false)
-#undef MRI3D_WG4
-      }
-    } else if (p.v2 == 1) {
-        dim3 grid(p.P, p.CIT, p.COB);
-#define MRI3D_WG3(CKv, Bv)                                                                                            \
-    {                                                                                                                 \
-        auto kern = conv_mfma_wgrad3_kernel<T, CKv, Bv>;                                                              \
-        MRI3D_SET_SMEM_ONCE(kern, p.smem);                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(256), p.smem, s, x, dy, part, g.n, g.di, g.hi, g.wi, g.ci, g.x_ld, g.co,  \
-                           g.y_ld, p.tilesD, p.tilesH, p.tilesW, p.ntiles);                                           \
-    }
-        if (bias) MRI3D_WG3(8, true)
-        else MRI3D_WG3(8, false)
-#undef MRI3D_WG3
-    } else {
-        launch_mfma_wgrad_cin1<T>(p, g, x, dy, part, bias, s);
-    }
-}
-
-static int run_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws, size_t ws_bytes,
-                     hipStream_t s, ConvSplit sp);
-
-int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
-                    size_t ws_bytes, hipStream_t s) {
-    return run_wgrad(g, x, dy, dw, dbias, ws, ws_bytes, s, ConvSplit{nullptr, 0, 0});
-}
-
-int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
-                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s) {
-    return run_wgrad(g, x, dy, dw, dbias, ws, ws_bytes, s, ConvSplit{x2, split, x2_ld});
 }
 
 static int run_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws, size_t ws_bytes,
@@ -2806,17 +2789,26 @@ static int run_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, floa
     MRI3D_REQUIRE(ws && ws_bytes >= p.part_floats * sizeof(float), MRI3D_EWORKSPACE,
                   "conv3d_wgrad(mfma): workspace %zu < %zu", ws_bytes, p.part_floats * sizeof(float));
     MRI3D_REQUIRE(aligned_vec4(g.dtype, x, dy), MRI3D_EINVAL, "conv3d_wgrad(mfma): x/dy must be aligned to 4 elements");
-    MRI3D_REQUIRE((p.v2 != 3 && p.v2 != 5) || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) == 0, MRI3D_EINVAL,
-                  "conv3d_wgrad(bf16 mfma): x/dy must be 16-byte aligned");
+    MRI3D_REQUIRE(!p.needs_16_byte_alignment() || aligned16(x, dy), MRI3D_EINVAL, "conv3d_wgrad(bf16 mfma): x/dy must be 16-byte aligned");
     float* part = static_cast<float*>(ws);
     const bool bias = dbias != nullptr;
-    MRI3D_REQUIRE(sp.second == nullptr || p.v2 >= 3, MRI3D_ENOTSUP, "conv3d_wgrad(mfma): split operands need the transposed-tile kernels");
+    MRI3D_REQUIRE(sp.second == nullptr || p.takes_split(), MRI3D_ENOTSUP, "conv3d_wgrad(mfma): split operands need the transposed-tile kernels");
     MRI3D_DISPATCH_DTYPE(g.dtype, T, { run_mfma_wgrad<T>(p, g, static_cast<const T*>(x), static_cast<const T*>(dy), part, bias, s, sp); });
     const int TGA = p.TG + (bias ? 1 : 0);
     const int nelem = p.CIT * p.COB * TGA * 256;
     hipLaunchKernelGGL(wgrad_mfma_reduce_kernel, dim3(cdiv(nelem, 64)), dim3(256), 0, s, part, dw, dbias, p.P, p.CIT,
-                       p.COB, p.CK, p.TG, TGA, g.ci, g.co, p.mode8);
+                       p.COB, p.CK, p.TG, TGA, g.ci, g.co, (p.ci8 ? 1 : 0) | (p.co8 ? 2 : 0));
     return check_launch("conv3d_wgrad(mfma)");
+}
+
+int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
+                    size_t ws_bytes, hipStream_t s) {
+    return run_wgrad(g, x, dy, dw, dbias, ws, ws_bytes, s, ConvSplit{});
+}
+
+int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
+                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s) {
+    return run_wgrad(g, x, dy, dw, dbias, ws, ws_bytes, s, ConvSplit{x2, split, x2_ld});
 }
 
 }  // namespace mri3d

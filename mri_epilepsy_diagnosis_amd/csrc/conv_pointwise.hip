@@ -7,6 +7,7 @@
 //   wgrad: lane = (voxel lane, 4-channel quad of x) with a 4 x CO register tile, block-reduced through LDS in double,
 //          one partial per block, fixed-order final sum (deterministic).
 #include "common.h"
+#include "conv_backends.h"
 
 namespace mri3d {
 

@@ -35,11 +35,12 @@ int main() {
     EXPECT(mri3d_version() >= 100);
     char fake[64];                       // a non-null pointer that is never dereferenced on the host
     void* P = fake;
+    alignas(16) static char A[64];       // the same, 16-byte aligned: passes the MFMA paths' alignment checks
 
     // ---- conv: workspace queries over a sweep of geometries (plan functions of every kernel family), incl. degenerate ones
     const int chans[] = {1, 2, 3, 4, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192};
     const int sizes[][3] = {{1, 1, 1}, {2, 3, 5}, {8, 8, 8}, {10, 12, 10}, {32, 32, 32}, {80, 96, 80}, {160, 192, 160}, {192, 192, 192}};
-    size_t checked = 0;
+    size_t checked = 0, stats_routes = 0;
     for (int dtype = 0; dtype < 2; ++dtype)
         for (int ci : chans)
             for (int co : chans)
@@ -56,9 +57,15 @@ int main() {
                                 EXPECT(ws % 256 == 0 && ws < ((size_t)1 << 40));
                                 ++checked;
                             }
+                            // where the query promises fused statistics, the launch path reaches the same route: with a 16-byte
+                            // workspace it stops at the packed-weight image (always larger), neither "not served" nor a launch
+                            if (mri3d_conv3d_fwd_stats_blocks(&g) > 0) {
+                                EXPECT(mri3d_conv3d_fwd_stats(&g, A, A, A, A, (double*)A, A, 16, nullptr) == MRI3D_EWORKSPACE);
+                                ++stats_routes;
+                            }
                         }
                     }
-    EXPECT(checked > 10000);
+    EXPECT(checked > 10000 && stats_routes > 1000);
     EXPECT(mri3d_conv3d_workspace_bytes(nullptr, 0) == 0);
 
     // ---- conv: argument validation (every branch returns before a launch)
@@ -91,6 +98,14 @@ int main() {
 
     // ---- split operands (conv over cat((x, x2))): the support query over a sweep, refusals without a launch
     {
+        // the *_cat entry point of a pass with a 16-byte workspace: MRI3D_EWORKSPACE exactly where the support query says 1 (the
+        // launch path found a kernel and stopped at its workspace), MRI3D_ENOTSUP where it says 0; never a launch
+        auto cat_agrees = [&](const Mri3dConvGeom& c, int split, int ld, int pass) {
+            const int rc = pass == 0   ? mri3d_conv3d_fwd_cat(&c, A, A, split, ld, A, A, A, nullptr, A, 16, nullptr)
+                           : pass == 1 ? mri3d_conv3d_dgrad_cat(&c, A, A, A, A, split, ld, A, 16, nullptr)
+                                       : mri3d_conv3d_wgrad_cat(&c, A, A, split, ld, A, A, A, A, 16, nullptr);
+            return rc == (mri3d_conv3d_cat_supported(&c, split, ld, pass) == 1 ? MRI3D_EWORKSPACE : MRI3D_ENOTSUP);
+        };
         int served = 0;
         for (int dtype = 0; dtype < 2; ++dtype)
             for (int ca : {8, 16, 32, 48})
@@ -98,7 +113,10 @@ int main() {
                     for (int sz : {6, 40, 160}) {
                         Mri3dConvGeom c = conv(2, sz, sz + 8, sz, ca + cb, 16, 3, 1, 1, 1, dtype, 0, 0);
                         c.x_ld = ca;
-                        for (int pass = 0; pass < 3; ++pass) served += mri3d_conv3d_cat_supported(&c, ca, cb, pass);
+                        for (int pass = 0; pass < 3; ++pass) {
+                            served += mri3d_conv3d_cat_supported(&c, ca, cb, pass);
+                            for (int extra : {0, 4, 8, 12}) EXPECT(cat_agrees(c, ca, cb + extra, pass));
+                        }
                         EXPECT(mri3d_conv3d_cat_supported(&c, 0, cb, 0) == 0);          // no first part
                         EXPECT(mri3d_conv3d_cat_supported(&c, ca + cb, cb, 0) == 0);    // no second part
                         EXPECT(mri3d_conv3d_fwd_cat_stats_blocks(&c, 0, cb) == 0);
@@ -127,6 +145,7 @@ int main() {
                             const int blocks = mri3d_conv3d_fwd_cat_stats_blocks(&c, 16, ld);
                             const int supported = mri3d_conv3d_cat_supported(&c, 16, ld, 0);
                             EXPECT((blocks > 0) == (supported == 1));
+                            for (int pass = 0; pass < 3; ++pass) EXPECT(cat_agrees(c, 16, ld, pass));
                             if (!supported) continue;
                             ++swept;
                             Mri3dConvGeom whole = c;
