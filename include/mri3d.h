@@ -77,6 +77,25 @@ int mri3d_conv3d_dgrad(const Mri3dConvGeom* g, const void* dy, const void* w, co
 int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, void* dw, void* dbias,
                        void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
+/* WHICH KERNEL the entry points above (split == 0) or the *_cat entry points below (split > 0, second_ld = pitch of the second
+ * tensor) launch for this geometry.  Host only: no device is needed, nothing is launched; the entry points take their backend
+ * from the same decision.  pass: MRI3D_PASS_*; stats != 0: the forward with fused statistics (mri3d_conv3d_fwd_stats, or a
+ * non-NULL stat_partials of mri3d_conv3d_fwd_cat); bias != 0: a bias pointer is passed; align: the largest power of two <= 16
+ * that divides the base address of every tensor and of the workspace.  name (at least 32 bytes) receives, as a C string:
+ *   "none"       the entry point refuses (MRI3D_ENOTSUP): only with stats or a split
+ *   "generic"    csrc/conv_generic.hip         "pointwise"  csrc/conv_pointwise.hip (1x1x1)
+ *   forward / data gradient on the 3x3x3 MFMA kernels — the kernel, then the template arguments that select code in it:
+ *   "march[ stats][ bias]"                conv_march_kernel<T, STATS, BIAS>
+ *   "direct nt{1,2,4} mode{0,1} split{0,1}"  conv_mfma_direct_kernel<T, NT, MODE, SPLIT> (mode 1: strided data gradient; split 1: the
+ *                                         taps of a unit spread over the workgroup's waves — not a split operand)
+ *   "tiled nt{1,2}[ stats]"               conv_mfma_fwd2_kernel<T, NT, STATS, false>
+ *   "tiled_n8"                            conv_mfma_fwd2_kernel<T, 1, false, true> (exactly eight output channels)
+ *   weight gradient: "cin1", "wgrad3", "wgrad4", "bf16", "bf16t", "wgrad6[ ci8][ co8]"  (conv_mfma_wgrad*_kernel)
+ * Grids, tile counts and other run-time arguments are not part of a name.  The names are stable: the test suite pins its parity
+ * cases to them. */
+int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
+                       int32_t align, char* name, size_t name_bytes);
+
 /* Convolution over torch.cat((x, x2), dim=1) WITHOUT the concatenation — `unet.UNet`'s decoder, x = cat((skip, upsampled))
  * in front of its first ConvolutionalBlock (segmentation/routine.py:346-356 -> unet DecodingBlock.forward).  g describes the
  * concatenated convolution (g->ci = all input channels, g->x_ld = voxel pitch of x); channels [0, split) are read from x,

@@ -39,6 +39,41 @@ static int conv_check(const Mri3dConvGeom* g, const char* who, int first_ci = -1
     return MRI3D_OK;
 }
 
+// THE backend decision of the Conv3d entry points: mri3d_conv3d_fwd / _fwd_stats / _dgrad / _wgrad (split == 0), the *_cat entry
+// points (split > 0) and the route query mri3d_conv3d_route all read it, so the query names what the entry point launches.
+// Forward tries the MFMA file before the pointwise kernels, the gradients the pointwise kernels first; whatever neither takes goes
+// to the generic kernels.  Fused statistics and split operands exist only in the MFMA file: `none` = the entry point refuses.
+// align_mfma: common alignment in bytes (ptr_align) of the tensors and the workspace the MFMA kernels move in 16-byte pieces;
+// align_pw: that of the tensor the pointwise kernels access four elements at a time.
+enum class ConvBackend { none, generic, pointwise, mfma };
+
+// largest power of two <= 16 that divides every given address (a null pointer divides by everything)
+static int ptr_align(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                           reinterpret_cast<uintptr_t>(d) | 16;
+    return (int)(bits & (~bits + 1));
+}
+
+static ConvBackend conv_backend(const Mri3dConvGeom& g, int pass, bool stats, int split, int second_ld, int align_mfma, int align_pw) {
+    const bool mfma_aligned = align_mfma >= 16;                                  // aligned16
+    const bool pw_aligned = align_pw >= (g.dtype == MRI3D_BF16 ? 8 : 16);        // aligned_vec4
+    if (split > 0) {
+        if (!(conv_mfma_cat_supported(g, split, second_ld, pass) && mfma_aligned)) return ConvBackend::none;
+        return (stats && conv_mfma_fwd_stat_blocks(g, split, second_ld) <= 0) ? ConvBackend::none : ConvBackend::mfma;
+    }
+    if (stats)
+        return (pass == MRI3D_PASS_FWD && conv_mfma_supported(g, MRI3D_PASS_FWD) && conv_mfma_fwd_stat_blocks(g) > 0 && mfma_aligned)
+                   ? ConvBackend::mfma : ConvBackend::none;
+    if (pass == MRI3D_PASS_FWD) {
+        if (conv_mfma_supported(g, pass) && mfma_aligned) return ConvBackend::mfma;
+        if (conv_pointwise_supported(g, pass) && pw_aligned) return ConvBackend::pointwise;
+        return ConvBackend::generic;
+    }
+    if (conv_pointwise_supported(g, pass) && pw_aligned) return ConvBackend::pointwise;
+    if (conv_mfma_supported(g, pass) && mfma_aligned) return ConvBackend::mfma;
+    return ConvBackend::generic;
+}
+
 }  // namespace mri3d
 
 using namespace mri3d;
@@ -61,11 +96,11 @@ extern "C" int mri3d_conv3d_fwd(const Mri3dConvGeom* g, const void* x, const voi
     if (rc) return rc;
     MRI3D_REQUIRE(x && w && y, MRI3D_EINVAL, "conv3d_fwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (conv_mfma_supported(*g, MRI3D_PASS_FWD) && aligned16(x, y, workspace))
-        return conv_mfma_fwd(*g, x, (const float*)w, (const float*)bias, y, workspace, ws_bytes, s);
-    if (conv_pointwise_supported(*g, MRI3D_PASS_FWD) && aligned_vec4(g->dtype, x))
-        return conv_pointwise_fwd(*g, x, (const float*)w, (const float*)bias, y, s);
-    return conv_generic_fwd(*g, x, (const float*)w, (const float*)bias, y, workspace, ws_bytes, s);
+    switch (conv_backend(*g, MRI3D_PASS_FWD, false, 0, 0, ptr_align(x, y, workspace), ptr_align(x))) {
+    case ConvBackend::mfma: return conv_mfma_fwd(*g, x, (const float*)w, (const float*)bias, y, workspace, ws_bytes, s);
+    case ConvBackend::pointwise: return conv_pointwise_fwd(*g, x, (const float*)w, (const float*)bias, y, s);
+    default: return conv_generic_fwd(*g, x, (const float*)w, (const float*)bias, y, workspace, ws_bytes, s);
+    }
 }
 
 extern "C" int32_t mri3d_conv3d_fwd_stats_blocks(const Mri3dConvGeom* g) {
@@ -78,7 +113,7 @@ extern "C" int mri3d_conv3d_fwd_stats(const Mri3dConvGeom* g, const void* x, con
     int rc = conv_check(g, "conv3d_fwd_stats");
     if (rc) return rc;
     MRI3D_REQUIRE(x && w && y && stat_partials, MRI3D_EINVAL, "conv3d_fwd_stats: null pointer");
-    MRI3D_REQUIRE(conv_mfma_supported(*g, MRI3D_PASS_FWD) && conv_mfma_fwd_stat_blocks(*g) > 0 && aligned16(x, y, workspace),
+    MRI3D_REQUIRE(conv_backend(*g, MRI3D_PASS_FWD, true, 0, 0, ptr_align(x, y, workspace), ptr_align(x)) == ConvBackend::mfma,
                   MRI3D_ENOTSUP, "conv3d_fwd_stats: geometry not served by the MFMA forward kernel (query mri3d_conv3d_fwd_stats_blocks)");
     return conv_mfma_fwd_stats(*g, x, (const float*)w, (const float*)bias, y, stat_partials, workspace, ws_bytes,
                                static_cast<hipStream_t>(stream));
@@ -90,11 +125,11 @@ extern "C" int mri3d_conv3d_dgrad(const Mri3dConvGeom* g, const void* dy, const 
     if (rc) return rc;
     MRI3D_REQUIRE(dy && w && dx, MRI3D_EINVAL, "conv3d_dgrad: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (conv_pointwise_supported(*g, MRI3D_PASS_DGRAD) && aligned_vec4(g->dtype, dx))
-        return conv_pointwise_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, s);
-    if (conv_mfma_supported(*g, MRI3D_PASS_DGRAD) && aligned16(dy, dx, workspace))
-        return conv_mfma_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, workspace, ws_bytes, s);
-    return conv_generic_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, workspace, ws_bytes, s);
+    switch (conv_backend(*g, MRI3D_PASS_DGRAD, false, 0, 0, ptr_align(dy, dx, workspace), ptr_align(dx))) {
+    case ConvBackend::pointwise: return conv_pointwise_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, s);
+    case ConvBackend::mfma: return conv_mfma_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, workspace, ws_bytes, s);
+    default: return conv_generic_dgrad(*g, dy, (const float*)w, (const float*)bias, dx, workspace, ws_bytes, s);
+    }
 }
 
 // ---- convolution over torch.cat((x, x2), dim=1) without the concatenation (unet.UNet decoder: cat((skip, upsampled)))
@@ -114,7 +149,7 @@ extern "C" int mri3d_conv3d_fwd_cat(const Mri3dConvGeom* g, const void* x, const
     int rc = conv_check(g, "conv3d_fwd_cat", split);
     if (rc) return rc;
     MRI3D_REQUIRE(x && x2 && w && y, MRI3D_EINVAL, "conv3d_fwd_cat: null pointer");
-    MRI3D_REQUIRE(conv_mfma_cat_supported(*g, split, x2_ld, MRI3D_PASS_FWD) && aligned16(x, y, workspace) && aligned16(x2),
+    MRI3D_REQUIRE(conv_backend(*g, MRI3D_PASS_FWD, false, split, x2_ld, ptr_align(x, y, workspace, x2), 0) == ConvBackend::mfma,
                   MRI3D_ENOTSUP, "conv3d_fwd_cat: geometry / alignment not served (query mri3d_conv3d_cat_supported)");
     MRI3D_REQUIRE(stat_partials == nullptr || conv_mfma_fwd_stat_blocks(*g, split, x2_ld) > 0, MRI3D_ENOTSUP,
                   "conv3d_fwd_cat: no fused statistics for this geometry (query mri3d_conv3d_fwd_cat_stats_blocks)");
@@ -127,7 +162,7 @@ extern "C" int mri3d_conv3d_dgrad_cat(const Mri3dConvGeom* g, const void* dy, co
     int rc = conv_check(g, "conv3d_dgrad_cat", split);
     if (rc) return rc;
     MRI3D_REQUIRE(dy && w && dx && dx2, MRI3D_EINVAL, "conv3d_dgrad_cat: null pointer");
-    MRI3D_REQUIRE(conv_mfma_cat_supported(*g, split, dx2_ld, MRI3D_PASS_DGRAD) && aligned16(dy, dx, workspace) && aligned16(dx2),
+    MRI3D_REQUIRE(conv_backend(*g, MRI3D_PASS_DGRAD, false, split, dx2_ld, ptr_align(dy, dx, workspace, dx2), 0) == ConvBackend::mfma,
                   MRI3D_ENOTSUP, "conv3d_dgrad_cat: geometry / alignment not served (query mri3d_conv3d_cat_supported)");
     return conv_mfma_dgrad_cat(*g, dy, (const float*)w, dx, dx2, split, dx2_ld, workspace, ws_bytes, static_cast<hipStream_t>(stream));
 }
@@ -138,7 +173,7 @@ extern "C" int mri3d_conv3d_wgrad_cat(const Mri3dConvGeom* g, const void* x, con
     int rc = conv_check(g, "conv3d_wgrad_cat", split);
     if (rc) return rc;
     MRI3D_REQUIRE(x && x2 && dy && dw, MRI3D_EINVAL, "conv3d_wgrad_cat: null pointer");
-    MRI3D_REQUIRE(conv_mfma_cat_supported(*g, split, x2_ld, MRI3D_PASS_WGRAD) && aligned16(x, dy, workspace) && aligned16(x2),
+    MRI3D_REQUIRE(conv_backend(*g, MRI3D_PASS_WGRAD, false, split, x2_ld, ptr_align(x, dy, workspace, x2), 0) == ConvBackend::mfma,
                   MRI3D_ENOTSUP, "conv3d_wgrad_cat: geometry / alignment not served (query mri3d_conv3d_cat_supported)");
     return conv_mfma_wgrad_cat(*g, x, x2, split, x2_ld, dy, (float*)dw, (float*)dbias, workspace, ws_bytes,
                                static_cast<hipStream_t>(stream));
@@ -183,9 +218,32 @@ extern "C" int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const v
     if (rc) return rc;
     MRI3D_REQUIRE(x && dy && dw, MRI3D_EINVAL, "conv3d_wgrad: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (conv_pointwise_supported(*g, MRI3D_PASS_WGRAD) && aligned_vec4(g->dtype, x))
-        return conv_pointwise_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
-    if (conv_mfma_supported(*g, MRI3D_PASS_WGRAD) && aligned16(x, dy, workspace))
-        return conv_mfma_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
-    return conv_generic_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
+    switch (conv_backend(*g, MRI3D_PASS_WGRAD, false, 0, 0, ptr_align(x, dy, workspace), ptr_align(x))) {
+    case ConvBackend::pointwise: return conv_pointwise_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
+    case ConvBackend::mfma: return conv_mfma_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
+    default: return conv_generic_wgrad(*g, x, dy, (float*)dw, (float*)dbias, workspace, ws_bytes, s);
+    }
+}
+
+// ---- which kernel would run (host only): the backend decision above, then the MFMA file's own route by name
+extern "C" int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
+                                  int32_t align, char* name, size_t name_bytes) {
+    int rc = conv_check(g, "conv3d_route", split > 0 ? split : -1);
+    if (rc) return rc;
+    MRI3D_REQUIRE(name != nullptr && name_bytes >= 32, MRI3D_EINVAL, "conv3d_route: name buffer of at least 32 bytes required");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD || pass == MRI3D_PASS_WGRAD, MRI3D_EINVAL, "conv3d_route: unknown pass %d", pass);
+    MRI3D_REQUIRE(split >= 0 && (!stats || pass == MRI3D_PASS_FWD), MRI3D_EINVAL, "conv3d_route: negative split, or statistics outside the forward");
+    const ConvSplit sp{nullptr, split, second_ld};
+    // mri3d_conv3d_dgrad_cat takes no bias; the weight gradient has none to add
+    const bool with_bias = bias != 0 && pass != MRI3D_PASS_WGRAD && !(split > 0 && pass == MRI3D_PASS_DGRAD);
+    switch (conv_backend(*g, pass, stats != 0, split, second_ld, align, align)) {
+    case ConvBackend::none: snprintf(name, name_bytes, "none"); break;
+    case ConvBackend::generic: snprintf(name, name_bytes, "generic"); break;
+    case ConvBackend::pointwise: snprintf(name, name_bytes, "pointwise"); break;
+    case ConvBackend::mfma:
+        MRI3D_REQUIRE(conv_mfma_route_name(*g, pass, stats != 0, with_bias, sp, name, name_bytes), MRI3D_ENOTSUP,
+                      "conv3d_route: the MFMA file names no kernel for a pass it supports");
+        break;
+    }
+    return MRI3D_OK;
 }

@@ -41,6 +41,9 @@ int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, i
                         float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
 int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, double* stat_part,
                         void* ws, size_t ws_bytes, hipStream_t s);
+// name of the kernel instantiation the pass launches (mri3d_conv3d_route; the vocabulary is in include/mri3d.h), written from the
+// same fwd_route / mfma_wgrad_plan answer the launch reads.  false: this file does not serve the pass.
+bool conv_mfma_route_name(const Mri3dConvGeom& g, int pass, bool stats, bool bias, const ConvSplit& sp, char* name, size_t name_bytes);
 
 // conv_march.hip: forward / data gradient marching along d.  `force` = the explicit entry points (every geometry the kernel can
 // compute); otherwise the dispatcher's own choice of the layers where it is the faster kernel.

@@ -2716,6 +2716,34 @@ bool conv_mfma_supported(const Mri3dConvGeom& g, int pass) {
     return pass == MRI3D_PASS_WGRAD && mfma_wgrad_plan(g, q);
 }
 
+// What run_mfma_fwd / run_wgrad launch for the pass, by name: the kernel and the template arguments that select code in it (no
+// grids, no plan values that are run-time arguments).  Read from the same fwd_route / mfma_wgrad_plan answer as the launch.
+bool conv_mfma_route_name(const Mri3dConvGeom& g, int pass, bool stats, bool bias, const ConvSplit& sp, char* name, size_t name_bytes) {
+    if (pass == MRI3D_PASS_WGRAD) {
+        MfmaWgradPlan q;
+        if (!mfma_wgrad_plan(g, q)) return false;
+        switch (q.kernel) {
+        case WgradKernel::cin1: snprintf(name, name_bytes, "cin1"); break;
+        case WgradKernel::wgrad3: snprintf(name, name_bytes, "wgrad3"); break;
+        case WgradKernel::wgrad4: snprintf(name, name_bytes, "wgrad4"); break;
+        case WgradKernel::bf16: snprintf(name, name_bytes, "bf16"); break;
+        case WgradKernel::wgrad6: snprintf(name, name_bytes, "wgrad6%s%s", q.ci8 ? " ci8" : "", q.co8 ? " co8" : ""); break;
+        case WgradKernel::bf16t: snprintf(name, name_bytes, "bf16t"); break;
+        }
+        return true;
+    }
+    if (pass != MRI3D_PASS_FWD && pass != MRI3D_PASS_DGRAD) return false;
+    const FwdRoute r = fwd_route(g, pass == MRI3D_PASS_DGRAD, stats, sp);
+    switch (r.kernel) {
+    case FwdKernel::none: return false;
+    case FwdKernel::march: snprintf(name, name_bytes, "march%s%s", stats ? " stats" : "", bias ? " bias" : ""); break;
+    case FwdKernel::direct: snprintf(name, name_bytes, "direct nt%d mode%d split%d", r.direct.nt, r.direct.mode, r.direct.split); break;
+    case FwdKernel::tiled: snprintf(name, name_bytes, "tiled nt%d%s", r.tiled.NT, stats ? " stats" : ""); break;
+    case FwdKernel::tiled_n8: snprintf(name, name_bytes, "tiled_n8"); break;
+    }
+    return true;
+}
+
 // Forward / data gradient: the caller asks before it knows whether statistics or a split operand will be requested, and
 // mri3d_conv3d_{fwd,dgrad}_march is documented to size its workspace with this query too.  So the answer is not the need of one
 // route but the maximum over the kernel families that accept the geometry at all: the tiled kernel's image where mfma_fwd_plan

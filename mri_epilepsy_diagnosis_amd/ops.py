@@ -341,6 +341,45 @@ def _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=None, y_ld=None, 
                     ci if x_ld is None else x_ld, co if y_ld is None else y_ld, dtype)
 
 
+def _ptr_align(*ts):
+    """Largest power of two <= 16 dividing the base address of every given tensor (None entries are skipped)."""
+    bits = 16
+    for t in ts:
+        if t is not None:
+            bits |= t.data_ptr()
+    return bits & -bits
+
+
+def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16):
+    """Name of the kernel the C ABI launches for geometry `g` (a ConvGeom from `_conv_geom`) in pass `pass_` (PASS_*): host only,
+    nothing is launched and no device is needed.  split > 0: the *_cat entry points; align: `_ptr_align` of the tensors involved (16:
+    what the allocator gives).  The vocabulary of names is documented at mri3d_conv3d_route in include/mri3d.h."""
+    name = ctypes.create_string_buffer(64)
+    check(_lib.lib().mri3d_conv3d_route(ctypes.byref(g), pass_, int(bool(stats)), int(bool(bias)), split, second_ld, align, name, 64),
+          "conv3d_route")
+    return name.value.decode()
+
+
+def conv3d_routes(xshape, wshape, stride=1, padding=0, dilation=1, dtype=F32, x_ld=None, dy_ld=None, bias=True, bn_stats=False,
+                  x_align=16, dy_align=16):
+    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv3d(x, w, b, ...)` and its backward launch, from the
+    geometries `_Conv3dFn` builds: x a slice of pitch x_ld, the incoming gradient one of pitch dy_ld, y and dx fresh dense tensors,
+    no bias in the data gradient, the stride-2 weight gradient on the stride-1 kernels where `_stuffed_wgrad_ok`.  *_align:
+    `_ptr_align` of x / of the incoming gradient.  With bn_stats the forward name is that of the fused-statistics entry point
+    where it serves the geometry (as `conv3d(bn_stats=True)` asks first)."""
+    stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
+    g = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=x_ld, dtype=dtype)
+    fwd = conv_route(g, PASS_FWD, bn_stats, bias, align=x_align) if bn_stats else "none"
+    if fwd == "none":
+        fwd = conv_route(g, PASS_FWD, False, bias, align=x_align)
+    gd = _conv_geom(xshape, wshape, stride, padding, dilation, y_ld=dy_ld, dtype=dtype)
+    gw = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=g.x_ld, y_ld=dy_ld, dtype=dtype)
+    w_align = min(x_align, dy_align)
+    if _stuffed_wgrad_ok(g):
+        gw, w_align = _conv_geom(xshape, wshape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=dtype), x_align
+    return {"fwd": fwd, "dgrad": conv_route(gd, PASS_DGRAD, align=dy_align), "wgrad": conv_route(gw, PASS_WGRAD, align=w_align)}
+
+
 def _conv_fwd(g, x, w, b):
     L = _lib.lib()
     y = _new((g.n, g.co, g.dout, g.ho, g.wo), x)

@@ -40,7 +40,8 @@ int main() {
     // ---- conv: workspace queries over a sweep of geometries (plan functions of every kernel family), incl. degenerate ones
     const int chans[] = {1, 2, 3, 4, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192};
     const int sizes[][3] = {{1, 1, 1}, {2, 3, 5}, {8, 8, 8}, {10, 12, 10}, {32, 32, 32}, {80, 96, 80}, {160, 192, 160}, {192, 192, 192}};
-    size_t checked = 0, stats_routes = 0;
+    size_t checked = 0, stats_routes = 0, routes = 0;
+    char name[32];
     for (int dtype = 0; dtype < 2; ++dtype)
         for (int ci : chans)
             for (int co : chans)
@@ -56,7 +57,21 @@ int main() {
                                 const size_t ws = mri3d_conv3d_workspace_bytes(&g, pass);
                                 EXPECT(ws % 256 == 0 && ws < ((size_t)1 << 40));
                                 ++checked;
+                                // the route query names a kernel for every pass, alignment and bias; only a request for fused
+                                // statistics can be refused ("none"), and a misaligned tensor never reaches the 16-byte MFMA kernels
+                                for (int align : {16, 8, 4})
+                                    for (int bias = 0; bias < 2; ++bias) {
+                                        memset(name, 0x7f, sizeof(name));
+                                        EXPECT(mri3d_conv3d_route(&g, pass, 0, bias, 0, 0, align, name, sizeof(name)) == MRI3D_OK);
+                                        EXPECT(memchr(name, 0, sizeof(name)) != nullptr && name[0] != 0 && strcmp(name, "none") != 0);
+                                        if (align < 16) EXPECT(strcmp(name, "generic") == 0 || strcmp(name, "pointwise") == 0);
+                                        ++routes;
+                                    }
                             }
+                            // statistics: served exactly where the block query promises them
+                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 16, name, sizeof(name)) == MRI3D_OK);
+                            EXPECT((strcmp(name, "none") != 0) == (mri3d_conv3d_fwd_stats_blocks(&g) > 0));
+                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 8, name, sizeof(name)) == MRI3D_OK && strcmp(name, "none") == 0);
                             // where the query promises fused statistics, the launch path reaches the same route: with a 16-byte
                             // workspace it stops at the packed-weight image (always larger), neither "not served" nor a launch
                             if (mri3d_conv3d_fwd_stats_blocks(&g) > 0) {
@@ -65,7 +80,7 @@ int main() {
                             }
                         }
                     }
-    EXPECT(checked > 10000 && stats_routes > 1000);
+    EXPECT(checked > 10000 && stats_routes > 1000 && routes > 60000);
     EXPECT(mri3d_conv3d_workspace_bytes(nullptr, 0) == 0);
 
     // ---- conv: argument validation (every branch returns before a launch)
@@ -96,6 +111,15 @@ int main() {
     bad = g; bad.pd = -1;
     EXPECT(mri3d_conv3d_fwd(&bad, P, P, P, P, P, 0, nullptr) == MRI3D_EINVAL);
 
+    // ---- route query: argument validation
+    EXPECT(mri3d_conv3d_route(nullptr, 0, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, nullptr, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, name, 8) == MRI3D_EINVAL);                  // name buffer too small
+    EXPECT(mri3d_conv3d_route(&g, 3, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);       // no such pass
+    EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_WGRAD, 1, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);   // statistics outside the forward
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, -16, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&bad, 0, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);     // (bad.pd = -1)
+
     // ---- split operands (conv over cat((x, x2))): the support query over a sweep, refusals without a launch
     {
         // the *_cat entry point of a pass with a 16-byte workspace: MRI3D_EWORKSPACE exactly where the support query says 1 (the
@@ -115,7 +139,12 @@ int main() {
                         c.x_ld = ca;
                         for (int pass = 0; pass < 3; ++pass) {
                             served += mri3d_conv3d_cat_supported(&c, ca, cb, pass);
-                            for (int extra : {0, 4, 8, 12}) EXPECT(cat_agrees(c, ca, cb + extra, pass));
+                            for (int extra : {0, 4, 8, 12}) {
+                                EXPECT(cat_agrees(c, ca, cb + extra, pass));
+                                // the route query names a kernel exactly where the split entry point is served
+                                EXPECT(mri3d_conv3d_route(&c, pass, 0, 1, ca, cb + extra, 16, name, sizeof(name)) == MRI3D_OK);
+                                EXPECT((strcmp(name, "none") != 0) == (mri3d_conv3d_cat_supported(&c, ca, cb + extra, pass) == 1));
+                            }
                         }
                         EXPECT(mri3d_conv3d_cat_supported(&c, 0, cb, 0) == 0);          // no first part
                         EXPECT(mri3d_conv3d_cat_supported(&c, ca + cb, cb, 0) == 0);    // no second part

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
@@ -37,25 +39,7 @@ def _dev(t, dtype=BF):
     return t.to("cuda").to(dtype).contiguous(memory_format=torch.channels_last_3d) if t.dim() == 5 else t.to("cuda")
 
 
-CONV_CASES = [
-    # (n, ci, co, size, k, stride, pad, dil)
-    (2, 8, 16, (12, 20, 18), 3, 1, 1, 1),       # MFMA-shaped 3x3x3
-    (1, 16, 16, (9, 17, 33), 3, 1, 1, 1),
-    (1, 48, 16, (8, 16, 16), 3, 1, 1, 1),
-    (2, 32, 64, (6, 9, 17), 3, 1, 1, 1),
-    (1, 96, 32, (5, 8, 16), 3, 1, 1, 1),
-    (2, 1, 8, (10, 12, 14), 3, 1, 1, 1),        # first layer
-    (2, 16, 2, (10, 12, 14), 1, 1, 0, 1),       # classifier
-    (1, 32, 2, (9, 10, 11), 1, 1, 0, 1),        # pointwise heads: 8 channels per lane, vector dy loads; ragged voxel counts
-    (2, 64, 4, (5, 7, 9), 1, 1, 0, 1),
-    (1, 16, 5, (6, 7, 8), 1, 1, 0, 1),
-    (1, 24, 3, (6, 7, 8), 1, 1, 0, 1),
-    (1, 8, 16, (11, 12, 13), 3, 2, 1, 1),       # strided (Modified3DUNet)
-    (1, 4, 6, (9, 10, 11), (3, 1, 1), (2, 1, 1), (1, 0, 0), 1),
-]
-
-
-@pytest.mark.parametrize("case", CONV_CASES, ids=lambda c: "n%d_%d-%d_%s_k%s_s%s" % (c[0], c[1], c[2], "x".join(map(str, c[3])), c[4], c[5]))
+@pytest.mark.parametrize("case", cc.BF16_CONV.cases, ids=cc.BF16_CONV.ids)      # tests/conv_cases.py
 def test_conv3d_bf16(case):
     ops = _ops()
     n, ci, co, size, k, stride, pad, dil = case
@@ -74,6 +58,7 @@ def test_conv3d_bf16(case):
     xg = _dev(x).requires_grad_(True)
     wg = w.cuda().requires_grad_(True)
     bg = b.cuda().requires_grad_(True)
+    cc.BF16_CONV.check(case, "bf16", x=xg)
     yg = ops.conv3d(xg, wg, bg, stride=stride, padding=pad, dilation=dil)
     assert yg.dtype == BF
     yg.backward(_dev(dy))

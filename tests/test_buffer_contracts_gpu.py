@@ -19,6 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as cc
 from guard import SentinelSlice, conv3d_ref_at, gather_voxels, guarded, kernels_launched, sample_voxels
 from mri_epilepsy_diagnosis_amd import _lib, ops
 
@@ -27,7 +28,7 @@ pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 F32 = torch.float32
 CL = torch.channels_last_3d
-FULL = (160, 192, 160)      # the U-Net's full-resolution level: >= 4 M voxels, where the fp32 marching kernel is chosen
+DT = {"f32": F32, "bf16": BF}
 
 
 def _rand(seed, shape, dtype):
@@ -109,29 +110,11 @@ def _check_stats(y, b, part, dtype, what):
     assert e1 <= tol and e2 <= tol, "%s: statistics sums off by %.3e (sum a, relative to sum |a|) / %.3e (sum a^2)" % (what, e1, e2)
 
 
-# (id, dtype, n, ca, cb, second-tensor pitch, co, volume, kernel the dispatcher must pick)
-TILED = r"conv_mfma_fwd2_kernel"
-N8 = r"conv_mfma_fwd2_kernel(<.*, false, true>|I.*Lb0ELb1EE)"     # <T, NT, stats = false, n8 = true>, demangled or not
-MARCH = r"conv_march_kernel"
-STATS_CASES = [
-    ("f32_tiled", F32, 2, 16, 0, 0, 32, (19, 37, 70), TILED),
-    ("bf16_tiled", BF, 2, 16, 0, 0, 32, (19, 37, 70), TILED),       # 32 output channels: two blocks, never the marching kernel
-    ("f32_march", F32, 1, 16, 0, 0, 16, FULL, MARCH),
-    ("bf16_march", BF, 1, 16, 0, 0, 16, FULL, MARCH),
-    ("f32_cat_tiled", F32, 2, 16, 16, 16, 16, (24, 40, 70), TILED),
-    ("bf16_cat_tiled", BF, 2, 16, 16, 16, 32, (24, 40, 70), TILED),
-    ("f32_cat_march", F32, 1, 16, 16, 16, 16, FULL, MARCH),
-    ("bf16_cat_march", BF, 1, 16, 16, 16, 16, FULL, MARCH),
-    # the split-operand overrun: a second tensor of pitch 20 / 28 (fp32, served) runs the tiled kernel (512 blocks) where the
-    # one-tensor query answers with the marching kernel's grid
-    ("f32_cat_ld20", F32, 1, 16, 16, 20, 16, FULL, TILED),
-    ("f32_cat_ld28", F32, 1, 16, 16, 28, 16, FULL, TILED),
-]
-
-
-@pytest.mark.parametrize("case", STATS_CASES, ids=lambda c: c[0])
+# the cases (id, dtype, n, ca, cb, second-tensor pitch, co, volume, kernel the dispatcher must pick): cc.CAPI_STATS
+@pytest.mark.parametrize("case", cc.CAPI_STATS.cases, ids=cc.CAPI_STATS.ids)
 def test_statistics_partials_stay_inside_the_queried_blocks(case):
-    cid, dtype, n, ca, cb, ld2, co, sp, route = case
+    cid, dtype_id, n, ca, cb, ld2, co, sp, route = case
+    dtype = DT[dtype_id]
     seed = 100 + sum(sp) + ca + cb + ld2 + co
     xa = _rand(seed, (n, ca) + sp, dtype)
     xb = None
@@ -142,6 +125,7 @@ def test_statistics_partials_stay_inside_the_queried_blocks(case):
     g = torch.Generator().manual_seed(seed + 2)
     w = (torch.randn(co, ca + cb, 3, 3, 3, generator=g) / np.sqrt(27 * (ca + cb))).cuda()
     b = (torch.randn(co, generator=g) * 0.1).cuda()
+    cc.CAPI_STATS.check(case, dtype_id, x=xa if xb is None else xb)
     y, part, blocks, names = _fwd_stats_capi(xa, w, b, xb)
     _route(names, route, cid)
     part.assert_guards_intact("%s: statistics partials (%d blocks x %d channels)" % (cid, blocks, co))
@@ -315,18 +299,19 @@ def _overlap_case():
     return run
 
 
-# (id, case, kernel that must be among the launched ones, or None)
-WS_CASES = [
-    ("conv_generic_odd_dilated", _conv_case(1, 3, 5, (9, 10, 11), F32, pad=2, dil=2, seed=30), r"conv_fwd_(generic|taps)_kernel"),
-    ("conv_pointwise", _conv_case(2, 32, 2, (9, 10, 11), F32, k=1, pad=0, seed=31), r"pw_fwd_kernel"),
-    ("conv_small_f32", _conv_case(1, 32, 32, (10, 12, 10), F32, seed=32), r"conv_mfma_direct_kernel"),
-    ("conv_narrow_f32", _conv_case(64, 16, 16, (8, 8, 8), F32, seed=33), r"conv_mfma_direct_kernel"),
-    ("conv_tiled_f32", _conv_case(5, 16, 16, (17, 40, 65), F32, seed=34), r"conv_mfma_fwd2_kernel"),   # >= 512 work units
-    ("conv_tiled_bf16", _conv_case(2, 16, 32, (19, 37, 70), BF, seed=35), r"conv_mfma_fwd2_kernel"),
-    ("conv_n8_bf16", _conv_case(1, 16, 8, (17, 40, 65), BF, seed=36), N8),
-    ("conv_march_f32", _conv_case(1, 16, 16, FULL, F32, seed=37), r"conv_march_kernel"),
-    ("conv_march_bf16", _conv_case(1, 16, 16, FULL, BF, seed=38), r"conv_march_kernel"),
-    ("conv_wgrad_bf16_march_d", _conv_case(8, 64, 64, (45, 17, 37), BF, seed=39), r"conv_mfma_wgrad_bf16t_kernel"),
+def _ws_conv(case):
+    """A row of cc.WS_CONV as (id, run, kernel pattern); the route the row declares is asserted when the case runs."""
+    cid, dtype_id, n, ci, co, sp, k, pad, dil, seed, pattern = case
+    run = _conv_case(n, ci, co, sp, DT[dtype_id], k=k, pad=pad, dil=dil, seed=seed)
+
+    def checked():
+        cc.WS_CONV.check(case, dtype_id)
+        return run()
+    return cid, checked, pattern
+
+
+# (id, case, kernel that must be among the launched ones, or None); the convolutions: cc.WS_CONV
+WS_CASES = [_ws_conv(c) for c in cc.WS_CONV.cases] + [
     ("conv_transpose3d", _convt_case(), None),
     ("upsample_conv3d", _upconv_case(), r"upconv"),
     ("conv3d_pair", _pair_case(), r"convpair|sepconv|pair"),

@@ -1,135 +1,130 @@
 """Seeded random-geometry sweep of the 3x3x3 MFMA conv kernels (fp32 and bf16 storage): ragged spatial sizes around the tile
 edges (4x8x16 forward tile, 2x6x16 / 2x6x32 weight-gradient tiles), every channel count the dispatcher routes to an MFMA
-kernel, pitched (channel-slice) inputs and outputs — against torch's CPU conv on the same (rounded) inputs."""
+kernel, pitched (channel-slice) inputs and outputs — against torch's CPU conv on the same (rounded) inputs.
+
+The case tables live in tests/conv_cases.py, each with the kernel route it is there for; tests/test_conv_routes.py checks those
+routes on the CPU, and every test here asserts them again with its real pointers before it launches."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases as cc
 from mri_epilepsy_diagnosis_amd import ops
 
 pytestmark = pytest.mark.gpu
 
 
-def _cases(n, seed):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    chans = [8, 16, 24, 32, 48, 64]
-    out = []
-    for _ in range(n):
-        ci, co = int(rng.choice(chans)), int(rng.choice(chans))
-        d, h, w = int(rng.integers(1, 11)), int(rng.integers(1, 15)), int(rng.integers(1, 40))
-        nb = int(rng.integers(1, 3))
-        pad_in, pad_out = int(rng.choice([0, 8, 16])), int(rng.choice([0, 8]))
-        out.append((nb, ci, co, d, h, w, pad_in, pad_out, int(rng.integers(0, 1 << 30))))
-    return out
+def _params(table):
+    """parametrize arguments of a table of tests/conv_cases.py (the comments on what each table is there for are next to it)."""
+    return dict(argnames="case", argvalues=table.cases, ids=table.ids)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", _cases(14, 2024), ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+_BOTH = dict(argnames="dtype", argvalues=[torch.float32, torch.bfloat16], ids=["f32", "bf16"])
+
+
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.RANDOM))
 def test_conv3x3x3_random_geometry(case, dtype):
-    _run_conv_case(case, dtype)
+    _run_conv_case(case, dtype, cc.RANDOM)
 
 
-# channel slices whose base address is NOT 16-byte aligned (pad_in = 2 fp32 elements / 2 or 4 bf16 elements, odd pitches):
-# legal inputs that the MFMA kernels (16-byte pieces) cannot take — the dispatcher must fall back to the generic kernels
-# instead of failing with EINVAL
-MISALIGNED = [(1, 16, 16, 5, 9, 20, 2, 0, 11), (2, 8, 16, 4, 8, 16, 2, 2, 12), (1, 48, 16, 3, 8, 17, 4, 4, 13),
-              (1, 16, 32, 6, 10, 18, 6, 0, 14), (1, 32, 32, 2, 3, 5, 1, 3, 15)]
-
-
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", MISALIGNED, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.MISALIGNED))
 def test_conv3x3x3_misaligned_channel_slices_fall_back_to_generic_kernels(case, dtype):
-    _run_conv_case(case, dtype)
+    _run_conv_case(case, dtype, cc.MISALIGNED)
 
 
-# fp32 volumes with fewer than 256 work units go to the wave-per-M-tile kernel (conv_mfma_small_kernel); these ragged shapes
-# have enough batch to stay on the TILED fp32 kernel, so that its border tiles keep their fp32 coverage
-TILED_F32 = [(40, 16, 16, 5, 9, 19, 0, 0, 21), (24, 8, 32, 6, 11, 17, 8, 0, 22), (48, 48, 16, 3, 7, 21, 0, 8, 23)]
-
-
-@pytest.mark.parametrize("case", TILED_F32, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_params(cc.TILED_F32))
 def test_conv3x3x3_ragged_tiles_with_large_batch_stay_on_the_tiled_kernel(case):
-    _run_conv_case(case, torch.float32)
+    _run_conv_case(case, torch.float32, cc.TILED_F32)
 
 
-# deep-level shapes of Modified3DUNet (batch 1): served by the small-volume kernel in fp32 (1, 2 and 4 N-tiles per wave)
-SMALL = [(1, 64, 64, 20, 24, 20, 0, 0, 31), (1, 128, 128, 10, 12, 10, 0, 0, 32), (1, 128, 64, 20, 24, 20, 0, 0, 33),
-         (1, 32, 32, 40, 48, 40, 0, 0, 34), (2, 24, 48, 7, 5, 9, 8, 8, 35), (1, 16, 16, 3, 3, 3, 0, 0, 36)]
+@pytest.mark.parametrize(**_params(cc.DIRECT_F32_BATCH))
+def test_conv3x3x3_ragged_volumes_under_512_work_units_take_the_lds_free_kernel(case):
+    _run_conv_case(case, torch.float32, cc.DIRECT_F32_BATCH)
 
 
-@pytest.mark.parametrize("case", SMALL, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_params(cc.SMALL))
 def test_conv3x3x3_small_volumes(case):
-    _run_conv_case(case, torch.float32)
+    _run_conv_case(case, torch.float32, cc.SMALL)
 
 
-# one-N-tile passes with >= 256 (tile, N-block) units take the 64-byte-chunk kernel (conv_mfma3.hip, 8x8x16 tiles): ragged tile
-# borders in every dimension, 1 / 2 / 3 chunks (fp32 16 channels, bf16 32 channels per chunk; bf16 48 = a half-empty second chunk),
-# three N-blocks (the 48-channel data gradient), pitched inputs and outputs
-LARGE_BATCH_CASES = [(64, 16, 16, 9, 13, 21, 0, 0, 41), (72, 48, 16, 5, 9, 19, 0, 8, 42), (96, 16, 48, 3, 10, 17, 16, 0, 43),
-            (40, 32, 16, 11, 9, 33, 8, 8, 44), (260, 16, 16, 2, 3, 5, 0, 0, 45),
-            # volumes at most 8 voxels wide go to the LDS-free MFMA kernel whatever the batch (two rows per 16-voxel M-tile; an M-tile
-            # may straddle rows, planes and samples): the patch CNN's 8^3 level, a ragged one, pitched, > 32 MB of input
-            (128, 32, 64, 8, 8, 8, 0, 0, 46), (70, 16, 24, 5, 7, 6, 8, 0, 47), (300, 64, 64, 8, 8, 8, 0, 0, 48)]
+@pytest.mark.parametrize(**_params(cc.DIRECT_WIDE))
+def test_conv3x3x3_lds_free_kernel_with_two_and_four_n_tiles_per_wave(case):
+    _run_conv_case(case, torch.float32, cc.DIRECT_WIDE)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", LARGE_BATCH_CASES, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.LARGE_BATCH))
 def test_conv3x3x3_many_small_volumes(case, dtype):
-    _run_conv_case(case, dtype)
+    _run_conv_case(case, dtype, cc.LARGE_BATCH)
 
 
-# bf16 weight gradient marching along d (conv_mfma_wgrad_bf16t_kernel, LDS-DMA rows + transposing reads: taken when columns x segments >= 3 tasks per workgroup): a last
-# segment of 5 / 3 / 1 planes, a last row tile of one row, a last column tile of 5 voxels, an 8-channel input tile (upper half
-# empty) read from a pitched buffer, 24 output channels (half-empty second block) written from a pitched gradient
-MARCH_CASES = [(8, 64, 64, 45, 17, 37, 0, 0, 91), (24, 8, 128, 23, 9, 33, 8, 0, 92), (64, 32, 24, 41, 12, 20, 0, 8, 93)]
-
-
-@pytest.mark.parametrize("case", MARCH_CASES, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_params(cc.MARCH_WGRAD))
 def test_bf16_weight_gradient_marching_along_d(case):
-    _run_conv_case(case, torch.bfloat16)
+    _run_conv_case(case, torch.bfloat16, cc.MARCH_WGRAD)
 
 
-# exactly 8 output channels in the forward (8 -> 8, 16 -> 8, 24 -> 8) or in the data gradient (8 -> 16, 8 -> 32): the row-paired
-# variant of the tiled MFMA kernel (two taps share the 16-row weight operand, 9 accumulators, halves folded in the epilogue);
-# big enough for the tiled path (>= 256 tiles) and ragged in every axis; pitched slices; one case with a single chunk
-N8_CASES = [(2, 8, 8, 21, 35, 50, 0, 0, 71), (1, 16, 8, 17, 40, 65, 8, 8, 72), (2, 24, 8, 9, 33, 47, 0, 0, 73),
-            (1, 8, 16, 13, 41, 70, 0, 8, 74), (1, 8, 32, 9, 34, 49, 8, 0, 75), (40, 8, 8, 4, 8, 16, 0, 0, 76),
-            # weight gradient with paired operand halves (v6, CI8 / CO8): 32 -> 8, pitched 8 -> 8, one-tile and W < 16 volumes
-            (1, 32, 8, 11, 19, 37, 0, 0, 77), (1, 8, 8, 7, 13, 33, 8, 8, 78), (3, 8, 8, 2, 6, 16, 0, 0, 79), (2, 16, 8, 5, 7, 9, 0, 0, 80)]
-
-
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", N8_CASES, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.N8))
 def test_conv3x3x3_eight_output_channels(case, dtype):
-    _run_conv_case(case, dtype)
+    _run_conv_case(case, dtype, cc.N8)
 
 
-# stride-2 3x3x3 layers (modified_3dunet.py:23-38, cnn_model.py:49-81) on the LDS-free MFMA kernel: forward over output M-tiles,
-# data gradient over same-parity input M-tiles with wave-uniform tap sets; even / odd extents (the last output voxel then has no
-# kw = 2 neighbour), pitched slices, few units (a workgroup per unit, taps split over its waves) and many, Kc = 8 (half a chunk)
-STRIDED = [(1, 8, 16, 16, 18, 20, 0, 0, 51), (1, 16, 32, 9, 11, 13, 0, 0, 52), (2, 32, 64, 10, 12, 9, 8, 16, 53),
-           (1, 64, 128, 6, 7, 5, 0, 0, 54), (1, 8, 16, 40, 48, 40, 0, 0, 55), (3, 24, 40, 5, 6, 33, 0, 8, 56),
-           (1, 16, 8, 7, 9, 37, 0, 0, 57), (1, 8, 16, 2, 3, 1, 0, 0, 58)]
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.N8_TILED))
+def test_conv3x3x3_eight_output_channels_on_the_row_paired_tiled_kernel(case, dtype):
+    _run_conv_case(case, dtype, cc.N8_TILED)
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", STRIDED, ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.STRIDED))
 def test_conv3x3x3_stride2(case, dtype):
-    _run_conv_case(case, dtype, stride=2)
+    _run_conv_case(case, dtype, cc.STRIDED)
 
 
-@pytest.mark.parametrize("case", [(1, 16, 32, 10, 11, 13, 0, 0, 61), (2, 8, 16, 7, 8, 19, 8, 0, 62)], ids=lambda c: "n%d_%d-%d_%dx%dx%d_p%d_%d" % c[:8])
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.STRIDED_WIDE))
+def test_conv3x3x3_stride2_wave_per_tile_and_wide_n_blocks(case, dtype):
+    _run_conv_case(case, dtype, cc.STRIDED_WIDE)
+
+
+@pytest.mark.parametrize(**_params(cc.STRIDE3))
 def test_conv3x3x3_stride3(case):
-    _run_conv_case(case, torch.float32, stride=3)
+    _run_conv_case(case, torch.float32, cc.STRIDE3)
 
 
-def _run_conv_case(case, dtype, stride=1):
+@pytest.mark.parametrize(**_params(cc.BF16_WGRAD_QUADS))
+def test_bf16_weight_gradient_with_channel_counts_the_bf16_kernels_cannot_take(case):
+    _run_conv_case(case, torch.bfloat16, cc.BF16_WGRAD_QUADS)
+
+
+@pytest.mark.parametrize(**_params(cc.MARCH_BF16))
+def test_bf16_marching_kernel_where_the_dispatcher_chooses_it(case):
+    _run_conv_case(case, torch.bfloat16, cc.MARCH_BF16)
+
+
+@pytest.mark.parametrize(**_params(cc.MARCH_BF16_NOBIAS))
+def test_bf16_marching_kernel_by_choice_without_a_bias(case):
+    _run_conv_case(case, torch.bfloat16, cc.MARCH_BF16_NOBIAS)
+
+
+def _dtype_id(dtype):
+    return "f32" if dtype == torch.float32 else "bf16"
+
+
+def _run_conv_case(case, dtype, table):
+    """One case of a "slice" table against torch's CPU conv on the same (rounded) inputs; the routes the table declares are asserted
+    with the real pointers before anything is launched."""
     nb, ci, co, d, h, w, pad_in, pad_out, seed = case
+    stride = table.stride
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(nb, ci, d, h, w, generator=g)
     wt = torch.randn(co, ci, 3, 3, 3, generator=g) * (1.0 / np.sqrt(27 * ci))
     b = torch.randn(co, generator=g)
+    if not table.bias:
+        b = None
     do, ho, wo = [(e - 1) // stride + 1 for e in (d, h, w)]     # k 3, pad 1
     dy = torch.randn(nb, co, do, ho, wo, generator=g)
     if dtype == torch.bfloat16:
@@ -138,18 +133,19 @@ def _run_conv_case(case, dtype, stride=1):
     xbuf = torch.zeros(nb, ci + pad_in, d, h, w, device="cuda", dtype=dtype).contiguous(memory_format=torch.channels_last_3d)
     xbuf[:, pad_in:] = x.cuda().to(dtype)
     xg = xbuf[:, pad_in:].detach().requires_grad_(True)
-    wg, bg = wt.cuda().requires_grad_(True), b.cuda().requires_grad_(True)
-    yg = ops.conv3d(xg, wg, bg, stride=stride, padding=1)
+    wg, bg = wt.cuda().requires_grad_(True), (b.cuda().requires_grad_(True) if b is not None else None)
     dybuf = torch.zeros(nb, co + pad_out, do, ho, wo, device="cuda", dtype=dtype).contiguous(memory_format=torch.channels_last_3d)
     dybuf[:, :co] = dy.cuda().to(dtype)
+    table.check(case, _dtype_id(dtype), x=xg, dy=dybuf[:, :co])
+    yg = ops.conv3d(xg, wg, bg, stride=stride, padding=1)
     yg.backward(dybuf[:, :co])
 
     def ref(wref):
         xr = x.clone().requires_grad_(True)
-        wr, br = wref.clone().requires_grad_(True), b.clone().requires_grad_(True)
+        wr, br = wref.clone().requires_grad_(True), (b.clone().requires_grad_(True) if b is not None else None)
         yr = F.conv3d(xr, wr, br, stride=stride, padding=1)
         yr.backward(dy)
-        return yr.detach(), xr.grad, wr.grad, br.grad
+        return yr.detach(), xr.grad, wr.grad, (br.grad if b is not None else None)
 
     if dtype == torch.float32:
         yr, dxr, dwr, dbr = ref(wt)
@@ -168,15 +164,52 @@ def _run_conv_case(case, dtype, stride=1):
     close(yg, yr, tol_act, "y")
     close(xg.grad, dxr, tol_act, "dx")
     close(wg.grad, dwr, tol_par, "dw")
-    close(bg.grad, dbr, tol_par, "db")
+    if b is not None:
+        close(bg.grad, dbr, tol_par, "db")
 
 
-FIRST = [(2, 8, 9, 13, 37, True, 0), (1, 16, 8, 16, 32, False, 0), (1, 8, 4, 8, 32, False, 8), (3, 16, 5, 7, 19, True, 0),
-         (1, 8, 1, 1, 1, True, 0), (1, 8, 17, 9, 70, True, 8), (2, 16, 6, 20, 33, True, 16), (1, 8, 12, 24, 64, False, 0)]
+def _sum_bounds(tol, amax, count):
+    """Bounds on |sum a - sum r| and |sum a^2 - sum r^2| over `count` values that each obey |a - r| <= tol * amax, |r| <= amax."""
+    return tol * amax * count, tol * amax * (2.0 + tol) * amax * count
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", FIRST, ids=lambda c: "n%d_1-%d_%dx%dx%d_b%d_p%d" % c)
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.STATS_ORACLE))
+def test_conv3x3x3_fused_statistics_against_the_cpu_reference(case, dtype):
+    """conv3d(bn_stats=True): y AND the per-channel statistics partials of the epilogue (sum a, sum a^2 of a = y - bias, float64 per
+    workgroup) against torch's CPU conv on the same (rounded) inputs — the tiled kernel's STATS instantiations and the marching
+    kernel's, which the other statistics tests only compare with a second device pass.  y: the tolerances of `_run_conv_case`.
+    Statistics: they are sums of the fp32 accumulators BEFORE the result is rounded for storage, and a bf16 product is exact in
+    fp32, so in both storage types every accumulator obeys the fp32 bound of 2e-5 of the reference's max-norm; the sums over the
+    N x D x H x W voxels of a channel are then within `_sum_bounds` of the reference's float64 sums."""
+    nb, ci, co, d, h, w, has_bias = case
+    g = torch.Generator().manual_seed(ci * 1000 + co * 10 + d)
+    x = torch.randn(nb, ci, d, h, w, generator=g) * 1.5 + 0.3
+    wt = torch.randn(co, ci, 3, 3, 3, generator=g) * (1.0 / np.sqrt(27 * ci))
+    b = torch.randn(co, generator=g) if has_bias else None
+    if dtype == torch.bfloat16:
+        x = x.to(dtype).float()
+    xg = x.cuda().to(dtype).contiguous(memory_format=torch.channels_last_3d)
+    cc.STATS_ORACLE.check(case, _dtype_id(dtype), x=xg)
+    yg = ops.conv3d(xg, wt.cuda(), b.cuda() if has_bias else None, padding=1, bn_stats=True)
+    part, blocks, _ = yg._mri3d_bn_stats
+    sums = part.view(blocks, co, 2).sum(0).cpu()                       # (co, 2) float64
+    wref = wt if dtype == torch.float32 else wt.to(dtype).float()      # the MFMA operands are the weights rounded to bf16
+    ar = F.conv3d(x, wref, None, padding=1).double()                    # a = y - bias
+    amax = ar.abs().max().item()
+    yr = ar + (b.double().view(1, -1, 1, 1, 1) if has_bias else 0.0)
+    tol_act = 2e-5 if dtype == torch.float32 else 1.2e-2
+    err = (yg.double().cpu() - yr).abs().max().item()
+    assert err <= tol_act * (yr.abs().max().item() + 1e-6), "y: %.3e vs scale %.3e" % (err, yr.abs().max().item())
+    b1, b2 = _sum_bounds(2e-5, amax, nb * d * h * w)
+    e1 = (sums[:, 0] - ar.sum((0, 2, 3, 4))).abs().max().item()
+    e2 = (sums[:, 1] - (ar * ar).sum((0, 2, 3, 4))).abs().max().item()
+    print("statistics: |d sum a| %.3e (bound %.3e), |d sum a^2| %.3e (bound %.3e)" % (e1, b1, e2, b2))
+    assert e1 <= b1 and e2 <= b2, "statistics sums off by %.3e (bound %.3e) / %.3e (bound %.3e)" % (e1, b1, e2, b2)
+
+
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.FIRST))
 def test_first_layer_conv_one_input_channel(case, dtype):
     """Conv3d(1, 8|16, 3, padding=1): the direct first-layer kernels (conv_cin1_{fwd,wgrad}_kernel), ragged tiles, outputs
     written into / gradients read from a pitched channel slice."""
@@ -191,9 +224,10 @@ def test_first_layer_conv_one_input_channel(case, dtype):
     xg = x.cuda().to(dtype).requires_grad_(True)
     wg = wt.cuda().requires_grad_(True)
     bg = b.cuda().requires_grad_(True) if bias else None
-    yg = ops.conv3d(xg, wg, bg, padding=1)
     dybuf = torch.zeros(nb, co + pad_out, d, h, w, device="cuda", dtype=dtype).contiguous(memory_format=torch.channels_last_3d)
     dybuf[:, pad_out:] = dy.cuda().to(dtype)
+    cc.FIRST.check(case, _dtype_id(dtype), x=xg, dy=dybuf[:, pad_out:])
+    yg = ops.conv3d(xg, wg, bg, padding=1)
     yg.backward(dybuf[:, pad_out:])
     x64, w64 = x.double().requires_grad_(True), wt.double().requires_grad_(True)
     b64 = b.double().requires_grad_(True) if bias else None
@@ -213,14 +247,7 @@ def test_first_layer_conv_one_input_channel(case, dtype):
         close(bg.grad, b64.grad, tol_par, "db")
 
 
-ONE_OUT = [(2, 8, (3, 1, 1), (1, 0, 0), (1, 1, 1), (9, 13, 37), True), (1, 1, (1, 3, 1), (0, 1, 0), (1, 1, 1), (4, 8, 32), False),
-           (1, 1, (1, 1, 3), (0, 0, 1), (1, 1, 1), (5, 7, 19), True), (2, 4, (1, 6, 1), (0, 2, 0), (1, 2, 1), (6, 20, 9), True),
-           (1, 16, (1, 1, 3), (0, 0, 1), (1, 1, 1), (3, 5, 70), False), (2, 1, (3, 3, 3), (1, 1, 1), (1, 1, 1), (9, 13, 37), True),
-           (1, 1, (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True), (1, 8, (6, 1, 1), (2, 0, 0), (2, 1, 1), (12, 6, 10), True)]
-
-
-@pytest.mark.parametrize("case", ONE_OUT, ids=lambda c: "n%d_%d-1_k%s_s%s_%s" % (c[0], c[1], "x".join(map(str, c[2])),
-                                                                                   "".join(map(str, c[4])), "x".join(map(str, c[5]))))
+@pytest.mark.parametrize(**_params(cc.ONE_OUT))
 def test_single_output_channel_convs(case):
     """The autoencoder's single-channel tail (AE_model.py:110-160): few-tap convs ending in one channel (co1 weight-gradient
     kernel) and the 1 -> 1 3x3x3 `vox` stencil (forward, data gradient, weight gradient)."""
@@ -232,6 +259,7 @@ def test_single_output_channel_convs(case):
     xg = x.cuda().contiguous(memory_format=torch.channels_last_3d).requires_grad_(True)
     wg = wt.cuda().requires_grad_(True)
     bg = b.cuda().requires_grad_(True) if bias else None
+    cc.ONE_OUT.check(case, "f32", x=xg)
     yg = ops.conv3d(xg, wg, bg, stride=stride, padding=pad)
     x64, w64 = x.double().requires_grad_(True), wt.double().requires_grad_(True)
     b64 = b.double().requires_grad_(True) if bias else None

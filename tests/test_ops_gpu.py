@@ -6,7 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from mri_epilepsy_diagnosis_amd import ops
+import conv_cases as cc
+from mri_epilepsy_diagnosis_amd import _lib, ops
 from util import assert_close, seeded_rand, seeded_randn, to_ncdhw
 
 pytestmark = pytest.mark.gpu
@@ -19,54 +20,8 @@ def _dev(t, grad=True):
 
 
 # ---------------------------------------------------------------------------------------------- conv
-CONV_CASES = [
-    # name, N, Cin, Cout, (D,H,W), k, s, p, d, bias
-    ("unet_1_8", 2, 1, 8, (12, 20, 16), 3, 1, 1, 1, True),
-    ("unet_8_16", 2, 8, 16, (12, 20, 16), 3, 1, 1, 1, True),
-    ("unet_16_16", 1, 16, 16, (16, 12, 20), 3, 1, 1, 1, True),
-    ("unet_16_32", 1, 16, 32, (8, 12, 16), 3, 1, 1, 1, True),
-    ("unet_32_32", 1, 32, 32, (8, 12, 8), 3, 1, 1, 1, True),
-    ("unet_32_64", 1, 32, 64, (8, 6, 8), 3, 1, 1, 1, True),
-    ("unet_96_32", 1, 96, 32, (8, 8, 12), 3, 1, 1, 1, True),
-    ("unet_48_16", 1, 48, 16, (12, 16, 16), 3, 1, 1, 1, True),
-    ("unet_cls_16_2", 2, 16, 2, (12, 20, 16), 1, 1, 0, 1, True),
-    ("pw_32_2", 1, 32, 2, (9, 10, 11), 1, 1, 0, 1, False),
-    ("pw_64_8", 2, 64, 8, (6, 7, 8), 1, 1, 0, 1, True),
-    ("pw_16_5", 1, 16, 5, (6, 7, 8), 1, 1, 0, 1, True),
-    ("pw_128_64", 1, 128, 64, (4, 5, 6), 1, 1, 0, 1, False),
-    ("pw_8_3", 2, 8, 3, (5, 9, 13), 1, 1, 0, 1, True),       # forward on the lanes-per-voxel kernel: 2 / 1 / 16 lanes per voxel,
-    ("pw_4_1", 1, 4, 1, (7, 6, 5), 1, 1, 0, 1, False),       # 1-4 output channels, voxel counts that are no multiple of anything
-    ("pw_64_4", 1, 64, 4, (3, 7, 11), 1, 1, 0, 1, True),
-    ("mfma_24_40", 1, 24, 40, (6, 9, 17), 3, 1, 1, 1, True),
-    ("mfma_64_128_ragged", 1, 64, 128, (3, 5, 7), 3, 1, 1, 1, False),
-    ("ragged_3x3x3", 1, 16, 16, (5, 7, 9), 3, 1, 1, 1, False),
-    ("tiny_1voxel", 1, 8, 16, (1, 1, 1), 3, 1, 1, 1, True),
-    ("sepx_k6s2p2", 2, 1, 8, (32, 12, 10), (6, 1, 1), (2, 1, 1), (2, 0, 0), 1, True),
-    ("sepy_k6s2p2", 2, 8, 8, (8, 24, 10), (1, 6, 1), (1, 2, 1), (0, 2, 0), 1, True),
-    ("sepz_k6s2p2", 2, 8, 16, (8, 6, 28), (1, 1, 6), (1, 1, 2), (0, 0, 2), 1, True),
-    ("sepx_k3p0", 3, 32, 64, (3, 3, 3), (3, 1, 1), 1, 0, 1, True),
-    ("sepz_k3p1", 1, 16, 8, (6, 5, 9), (1, 1, 3), 1, (0, 0, 1), 1, True),
-    ("stride2_m3d", 1, 8, 16, (12, 10, 14), 3, 2, 1, 1, False),
-    ("stride2_odd", 1, 16, 32, (9, 7, 11), 3, 2, 1, 1, False),
-    ("dilated_s2", 1, 1, 4, (25, 23, 27), 3, 2, 0, 3, True),
-    ("dilated_p3", 1, 4, 4, (11, 12, 13), 3, 1, 3, 3, True),
-    ("reduce_k4s4", 1, 1, 1, (16, 12, 8), 4, 4, 0, 1, True),
-    ("vox_1_1", 2, 1, 1, (9, 10, 11), 3, 1, 1, 1, True),
-    # 1 -> 1 separable convs of the autoencoder's last block (AE_model.py:110-160): the 16-byte stencil kernels (W % 4 == 0) ...
-    ("c1_sepy", 2, 1, 1, (9, 10, 12), (1, 3, 1), 1, (0, 1, 0), 1, True),
-    ("c1_sepz", 2, 1, 1, (5, 7, 16), (1, 1, 3), 1, (0, 0, 1), 1, True),
-    ("c1_sepx_nobias", 1, 1, 1, (6, 5, 8), (3, 1, 1), 1, (1, 0, 0), 1, False),
-    ("c1_sepz_k6_p2", 1, 1, 1, (4, 6, 20), (1, 1, 6), 1, (0, 0, 2), 1, True),      # output narrower than the input (W 20 -> 19: gather path)
-    ("c1_sepz_k5_p2_dil2", 1, 1, 1, (4, 6, 24), (1, 1, 5), 1, (0, 0, 4), 2, True),  # dilation 2, same width: shifted 16-byte loads
-    ("c1_sepy_k2", 2, 1, 1, (4, 9, 8), (1, 2, 1), 1, (0, 1, 0), 1, True),           # even filter: H 9 -> 10
-    # ... and a width that is not a multiple of 4 (gather kernels)
-    ("c1_sepz_ragged", 1, 1, 1, (5, 6, 10), (1, 1, 3), 1, (0, 0, 1), 1, True),
-    ("odd_channels", 1, 3, 5, (6, 7, 8), 3, 1, 1, 1, True),
-    ("wide_128", 1, 128, 128, (4, 4, 4), 3, 1, 1, 1, False),
-]
-
-
-@pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
+# (the conv case tables are in tests/conv_cases.py, each with the kernel routes it is there for)
+@pytest.mark.parametrize("case", cc.OPS_CONV.cases, ids=cc.OPS_CONV.ids)
 def test_conv3d_fwd_dgrad_wgrad(case):
     _, n, ci, co, sp, k, s, p, d, bias = case
     x = seeded_randn(1, (n, ci, *sp))
@@ -84,6 +39,7 @@ def test_conv3d_fwd_dgrad_wgrad(case):
     xd = _dev(x)
     w = conv.weight.detach().to(DEV).requires_grad_(True)
     b = conv.bias.detach().to(DEV).requires_grad_(True) if bias else None
+    cc.OPS_CONV.check(case, "f32", x=xd)
     yd = ops.conv3d(xd, w, b, s, p, d)
     assert tuple(yd.shape) == tuple(yr.shape)
     yd.backward(_dev(gy, False))
@@ -585,10 +541,7 @@ def test_surface_element_lists_and_order_metrics_bit_exact():
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", [(2, 16, 16, 9, 13, 21, True), (1, 48, 16, 8, 16, 32, True), (2, 8, 32, 5, 8, 16, False),
-                                  (1, 32, 64, 4, 9, 17, True), (1, 16, 48, 6, 7, 19, True),
-                                  (64, 16, 16, 9, 13, 21, True), (90, 48, 16, 3, 9, 17, False), (88, 16, 48, 5, 7, 19, True)],
-                         ids=lambda c: "n%d_%d-%d_%dx%dx%d_b%d" % c)
+@pytest.mark.parametrize("case", cc.OPS_STATS.cases, ids=cc.OPS_STATS.ids)
 def test_batchnorm_statistics_from_the_conv_epilogue_equal_the_statistics_pass(case, dtype):
     """conv3d(bn_stats=True) accumulates the BatchNorm batch statistics in the MFMA kernel's epilogue (float64 partials per
     workgroup, shift = bias); norm_act must then give what it gives with its own statistics pass over y: outputs, running
@@ -600,6 +553,7 @@ def test_batchnorm_statistics_from_the_conv_epilogue_equal_the_statistics_pass(c
     b = (torch.randn(co, generator=g) * 2.0).cuda() if has_bias else None
     gamma, beta = (torch.rand(co, generator=g) + 0.5).cuda(), torch.randn(co, generator=g).cuda()
     dy = torch.randn(nb, co, d, h, w, generator=g).cuda().to(dtype).contiguous(memory_format=torch.channels_last_3d)
+    cc.OPS_STATS.check(case, "f32" if dtype == torch.float32 else "bf16", x=x, dy=dy)
     res = []
     for fused in (False, True):
         xs = x.clone().requires_grad_(True)
@@ -654,18 +608,6 @@ def test_max_pool3d_2_nan_and_index_semantics_equal_torch(dtype):
     assert torch.equal(to_ncdhw(xd.grad).float().cpu(), xr.grad)
 
 
-# (batch, Ca, Cb, Cout, volume, channel padding of the second tensor's buffer, bias, served by the split kernels in fp32 / bf16)
-CAT_CASES = [(2, 16, 32, 16, (24, 40, 70), 0, True, True, True), (2, 32, 64, 32, (21, 33, 70), 8, True, True, True),
-             (8, 32, 64, 32, (45, 17, 37), 8, True, True, True),       # bf16: the weight gradient marches along d (3 segments of 20)
-             (5, 16, 16, 8, (17, 40, 65), 0, False, True, True),       # (>= 512 work units in every pass: below that the plain convolution
-                                                                       #  prefers the LDS-free kernel and the sums are ordered differently)
-             (2, 16, 24, 16, (24, 40, 70), 0, True, False, True),      # 24 trailing channels: not a ci-tile multiple for the fp32 weight gradient
-             (1, 8, 16, 16, (24, 40, 70), 0, True, False, False),      # 8 leading channels: the split must be a multiple of 16
-             (1, 16, 32, 16, (6, 7, 9), 0, True, False, True),         # tiny volume: fp32 runs on the LDS-free kernel (no split support)
-             (5, 16, 16, 16, (17, 40, 65), 4, True, True, False)]      # second tensor of pitch 20: fp32 served (16-byte aligned slice),
-                                                                       # bf16 falls back (the slice starts 8 bytes into the voxel)
-
-
 def test_conv3d_cat_between_256_and_512_work_units_stays_on_the_tiled_kernel():
     """256 <= work units < 512 (fp32): the plain convolution prefers the LDS-free MFMA kernel, the split-operand one keeps the
     tiled kernel — different summation orders, so the two agree to rounding, not bit for bit; the split path must still be served."""
@@ -675,6 +617,11 @@ def test_conv3d_cat_between_256_and_512_work_units_stays_on_the_tiled_kernel():
     xb = torch.randn(3, 16, *sp, generator=g).cuda().contiguous(memory_format=torch.channels_last_3d)
     wt = (torch.randn(8, 32, 3, 3, 3, generator=g) / np.sqrt(27 * 32)).cuda()
     dy = torch.randn(3, 8, *sp, generator=g).cuda().contiguous(memory_format=torch.channels_last_3d)
+    one = (1, 1, 1)
+    whole = ops._conv_geom((3, 32) + sp, wt.shape, one, one, one)
+    halves = ops._conv_geom((3, 32) + sp, wt.shape, one, one, one, x_ld=16)
+    assert ops.conv_route(whole, _lib.PASS_FWD) == "direct nt1 mode0 split0" and ops.conv_route(halves, _lib.PASS_FWD, split=16, second_ld=16) == "tiled_n8"
+    assert ops.conv_route(whole, _lib.PASS_DGRAD) == "direct nt2 mode0 split0" and ops.conv_route(halves, _lib.PASS_DGRAD, split=16, second_ld=16) == "tiled nt2"
     res = []
     for split in (True, False):
         a, b, w = xa.clone().requires_grad_(True), xb.clone().requires_grad_(True), wt.clone().requires_grad_(True)
@@ -691,7 +638,7 @@ def test_conv3d_cat_between_256_and_512_work_units_stays_on_the_tiled_kernel():
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
-@pytest.mark.parametrize("case", CAT_CASES, ids=lambda c: "n%d_%d+%d-%d_%s_p%d_b%d" % (c[0], c[1], c[2], c[3], "x".join(map(str, c[4])), c[5], c[6]))
+@pytest.mark.parametrize("case", cc.CAT.cases, ids=cc.CAT.ids)
 def test_conv3d_cat_equals_conv_of_the_concatenation(case, dtype):
     """ops.conv3d_cat(xa, xb, w) — the U-Net decoder's conv over cat((skip, upsampled)) read from the two tensors — against
     ops.conv3d on the explicit concatenation: same kernels, same summation order, so outputs, both input gradients, weight and bias
@@ -707,6 +654,8 @@ def test_conv3d_cat_equals_conv_of_the_concatenation(case, dtype):
     wt = (torch.randn(co, ca + cb, 3, 3, 3, generator=g) / np.sqrt(27 * (ca + cb))).cuda()
     b = torch.randn(co, generator=g).cuda() if has_bias else None
     dy = torch.randn(nb, co, *sp, generator=g).cuda().to(dtype).contiguous(memory_format=torch.channels_last_3d)
+    routes = cc.CAT.check(case, "f32" if dtype == torch.float32 else "bf16", x=bbuf[:, pad_b:])
+    assert served == all(r != "none" for p, r in routes.items() if p != "stats"), routes     # served: the split kernels take all three passes
     res = []
     for split in (False, True):
         a = xa.clone().requires_grad_(True)
