@@ -204,11 +204,34 @@ int mri3d_norm_act_fwd(const Mri3dNormGeom* g, const void* x, const float* mean,
                        const float* gamma, const float* beta, const float* alpha, void* y,
                        mri3d_stream_t stream);
 /* Backward of norm_act_fwd.  training != 0: statistics were computed from x (batch/instance mode);
- * training == 0: mean/invstd are constants (eval-mode BatchNorm).  dgamma/dbeta/dalpha may be NULL. */
+ * training == 0: mean/invstd are constants (eval-mode BatchNorm, activation-only layers): dx does not depend on the sums then, and
+ * one pass over (x, dy) writes dx and the partial sums.  dgamma/dbeta/dalpha may be NULL. */
 int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const void* x, const void* dy,
                        const float* mean, const float* invstd, const float* gamma, const float* beta,
                        const float* alpha, void* dx, float* dgamma, float* dbeta, float* dalpha,
                        void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+
+/* norm_act followed by a narrow 1x1x1 convolution, as ONE operator: out = W . act(norm(x)) + bias — `unet.UNet`'s classifier
+ * (Conv3d(2*c0, out_classes, 1), segmentation/routine.py:346-356) right after the last conv -> BatchNorm3d -> PReLU block.  The
+ * activation and its gradient, full-resolution tensors that exist only to cross a kernel boundary, are never stored.
+ * g describes the norm_act part with batch (training != 0), running or no statistics (mean = invstd = NULL); g->x_ld = voxel pitch
+ * of x / dx, g->y_ld = voxel pitch of out / dout; w is the head's weight (co, c), bias (co) or NULL.  fp32 results of _fwd are
+ * bit-identical to mri3d_norm_act_fwd + mri3d_conv3d_fwd; in bf16 the activation is rounded to bf16 before the dot product, as
+ * the stored tensor would be.
+ * mri3d_norm_act_pw_supported(g, co) = 1 (host only): batch-type statistics (not instance / group), c % 4 == 0 with c/4 a power
+ * of two <= 16, 1 <= co <= 4, x_ld % 4 == 0; x and dx must be aligned to 4 elements.  Otherwise 0: keep the two operators.
+ * _bwd: dx (pitch x_ld), dgamma, dbeta, dalpha, dw (co, c), dbias (co); every one of them may be NULL.  With training == 0 and
+ * a parameter gradient wanted, dx and all sums come from one pass over (x, dout).  Workspace: mri3d_norm_act_pw_workspace_bytes
+ * (host only; 0 when not supported), 8-byte aligned. */
+int32_t mri3d_norm_act_pw_supported(const Mri3dNormGeom* g, int32_t co);
+size_t mri3d_norm_act_pw_workspace_bytes(const Mri3dNormGeom* g, int32_t co);
+int mri3d_norm_act_pw_fwd(const Mri3dNormGeom* g, int32_t co, const void* x, const float* mean, const float* invstd,
+                          const float* gamma, const float* beta, const float* alpha, const float* w, const float* bias,
+                          void* out, mri3d_stream_t stream);
+int mri3d_norm_act_pw_bwd(const Mri3dNormGeom* g, int32_t co, int training, const void* x, const void* dout,
+                          const float* mean, const float* invstd, const float* gamma, const float* beta, const float* alpha,
+                          const float* w, void* dx, float* dgamma, float* dbeta, float* dalpha, float* dw, float* dbias,
+                          void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MaxPool3d — nn.MaxPool3d(2) in unet.UNet / AE_model.py:27 / cnn_model.py:115-148, (4,2) in cnn_model.py:221,232.

@@ -82,6 +82,11 @@ SIGNATURES = {
     "mri3d_norm_act_fwd": (c_int32, [POINTER(NormGeom), _P, _FP, _FP, _FP, _FP, _FP, _P, _P]),
     "mri3d_norm_act_bwd": (c_int32, [POINTER(NormGeom), c_int32, _P, _P, _FP, _FP, _FP, _FP, _FP, _P, _FP, _FP, _FP,
                                      _P, c_size_t, _P]),
+    "mri3d_norm_act_pw_supported": (c_int32, [POINTER(NormGeom), c_int32]),
+    "mri3d_norm_act_pw_workspace_bytes": (c_size_t, [POINTER(NormGeom), c_int32]),
+    "mri3d_norm_act_pw_fwd": (c_int32, [POINTER(NormGeom), c_int32, _P, _FP, _FP, _FP, _FP, _FP, _FP, _FP, _P, _P]),
+    "mri3d_norm_act_pw_bwd": (c_int32, [POINTER(NormGeom), c_int32, c_int32, _P, _P, _FP, _FP, _FP, _FP, _FP, _FP, _P, _FP, _FP,
+                                        _FP, _FP, _FP, _P, c_size_t, _P]),
     "mri3d_maxpool3d_fwd": (c_int32, [POINTER(PoolGeom), _P, _P, _P, _P]),
     "mri3d_maxpool3d_bwd": (c_int32, [POINTER(PoolGeom), _P, _P, _P, _P]),
     "mri3d_maxpool3d_bwd_add": (c_int32, [POINTER(PoolGeom), _P, _P, _P, c_int32, _P, _P]),

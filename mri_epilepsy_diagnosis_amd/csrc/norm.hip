@@ -12,6 +12,7 @@
 // registers, are combined across the VT voxel rows through LDS once per block, and one partial per block goes to
 // the workspace.  A finalize kernel sums the partials in a fixed order in double precision (deterministic).
 #include "common.h"
+#include <algorithm>
 
 namespace mri3d {
 
@@ -301,13 +302,15 @@ norm_act_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __r
 
 // ------------------------------------------------------------------ backward: reductions
 // part[group][blk][c][3] = (sum du, sum du*xhat, sum dy*u*[u<=0])
-template <typename T, int VEC>
-__global__ void __launch_bounds__(256)
-norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, double* __restrict__ part,
-                           const float* __restrict__ mean, const float* __restrict__ invstd,
-                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                           const float* __restrict__ alpha, int alpha_n, int act, float slope, int C, int x_ld,
-                           int y_ld, int64_t gvox, int CL, int VT) {
+// DX: also write dx = gamma*invstd*du, the whole data gradient when the statistics do not depend on x (training == 0: eval-mode
+// BatchNorm, activation-only layers, the frozen-statistics formula of the sync mode) — one pass over x and dy instead of two.
+template <typename T, int VEC, bool DX>
+__device__ __forceinline__ void
+norm_act_bwd_reduce_body(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, double* __restrict__ part,
+                         const float* __restrict__ mean, const float* __restrict__ invstd,
+                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                         const float* __restrict__ alpha, int alpha_n, int act, float slope, int C, int x_ld,
+                         int y_ld, int64_t gvox, int CL, int VT) {
     __shared__ double red[256 * 3 * VEC];
     const int tid = threadIdx.x;
     const int cl = tid % CL, vt = tid / CL;
@@ -331,7 +334,9 @@ norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, do
         }
         const T* xg = x + (int64_t)group * gvox * x_ld;
         const T* dg = dy + (int64_t)group * gvox * y_ld;
-        auto accumulate = [&](const float (&xv)[VEC], const float (&gv)[VEC]) {
+        T* og = DX ? dx + (int64_t)group * gvox * x_ld : nullptr;
+        auto accumulate = [&](const float (&xv)[VEC], const float (&gv)[VEC], int64_t v) {
+            float ov[VEC];
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 float xh = (xv[j] - mu[j]) * is[j];
@@ -341,7 +346,9 @@ norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, do
                 s0[j] += (double)du;
                 s1[j] = fma((double)du, (double)xh, s1[j]);
                 s2[j] += pos ? 0.0 : (double)gv[j] * (double)u;
+                if constexpr (DX) ov[j] = (gm[j] * is[j]) * du;
             }
+            if constexpr (DX) Ld<VEC>::store(og + v * x_ld + c0, ov);
         };
         // two voxel rows per trip: four independent 16-byte loads in flight per lane, sums still in voxel order
         const int64_t step = (int64_t)gridDim.x * VT;
@@ -352,14 +359,14 @@ norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, do
             Ld<VEC>::load(dg + v * y_ld + c0, ga);
             Ld<VEC>::load(xg + (v + step) * x_ld + c0, xb);
             Ld<VEC>::load(dg + (v + step) * y_ld + c0, gb);
-            accumulate(xa, ga);
-            accumulate(xb, gb);
+            accumulate(xa, ga, v);
+            accumulate(xb, gb, v + step);
         }
         for (; v < gvox; v += step) {
             float xv[VEC], gv[VEC];
             Ld<VEC>::load(xg + v * x_ld + c0, xv);
             Ld<VEC>::load(dg + v * y_ld + c0, gv);
-            accumulate(xv, gv);
+            accumulate(xv, gv, v);
         }
     }
 #pragma unroll
@@ -384,6 +391,29 @@ norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, do
             o[2] = d;
         }
     }
+}
+
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256)
+norm_act_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy, double* __restrict__ part,
+                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                           const float* __restrict__ alpha, int alpha_n, int act, float slope, int C, int x_ld,
+                           int y_ld, int64_t gvox, int CL, int VT) {
+    norm_act_bwd_reduce_body<T, VEC, false>(x, dy, nullptr, part, mean, invstd, gamma, beta, alpha, alpha_n, act, slope, C, x_ld,
+                                            y_ld, gvox, CL, VT);
+}
+
+// training == 0 with a parameter gradient wanted: the sums AND dx in one pass (norm_act_bwd_apply_kernel's k1 = k2 = 0)
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256)
+norm_act_bwd_frozen_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, double* __restrict__ part,
+                           const float* __restrict__ mean, const float* __restrict__ invstd,
+                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                           const float* __restrict__ alpha, int alpha_n, int act, float slope, int C, int x_ld,
+                           int y_ld, int64_t gvox, int CL, int VT) {
+    norm_act_bwd_reduce_body<T, VEC, true>(x, dy, dx, part, mean, invstd, gamma, beta, alpha, alpha_n, act, slope, C, x_ld, y_ld,
+                                           gvox, CL, VT);
 }
 
 // Stage A: sums[group][c][3] = fixed-order double sums of the per-block partials.
@@ -545,6 +575,345 @@ norm_act_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* 
     }
 }
 
+
+// ------------------------------------------------------------------ norm + activation + pointwise head, fused
+// out = W . act(norm(x)) + b for a narrow 1x1x1 head (unet.UNet's 16 -> 2 classifier after its last conv -> BatchNorm -> PReLU
+// block): the activation a and its gradient da are never stored.  Lane = (voxel row, 4-channel quad), the QC = C/4 lanes of a
+// voxel are neighbours (the mapping of norm_act_* with VEC = 4 and of pw_fwd_kernel / pw_dgrad_kernel), so the arithmetic below
+// is theirs, expression for expression: the fp32 logits are bit-identical to norm_act_fwd_kernel + pw_fwd_kernel.  In bf16 the
+// values the two-operator path stores (a, da) are rounded through bf16 here too.
+struct NapArgs {
+    const float *mean, *invstd, *gamma, *beta, *alpha;
+    int alpha_n, act;
+    float slope;
+    int C, x_ld;
+    int64_t nvox;
+};
+
+constexpr int kNapMaxCo = 4;
+
+template <typename T>
+__device__ __forceinline__ float through_storage(float v) {
+    if constexpr (sizeof(T) == 2) return (float)(bf16_t)v;
+    else return v;
+}
+
+// per-lane constants of the forward: y = act(x * sc + sh), as norm_act_fwd_kernel forms them
+__device__ __forceinline__ void nap_fwd_consts(const NapArgs& p, int c0, float (&sc)[4], float (&sh)[4], float (&al)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int c = c0 + j;
+        float gm = p.gamma ? p.gamma[c] : 1.f;
+        float bt = p.beta ? p.beta[c] : 0.f;
+        float mu = p.mean ? p.mean[c] : 0.f;
+        float is = p.invstd ? p.invstd[c] : 1.f;
+        sc[j] = gm * is;
+        sh[j] = bt - mu * sc[j];
+        al[j] = (p.act == MRI3D_ACT_PRELU) ? p.alpha[p.alpha_n == 1 ? 0 : c] : p.slope;
+    }
+}
+
+template <typename T, int CO>
+__global__ void __launch_bounds__(256)
+norm_act_pw_fwd_kernel(const T* __restrict__ x, T* __restrict__ out, const float* __restrict__ w,
+                       const float* __restrict__ bias, int Co, int o_ld, NapArgs p) {
+    const int QC = p.C >> 2, VT = 256 / QC;
+    const int q = threadIdx.x % QC, vt = threadIdx.x / QC;
+    float sc[4], sh[4], al[4];
+    nap_fwd_consts(p, 4 * q, sc, sh, al);
+    float4 wq[CO];
+    float bq[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) {   // scalar loads: parameters may be views into a flat buffer (only 4-byte aligned)
+        const float* wr = w + (size_t)(co < Co ? co : 0) * p.C + 4 * q;
+        wq[co] = co < Co ? make_float4(wr[0], wr[1], wr[2], wr[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bq[co] = (bias != nullptr && co < Co) ? bias[co] : 0.f;
+    }
+    constexpr int U = 4;   // read-mostly pass: four voxel rows in flight (as pw_fwd_kernel and norm_stats_kernel)
+    const int64_t stride = (int64_t)gridDim.x * VT;
+    for (int64_t v0 = (int64_t)blockIdx.x * VT + vt; v0 < p.nvox; v0 += stride * U) {
+        float xv[U][4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {   // out-of-range voxels re-read the last one (every lane takes part in the exchanges below)
+            const int64_t v = v0 + u * stride;
+            Ld<4>::load(x + (v < p.nvox ? v : p.nvox - 1) * p.x_ld + 4 * q, xv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t v = v0 + u * stride;
+            float a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = through_storage<T>(apply_act(fmaf(xv[u][j], sc[j], sh[j]), p.act, al[j]));
+            float acc[CO];
+#pragma unroll
+            for (int co = 0; co < CO; ++co) {
+                float t = a[0] * wq[co].x;
+                t = fmaf(a[1], wq[co].y, t);
+                t = fmaf(a[2], wq[co].z, t);
+                t = fmaf(a[3], wq[co].w, t);
+                for (int d = 1; d < QC; d <<= 1) t += __shfl_xor(t, d, 64);   // the voxel's quads are QC neighbouring lanes
+                acc[co] = t + bq[co];
+            }
+            if (q == 0 && v < p.nvox) {
+                T* op = out + v * o_ld;
+#pragma unroll
+                for (int co = 0; co < CO; ++co)
+                    if (co < Co) stf(op + co, acc[co]);
+            }
+        }
+    }
+}
+
+// Where the backward kernels below take the gradient of the activation from.  Here: da = W^T dout of the pointwise head, with
+// the head's own parameter gradients (dw, dbias) as side sums.  Another source (a skip gradient plus a pool scatter) plugs in
+// with the same five members.
+template <typename T, int CO>
+struct PwHeadGrad {
+    struct Args {
+        const T* dout;
+        const float* w;
+        int Co, ld;
+    };
+    static constexpr int kCo = CO;         // gradient values loaded per voxel
+    static constexpr int kSide = 5 * CO;   // doubles per lane: dw[4][CO], dbias[CO]
+    const T* dout;
+    int Co, ld;
+    float4 wq[CO];
+    double dw[4][CO], db[CO];
+
+    __device__ __forceinline__ void init(const Args& a, int C, int q) {
+        dout = a.dout, Co = a.Co, ld = a.ld;
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+            const float* wr = a.w + (size_t)(co < Co ? co : 0) * C + 4 * q;
+            wq[co] = co < Co ? make_float4(wr[0], wr[1], wr[2], wr[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            db[co] = 0.0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dw[j][co] = 0.0;
+        }
+    }
+    __device__ __forceinline__ void load(int64_t v, float (&gv)[CO]) const {
+#pragma unroll
+        for (int co = 0; co < CO; ++co) gv[co] = co < Co ? ldf(dout + v * ld + co) : 0.f;
+    }
+    // pw_dgrad_kernel's order; the two-operator path stores da in the activation's storage type
+    __device__ __forceinline__ void grad(const float (&gv)[CO], float (&da)[4]) const {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+            acc.x = fmaf(gv[co], wq[co].x, acc.x);
+            acc.y = fmaf(gv[co], wq[co].y, acc.y);
+            acc.z = fmaf(gv[co], wq[co].z, acc.z);
+            acc.w = fmaf(gv[co], wq[co].w, acc.w);
+        }
+        da[0] = through_storage<T>(acc.x), da[1] = through_storage<T>(acc.y);
+        da[2] = through_storage<T>(acc.z), da[3] = through_storage<T>(acc.w);
+    }
+    // a = the forward's activation of this lane's quad (pw_wgrad_kernel: float product, double sum)
+    __device__ __forceinline__ void side(const float (&a)[4], const float (&gv)[CO], bool lead) {
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dw[j][co] += (double)(a[j] * gv[co]);
+            if (lead) db[co] += (double)gv[co];
+        }
+    }
+    // block partial: spart[blk][Co*C + Co] = (dw[co][c], dbias[co]), summed over the block's VT voxel rows in row order
+    __device__ __forceinline__ void flush(double* red, double* __restrict__ spart, int C, int QC, int VT) const {
+        const int tid = threadIdx.x;
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) red[tid * kSide + j * CO + co] = dw[j][co];
+            red[tid * kSide + 4 * CO + co] = db[co];
+        }
+        __syncthreads();
+        double* o = spart + (size_t)blockIdx.x * (Co * C + Co);
+        for (int e = tid; e < QC * 4 * CO; e += 256) {
+            const int co = e % CO, j = (e / CO) % 4, qq = e / (4 * CO);
+            double s = 0.0;
+            for (int l = 0; l < VT; ++l) s += red[(l * QC + qq) * kSide + j * CO + co];
+            if (co < Co) o[co * C + 4 * qq + j] = s;
+        }
+        if (tid < Co) {
+            double s = 0.0;
+            for (int l = 0; l < VT; ++l) s += red[(l * QC) * kSide + 4 * CO + tid];
+            o[Co * C + tid] = s;
+        }
+    }
+};
+
+// SUMS: the per-block partials of (sum du, sum du*xhat, sum da*u*[u<=0]) as norm_act_bwd_reduce_kernel forms them, plus the
+// source's side sums.  DX: dx = k0*du - k1 - xhat*k2 as norm_act_bwd_apply_kernel writes it.  Training statistics take two
+// launches (<true, false>, then <false, true> once the sums are combined); with frozen statistics k1 = k2 = 0 and <true, true>
+// does both in one pass.
+template <typename T, class SRC, bool SUMS, bool DX>
+__global__ void __launch_bounds__(256)
+norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SRC::Args sa, NapArgs p,
+                        const float* __restrict__ sums, int training, double* __restrict__ part, double* __restrict__ spart,
+                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dalpha) {
+    constexpr int kRed = SUMS ? (SRC::kSide > 12 ? SRC::kSide : 12) : 1;
+    __shared__ double red[256 * kRed];
+    // the parameter gradients ride on the first workgroup of the dx pass that follows the combined sums (uniform branch)
+    if (!SUMS && (dgamma != nullptr || dbeta != nullptr || dalpha != nullptr) && blockIdx.x == 0)
+        norm_act_bwd_params_block(sums, dgamma, dbeta, dalpha, p.alpha_n, p.C, 1);
+    const int QC = p.C >> 2, VT = 256 / QC;
+    const int tid = threadIdx.x;
+    const int q = tid % QC, vt = tid / QC;
+    const int c0 = 4 * q;
+    float mu[4], is[4], gm[4], bt[4], al[4], k0[4], k1[4], k2[4];
+    const float invM = 1.f / (float)p.nvox;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int c = c0 + j;
+        gm[j] = p.gamma ? p.gamma[c] : 1.f;
+        bt[j] = p.beta ? p.beta[c] : 0.f;
+        mu[j] = p.mean ? p.mean[c] : 0.f;
+        is[j] = p.invstd ? p.invstd[c] : 1.f;
+        al[j] = (p.act == MRI3D_ACT_PRELU) ? p.alpha[p.alpha_n == 1 ? 0 : c]
+                                            : (p.act == MRI3D_ACT_LEAKY ? p.slope : (p.act == MRI3D_ACT_RELU ? 0.f : 1.f));
+        k0[j] = gm[j] * is[j];
+        if (DX && !SUMS && training) {
+            k1[j] = k0[j] * sums[(size_t)c * 3] * invM;
+            k2[j] = k0[j] * sums[(size_t)c * 3 + 1] * invM;
+        } else {
+            k1[j] = 0.f;
+            k2[j] = 0.f;
+        }
+    }
+    float sc[4], sh[4], af[4];   // the forward's constants: the side sums want the activation exactly as the forward formed it
+    if constexpr (SUMS) nap_fwd_consts(p, c0, sc, sh, af);
+    SRC src;
+    src.init(sa, p.C, q);
+    double s0[4], s1[4], s2[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s0[j] = 0.0; s1[j] = 0.0; s2[j] = 0.0; }
+    auto row = [&](const float (&xv)[4], const float (&gv)[SRC::kCo], int64_t v) {
+        float da[4], ov[4];
+        src.grad(gv, da);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float xh = (xv[j] - mu[j]) * is[j];
+            float u = fmaf(gm[j], xh, bt[j]);
+            bool pos = u > 0.f;
+            float du = pos ? da[j] : da[j] * al[j];
+            if constexpr (SUMS) {
+                s0[j] += (double)du;
+                s1[j] = fma((double)du, (double)xh, s1[j]);
+                s2[j] += pos ? 0.0 : (double)da[j] * (double)u;
+            }
+            if constexpr (DX) ov[j] = fmaf(k0[j], du, -k1[j]) - xh * k2[j];
+        }
+        if constexpr (SUMS) {
+            float a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = through_storage<T>(apply_act(fmaf(xv[j], sc[j], sh[j]), p.act, af[j]));
+            src.side(a, gv, q == 0);
+        }
+        if constexpr (DX) Ld<4>::store(dx + v * p.x_ld + c0, ov);
+    };
+    // two voxel rows per trip, sums in voxel order
+    const int64_t step = (int64_t)gridDim.x * VT;
+    int64_t v = (int64_t)blockIdx.x * VT + vt;
+    for (; v + step < p.nvox; v += 2 * step) {
+        float xa[4], xb[4], ga[SRC::kCo], gb[SRC::kCo];
+        Ld<4>::load(x + v * p.x_ld + c0, xa);
+        src.load(v, ga);
+        Ld<4>::load(x + (v + step) * p.x_ld + c0, xb);
+        src.load(v + step, gb);
+        row(xa, ga, v);
+        row(xb, gb, v + step);
+    }
+    for (; v < p.nvox; v += step) {
+        float xv[4], gv[SRC::kCo];
+        Ld<4>::load(x + v * p.x_ld + c0, xv);
+        src.load(v, gv);
+        row(xv, gv, v);
+    }
+    if constexpr (SUMS) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            red[(tid * 4 + j) * 3] = s0[j];
+            red[(tid * 4 + j) * 3 + 1] = s1[j];
+            red[(tid * 4 + j) * 3 + 2] = s2[j];
+        }
+        __syncthreads();
+        if (vt == 0) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double a = 0.0, b = 0.0, d = 0.0;
+                for (int l = 0; l < VT; ++l) {
+                    a += red[((l * QC + q) * 4 + j) * 3];
+                    b += red[((l * QC + q) * 4 + j) * 3 + 1];
+                    d += red[((l * QC + q) * 4 + j) * 3 + 2];
+                }
+                double* o = part + ((size_t)blockIdx.x * p.C + c0 + j) * 3;
+                o[0] = a;
+                o[1] = b;
+                o[2] = d;
+            }
+        }
+        __syncthreads();
+        src.flush(red, spart, p.C, QC, VT);
+    }
+}
+
+// dw[co][c], dbias[co] = fixed-order double sums of the per-block side partials: 256 threads = 8 elements x 32 partial lanes
+__global__ void __launch_bounds__(256)
+norm_act_pw_wsum_kernel(const double* __restrict__ spart, float* __restrict__ dw, float* __restrict__ dbias, int nb, int nw,
+                        int Co) {
+    __shared__ double red[256];
+    const int el = threadIdx.x >> 5, ql = threadIdx.x & 31;
+    const int ntot = nw + Co;
+    const int i = blockIdx.x * 8 + el;
+    double s = 0.0;
+    if (i < ntot)
+        for (int b = ql; b < nb; b += 32) s += spart[(size_t)b * ntot + i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if (ql == 0 && i < ntot) {
+        double t = 0.0;
+        for (int k = 0; k < 32; ++k) t += red[el * 32 + k];
+        if (i < nw) {
+            if (dw != nullptr) dw[i] = (float)t;
+        } else if (dbias != nullptr) {
+            dbias[i - nw] = (float)t;
+        }
+    }
+}
+
+struct NapPlan {
+    int QC, VT, nblk;
+    size_t part_off, sums_off, side_off, bytes;   // byte offsets into the workspace
+};
+
+static bool nap_supported(const Mri3dNormGeom& g, int co) {
+    if (g.dtype != MRI3D_F32 && g.dtype != MRI3D_BF16) return false;
+    if (g.n <= 0 || g.vox <= 0 || g.instance || g.group_c != 0) return false;
+    const int qc = g.c / 4;
+    if (g.c <= 0 || g.c % 4 != 0 || qc > 16 || (qc & (qc - 1)) != 0) return false;
+    if (co < 1 || co > kNapMaxCo) return false;
+    if (g.x_ld < g.c || g.x_ld % 4 != 0 || g.y_ld < co) return false;
+    if (g.act < MRI3D_ACT_NONE || g.act > MRI3D_ACT_PRELU) return false;
+    if (g.act == MRI3D_ACT_PRELU && g.alpha_n != 1 && g.alpha_n != g.c) return false;
+    return true;
+}
+
+static NapPlan nap_plan(const Mri3dNormGeom& g, int co) {
+    NapPlan p;
+    p.QC = g.c / 4;
+    p.VT = 256 / p.QC;
+    const int64_t nvox = (int64_t)g.n * g.vox;
+    const int64_t want = cdiv64(nvox, (int64_t)p.VT * 8);   // >= 8 voxel rows per thread, as norm_plan
+    p.nblk = (int)(want < kNormMaxBlocks ? want : kNormMaxBlocks);
+    if (p.nblk < 1) p.nblk = 1;
+    p.part_off = 0;
+    p.sums_off = (size_t)p.nblk * g.c * 3 * sizeof(double);
+    p.side_off = p.sums_off + align_up((size_t)g.c * 3 * sizeof(float), sizeof(double));
+    p.bytes = p.side_off + (size_t)p.nblk * (co * g.c + co) * sizeof(double);
+    return p;
+}
+
 }  // namespace mri3d
 
 using namespace mri3d;
@@ -667,6 +1036,22 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
         const T* xf = static_cast<const T*>(x);
         const T* df = static_cast<const T*>(dy);
         T* of = static_cast<T*>(dx);
+        if (need_reduce && !training) {
+            // nothing in dx depends on the sums: one pass writes dx and the per-block partials, then the two small kernels
+            if (p.vec == 4)
+                hipLaunchKernelGGL((norm_act_bwd_frozen_kernel<T, 4>), grid, dim3(256), 0, s, xf, df, of, part, mean, invstd,
+                                   gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
+                                   p.VT);
+            else if (p.vec == 1)
+                hipLaunchKernelGGL((norm_act_bwd_frozen_kernel<T, 1>), grid, dim3(256), 0, s, xf, df, of, part, mean, invstd,
+                                   gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
+                                   p.VT);
+            hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(p.groups * g->c, 256 / kFinQL)), dim3(256), 0, s, part,
+                               sums, g->c, p.nblk, p.groups);
+            hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g->alpha_n,
+                               g->c, p.groups);
+            return check_launch("norm_act_bwd");
+        }
         if (need_reduce) {
             if (p.vec == 4)
                 hipLaunchKernelGGL((norm_act_bwd_reduce_kernel<T, 4>), grid, dim3(256), 0, s, xf, df, part, mean, invstd,
@@ -702,4 +1087,108 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
                                p.CL, p.VT, g->group_c, pg, pb, pa);
     });
     return check_launch("norm_act_bwd");
+}
+
+extern "C" int32_t mri3d_norm_act_pw_supported(const Mri3dNormGeom* g, int32_t co) {
+    return (g != nullptr && nap_supported(*g, co)) ? 1 : 0;
+}
+
+extern "C" size_t mri3d_norm_act_pw_workspace_bytes(const Mri3dNormGeom* g, int32_t co) {
+    if (g == nullptr || !nap_supported(*g, co)) return 0;
+    return nap_plan(*g, co).bytes;
+}
+
+static NapArgs nap_args(const Mri3dNormGeom& g, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                        const float* alpha) {
+    NapArgs a;
+    a.mean = mean, a.invstd = invstd, a.gamma = gamma, a.beta = beta, a.alpha = alpha;
+    a.alpha_n = g.alpha_n, a.act = g.act, a.slope = g.slope, a.C = g.c, a.x_ld = g.x_ld;
+    a.nvox = (int64_t)g.n * g.vox;
+    return a;
+}
+
+extern "C" int mri3d_norm_act_pw_fwd(const Mri3dNormGeom* g, int32_t co, const void* x, const float* mean, const float* invstd,
+                                     const float* gamma, const float* beta, const float* alpha, const float* w,
+                                     const float* bias, void* out, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "norm_act_pw_fwd: null geometry");
+    MRI3D_REQUIRE(nap_supported(*g, co), MRI3D_ENOTSUP, "norm_act_pw_fwd: c=%d co=%d x_ld=%d y_ld=%d instance=%d not served",
+                  g->c, co, g->x_ld, g->y_ld, g->instance);
+    MRI3D_REQUIRE(x && w && out, MRI3D_EINVAL, "norm_act_pw_fwd: null pointer");
+    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pw_fwd: mean/invstd must both be set");
+    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pw_fwd: PReLU needs alpha");
+    MRI3D_REQUIRE(aligned_vec4(g->dtype, x), MRI3D_EINVAL, "norm_act_pw_fwd: x must be aligned to 4 elements");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
+    const int VT = 256 / (g->c / 4);
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(a.nvox, (int64_t)VT * 4), kMaxStreamBlocks));
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, {
+        if (co <= 2)
+            hipLaunchKernelGGL((norm_act_pw_fwd_kernel<T, 2>), dim3(grid), dim3(256), 0, s, (const T*)x, (T*)out, w, bias, co,
+                               g->y_ld, a);
+        else
+            hipLaunchKernelGGL((norm_act_pw_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, (const T*)x, (T*)out, w, bias, co,
+                               g->y_ld, a);
+    });
+    return check_launch("norm_act_pw_fwd");
+}
+
+template <typename T, int CO>
+static void nap_bwd_launch(const Mri3dNormGeom& g, int co, int training, const T* x, const T* dout, const float* w, T* dx,
+                           float* dgamma, float* dbeta, float* dalpha, float* dw, float* dbias, const NapArgs& a,
+                           const NapPlan& p, char* ws, hipStream_t s) {
+    using SRC = PwHeadGrad<T, CO>;
+    const typename SRC::Args sa = {dout, w, co, g.y_ld};
+    double* part = reinterpret_cast<double*>(ws + p.part_off);
+    float* sums = reinterpret_cast<float*>(ws + p.sums_off);
+    double* spart = reinterpret_cast<double*>(ws + p.side_off);
+    const dim3 grid(p.nblk), blk(256);
+    const bool params = dgamma || dbeta || dalpha;
+    const bool need_sums = training || params || dw || dbias;
+    if (need_sums) {
+        if (training || dx == nullptr)
+            hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, true, false>), grid, blk, 0, s, x, dx, sa, a, sums, training,
+                               part, spart, dgamma, dbeta, dalpha);
+        else   // frozen statistics: dx does not wait for the sums
+            hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, true, true>), grid, blk, 0, s, x, dx, sa, a, sums, training,
+                               part, spart, dgamma, dbeta, dalpha);
+        hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(g.c, 256 / kFinQL)), dim3(256), 0, s, part, sums, g.c, p.nblk, 1);
+        if (dw || dbias)
+            hipLaunchKernelGGL(norm_act_pw_wsum_kernel, dim3(cdiv(co * g.c + co, 8)), dim3(256), 0, s, spart, dw, dbias, p.nblk,
+                               co * g.c, co);
+        if (params && !(training && dx != nullptr))
+            hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g.alpha_n, g.c,
+                               1);
+    }
+    if (dx != nullptr && (training || !need_sums))
+        hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, false, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
+                           spart, dgamma, dbeta, dalpha);
+}
+
+extern "C" int mri3d_norm_act_pw_bwd(const Mri3dNormGeom* g, int32_t co, int training, const void* x, const void* dout,
+                                     const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                     const float* alpha, const float* w, void* dx, float* dgamma, float* dbeta, float* dalpha,
+                                     float* dw, float* dbias, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "norm_act_pw_bwd: null geometry");
+    MRI3D_REQUIRE(nap_supported(*g, co), MRI3D_ENOTSUP, "norm_act_pw_bwd: c=%d co=%d x_ld=%d y_ld=%d instance=%d not served",
+                  g->c, co, g->x_ld, g->y_ld, g->instance);
+    MRI3D_REQUIRE(x && dout && w, MRI3D_EINVAL, "norm_act_pw_bwd: null pointer");
+    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pw_bwd: mean/invstd must both be set");
+    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "norm_act_pw_bwd: training mode needs statistics");
+    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pw_bwd: PReLU needs alpha");
+    MRI3D_REQUIRE(aligned_vec4(g->dtype, x, dx), MRI3D_EINVAL, "norm_act_pw_bwd: x and dx must be aligned to 4 elements");
+    const NapPlan p = nap_plan(*g, co);
+    MRI3D_REQUIRE(workspace && ws_bytes >= p.bytes && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, MRI3D_EWORKSPACE,
+                  "norm_act_pw_bwd: workspace %zu < %zu (or not 8-byte aligned)", ws_bytes, p.bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
+    char* ws = static_cast<char*>(workspace);
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, {
+        if (co <= 2)
+            nap_bwd_launch<T, 2>(*g, co, training, (const T*)x, (const T*)dout, w, (T*)dx, dgamma, dbeta, dalpha, dw, dbias, a, p, ws,
+                                 s);
+        else
+            nap_bwd_launch<T, 4>(*g, co, training, (const T*)x, (const T*)dout, w, (T*)dx, dgamma, dbeta, dalpha, dw, dbias, a, p, ws,
+                                 s);
+    });
+    return check_launch("norm_act_pw_bwd");
 }

@@ -70,10 +70,48 @@ def fused_norm_act(norm, act, x, out=None):
     raise NotImplementedError("unsupported normalisation module %r" % (norm,))
 
 
-def conv_norm_act(conv, norm, act, x, out=None):
+def _plain_pointwise(head):
+    return (isinstance(head, Conv3d) and tuple(head.kernel_size) == (1, 1, 1) and tuple(head.stride) == (1, 1, 1)
+            and tuple(head.dilation) == (1, 1, 1) and head.groups == 1 and head.padding_mode == "zeros"
+            and not isinstance(head.padding, str) and tuple(head.padding) == (0, 0, 0))
+
+
+def fused_norm_act_head(norm, act, x, head):
+    """head(act(norm(x))) as ONE operator (ops.norm_act_pointwise) where that is served: `head` a plain 1x1x1 Conv3d with at most
+    four output channels, `norm` a BatchNorm3d with local batch or running statistics (or None), channels and layout as the native
+    predicate asks.  Returns None — with nothing run and no counter touched — where it is not: the caller keeps the two operators."""
+    if not _plain_pointwise(head):
+        return None
+    kind, alpha, slope = _act_spec(act)
+    cast = ops.autocast_dtype()
+    if cast is not None and x.dtype != cast:   # the head's conv3d would convert its input first
+        return None
+    if norm is None:
+        mode, args = "none", (None, None, alpha, None, None, "none", 0.1, 0.0)
+    elif isinstance(norm, tnn.modules.batchnorm._BatchNorm):
+        use_batch = norm.training or norm.running_mean is None
+        if use_batch and norm.training and ops.sync_batchnorm_reducer() is not None:
+            return None
+        if norm.momentum is None:
+            return None
+        mode = "batch" if use_batch else "running"
+        args = (norm.weight, norm.bias, alpha, norm.running_mean if norm.track_running_stats else None,
+                norm.running_var if norm.track_running_stats else None, mode, norm.momentum, norm.eps)
+    else:
+        return None
+    if not ops.norm_act_pointwise_supported(x, head.weight, mode, kind, alpha):
+        return None
+    if mode != "none" and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
+        norm.num_batches_tracked.add_(1)
+    return ops.norm_act_pointwise(x, head.weight, head.bias, *args, act=kind, slope=slope)
+
+
+def conv_norm_act(conv, norm, act, x, out=None, head=None):
     """act(norm(conv(x))) for a Conv3d module followed by a normalisation (`unet.UNet`'s ConvolutionalBlock, the conv -> BN ->
     ReLU stems of cnn_model.py).  When `norm` is a BatchNorm3d that will use BATCH statistics (training mode, local statistics)
-    the convolution is asked to accumulate them in its epilogue, which saves the statistics pass over its output."""
+    the convolution is asked to accumulate them in its epilogue, which saves the statistics pass over its output.
+    head: a Conv3d module applied to the result (`unet.UNet`'s 1x1x1 classifier); the return value is then head(act(norm(conv(x)))),
+    computed without storing the activation where `fused_norm_act_head` serves the case."""
     wants = (isinstance(norm, tnn.modules.batchnorm._BatchNorm) and (norm.training or norm.running_mean is None)
              and ops.sync_batchnorm_reducer() is None and isinstance(conv, Conv3d) and conv.padding_mode == "zeros"
              and conv.groups == 1 and not isinstance(conv.padding, str))
@@ -90,6 +128,9 @@ def conv_norm_act(conv, norm, act, x, out=None):
         y = ops.conv3d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, bn_stats=True)
     else:
         y = conv(x)
+    if head is not None:
+        logits = fused_norm_act_head(norm, act, y, head) if out is None else None
+        return logits if logits is not None else head(fused_norm_act(norm, act, y, out))
     return fused_norm_act(norm, act, y, out)
 
 

@@ -989,6 +989,132 @@ def norm_act(x, gamma=None, beta=None, alpha=None, running_mean=None, running_va
                             group_c, fused)
 
 
+def _head_geom(x, x_ld, o_ld, act_code, alpha, slope, eps):
+    n, c, d, h, w = x.shape
+    alpha_n = alpha.numel() if act_code == ACT_PRELU else 1
+    return NormGeom(n, d * h * w, c, x_ld, o_ld, 0, act_code, alpha_n, float(slope), float(eps), 0, _dt(x))
+
+
+def norm_act_pointwise_supported(x, weight, stats_mode="batch", act=None, alpha=None):
+    """True when `norm_act_pointwise` serves act(norm(x)) followed by the 1x1x1 convolution `weight` (co, c, 1, 1, 1) as one
+    operator: the native predicate on the geometry, plus what only the caller can see (statistics mode, memory layout)."""
+    if stats_mode not in ("batch", "running", "none") or act not in _ACT_CODES:
+        return False
+    if not (x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (1, 1, 1) or weight.shape[1] != x.shape[1] or weight.dtype != torch.float32:
+        return False
+    x_ld = _pitch_of(x)
+    if x_ld is None:
+        x_ld = x.shape[1]          # _nd makes a dense copy
+    elif x.data_ptr() % (4 * x.element_size()):
+        return False
+    g = _head_geom(x, x_ld, weight.shape[0], _ACT_CODES[act], alpha if alpha is not None else weight, 0.0, 0.0)
+    return bool(_lib.lib().mri3d_norm_act_pw_supported(ctypes.byref(g), weight.shape[0]))
+
+
+class _NormActPointwiseFn(torch.autograd.Function):
+    """logits = conv1x1x1(act(gamma * (x - mean) / sqrt(var + eps) + beta), weight, bias) with batch, running or no statistics:
+    the activation between the two operators and its gradient are never stored (mri3d_norm_act_pw_*)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, alpha, weight, bias, running_mean, running_var, stats_mode, momentum, eps, act, slope,
+                fused_stats=None):
+        _require_device(x)
+        _require_param(gamma, beta, alpha, weight, bias)
+        ctx.params = (gamma, beta, alpha, weight, bias)
+        L = _lib.lib()
+        x, x_ld = _nd(x)
+        n, c, d, h, w = x.shape
+        co = weight.shape[0]
+        act_code = _ACT_CODES[act]
+        wm = weight.contiguous()
+        g = _head_geom(x, x_ld, co, act_code, alpha, slope, eps)
+        if not L.mri3d_norm_act_pw_supported(ctypes.byref(g), co):
+            raise RuntimeError("norm_act_pointwise: c=%d co=%d pitch %d is not served (ask norm_act_pointwise_supported first)"
+                               % (c, co, x_ld))
+        mean = invstd = None
+        gn = _head_geom(x, x_ld, x_ld, act_code, alpha, slope, eps)   # the statistics entry points: y_ld is a pitch of c channels
+        if stats_mode == "batch":
+            mean = torch.empty(c, dtype=torch.float32, device=x.device)
+            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+            upd = running_mean is not None
+            if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
+                part, blocks, shift = fused_stats
+                with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
+                    check(L.mri3d_norm_stats_from_partials(ctypes.byref(gn), _ptr(part), blocks, _ptr(shift), _ptr(mean),
+                                                           _ptr(invstd), _ptr(running_mean) if upd else None,
+                                                           _ptr(running_var) if upd else None, float(momentum), _stream()),
+                          "norm_stats_from_partials")
+            else:
+                ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(gn)), x.device)
+                with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
+                    check(L.mri3d_norm_stats(ctypes.byref(gn), _ptr(x), _ptr(mean), _ptr(invstd),
+                                             _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None,
+                                             float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
+        elif stats_mode == "running":
+            mean = running_mean.detach().to(torch.float32).contiguous()
+            invstd = torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous()
+        elif stats_mode != "none":
+            raise RuntimeError("norm_act_pointwise: statistics mode %r is not served" % (stats_mode,))
+        out = _new((n, co, d, h, w), x)
+        with _timed(lambda: "norm_act_pw_fwd c%d->%d vox%d n%d" % (c, co, g.vox, n),
+                    lambda: {"flops": 2.0 * co * c * n * g.vox, "bytes": _esz(x) * (x.numel() + out.numel())}):
+            check(L.mri3d_norm_act_pw_fwd(ctypes.byref(g), co, _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
+                                          _ptr(alpha) if act_code == ACT_PRELU else None, _ptr(wm), _ptr(bias), _ptr(out),
+                                          _stream()), "norm_act_pw_fwd")
+        ctx.save_for_backward(x, mean, invstd, gamma, beta, alpha, wm)
+        ctx.geom = g
+        ctx.training_stats = stats_mode == "batch"
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        x, mean, invstd, gamma, beta, alpha, wm = ctx.saved_tensors
+        g0 = ctx.geom
+        co = wm.shape[0]
+        dout, o_ld = _nd(dout)
+        if dout.dtype != x.dtype:
+            raise RuntimeError("norm_act_pointwise backward: gradient dtype %s does not match activation dtype %s" % (dout.dtype, x.dtype))
+        if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
+            x = x.contiguous(memory_format=CL3D)
+        g = NormGeom(g0.n, g0.vox, g0.c, g0.c, o_ld, 0, g0.act, g0.alpha_n, g0.slope, g0.eps, 0, g0.dtype)
+        pg, pb, pa, pw, pbias = ctx.params
+        prelu = g.act == ACT_PRELU
+        need = ctx.needs_input_grad
+        want = (gamma is not None and need[1], beta is not None and need[2], prelu and need[3], need[4],
+                pbias is not None and need[5])
+        srcs = (gamma, beta, alpha, wm, pbias)
+        sinks = [_sink_take(p) if wt else None for p, wt in zip(ctx.params, want)]
+        grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
+                 for sk, t, wt in zip(sinks, srcs, want)]
+        dx = _new(x.shape, x) if need[0] else None
+        ws = _workspace(L.mri3d_norm_act_pw_workspace_bytes(ctypes.byref(g), co), x.device)
+        # training statistics: x and dout are read twice and dx written once; frozen statistics: one read
+        reads = 2 if ctx.training_stats else 1
+        with _timed(lambda: "norm_act_pw_bwd c%d->%d vox%d n%d" % (g.c, co, g.vox, g.n),
+                    lambda: {"flops": 4.0 * co * g.c * g.n * g.vox,
+                             "bytes": _esz(x) * (reads * (x.numel() + dout.numel()) + (x.numel() if dx is not None else 0))}):
+            check(L.mri3d_norm_act_pw_bwd(ctypes.byref(g), co, 1 if ctx.training_stats else 0, _ptr(x), _ptr(dout), _ptr(mean),
+                                          _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(alpha) if prelu else None, _ptr(wm),
+                                          _ptr(dx), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
+                                          _ptr(grads[4]), _ptr(ws), ws.numel(), _stream()), "norm_act_pw_bwd")
+        outs = [_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks)]
+        return (dx, outs[0], outs[1], outs[2], outs[3], outs[4], None, None, None, None, None, None, None, None)
+
+
+def norm_act_pointwise(x, weight, bias=None, gamma=None, beta=None, alpha=None, running_mean=None, running_var=None,
+                       stats_mode="batch", momentum=0.1, eps=1e-5, act=None, slope=0.01):
+    """conv3d(norm_act(x, ...), weight, bias) for a 1x1x1 `weight` with at most four output channels, as one operator (see
+    `norm_act_pointwise_supported`); the producer's fused BatchNorm statistics are picked up from x as `norm_act` does."""
+    if momentum is None:
+        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
+    fused = getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+    return _NormActPointwiseFn.apply(x, gamma, beta, alpha, weight, bias, running_mean, running_var, stats_mode, momentum, eps,
+                                     act, slope, fused)
+
+
 def activation(x, act, alpha=None, slope=0.01):
     return norm_act(x, None, None, alpha, None, None, "none", 0.1, 0.0, act, slope)
 

@@ -44,8 +44,9 @@ class ConvolutionalBlock(tnn.Module):
         self.dropout_layer = None
         self.block = tnn.Sequential(*[m for m in (conv, norm, act) if m is not None])
 
-    def forward(self, x, out=None):
-        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out)
+    def forward(self, x, out=None, head=None):
+        # head: the classifier's 1x1x1 Conv3d, applied to this block's result (mnn.conv_norm_act)
+        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out, head)
 
 
 class EncodingBlock(tnn.Module):
@@ -67,11 +68,11 @@ class EncodingBlock(tnn.Module):
                 raise NotImplementedError("only max pooling is used by the reference")
             self.downsample = mnn.MaxPool3d(kernel_size=2)
 
-    def forward(self, x, skip_out=None):
+    def forward(self, x, skip_out=None, head=None):
         # skip_out = (concat buffer, 0): the block's output is written straight into the decoder's concat buffer
-        x = self.conv2(self.conv1(x), skip_out)
         if self.downsample is None:
-            return x
+            return self.conv2(self.conv1(x), skip_out, head)
+        x = self.conv2(self.conv1(x), skip_out)
         # (pooled, skip) from one autograd node: the two gradients of x are summed inside the pool-backward kernel
         return self.downsample.forward_with_skip(x)
 
@@ -126,19 +127,19 @@ class DecodingBlock(tnn.Module):
                                         normalization=normalization, padding=padding, activation=activation,
                                         dilation=dilation)
 
-    def forward(self, skip, x, cat_buf=None):
+    def forward(self, skip, x, cat_buf=None, head=None):
         if cat_buf is not None and isinstance(self.upsample, mnn.Upsample):
             # copy-free torch.cat((skip, up)) through a shared buffer: `skip` already lives in cat_buf[:, :Cs]; the upsample kernel
             # writes cat_buf[:, Cs:]; join_channels only ties the two producers together for autograd (skip first: SURVEY A.3)
             up = ops.upsample3d(x, self.upsample.size, self.upsample.scale_factor, self.upsample.mode,
                                 self.upsample.align_corners, out=(cat_buf, skip.shape[1]))
-            return self.conv2(self.conv1(ops.join_channels(cat_buf, [skip, up])))
+            return self.conv2(self.conv1(ops.join_channels(cat_buf, [skip, up])), head=head)
         x = self.upsample(x)
         if skip.shape[2:] != x.shape[2:]:
             raise NotImplementedError("padding=False (centre-cropped skips) is not used by the reference")
         # cat((skip, x)) is never formed: the first convolution reads the two dense tensors (ops.conv3d_cat) and hands back two
         # dense gradients.  Slice writes into a shared 3C-channel buffer cost 1.5x (fp32) - 3.6x (bf16) of dense writes.
-        return self.conv2(self.conv1((skip, x)))
+        return self.conv2(self.conv1((skip, x)), head=head)
 
 
 class Decoder(tnn.Module):
@@ -155,9 +156,11 @@ class Decoder(tnn.Module):
             if self.dilation is not None:
                 self.dilation //= 2
 
-    def forward(self, skips, x, cat_bufs=None):
+    def forward(self, skips, x, cat_bufs=None, head=None):
+        # head: applied to the last block's result (see UNet.forward)
+        last = min(len(skips), len(self.decoding_blocks)) - 1
         for j, (skip, blk) in enumerate(zip(reversed(skips), self.decoding_blocks)):
-            x = blk(skip, x, None if cat_bufs is None else cat_bufs[len(skips) - 1 - j])
+            x = blk(skip, x, None if cat_bufs is None else cat_bufs[len(skips) - 1 - j], head if j == last else None)
         return x
 
 
@@ -186,6 +189,9 @@ class UNet(tnn.Module):
                                activation=activation, initial_dilation=self.encoder.dilation)
         self.monte_carlo_layer = None
         self.shared_concat_buffers = False   # round 1's concat-buffer scheme (A/B switch; not part of the reference's API)
+        # the classifier's 1x1x1 convolution runs inside the last block's BatchNorm + activation pass (A/B switch; not part of the
+        # reference's API): same logits bit for bit in fp32, without the full-resolution activation in between
+        self.fused_head = True
         self.classifier = ConvolutionalBlock(dimensions, 2 * out_channels_first_layer, out_classes, kernel_size=1,
                                              activation=None)
 
@@ -203,7 +209,13 @@ class UNet(tnn.Module):
                     break
                 cat_bufs.append(ops.new_cat_buffer(n, 3 * blk.out_channels, sp, x))
                 sp = tuple(s // 2 for s in sp)
+        # the classifier as a plain 1x1x1 convolution (no normalisation, no activation of its own) can ride on the last block
+        clf = self.classifier
+        head = clf.conv_layer if (self.fused_head and x.is_cuda and clf.norm_layer is None and clf.activation_layer is None
+                                  and clf.dropout_layer is None) else None
         skips, enc = self.encoder(x, cat_bufs)
+        if not skips:
+            return self.bottom_block(enc, head=head) if head is not None else self.classifier(self.bottom_block(enc))
         enc = self.bottom_block(enc)
-        x = self.decoder(skips, enc, cat_bufs)
-        return self.classifier(x)
+        x = self.decoder(skips, enc, cat_bufs, head)
+        return x if head is not None else self.classifier(x)

@@ -1,0 +1,364 @@
+"""The 1x1x1 classifier folded into the last BatchNorm + activation passes (ops.norm_act_pointwise, mri3d_norm_act_pw_*) and the
+one-pass backward of norm_act with frozen statistics.
+
+Bars.  fp32 logits of the fused operator are BIT-EQUAL to norm_act followed by conv3d (same expressions in the same order).
+Gradients, and everything in bf16, may group their sums differently; they are held against a float64 CPU evaluation of the same
+(for bf16: storage-rounded) inputs:  rel_err(fused, ref) <= max(2 * rel_err(unfused, ref), 4 * eps), eps = 2^-23 (fp32) or 2^-8
+(bf16) — the factor 2 covers regrouped double-precision partial sums — and, in fp32, the project's REL_TOL on top."""
+import copy
+import ctypes
+import re
+
+import pytest
+import torch
+
+from guard import SentinelSlice, guarded, kernels_launched
+from util import REL_TOL, rel_err, to_ncdhw
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+CL3D = torch.channels_last_3d
+EPS = {torch.float32: 2.0 ** -23, torch.bfloat16: 2.0 ** -8}
+
+
+def _dev(t, dtype=torch.float32):
+    return t.to(DEV).to(dtype).contiguous(memory_format=CL3D) if t.dim() == 5 else t.to(DEV)
+
+
+def _held(name, fused, unfused, ref, dtype, scale=None):
+    """`scale`: the magnitude the errors are relative to when the reference itself is zero by construction (see the model test);
+    the comparison of the two errors with each other does not depend on it, only the 4 * eps floor and REL_TOL do."""
+    if scale is None:
+        ef, eu = rel_err(fused, ref), rel_err(unfused, ref)
+    else:
+        ef, eu = ((v.detach().double().cpu() - ref).abs().max().item() / scale for v in (fused, unfused))
+    bound = max(2.0 * eu, 4.0 * EPS[dtype])
+    print("%-8s fused %.3e  unfused %.3e  bound %.3e" % (name, ef, eu, bound))
+    assert ef <= bound, "%s: fused %.3e vs unfused %.3e (bound %.3e)" % (name, ef, eu, bound)
+    if dtype == torch.float32:
+        assert ef <= REL_TOL, "%s: %.3e > REL_TOL" % (name, ef)
+
+
+def _inputs(n, c, co, sp, mode, act, alpha_n, bias, dtype, seed):
+    g = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=g)
+    p = {"x": r(n, c, *sp) * 1.5 + 0.3, "dout": r(n, co, *sp), "w": r(co, c, 1, 1, 1) * 0.3, "b": r(co) if bias else None,
+         "gamma": None, "beta": None, "alpha": None, "rm": None, "rv": None}
+    if mode != "none":
+        p["gamma"], p["beta"] = 1.0 + 0.2 * r(c), 0.2 * r(c)
+        p["rm"], p["rv"] = 0.3 + 0.1 * r(c), 2.0 + 0.3 * torch.rand(c, generator=g)
+    if act == "prelu":
+        p["alpha"] = 0.25 + 0.1 * torch.rand(alpha_n, generator=g)
+    if dtype == torch.bfloat16:   # the reference sees the values the kernels see
+        p["x"], p["dout"] = p["x"].bfloat16().float(), p["dout"].bfloat16().float()
+    return p
+
+
+def _reference(p, mode, act, eps=1e-5):
+    """float64 CPU: logits and the gradients of sum(logits * dout)."""
+    leaf = {k: (v.double().requires_grad_(True) if v is not None and k not in ("dout", "rm", "rv") else v) for k, v in p.items()}
+    x, bc = leaf["x"], (lambda v: v[None, :, None, None, None])
+    if mode == "batch":
+        mean, var = x.mean((0, 2, 3, 4)), x.var((0, 2, 3, 4), unbiased=False)
+    elif mode == "running":
+        mean, var = p["rm"].double(), p["rv"].double()
+    u = x if mode == "none" else (x - bc(mean)) / torch.sqrt(bc(var) + eps) * bc(leaf["gamma"]) + bc(leaf["beta"])
+    if act == "prelu":
+        al = leaf["alpha"]
+        a = torch.where(u > 0, u, u * (bc(al) if al.numel() > 1 else al))
+    else:
+        a = torch.relu(u) if act == "relu" else u
+    out = torch.einsum("ncdhw,oc->nodhw", a, leaf["w"][:, :, 0, 0, 0])
+    if leaf["b"] is not None:
+        out = out + bc(leaf["b"])
+    out.backward(p["dout"].double())
+    res = {"out": out.detach()}
+    for k in ("x", "gamma", "beta", "alpha", "w", "b"):
+        res["d" + k] = leaf[k].grad if leaf[k] is not None else None
+    if mode == "batch":   # torch's update: momentum 0.1, unbiased variance
+        cnt = x.numel() / x.shape[1]
+        res["rm"] = 0.9 * p["rm"].double() + 0.1 * mean.detach()
+        res["rv"] = 0.9 * p["rv"].double() + 0.1 * var.detach() * cnt / (cnt - 1)
+    return res
+
+
+def _run(p, mode, act, dtype, fused):
+    from mri_epilepsy_diagnosis_amd import ops
+    t = {k: (_dev(v, dtype if k in ("x", "dout") else torch.float32) if v is not None else None) for k, v in p.items()}
+    for k in ("x", "gamma", "beta", "alpha", "w", "b"):
+        if t[k] is not None:
+            t[k].requires_grad_(True)
+    if fused:
+        assert ops.norm_act_pointwise_supported(t["x"], t["w"], mode, act, t["alpha"]), "the predicate declined a listed case"
+        out = ops.norm_act_pointwise(t["x"], t["w"], t["b"], t["gamma"], t["beta"], t["alpha"], t["rm"], t["rv"], mode, 0.1, 1e-5, act)
+    else:
+        a = ops.norm_act(t["x"], t["gamma"], t["beta"], t["alpha"], t["rm"], t["rv"], mode, 0.1, 1e-5 if mode != "none" else 0.0, act)
+        out = ops.conv3d(a, t["w"], t["b"])
+    out.backward(t["dout"])
+    torch.cuda.synchronize()
+    res = {"out": to_ncdhw(out).float(), "rm": t["rm"], "rv": t["rv"]}
+    for k in ("x", "gamma", "beta", "alpha", "w", "b"):
+        gk = t[k].grad if t[k] is not None else None
+        res["d" + k] = None if gk is None else (to_ncdhw(gk).float() if gk.dim() == 5 and k == "x" else gk.detach().float().cpu())
+    return res
+
+
+# (n, c, co, spatial), statistics, activation, alpha_n, head bias, dtype
+S1, S2, S3, S4, S5 = (2, 16, 2, (5, 6, 7)), (1, 8, 1, (3, 5, 9)), (2, 32, 3, (4, 7, 5)), (1, 64, 4, (3, 4, 5)), (2, 16, 2, (17, 20, 23))
+CASES = [
+    (S1, "batch", "prelu", 1, True, torch.float32),
+    (S1, "batch", "prelu", 16, False, torch.bfloat16),
+    (S2, "running", "relu", 1, False, torch.float32),
+    (S2, "batch", "prelu", 8, True, torch.float32),
+    (S3, "none", "prelu", 32, True, torch.float32),
+    (S3, "batch", "relu", 1, False, torch.float32),
+    (S4, "batch", None, 1, False, torch.float32),
+    (S4, "running", "prelu", 1, True, torch.float32),
+    (S5, "batch", "prelu", 16, True, torch.float32),
+    (S5, "none", "relu", 1, False, torch.float32),
+    (S5, "running", "prelu", 1, True, torch.bfloat16),
+    (S5, "batch", "prelu", 1, True, torch.bfloat16),
+]
+
+
+@pytest.mark.parametrize("shape,mode,act,alpha_n,bias,dtype", CASES,
+                         ids=["%dx%d-%d_%s_%s%d_%s_%s" % (s[0], s[1], s[2], m, a, an, "b" if b else "nob", "bf16" if d == torch.bfloat16 else "f32")
+                              for s, m, a, an, b, d in CASES])
+def test_fused_operator_against_unfused_and_float64(shape, mode, act, alpha_n, bias, dtype):
+    n, c, co, sp = shape
+    p = _inputs(n, c, co, sp, mode, act, alpha_n, bias, dtype, seed=c * 100 + co)
+    ref = _reference(p, mode, act)
+    un = _run(p, mode, act, dtype, fused=False)
+    fu = _run(p, mode, act, dtype, fused=True)
+    if dtype == torch.float32:
+        assert torch.equal(fu["out"], un["out"]), "fp32 logits moved: max |diff| %.3e" % (fu["out"] - un["out"]).abs().max().item()
+    _held("out", fu["out"], un["out"], ref["out"], dtype)
+    for k in ("dx", "dgamma", "dbeta", "dalpha", "dw", "db"):
+        assert (fu[k] is None) == (ref[k] is None) == (un[k] is None), k
+        if ref[k] is not None:
+            _held(k, fu[k], un[k], ref[k], dtype)
+    if mode == "batch":     # running statistics after the call: the same statistics kernel, so the same bits; and right
+        for k in ("rm", "rv"):
+            assert torch.equal(fu[k], un[k]), k
+            assert rel_err(fu[k], ref[k]) <= REL_TOL, k
+    elif mode == "running":
+        assert torch.equal(fu["rm"].cpu(), p["rm"]) and torch.equal(fu["rv"].cpu(), p["rv"])
+
+
+def _geom(n, vox, c, x_ld, o_ld, act, alpha_n, dtype=0, instance=0):
+    from mri_epilepsy_diagnosis_amd import _lib
+    return _lib.NormGeom(n, vox, c, x_ld, o_ld, instance, act, alpha_n, 0.0, 1e-5, 0, dtype)
+
+
+@pytest.mark.parametrize("c,co,mode", [(12, 2, "batch"), (6, 2, "batch"), (16, 5, "batch"), (16, 2, "instance")])
+def test_predicate_declines_and_the_model_keeps_two_operators(c, co, mode):
+    from mri_epilepsy_diagnosis_amd import _lib, ops
+    from mri_epilepsy_diagnosis_amd.unet import UNet
+    L = _lib.lib()
+    g = _geom(1, 512, c, c, co, _lib.ACT_PRELU, 1, instance=1 if mode == "instance" else 0)
+    assert L.mri3d_norm_act_pw_supported(ctypes.byref(g), co) == 0
+    assert L.mri3d_norm_act_pw_workspace_bytes(ctypes.byref(g), co) == 0
+    x = torch.randn(1, c, 8, 8, 8, device=DEV).contiguous(memory_format=CL3D)
+    w = torch.randn(co, c, 1, 1, 1, device=DEV)
+    assert not ops.norm_act_pointwise_supported(x, w, mode, "prelu", torch.full((1,), 0.25, device=DEV))
+    torch.manual_seed(0)
+    net = UNet(in_channels=1, out_classes=co, dimensions=3, num_encoding_blocks=2, out_channels_first_layer=c // 2,
+               normalization=mode, upsampling_type="linear", padding=True, activation="PReLU").to(DEV)
+    assert net.fused_head
+    xin = torch.randn(1, 1, 8, 8, 8, device=DEV)
+    out, names = kernels_launched(lambda: net(xin))
+    assert out.shape == (1, co, 8, 8, 8) and bool(torch.isfinite(out).all())
+    assert not any("norm_act_pw" in k for k in names), names
+    net.fused_head = False      # train mode: the result does not depend on the running statistics the first call advanced
+    assert torch.equal(net(xin), out)
+
+
+def _raw(L, g, co, training, t, ws, ws_bytes, out, dx, dw, db, dgamma, dbeta, dalpha):
+    from mri_epilepsy_diagnosis_amd import _lib
+    P = lambda v: None if v is None else ctypes.c_void_p(v.data_ptr())
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(L.mri3d_norm_act_pw_fwd(ctypes.byref(g), co, P(t["x"]), P(t["mean"]), P(t["invstd"]), P(t["gamma"]), P(t["beta"]),
+                                       P(t["alpha"]), P(t["w"]), P(t["b"]), P(out), s), "fwd")
+    _lib.check(L.mri3d_norm_act_pw_bwd(ctypes.byref(g), co, training, P(t["x"]), P(t["dout"]), P(t["mean"]), P(t["invstd"]),
+                                       P(t["gamma"]), P(t["beta"]), P(t["alpha"]), P(t["w"]), P(dx), P(dgamma), P(dbeta), P(dalpha),
+                                       P(dw), P(db), P(ws), ws_bytes, s), "bwd")
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("training", [1, 0])
+def test_buffers_guards_exact_workspace_and_pitched_out(training):
+    """Guard bands around out, dx, dw, dbias; the workspace at exactly the queried size, poisoned with 0xA5 and with NaN, gives the
+    bits of the roomy grow-only one; `out` as channels [1, 3) of a 4-channel buffer leaves channels 0 and 3 alone."""
+    from mri_epilepsy_diagnosis_amd import _lib
+    L = _lib.lib()
+    n, c, co, sp = S5
+    vox = sp[0] * sp[1] * sp[2]
+    p = _inputs(n, c, co, sp, "batch", "prelu", c, True, torch.float32, seed=7)
+    t = {k: (_dev(v) if v is not None else None) for k, v in p.items()}
+    t["mean"], t["invstd"] = t["rm"], torch.rsqrt(t["rv"] + 1e-5)
+    g = _geom(n, vox, c, c, 4, _lib.ACT_PRELU, c)          # out / dout: pitch 4
+    need = L.mri3d_norm_act_pw_workspace_bytes(ctypes.byref(g), co)
+    assert need > 0 and L.mri3d_norm_act_pw_supported(ctypes.byref(g), co) == 1
+    dout4 = torch.zeros(n, 4, *sp, device=DEV).contiguous(memory_format=CL3D)
+    dout4[:, 1:3] = t["dout"]
+    t["dout"] = dout4[:, 1:3]
+    assert t["dout"].data_ptr() == dout4.data_ptr() + 4
+
+    def once(ws_bytes, poison):
+        out = SentinelSlice(n, 4, sp, torch.float32, 1, co)
+        dx = guarded((n, *sp, c), torch.float32)
+        dw, db = guarded(co * c, torch.float32), guarded(co, torch.float32)
+        dg, dbt, da = (torch.empty(c, device=DEV) for _ in range(3))
+        ws = guarded(ws_bytes, torch.uint8)
+        if poison == "nan":
+            ws.flat[:ws_bytes // 8 * 8].view(torch.float64).fill_(float("nan"))
+        else:
+            ws.flat.fill_(0xA5)
+        _raw(L, g, co, training, t, ws.flat, ws_bytes, out.slice, dx.region, dw.region, db.region, dg, dbt, da)
+        out.assert_outside_intact("out")
+        for gd, what in ((dx, "dx"), (dw, "dw"), (db, "dbias"), (ws, "workspace")):
+            gd.assert_guards_intact(what)
+        assert not bool(out.slice_untouched().any()) and not bool(dx.untouched().any())
+        assert not bool(dw.untouched().any()) and not bool(db.untouched().any())
+        return [v.clone() for v in (out.slice, dx.region, dw.region, db.region, dg, dbt, da)]
+
+    roomy = once(need + (1 << 20), "a5")
+    for poison in ("a5", "nan"):
+        for a, b in zip(once(need, poison), roomy):
+            assert bool(torch.isfinite(a).all()) and torch.equal(a, b), poison
+
+
+def _model(seed=0):
+    from mri_epilepsy_diagnosis_amd.unet import UNet
+    torch.manual_seed(seed)
+    return UNet(in_channels=1, out_classes=2, dimensions=3, num_encoding_blocks=3, out_channels_first_layer=8,
+                normalization="batch", upsampling_type="linear", padding=True, activation="PReLU")
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 16, 16, 16), (2, 1, 16, 24, 16)])
+def test_model_fused_head_equals_two_operator_head(shape):
+    from mri_epilepsy_diagnosis_amd import ops
+    from oracle import losses, unet_recon
+    base = _model()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(*shape, generator=g)
+    t = (torch.rand(*shape, generator=g) < 0.2).float()
+    orc = unet_recon.UNetRecon(out_channels_first_layer=8)
+    orc.load_state_dict(base.state_dict())
+    orc.double()
+    losses.softmax_dice_loss(orc(x.double()), t.double()).backward()
+    ref = {k: v.grad for k, v in orc.named_parameters()}
+    runs = {}
+    for fused in (True, False):
+        net = copy.deepcopy(base).to(DEV)
+        net.fused_head = fused
+        fn = lambda: net(x.to(DEV))
+        logits, names = kernels_launched(fn)
+        loss = ops.softmax_dice_loss(logits, t.to(DEV))
+        loss.backward()
+        net.eval()
+        with torch.no_grad():
+            ev = net(x.to(DEV))
+        runs[fused] = (logits.detach(), loss.detach(), {k: v.grad for k, v in net.named_parameters()}, ev, names,
+                       net.decoder.decoding_blocks[-1].conv2.norm_layer)
+    (lf, ff, gf, ef, nf, bnf), (lu, fu, gu, eu, nu, bnu) = runs[True], runs[False]
+    assert lf.shape == lu.shape and lf.dtype == lu.dtype and lf.is_contiguous(memory_format=CL3D)
+    assert torch.equal(lf, lu), "train-mode logits"
+    assert torch.equal(ff, fu), "loss"
+    assert torch.equal(ef, eu), "eval-mode logits"
+    assert int(bnf.num_batches_tracked) == int(bnu.num_batches_tracked) == 1
+    assert torch.equal(bnf.running_mean, bnu.running_mean) and torch.equal(bnf.running_var, bnu.running_var)
+    # A conv bias in front of a train-mode BatchNorm has a gradient that is zero by construction: the float64 reference holds
+    # 1e-17 of rounding noise there and an error relative to it means nothing in any fp32 implementation.  Those tensors (as in
+    # test_models_gpu.py: reference below 1e-6 of the model's largest gradient) are held by the same bound with the errors taken
+    # relative to the model's largest gradient instead of to the tensor's own; they can only be such biases.
+    gmax = max(v.abs().max().item() for v in ref.values())
+    zero = [k for k, v in ref.items() if v.abs().max().item() < 1e-6 * gmax]
+    assert all(k.endswith("conv_layer.bias") and k != "classifier.conv_layer.bias" for k in zero), zero
+    for k in ref:
+        _held(k, gf[k], gu[k], ref[k], torch.float32, scale=gmax if k in zero else None)
+    # launches of the forward
+    assert any("norm_act_pw_fwd_kernel" in k for k in nf) and not any("norm_act_pw" in k for k in nu)
+    assert not any(("pw_fwd_kernel" in k and "norm_act_pw" not in k) for k in nf), nf
+
+
+def test_model_fused_head_launches():
+    """A whole step with the fused head: no pointwise-conv kernel at all and one norm_act_fwd_kernel launch fewer."""
+    from torch.profiler import ProfilerActivity, profile
+    from mri_epilepsy_diagnosis_amd import ops
+    x = torch.randn(1, 1, 16, 16, 16, device=DEV)
+    t = (torch.rand(1, 1, 16, 16, 16, device=DEV) < 0.2).float()
+    counts = {}
+    for fused in (True, False):
+        net = _model().to(DEV)
+        net.fused_head = fused
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            ops.softmax_dice_loss(net(x), t).backward()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        counts[fused] = names
+    plain = lambda names, key: sum(1 for k in names if key in k and "norm_act_pw" not in k)
+    for key in ("pw_fwd_kernel", "pw_dgrad_kernel", "pw_wgrad_kernel"):
+        assert plain(counts[True], key) == 0, key
+        assert plain(counts[False], key) == 1, key
+    assert plain(counts[True], "norm_act_fwd_kernel") == plain(counts[False], "norm_act_fwd_kernel") - 1
+    assert sum(1 for k in counts[True] if "norm_act_src_bwd_kernel" in k) == 2
+
+
+def test_captured_step_with_fused_head_replays_eager_bit_exactly():
+    from mri_epilepsy_diagnosis_amd import ops, parallel
+    net = _model(3).to(DEV)
+    assert net.fused_head
+    flat = parallel.FlatParams(net)
+    x = torch.randn(1, 1, 16, 16, 16, device=DEV)
+    t = (torch.rand(1, 1, 16, 16, 16, device=DEV) < 0.2).float()
+    cap = parallel.CapturedStep(flat, lambda: ops.softmax_dice_loss(net(x), t)).capture()
+    state = {k: v.clone() for k, v in net.state_dict().items()}
+    net.load_state_dict(state)
+    l_g, g_g = cap.run().clone(), flat.grad.clone()
+    net.load_state_dict(state)
+    l_e = cap._eager().clone()
+    assert torch.equal(l_g, l_e) and torch.equal(g_g, flat.grad) and g_g.abs().max().item() > 0
+    cap.release()
+
+
+@pytest.mark.parametrize("shape", [(3, 8, (6, 10, 7)), (2, 12, (5, 7, 3))])
+@pytest.mark.parametrize("vec", [4, 1])
+@pytest.mark.parametrize("mode", ["none", "running"])
+def test_frozen_statistics_backward_is_one_pass(shape, vec, mode):
+    """norm_act backward with statistics that do not depend on x (activation only; eval-mode BatchNorm): against torch on the CPU,
+    and the reduce kernel is no longer launched.  vec 1: x at a 4-byte offset, so the kernels cannot use vector accesses."""
+    import torch.nn.functional as F
+    from mri_epilepsy_diagnosis_amd import ops
+    n, c, sp = shape
+    g = torch.Generator().manual_seed(c)
+    xr = (torch.randn(n, c, *sp, generator=g) * 1.5).requires_grad_(True)
+    dy = torch.randn(n, c, *sp, generator=g)
+    alpha = (0.25 + 0.1 * torch.rand(c, generator=g)).requires_grad_(True)
+    gamma = (1.0 + 0.2 * torch.randn(c, generator=g)).requires_grad_(True)
+    beta = (0.2 * torch.randn(c, generator=g)).requires_grad_(True)
+    rm, rv = 0.1 * torch.randn(c, generator=g), 1.0 + torch.rand(c, generator=g)
+    u = xr if mode == "none" else F.batch_norm(xr, rm, rv, gamma, beta, False, 0.1, 1e-5)
+    F.prelu(u, alpha).backward(dy)
+
+    if vec == 4:
+        xd = xr.detach().to(DEV).contiguous(memory_format=CL3D)
+    else:
+        store = torch.empty(xr.numel() + 1, device=DEV)
+        xd = store[1:].view(n, *sp, c).permute(0, 4, 1, 2, 3)
+        xd.copy_(xr.detach())
+        assert xd.data_ptr() % 16 == 4
+    xd.requires_grad_(True)
+    ad = alpha.detach().to(DEV).requires_grad_(True)
+    gd, bd = (gamma.detach().to(DEV).requires_grad_(True), beta.detach().to(DEV).requires_grad_(True)) if mode == "running" else (None, None)
+    y = ops.norm_act(xd, gd, bd, ad, rm.to(DEV) if mode == "running" else None, rv.to(DEV) if mode == "running" else None, mode,
+                     0.1, 1e-5 if mode == "running" else 0.0, "prelu")
+    _, names = kernels_launched(lambda: y.backward(_dev(dy)))
+    assert any(re.search(r"norm_act_bwd_frozen_kernel<float,\s*%d>" % vec, k) for k in names), names
+    assert not any("norm_act_bwd_reduce_kernel" in k or "norm_act_bwd_apply_kernel" in k for k in names), names
+    assert rel_err(to_ncdhw(xd.grad), xr.grad) <= REL_TOL
+    assert rel_err(ad.grad.cpu(), alpha.grad) <= REL_TOL
+    if mode == "running":
+        assert rel_err(gd.grad.cpu(), gamma.grad) <= REL_TOL and rel_err(bd.grad.cpu(), beta.grad) <= REL_TOL
