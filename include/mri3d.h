@@ -373,6 +373,35 @@ int mri3d_aggregate_patches_argmax(const void* logits, int32_t c, int32_t ld, in
                                    uint8_t* out, int32_t nvol, int32_t d, int32_t h, int32_t w, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Augmentation: the random stages of the reference's TorchIO `training_transform`
+ * (segmentation/results_validation.ipynb, the `training_transform = Compose([...])` cell; pretraining_3d_unet.ipynb cell 24:
+ * RandomBiasField, RandomFlip(axes=(0,)), OneOf({RandomAffine(): 0.8, RandomElasticDeformation(): 0.2}); applied through
+ * torchio.ImagesDataset(subjects, transform=transform), segmentation/routine.py:91).  Third-party arithmetic, absent from the
+ * reference tree: defined here and restated in tests/augment_ref.py ("parity unpinned").  Random parameters are drawn by the
+ * caller on the host; both entries are deterministic.
+ *   warp3d:  resamples `s` contiguous (d,h,w) volumes.  For output voxel o = (d,h,w) of subject n, in voxel indices,
+ *              src = A[n][:, :3] o + A[n][:, 3] + u_n(o)        A: DEVICE (s,3,4) fp32, row-major
+ *            u_n = 0 when `grid` is NULL, else the tensor-product uniform cubic B-spline over the DEVICE control grid
+ *            (s,3,gd,gh,gw) fp32 (component, then d,h,w; every g >= 4, gw <= 64): per axis of extent N with m = g - 3,
+ *            p = (o + 0.5) m / N, i = clamp(floor p, 0, m - 1), f = p - i, weights (1-f)^3/6, (3f^3-6f^2+4)/6,
+ *            (-3f^3+3f^2+3f+1)/6, f^3/6 on control points i .. i+3.
+ *            A sample is inside when -0.5 <= src_a <= N_a - 0.5 on all axes.  image (fp32, may be NULL with image_out):
+ *            trilinear over floor(src), floor(src)+1 with indices clamped to the volume; outside: pad_values[n] when
+ *            `pad_values` (DEVICE, s floats) is given, else pad_value.  label (label_bytes = 1, 2 or 4, raw bits, may be NULL
+ *            with label_out): the element at clamp(floor(src + 0.5)); outside: zero bits.  Both are written in one pass.
+ *            No destination may overlap a source, the other destination or a parameter buffer (MRI3D_EINVAL).
+ *   bias_field: y = x * exp(P(xh,yh,zh)), (xh,yh,zh) = the voxel's (d,h,w) mapped to np.linspace(-1,1,N) per axis (0 when
+ *            N == 1); P = sum c_ijk xh^i yh^j zh^k over i in 0..order, j in 0..order-i, k in 0..order-i-j, coefficients in
+ *            that nesting order: coef_host is a HOST array of s x (order+1)(order+2)(order+3)/6 floats handed to the kernel by
+ *            value.  order <= 3 (MRI3D_ENOTSUP above).  y == x (in place) is allowed, a partial overlap is not.
+ * ---------------------------------------------------------------------------------------------- */
+int mri3d_warp3d(const float* image, float* image_out, const void* label, void* label_out, int32_t label_bytes, int32_t s,
+                 int32_t d, int32_t h, int32_t w, const float* affine, const float* grid, int32_t gd, int32_t gh, int32_t gw,
+                 float pad_value, const float* pad_values, mri3d_stream_t stream);
+int mri3d_bias_field_f32(const float* x, float* y, int32_t s, int32_t d, int32_t h, int32_t w, const float* coef_host,
+                         int32_t order, mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Channel-slice plumbing: torch.cat along channels (unet.UNet decoder, modified_3dunet.py:158-178) and
  * residual adds (modified_3dunet.py:108, cnn_model.py:34).
  *   copy: dst[v, 0:c] = src[v, 0:c]      add: dst[v, 0:c] = a[v,0:c] + b[v,0:c]

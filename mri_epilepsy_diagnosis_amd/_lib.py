@@ -114,6 +114,9 @@ SIGNATURES = {
                                              c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_aggregate_patches_argmax": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, c_int32,
                                                  c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    "mri3d_warp3d": (c_int32, [_FP, _FP, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _FP, _FP, c_int32, c_int32,
+                               c_int32, c_float, _FP, _P]),
+    "mri3d_bias_field_f32": (c_int32, [_FP, _FP, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),
     "mri3d_copy_channels": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_add_channels": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_convert_channels": (c_int32, [_P, c_int32, _P, c_int32, c_int64, c_int32, c_int32, c_int32, _P]),

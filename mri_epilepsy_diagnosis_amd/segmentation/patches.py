@@ -13,6 +13,7 @@ whole batch of windows is cut by ONE `mri3d_extract_patches` launch per image (o
 predicted label windows are written back by `mri3d_aggregate_patches_{u8,argmax}`, the second taking the arg-max of the
 logits in flight so no label tensor is materialised.  Window origins are host integers; there is no CPU data path.
 """
+import copy
 import ctypes
 
 import numpy as np
@@ -255,10 +256,16 @@ class Queue:
     `shuffle_subjects`), shuffled when `shuffle_patches`, and popped from the end, as TorchIO's does.  The random stream is
     numpy's `default_rng(seed)`, not TorchIO's — which windows are drawn is a property of the seed, not of the reference.
     `num_workers` is accepted for signature compatibility; nothing is loaded, so there is nothing to parallelise.
+
+    `transform` (a `transforms.Transform`, e.g. the reference's `training_transform`): every fill augments the subjects it
+    picked into a scratch batch — parameters per subject from the queue's generator, one `mri3d_warp3d` launch for the whole
+    batch — and every window is cut from the batch of the fill that drew it (a batch that straddles a refill is cut in two
+    segments); `out["subject"]` still reports the original subject index and
+    `last_fill` records what was drawn.  With `transform=None` nothing changes.
     """
 
     def __init__(self, subjects_dataset, max_length, samples_per_volume, patch_size, sampler_class=ImageSampler,
-                 num_workers=0, shuffle_subjects=True, shuffle_patches=True, seed=0):
+                 num_workers=0, shuffle_subjects=True, shuffle_patches=True, seed=0, transform=None):
         self.subjects = list(subjects_dataset)
         if not self.subjects:
             raise ValueError("Queue: no subjects")
@@ -281,6 +288,8 @@ class Queue:
                                      % (tuple(v.shape), shape0))
             self._resident[name] = torch.cat(vols, dim=0).contiguous()  # (S, D, H, W) in HBM
         self.shape = shape0[1:]
+        self.transform, self.last_fill = transform, None
+        self._scratch, self._slot_subject = None, None   # the augmented batch of the last fill and its original indices
         self.patches_list = np.empty((0, 4), dtype=np.int32)  # (subject index, d0, h0, w0); popped from the end
         self._order, self._next = [], 0
 
@@ -296,13 +305,36 @@ class Queue:
         self._next += 1
         return s
 
+    def _augment(self, picked):
+        """Scratch batch {name: (n, D', H', W')} of the picked subjects under freshly drawn parameters; returns its shape."""
+        from . import transforms as T
+        plans, params, shape = [], [], self.shape
+        for _ in picked:
+            steps, shape = self.transform.plan(self.shape, self.rng)
+            plans.append(T.fold(steps))
+            params.append(copy.deepcopy(self.transform.last_params))
+        index = torch.as_tensor(picked, device=self._resident[self.names[0]].device)
+        batch = {name: v.index_select(0, index) for name, v in self._resident.items()}
+        images, labels = T.execute({k: v for k, v in batch.items() if k != LABEL}, {k: v for k, v in batch.items() if k == LABEL},
+                                   plans)
+        self._scratch = {name: (labels if name == LABEL else images)[name].contiguous() for name in self.names}
+        self._slot_subject = np.asarray(picked, dtype=np.int64)
+        self.last_fill = {"subjects": list(picked), "params": params}
+        return tuple(shape)
+
     def fill(self):
         n_subjects = min(self.max_length // self.samples_per_volume, len(self.subjects))
         spv = self.samples_per_volume
         new = np.empty((n_subjects * spv, 4), dtype=np.int32)
+        shape = self.shape
+        if self.transform is not None:
+            if len(self.patches_list):
+                raise RuntimeError("Queue.fill: with a transform the scratch batch is replaced, so only an empty queue is refilled")
+            picked = [self._next_subject() for _ in range(n_subjects)]
+            shape = self._augment(picked)
         for i in range(n_subjects):
-            sampler = self.sampler_class(self.shape, self.patch_size, self.rng)
-            new[i * spv:(i + 1) * spv, 0] = self._next_subject()
+            sampler = self.sampler_class(shape, self.patch_size, self.rng)
+            new[i * spv:(i + 1) * spv, 0] = i if self.transform is not None else self._next_subject()
             if hasattr(sampler, "draw"):
                 new[i * spv:(i + 1) * spv, 1:] = sampler.draw(spv)
             else:
@@ -325,15 +357,34 @@ class Queue:
         return np.ascontiguousarray(np.concatenate(parts))
 
     def _cut(self, table):
-        out = {name: {DATA: extract_patches(v, table, self.patch_size)} for name, v in self._resident.items()}
+        source = self._resident if self.transform is None else self._scratch   # with a transform, column 0 is the scratch slot
+        out = {name: {DATA: extract_patches(v, table, self.patch_size)} for name, v in source.items()}
         ini = table[:, 1:].astype(np.int64)
         out[LOCATION] = torch.from_numpy(np.concatenate([ini, ini + np.asarray(self.patch_size)], axis=1))
-        out["subject"] = torch.from_numpy(table[:, 0].astype(np.int64))
+        subject = table[:, 0].astype(np.int64)
+        out["subject"] = torch.from_numpy(subject if self.transform is None else self._slot_subject[subject])
         return out
+
+    def _take(self, n):
+        """The next n windows, cut.  With a transform a fill replaces the scratch batch, so a request that straddles a refill is
+        cut in segments: the rows left over from the old fill from its scratch batch BEFORE the refill, the rest after it."""
+        if self.transform is None:
+            return self._cut(self._pop(n))
+        parts = []
+        while n > 0:
+            if len(self.patches_list) == 0:
+                self.fill()
+            k = min(n, len(self.patches_list))
+            parts.append(self._cut(self._pop(k)))   # k rows are there: this _pop never refills
+            n -= k
+        if len(parts) == 1:
+            return parts[0]
+        return {key: ({DATA: torch.cat([p[key][DATA] for p in parts])} if isinstance(v, dict) else torch.cat([p[key] for p in parts]))
+                for key, v in parts[0].items()}
 
     def __getitem__(self, _):
         """One window (the DataLoader protocol of the reference: the index is ignored, the queue decides)."""
-        b = self._cut(self._pop(1))
+        b = self._take(1)
         return {k: ({DATA: v[DATA][0]} if isinstance(v, dict) else v[0]) for k, v in b.items()}
 
     def batches(self, batch_size, drop_last=False):
@@ -343,5 +394,5 @@ class Queue:
             n = min(int(batch_size), left)
             if n < int(batch_size) and drop_last:
                 return
-            yield self._cut(self._pop(n))
+            yield self._take(n)
             left -= n
