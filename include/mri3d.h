@@ -80,10 +80,25 @@ int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, vo
 /* WHICH KERNEL the entry points above (split == 0) or the *_cat entry points below (split > 0, second_ld = pitch of the second
  * tensor) launch for this geometry.  Host only: no device is needed, nothing is launched; the entry points take their backend
  * from the same decision.  pass: MRI3D_PASS_*; stats != 0: the forward with fused statistics (mri3d_conv3d_fwd_stats, or a
- * non-NULL stat_partials of mri3d_conv3d_fwd_cat); bias != 0: a bias pointer is passed; align: the largest power of two <= 16
- * that divides the base address of every tensor and of the workspace.  name (at least 32 bytes) receives, as a C string:
+ * non-NULL stat_partials of mri3d_conv3d_fwd_cat); bias != 0: a bias pointer is passed; align_x / align_y: the largest power of
+ * two <= 16 that divides the base address of the x-side tensor (x, or dx in the data gradient; with a split: of both input
+ * tensors) / of the y-side tensor (y, or dy in the gradients).  The workspace counts as 16-byte aligned.  The 3x3x3 MFMA kernels
+ * need both tensors at 16, the pointwise kernels the x-side tensor at four elements; the generic kernels test each tensor on
+ * its own.  name (at least 32 bytes) receives, as a C string whose first word is the kernel file:
  *   "none"       the entry point refuses (MRI3D_ENOTSUP): only with stats or a split
- *   "generic"    csrc/conv_generic.hip         "pointwise"  csrc/conv_pointwise.hip (1x1x1)
+ *   "generic ..."    csrc/conv_generic.hip — the kernel, then the template arguments and branches that select code; a data gradient
+ *                    that adds a bias (the forward of a ConvTranspose3d) ends in " bias":
+ *     "generic c1c1"                        conv_c1c1_stencil_kernel / conv_c1c1_wgrad_kernel (1 -> 1 channel, 3x3x3)
+ *     "generic c1taps nt{3,8}"              conv_c1_taps_kernel / conv_c1_taps_wgrad_kernel<NT> (1 -> 1 channel, <= 8 taps, fp32)
+ *     "generic cin1 co{8,16}"               conv_cin1_fwd_kernel / conv_cin1_wgrad_kernel<T, CO> (first layer, one input channel)
+ *     "generic taps tl{16,8,4,2} nt{3,4,6,8} cv{4,1}"   conv_fwd_taps_kernel / conv_dgrad_taps_kernel<T, TL, NT, CV> (<= 8 taps)
+ *     "generic gather tl{..} vec{0,1}"      conv_fwd_generic_kernel / conv_dgrad_generic_kernel<T, TL, VEC4>
+ *     "generic staps tl{..} nt{3,4,8}"      conv_dgrad_strided_taps_kernel<T, TL, NT> (strided data gradient, <= 8 valid taps)
+ *     "generic strided tl{..} vec{0,1}"     conv_dgrad_strided_kernel<T, TL, VEC4>
+ *     weight gradient: "generic co1 ci{1,4,8,16}" conv_wgrad_co1_kernel<T, CI>, "generic quads nt{4,6,8} civ{4,1}"
+ *     conv_wgrad_quads_kernel<T, NT, CIV>, "generic small" conv_wgrad_small_kernel, "generic lds" conv_wgrad_generic_kernel
+ *   "pointwise ..."  csrc/conv_pointwise.hip (1x1x1): "pointwise co{2,4}" pw_fwd_kernel<T, CO>, "pointwise co{2,4,8}[ bias]"
+ *                    pw_dgrad_kernel<T, CO>, "pointwise co{2,4,8} vx{4,8} dv{0,1}" pw_wgrad_kernel<T, CO, VX, DYV>
  *   forward / data gradient on the 3x3x3 MFMA kernels — the kernel, then the template arguments that select code in it:
  *   "march[ stats][ bias]"                conv_march_kernel<T, STATS, BIAS>
  *   "direct nt{1,2,4} mode{0,1} split{0,1}"  conv_mfma_direct_kernel<T, NT, MODE, SPLIT> (mode 1: strided data gradient; split 1: the
@@ -94,7 +109,7 @@ int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, vo
  * Grids, tile counts and other run-time arguments are not part of a name.  The names are stable: the test suite pins its parity
  * cases to them. */
 int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
-                       int32_t align, char* name, size_t name_bytes);
+                       int32_t align_x, int32_t align_y, char* name, size_t name_bytes);
 
 /* Convolution over torch.cat((x, x2), dim=1) WITHOUT the concatenation — `unet.UNet`'s decoder, x = cat((skip, upsampled))
  * in front of its first ConvolutionalBlock (segmentation/routine.py:346-356 -> unet DecodingBlock.forward).  g describes the

@@ -58,7 +58,7 @@ SIGNATURES = {
     "mri3d_conv3d_fwd_stats": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_dgrad": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_wgrad": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, c_size_t, _P]),
-    "mri3d_conv3d_route": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "mri3d_conv3d_route": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "mri3d_conv3d_cat_supported": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32]),
     "mri3d_conv3d_fwd_cat_stats_blocks": (c_int32, [POINTER(ConvGeom), c_int32, c_int32]),
     "mri3d_conv3d_fwd_cat": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),

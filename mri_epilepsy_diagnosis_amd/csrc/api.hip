@@ -47,13 +47,6 @@ static int conv_check(const Mri3dConvGeom* g, const char* who, int first_ci = -1
 // align_pw: that of the tensor the pointwise kernels access four elements at a time.
 enum class ConvBackend { none, generic, pointwise, mfma };
 
-// largest power of two <= 16 that divides every given address (a null pointer divides by everything)
-static int ptr_align(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-                           reinterpret_cast<uintptr_t>(d) | 16;
-    return (int)(bits & (~bits + 1));
-}
-
 static ConvBackend conv_backend(const Mri3dConvGeom& g, int pass, bool stats, int split, int second_ld, int align_mfma, int align_pw) {
     const bool mfma_aligned = align_mfma >= 16;                                  // aligned16
     const bool pw_aligned = align_pw >= (g.dtype == MRI3D_BF16 ? 8 : 16);        // aligned_vec4
@@ -225,9 +218,9 @@ extern "C" int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const v
     }
 }
 
-// ---- which kernel would run (host only): the backend decision above, then the MFMA file's own route by name
+// ---- which kernel would run (host only): the backend decision above, then the chosen file's own plan by name
 extern "C" int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
-                                  int32_t align, char* name, size_t name_bytes) {
+                                  int32_t align_x, int32_t align_y, char* name, size_t name_bytes) {
     int rc = conv_check(g, "conv3d_route", split > 0 ? split : -1);
     if (rc) return rc;
     MRI3D_REQUIRE(name != nullptr && name_bytes >= 32, MRI3D_EINVAL, "conv3d_route: name buffer of at least 32 bytes required");
@@ -236,10 +229,17 @@ extern "C" int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t 
     const ConvSplit sp{nullptr, split, second_ld};
     // mri3d_conv3d_dgrad_cat takes no bias; the weight gradient has none to add
     const bool with_bias = bias != 0 && pass != MRI3D_PASS_WGRAD && !(split > 0 && pass == MRI3D_PASS_DGRAD);
-    switch (conv_backend(*g, pass, stats != 0, split, second_ld, align, align)) {
+    // the MFMA kernels move both tensors in 16-byte pieces; the pointwise kernels need only the x-side tensor aligned
+    switch (conv_backend(*g, pass, stats != 0, split, second_ld, align_x < align_y ? align_x : align_y, align_x)) {
     case ConvBackend::none: snprintf(name, name_bytes, "none"); break;
-    case ConvBackend::generic: snprintf(name, name_bytes, "generic"); break;
-    case ConvBackend::pointwise: snprintf(name, name_bytes, "pointwise"); break;
+    case ConvBackend::generic:
+        MRI3D_REQUIRE(conv_generic_route_name(*g, pass, with_bias, align_x, align_y, name, name_bytes), MRI3D_EINVAL,
+                      "conv3d_route: name buffer too small");
+        break;
+    case ConvBackend::pointwise:
+        MRI3D_REQUIRE(conv_pointwise_route_name(*g, pass, with_bias, align_x, align_y, name, name_bytes), MRI3D_EINVAL,
+                      "conv3d_route: name buffer too small");
+        break;
     case ConvBackend::mfma:
         MRI3D_REQUIRE(conv_mfma_route_name(*g, pass, stats != 0, with_bias, sp, name, name_bytes), MRI3D_ENOTSUP,
                       "conv3d_route: the MFMA file names no kernel for a pass it supports");

@@ -88,6 +88,17 @@ inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nu
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
+// largest power of two <= 16 that divides every given address (a null pointer divides by everything): what the route query is
+// told about a tensor instead of its pointer
+inline int ptr_align(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+                           reinterpret_cast<uintptr_t>(d) | 16;
+    return (int)(bits & (~bits + 1));
+}
+// aligned_vec4 / aligned16 of a tensor known by its ptr_align
+inline bool align_vec4(int dtype, int align) { return align >= (dtype == MRI3D_BF16 ? 8 : 16); }
+inline bool align16(int align) { return align >= 16; }
+
 // Run `body` with `T` bound to the storage type of `dtype`.
 #define MRI3D_DISPATCH_DTYPE(dtype, T, ...)  \
     do {                                     \

@@ -21,6 +21,9 @@ int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, c
                        size_t ws_bytes, hipStream_t s);
 int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                        size_t ws_bytes, hipStream_t s);
+// name of the kernel instantiation the pass launches (mri3d_conv3d_route; the vocabulary is in include/mri3d.h), written from the
+// plan the launch reads.  ax / ay: ptr_align of the x-side tensor (x, dx) / of the y-side tensor (y, dy).  false: name too long.
+bool conv_generic_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax, int ay, char* name, size_t name_bytes);
 
 // conv_mfma.hip
 bool conv_mfma_supported(const Mri3dConvGeom& g, int pass);
@@ -60,5 +63,6 @@ int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w,
                          hipStream_t s);
 int conv_pointwise_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                          size_t ws_bytes, hipStream_t s);
+bool conv_pointwise_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax, int ay, char* name, size_t name_bytes);   // as above
 
 }  // namespace mri3d

@@ -1399,6 +1399,123 @@ static WgradPlan wgrad_plan(const Mri3dConvGeom& g) {
     return p;
 }
 
+// ------------------------------------------------------------------ THE decision of each pass
+// Which kernel and instantiation a pass launches, from the geometry and the alignment (ptr_align) of its two activation tensors:
+// ax = that of x (forward, weight gradient) / dx (data gradient), ay = that of y / dy.  conv_generic_fwd / _dgrad / _wgrad launch
+// from it, conv_generic_route_name prints it and conv_generic_workspace_bytes sizes the weight gradient's partials by it.
+enum class GenKernel { c1c1, c1taps, cin1, taps, gather, strided_taps, strided, co1, quads, small, lds };
+struct GenericPlan {
+    GenKernel kernel = GenKernel::gather;
+    int tl = 0;           // taps / gather / strided_taps / strided: channel tile of a thread, the padding of the packed weights
+    int nt = 0;           // tap slots: c1taps 3 | 8, taps 3 | 4 | 6 | 8, strided_taps 3 | 4 | 8, quads 4 | 6 | 8
+    int cv = 0;           // taps: channels per load (4 | 1); gather / strided: vector loads (1 | 0); quads: CIV (4 | 1); cin1: Co (8 | 16);
+                          // co1: the CI instance (1 | 4 | 8 | 16)
+    int cp = 0;           // taps / gather / strided*: channels of the packed weights (Co or Ci rounded up to tl)
+    size_t ws_bytes = 0;  // workspace the launch requires
+};
+
+static GenericPlan generic_fwd_plan(const Mri3dConvGeom& g, int ax, int ay) {
+    GenericPlan p;
+    const int taps = g.kd * g.kh * g.kw;
+    if (c1c1_ok(g)) { p.kernel = GenKernel::c1c1; return p; }
+    if (c1_taps_ok(g) && align16(ay)) { p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps; return p; }
+    if (cin1_ok(g) && align_vec4(g.dtype, ay)) {
+        p.kernel = GenKernel::cin1, p.cv = g.co == 8 ? 8 : 16, p.ws_bytes = (size_t)27 * g.co * sizeof(float);
+        return p;
+    }
+    p.tl = pick_tile(g.co), p.cp = cdiv(g.co, p.tl) * p.tl;
+    p.ws_bytes = (size_t)taps * g.ci * p.cp * sizeof(float);
+    const bool vec = (g.ci % 4 == 0) && (g.x_ld % 4 == 0) && align_vec4(g.dtype, ax);
+    if ((vec || g.ci == 1) && taps <= 8 && align_vec4(g.dtype, ay) && (int64_t)g.ho * g.wo < 0x7fffffffLL && (int64_t)g.n * g.dout * g.ho < 0x7fffffffLL) {
+        // tap slots = the filter's taps where an instance exists (3: the decoder's k = 3 filters, 6: the encoder's k = 6 ones): a
+        // slot past the filter still costs its address arithmetic and a (cached) load
+        p.kernel = GenKernel::taps, p.cv = vec ? 4 : 1;
+        p.nt = vec ? (taps <= 3 ? 3 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8))) : (taps <= 3 ? 3 : (taps <= 6 ? 6 : 8));
+        return p;
+    }
+    p.kernel = GenKernel::gather, p.cv = vec ? 1 : 0;
+    return p;
+}
+
+// (ax: dx, ay: dy)
+static GenericPlan generic_dgrad_plan(const Mri3dConvGeom& g, int ax, int ay) {
+    GenericPlan p;
+    const int taps = g.kd * g.kh * g.kw;
+    if (c1c1_ok(g)) { p.kernel = GenKernel::c1c1; return p; }
+    if (c1_taps_ok(g) && align16(ax)) { p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps; return p; }
+    p.tl = pick_tile(g.ci), p.cp = cdiv(g.ci, p.tl) * p.tl;
+    p.ws_bytes = (size_t)taps * g.co * p.cp * sizeof(float);
+    const bool vec = (g.co % 4 == 0) && (g.y_ld % 4 == 0) && align_vec4(g.dtype, ay);
+    const bool unit_stride = g.sd == 1 && g.sh == 1 && g.sw == 1;   // strided layers: the wave-uniform tap sets below are faster (0.29 vs 0.33 ms)
+    if ((vec || g.co == 1) && unit_stride && taps <= 8 && align_vec4(g.dtype, ax) && (int64_t)g.hi * g.wi < 0x7fffffffLL && (int64_t)g.n * g.di * g.hi < 0x7fffffffLL) {
+        p.kernel = GenKernel::taps, p.cv = vec ? 4 : 1;
+        p.nt = vec ? (taps <= 3 ? 3 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8))) : (taps <= 3 ? 3 : 8);
+        return p;
+    }
+    const int64_t rows = (int64_t)g.n * g.di * g.hi * g.sw;
+    if ((g.sd > 1 || g.sh > 1 || g.sw > 1) && g.dd == 1 && g.dh == 1 && g.dw == 1 && rows <= 0x7fffffff) {
+        // valid taps per input voxel: ceil(k / s) per axis; up to 4 (the separable stride-2 filters: 3) or 8 take the batched kernel
+        const int vt = cdiv(g.kd, g.sd) * cdiv(g.kh, g.sh) * cdiv(g.kw, g.sw);
+        if (vec && vt <= 8 && align_vec4(g.dtype, ax)) {
+            p.kernel = GenKernel::strided_taps, p.nt = vt <= 3 ? 3 : (vt <= 4 ? 4 : 8);
+            return p;
+        }
+        p.kernel = GenKernel::strided, p.cv = vec ? 1 : 0;
+        return p;
+    }
+    p.kernel = GenKernel::gather, p.cv = vec ? 1 : 0;
+    return p;
+}
+
+// (ax: x, ay: dy)
+static GenericPlan generic_wgrad_plan(const Mri3dConvGeom& g, int ax, int ay) {
+    GenericPlan p;
+    const int taps = g.kd * g.kh * g.kw;
+    if (c1c1_ok(g)) {
+        p.kernel = GenKernel::c1c1, p.ws_bytes = (size_t)kC1C1Blocks * 28 * sizeof(float);
+    } else if (c1_taps_ok(g) && align16(ay)) {
+        p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps, p.ws_bytes = (size_t)kC1TBlocks * (kSmTaps + 1) * sizeof(float);
+    } else if (cin1_ok(g) && align_vec4(g.dtype, ay)) {
+        p.kernel = GenKernel::cin1, p.cv = g.co == 8 ? 8 : 16, p.ws_bytes = (size_t)kCin1Shares * (27 + 1) * g.co * sizeof(float);
+    } else if (wgrad_co1_ok(g) && align_vec4(g.dtype, ax)) {
+        p.kernel = GenKernel::co1, p.cv = (g.ci == 1 || g.ci == 4 || g.ci == 8) ? g.ci : 16;
+        p.ws_bytes = (size_t)kCo1Blocks * (kSmTaps * 16 + 1) * sizeof(float);
+    } else if (wgrad_quads_ok(g) && align_vec4(g.dtype, ay) && (g.ci == 1 || align_vec4(g.dtype, ax))) {
+        const WgradQuadsPlan q = wgrad_quads_plan(g);
+        p.kernel = GenKernel::quads, p.cv = g.ci == 1 ? 1 : 4, p.nt = g.ci == 1 ? 8 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8));
+        p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+    } else if (wgrad_small_ok(g)) {
+        const WgradSmallPlan q = wgrad_small_plan(g);
+        p.kernel = GenKernel::small, p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+    } else {
+        const WgradPlan q = wgrad_plan(g);
+        p.kernel = GenKernel::lds, p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+    }
+    return p;
+}
+
+bool conv_generic_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax, int ay, char* name, size_t name_bytes) {
+    const GenericPlan p = pass == MRI3D_PASS_FWD ? generic_fwd_plan(g, ax, ay)
+                                                 : (pass == MRI3D_PASS_DGRAD ? generic_dgrad_plan(g, ax, ay) : generic_wgrad_plan(g, ax, ay));
+    // the bias of a data gradient (the forward of a ConvTranspose3d) is part of the name, as in the MFMA file's names
+    const char* b = (bias && pass == MRI3D_PASS_DGRAD) ? " bias" : "";
+    int len = 0;
+    switch (p.kernel) {
+    case GenKernel::c1c1: len = snprintf(name, name_bytes, "generic c1c1%s", b); break;
+    case GenKernel::c1taps: len = snprintf(name, name_bytes, "generic c1taps nt%d%s", p.nt, b); break;
+    case GenKernel::cin1: len = snprintf(name, name_bytes, "generic cin1 co%d", p.cv); break;
+    case GenKernel::taps: len = snprintf(name, name_bytes, "generic taps tl%d nt%d cv%d%s", p.tl, p.nt, p.cv, b); break;
+    case GenKernel::gather: len = snprintf(name, name_bytes, "generic gather tl%d vec%d%s", p.tl, p.cv, b); break;
+    case GenKernel::strided_taps: len = snprintf(name, name_bytes, "generic staps tl%d nt%d%s", p.tl, p.nt, b); break;
+    case GenKernel::strided: len = snprintf(name, name_bytes, "generic strided tl%d vec%d%s", p.tl, p.cv, b); break;
+    case GenKernel::co1: len = snprintf(name, name_bytes, "generic co1 ci%d", p.cv); break;
+    case GenKernel::quads: len = snprintf(name, name_bytes, "generic quads nt%d civ%d", p.nt, p.cv); break;
+    case GenKernel::small: len = snprintf(name, name_bytes, "generic small"); break;
+    case GenKernel::lds: len = snprintf(name, name_bytes, "generic lds"); break;
+    }
+    return len > 0 && (size_t)len < name_bytes;
+}
+
 size_t conv_generic_workspace_bytes(const Mri3dConvGeom& g, int pass) {
     const int taps = g.kd * g.kh * g.kw;
     if (pass == MRI3D_PASS_FWD) {
@@ -1409,47 +1526,35 @@ size_t conv_generic_workspace_bytes(const Mri3dConvGeom& g, int pass) {
         int t = pick_tile(g.ci);
         return (size_t)taps * g.co * cdiv(g.ci, t) * t * sizeof(float);
     }
-    WgradPlan p = wgrad_plan(g);
-    size_t a = (p.part_floats + p.bias_floats) * sizeof(float);
-    if (cin1_ok(g)) a = std::max(a, (size_t)kCin1Shares * (27 + 1) * g.co * sizeof(float));
-    if (c1c1_ok(g)) a = std::max(a, (size_t)kC1C1Blocks * 28 * sizeof(float));
-    if (c1_taps_ok(g)) a = std::max(a, (size_t)kC1TBlocks * (kSmTaps + 1) * sizeof(float));
-    if (wgrad_co1_ok(g)) a = std::max(a, (size_t)kCo1Blocks * (kSmTaps * 16 + 1) * sizeof(float));
-    if (wgrad_small_ok(g)) {
-        WgradSmallPlan q = wgrad_small_plan(g);
-        a = std::max(a, (q.part_floats + q.bias_floats) * sizeof(float));
-    }
-    if (wgrad_quads_ok(g)) {
-        WgradQuadsPlan q = wgrad_quads_plan(g);
-        a = std::max(a, (q.part_floats + q.bias_floats) * sizeof(float));
-    }
+    // the weight gradient falls through a chain of `geometry && alignment` tests whose kernels lay their partials out differently:
+    // the largest need of the kernels the chain can end at, over the alignments x and dy may have
+    size_t a = 0;
+    for (int ax : {16, 8, 4})
+        for (int ay : {16, 8, 4}) a = std::max(a, generic_wgrad_plan(g, ax, ay).ws_bytes);
     return a;
 }
 
 template <int TL>
-static void launch_fwd(const Mri3dConvGeom& g, const void* x, const float* wp, const float* bias, void* y, int CoP,
+static void launch_fwd(const Mri3dConvGeom& g, const GenericPlan& p, const void* x, const float* wp, const float* bias, void* y,
                        hipStream_t s) {
+    const int CoP = p.cp;
     int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
     dim3 grid((unsigned)std::min<int64_t>(cdiv64(nvox, 256), 8192), CoP / TL);
-    bool vec = (g.ci % 4 == 0) && (g.x_ld % 4 == 0) && aligned_vec4(g.dtype, x);
-    const int taps = g.kd * g.kh * g.kw;
-    if ((vec || g.ci == 1) && taps <= 8 && aligned_vec4(g.dtype, y) && (int64_t)g.ho * g.wo < 0x7fffffffLL && (int64_t)g.n * g.dout * g.ho < 0x7fffffffLL) {
+    if (p.kernel == GenKernel::taps) {
         // few taps: slab walk + batched tap loads (conv_fwd_taps_kernel)
         const int hch = (int)std::max<int64_t>(1, std::min<int64_t>(g.ho, (int64_t)2048 / std::max(g.wo, 1)));
         const int64_t slabs = (int64_t)g.n * g.dout * cdiv(g.ho, hch);
         dim3 tgrid((unsigned)std::min<int64_t>(slabs, 4096), CoP / TL);
 #define MRI3D_FT(NTv, CVv) hipLaunchKernelGGL((conv_fwd_taps_kernel<T, TL, NTv, CVv>), tgrid, dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y, CoP, hch)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            // tap slots = the filter's taps where an instance exists (3: the decoder's k = 3 filters, 6: the encoder's k = 6 ones): a
-            // slot past the filter still costs its address arithmetic and a (cached) load
-            if (vec) { if (taps <= 3) MRI3D_FT(3, 4); else if (taps <= 4) MRI3D_FT(4, 4); else if (taps <= 6) MRI3D_FT(6, 4); else MRI3D_FT(8, 4); }
-            else { if (taps <= 3) MRI3D_FT(3, 1); else if (taps <= 6) MRI3D_FT(6, 1); else MRI3D_FT(8, 1); }
+            if (p.cv == 4) { if (p.nt == 3) MRI3D_FT(3, 4); else if (p.nt == 4) MRI3D_FT(4, 4); else if (p.nt == 6) MRI3D_FT(6, 4); else MRI3D_FT(8, 4); }
+            else { if (p.nt == 3) MRI3D_FT(3, 1); else if (p.nt == 6) MRI3D_FT(6, 1); else MRI3D_FT(8, 1); }
         });
 #undef MRI3D_FT
         return;
     }
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (vec)
+        if (p.cv)
             hipLaunchKernelGGL((conv_fwd_generic_kernel<T, TL, true>), grid, dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y, CoP);
         else
             hipLaunchKernelGGL((conv_fwd_generic_kernel<T, TL, false>), grid, dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y, CoP);
@@ -1458,14 +1563,15 @@ static void launch_fwd(const Mri3dConvGeom& g, const void* x, const float* wp, c
 
 int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, void* ws,
                      size_t ws_bytes, hipStream_t s) {
-    if (c1c1_ok(g)) {
+    const GenericPlan p = generic_fwd_plan(g, ptr_align(x), ptr_align(y));
+    if (p.kernel == GenKernel::c1c1) {
         MRI3D_DISPATCH_DTYPE(g.dtype, T, { launch_c1c1_stencil<T>(g, (const T*)x, g.x_ld, w, bias, 0, (T*)y, g.y_ld, s); });
         return check_launch("conv3d_fwd(1->1 stencil)");
     }
-    if (c1_taps_ok(g) && aligned16(y)) {
+    if (p.kernel == GenKernel::c1taps) {
         const int64_t items = (int64_t)g.n * g.dout * g.ho * (g.wo / 4);
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256), 8192));
-        if (g.kd * g.kh * g.kw <= 3)
+        if (p.nt == 3)
             hipLaunchKernelGGL(conv_c1_taps_kernel<3>, dim3(grid), dim3(256), 0, s, g, (const float*)x, w, bias, (float*)y, 1, g.di, g.hi,
                                g.wi, g.dout, g.ho, g.wo);
         else
@@ -1473,8 +1579,8 @@ int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, cons
                                g.hi, g.wi, g.dout, g.ho, g.wo);
         return check_launch("conv3d_fwd(1->1 taps)");
     }
-    if (cin1_ok(g) && aligned_vec4(g.dtype, y)) {
-        const size_t need1 = (size_t)27 * g.co * sizeof(float);
+    if (p.kernel == GenKernel::cin1) {
+        const size_t need1 = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need1, MRI3D_EWORKSPACE, "conv3d_fwd: workspace %zu < %zu", ws_bytes, need1);
         float* wp = static_cast<float*>(ws);
         hipLaunchKernelGGL(repack_w_fwd_kernel, dim3(1), dim3(256), 0, s, w, wp, g.co, 1, 27, g.co);
@@ -1483,7 +1589,7 @@ int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, cons
         const int ntiles = g.n * tilesD * tilesH * tilesW;
         const int grid = std::min(ntiles, 256 * 8);
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (g.co == 8)
+            if (p.cv == 8)
                 hipLaunchKernelGGL((conv_cin1_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y,
                                    tilesD, tilesH, tilesW, ntiles);
             else
@@ -1493,19 +1599,18 @@ int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, cons
         return check_launch("conv3d_fwd(cin1)");
     }
     const int taps = g.kd * g.kh * g.kw;
-    const int TL = pick_tile(g.co);
-    const int CoP = cdiv(g.co, TL) * TL;
-    size_t need = (size_t)taps * g.ci * CoP * sizeof(float);
+    const int TL = p.tl, CoP = p.cp;
+    size_t need = p.ws_bytes;
     MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_fwd: workspace %zu < %zu", ws_bytes, need);
     float* wp = static_cast<float*>(ws);
     int total = taps * g.ci * CoP;
     hipLaunchKernelGGL(repack_w_fwd_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co, g.ci,
                        taps, CoP);
     switch (TL) {
-        case 16: launch_fwd<16>(g, x, wp, bias, y, CoP, s); break;
-        case 8: launch_fwd<8>(g, x, wp, bias, y, CoP, s); break;
-        case 4: launch_fwd<4>(g, x, wp, bias, y, CoP, s); break;
-        default: launch_fwd<2>(g, x, wp, bias, y, CoP, s); break;
+        case 16: launch_fwd<16>(g, p, x, wp, bias, y, s); break;
+        case 8: launch_fwd<8>(g, p, x, wp, bias, y, s); break;
+        case 4: launch_fwd<4>(g, p, x, wp, bias, y, s); break;
+        default: launch_fwd<2>(g, p, x, wp, bias, y, s); break;
     }
     return check_launch("conv3d_fwd(generic)");
 }
@@ -1673,36 +1778,31 @@ conv_dgrad_strided_taps_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const 
 }
 
 template <int TL>
-static void launch_dgrad(const Mri3dConvGeom& g, const void* dy, const float* wp, const float* bias, void* dx,
-                         int CiP, hipStream_t s) {
+static void launch_dgrad(const Mri3dConvGeom& g, const GenericPlan& p, const void* dy, const float* wp, const float* bias, void* dx,
+                         hipStream_t s) {
+    const int CiP = p.cp;
     int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
     dim3 grid((unsigned)std::min<int64_t>(cdiv64(nvox, 256), 8192), CiP / TL);
-    bool vec = (g.co % 4 == 0) && (g.y_ld % 4 == 0) && aligned_vec4(g.dtype, dy);
-    const int taps = g.kd * g.kh * g.kw;
-    const bool unit_stride = g.sd == 1 && g.sh == 1 && g.sw == 1;   // strided layers: the wave-uniform tap sets below are faster (0.29 vs 0.33 ms)
-    if ((vec || g.co == 1) && unit_stride && taps <= 8 && aligned_vec4(g.dtype, dx) && (int64_t)g.hi * g.wi < 0x7fffffffLL && (int64_t)g.n * g.di * g.hi < 0x7fffffffLL) {
+    if (p.kernel == GenKernel::taps) {
         // few taps, stride 1: slab walk + batched tap loads (conv_dgrad_taps_kernel)
         const int hch = (int)std::max<int64_t>(1, std::min<int64_t>(g.hi, (int64_t)2048 / std::max(g.wi, 1)));
         const int64_t slabs = (int64_t)g.n * g.di * cdiv(g.hi, hch);
         dim3 tgrid((unsigned)std::min<int64_t>(slabs, 4096), CiP / TL);
 #define MRI3D_DT(NTv, CVv) hipLaunchKernelGGL((conv_dgrad_taps_kernel<T, TL, NTv, CVv>), tgrid, dim3(256), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP, hch)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (vec) { if (taps <= 3) MRI3D_DT(3, 4); else if (taps <= 4) MRI3D_DT(4, 4); else if (taps <= 6) MRI3D_DT(6, 4); else MRI3D_DT(8, 4); }
-            else { if (taps <= 3) MRI3D_DT(3, 1); else MRI3D_DT(8, 1); }
+            if (p.cv == 4) { if (p.nt == 3) MRI3D_DT(3, 4); else if (p.nt == 4) MRI3D_DT(4, 4); else if (p.nt == 6) MRI3D_DT(6, 4); else MRI3D_DT(8, 4); }
+            else { if (p.nt == 3) MRI3D_DT(3, 1); else MRI3D_DT(8, 1); }
         });
 #undef MRI3D_DT
         return;
     }
-    const int64_t rows = (int64_t)g.n * g.di * g.hi * g.sw;
-    if ((g.sd > 1 || g.sh > 1 || g.sw > 1) && g.dd == 1 && g.dh == 1 && g.dw == 1 && rows <= 0x7fffffff) {
-        dim3 sgrid((unsigned)rows, CiP / TL);
-        // valid taps per input voxel: ceil(k / s) per axis; up to 4 (the separable stride-2 filters: 3) or 8 take the batched kernel
-        const int vt = cdiv(g.kd, g.sd) * cdiv(g.kh, g.sh) * cdiv(g.kw, g.sw);
-        if (vec && vt <= 8 && aligned_vec4(g.dtype, dx)) {
+    if (p.kernel == GenKernel::strided_taps || p.kernel == GenKernel::strided) {
+        dim3 sgrid((unsigned)((int64_t)g.n * g.di * g.hi * g.sw), CiP / TL);
+        if (p.kernel == GenKernel::strided_taps) {
             MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-                if (vt <= 3)
+                if (p.nt == 3)
                     hipLaunchKernelGGL((conv_dgrad_strided_taps_kernel<T, TL, 3>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
-                else if (vt <= 4)
+                else if (p.nt == 4)
                     hipLaunchKernelGGL((conv_dgrad_strided_taps_kernel<T, TL, 4>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
                 else
                     hipLaunchKernelGGL((conv_dgrad_strided_taps_kernel<T, TL, 8>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
@@ -1710,7 +1810,7 @@ static void launch_dgrad(const Mri3dConvGeom& g, const void* dy, const float* wp
             return;
         }
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (vec)
+            if (p.cv)
                 hipLaunchKernelGGL((conv_dgrad_strided_kernel<T, TL, true>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
             else
                 hipLaunchKernelGGL((conv_dgrad_strided_kernel<T, TL, false>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
@@ -1718,7 +1818,7 @@ static void launch_dgrad(const Mri3dConvGeom& g, const void* dy, const float* wp
         return;
     }
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (vec)
+        if (p.cv)
             hipLaunchKernelGGL((conv_dgrad_generic_kernel<T, TL, true>), grid, dim3(256), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
         else
             hipLaunchKernelGGL((conv_dgrad_generic_kernel<T, TL, false>), grid, dim3(256), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
@@ -1727,15 +1827,16 @@ static void launch_dgrad(const Mri3dConvGeom& g, const void* dy, const float* wp
 
 int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
                        size_t ws_bytes, hipStream_t s) {
-    if (c1c1_ok(g)) {
+    const GenericPlan p = generic_dgrad_plan(g, ptr_align(dx), ptr_align(dy));
+    if (p.kernel == GenKernel::c1c1) {
         // dx = the same stencil with reversed taps, applied to dy (pad 1, stride 1: the transposed conv is a conv)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, { launch_c1c1_stencil<T>(g, (const T*)dy, g.y_ld, w, bias, 1, (T*)dx, g.x_ld, s); });
         return check_launch("conv3d_dgrad(1->1 stencil)");
     }
-    if (c1_taps_ok(g) && aligned16(dx)) {
+    if (p.kernel == GenKernel::c1taps) {
         const int64_t items = (int64_t)g.n * g.di * g.hi * (g.wi / 4);
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256), 8192));
-        if (g.kd * g.kh * g.kw <= 3)
+        if (p.nt == 3)
             hipLaunchKernelGGL(conv_c1_taps_kernel<3>, dim3(grid), dim3(256), 0, s, g, (const float*)dy, w, bias, (float*)dx, -1, g.dout,
                            g.ho, g.wo, g.di, g.hi, g.wi);
         else
@@ -1744,9 +1845,8 @@ int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, c
         return check_launch("conv3d_dgrad(1->1 taps)");
     }
     const int taps = g.kd * g.kh * g.kw;
-    const int TL = pick_tile(g.ci);
-    const int CiP = cdiv(g.ci, TL) * TL;
-    size_t need = (size_t)taps * g.co * CiP * sizeof(float);
+    const int TL = p.tl, CiP = p.cp;
+    size_t need = p.ws_bytes;
     MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_dgrad: workspace %zu < %zu", ws_bytes,
                   need);
     float* wp = static_cast<float*>(ws);
@@ -1754,18 +1854,19 @@ int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, c
     hipLaunchKernelGGL(repack_w_dgrad_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co,
                        g.ci, taps, CiP);
     switch (TL) {
-        case 16: launch_dgrad<16>(g, dy, wp, bias, dx, CiP, s); break;
-        case 8: launch_dgrad<8>(g, dy, wp, bias, dx, CiP, s); break;
-        case 4: launch_dgrad<4>(g, dy, wp, bias, dx, CiP, s); break;
-        default: launch_dgrad<2>(g, dy, wp, bias, dx, CiP, s); break;
+        case 16: launch_dgrad<16>(g, p, dy, wp, bias, dx, s); break;
+        case 8: launch_dgrad<8>(g, p, dy, wp, bias, dx, s); break;
+        case 4: launch_dgrad<4>(g, p, dy, wp, bias, dx, s); break;
+        default: launch_dgrad<2>(g, p, dy, wp, bias, dx, s); break;
     }
     return check_launch("conv3d_dgrad(generic)");
 }
 
 int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                        size_t ws_bytes, hipStream_t s) {
-    if (c1c1_ok(g)) {
-        const size_t need = (size_t)kC1C1Blocks * 28 * sizeof(float);
+    const GenericPlan p = generic_wgrad_plan(g, ptr_align(x), ptr_align(dy));
+    if (p.kernel == GenKernel::c1c1) {
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         const int tilesD = cdiv(g.dout, C1D), tilesH = cdiv(g.ho, C1H), tilesW = cdiv(g.wo, C1WQ * 4);
         const int ntiles = g.n * tilesD * tilesH * tilesW;
@@ -1779,23 +1880,23 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(27 + 1, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb, 27, 1, 1, 1, 1);
         return check_launch("conv3d_wgrad(1->1 stencil)");
     }
-    if (c1_taps_ok(g) && aligned16(dy)) {
+    if (p.kernel == GenKernel::c1taps) {
         const int taps = g.kd * g.kh * g.kw;
         const int64_t items = (int64_t)g.n * g.dout * g.ho * (g.wo / 4);
         const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256 * 4), kC1TBlocks));
-        const size_t need = (size_t)kC1TBlocks * (kSmTaps + 1) * sizeof(float);
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         float* part = static_cast<float*>(ws);
         float* bias_part = dbias ? part + (size_t)kC1TBlocks * kSmTaps : nullptr;
-        if (g.kd * g.kh * g.kw <= 3)
+        if (p.nt == 3)
             hipLaunchKernelGGL(conv_c1_taps_wgrad_kernel<3>, dim3(nb), dim3(256), 0, s, g, (const float*)x, (const float*)dy, part, bias_part);
         else
             hipLaunchKernelGGL(conv_c1_taps_wgrad_kernel<kSmTaps>, dim3(nb), dim3(256), 0, s, g, (const float*)x, (const float*)dy, part, bias_part);
         hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(taps + 1, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb, taps, 1, 1, 1, 1);
         return check_launch("conv3d_wgrad(1->1 taps)");
     }
-    if (cin1_ok(g) && aligned_vec4(g.dtype, dy)) {
-        const size_t need = (size_t)kCin1Shares * (27 + 1) * g.co * sizeof(float);
+    if (p.kernel == GenKernel::cin1) {
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         const int vpt = g.co <= 8 ? 4 : 2;
         const int tilesD = cdiv(g.dout, C1D), tilesH = cdiv(g.ho, C1H), tilesW = cdiv(g.wo, C1WQ * vpt);
@@ -1804,7 +1905,7 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
         float* bias_part = dbias ? part + (size_t)kCin1Shares * 27 * g.co : nullptr;
         // every (share, kd) workgroup writes its slots, also when its share of the tiles is empty (zeros)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (g.co == 8)
+            if (p.cv == 8)
                 hipLaunchKernelGGL((conv_cin1_wgrad_kernel<T, 8>), dim3(kCin1Shares), dim3(768), 0, s, g, (const T*)x,
                                    (const T*)dy, part, bias_part, tilesD, tilesH, tilesW, ntiles, kCin1Shares);
             else
@@ -1815,8 +1916,8 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
                            kCin1Shares, 27, 1, g.co, 1, g.co);
         return check_launch("conv3d_wgrad(cin1)");
     }
-    if (wgrad_co1_ok(g) && aligned_vec4(g.dtype, x)) {
-        const size_t need = (size_t)kCo1Blocks * (kSmTaps * 16 + 1) * sizeof(float);
+    if (p.kernel == GenKernel::co1) {
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         const int taps = g.kd * g.kh * g.kw;
         const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
@@ -1825,7 +1926,7 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
         float* bias_part = dbias ? part + (size_t)kCo1Blocks * kSmTaps * 16 : nullptr;
 #define MRI3D_CO1(CIv) hipLaunchKernelGGL((conv_wgrad_co1_kernel<T, CIv>), dim3(nb), dim3(256), 0, s, g, (const T*)x, (const T*)dy, part, bias_part)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            switch (g.ci) {
+            switch (p.cv) {
                 case 1: MRI3D_CO1(1); break;
                 case 4: MRI3D_CO1(4); break;
                 case 8: MRI3D_CO1(8); break;
@@ -1837,9 +1938,9 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
                            g.ci, 1, g.ci, 1);
         return check_launch("conv3d_wgrad(co1)");
     }
-    if (wgrad_quads_ok(g) && aligned_vec4(g.dtype, dy) && (g.ci == 1 || aligned_vec4(g.dtype, x))) {
+    if (p.kernel == GenKernel::quads) {
         WgradQuadsPlan q = wgrad_quads_plan(g);
-        const size_t need = (q.part_floats + q.bias_floats) * sizeof(float);
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         float* part = static_cast<float*>(ws);
         float* bias_part = dbias ? part + q.part_floats : nullptr;
@@ -1848,9 +1949,9 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
     hipLaunchKernelGGL((conv_wgrad_quads_kernel<T, NTv, CIVv>), dim3(q.gx), dim3(256), 0, s, g, (const T*)x, (const T*)dy,  \
                        part, bias_part, q.QI, q.QO, q.hch, q.CiP, q.CoP)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (g.ci == 1) MRI3D_WGQ(8, 1);
-            else if (taps <= 4) MRI3D_WGQ(4, 4);
-            else if (taps <= 6) MRI3D_WGQ(6, 4);
+            if (p.cv == 1) MRI3D_WGQ(8, 1);
+            else if (p.nt == 4) MRI3D_WGQ(4, 4);
+            else if (p.nt == 6) MRI3D_WGQ(6, 4);
             else MRI3D_WGQ(8, 4);
         });
 #undef MRI3D_WGQ
@@ -1859,9 +1960,9 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
                            g.ci, g.co, q.CiP, q.CoP);
         return check_launch("conv3d_wgrad(quads)");
     }
-    if (wgrad_small_ok(g)) {
+    if (p.kernel == GenKernel::small) {
         WgradSmallPlan q = wgrad_small_plan(g);
-        const size_t need = (q.part_floats + q.bias_floats) * sizeof(float);
+        const size_t need = p.ws_bytes;
         MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
         float* part = static_cast<float*>(ws);
         float* bias_part = dbias ? part + q.part_floats : nullptr;
@@ -1876,25 +1977,25 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
                            dbias, q.gx, taps, g.ci, g.co, q.CiP, q.CoP);
         return check_launch("conv3d_wgrad(small)");
     }
-    WgradPlan p = wgrad_plan(g);
-    size_t need = (p.part_floats + p.bias_floats) * sizeof(float);
+    const WgradPlan lp = wgrad_plan(g);
+    size_t need = p.ws_bytes;
     MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes,
                   need);
-    MRI3D_REQUIRE(p.smem <= 160 * 1024, MRI3D_ENOTSUP, "conv3d_wgrad: Ci=%d Co=%d needs %zu B of LDS", g.ci, g.co,
-                  p.smem);
+    MRI3D_REQUIRE(lp.smem <= 160 * 1024, MRI3D_ENOTSUP, "conv3d_wgrad: Ci=%d Co=%d needs %zu B of LDS", g.ci, g.co,
+                  lp.smem);
     float* part = static_cast<float*>(ws);
-    float* bias_part = dbias ? part + p.part_floats : nullptr;
+    float* bias_part = dbias ? part + lp.part_floats : nullptr;
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
         // the kernel's dynamic-LDS limit is raised once (to the CU's 160 KB), not per launch
         static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_generic_kernel<T>),
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)attr_;
-        hipLaunchKernelGGL(conv_wgrad_generic_kernel<T>, dim3(p.gx, p.taps, p.gz), dim3(256), p.smem, s, g, (const T*)x,
-                           (const T*)dy, part, bias_part, p.Ci4, p.Co4, p.nitems, p.vsplit);
+        hipLaunchKernelGGL(conv_wgrad_generic_kernel<T>, dim3(lp.gx, lp.taps, lp.gz), dim3(256), lp.smem, s, g, (const T*)x,
+                           (const T*)dy, part, bias_part, lp.Ci4, lp.Co4, lp.nitems, lp.vsplit);
     });
-    int total = g.co * g.ci * p.taps;
+    int total = g.co * g.ci * lp.taps;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total + g.co, 8)), dim3(256), 0, s, part, bias_part, dw,
-                       dbias, p.gx, p.taps, g.ci, g.co, p.Ci4 * 4, p.Co4 * 4);
+                       dbias, lp.gx, lp.taps, g.ci, g.co, lp.Ci4 * 4, lp.Co4 * 4);
     return check_launch("conv3d_wgrad(generic)");
 }
 

@@ -235,14 +235,47 @@ bool conv_pointwise_supported(const Mri3dConvGeom& g, int pass) {
     return false;
 }
 
+// THE decision of a pass: the instantiation, from the geometry and the alignment (ptr_align) of x / dx (ax) and of y / dy (ay).
+// The launches below read it, conv_pointwise_route_name prints it.
+struct PointwisePlan {
+    int co = 0;        // compile-time bound on Co: forward 2 | 4, gradients 2 | 4 | 8
+    int vx = 4;        // weight gradient: input channels per lane, 8 = 16-byte bf16 loads
+    bool dv = false;   // weight gradient: a voxel's dy is one vector load
+    int blocks = 0;    // weight gradient: partials
+    size_t ws_bytes = 0, smem = 0;
+};
+
+static PointwisePlan pw_plan(const Mri3dConvGeom& g, int pass, int ax, int ay) {
+    PointwisePlan p;
+    if (pass == MRI3D_PASS_FWD) { p.co = g.co <= 2 ? 2 : 4; return p; }
+    p.co = g.co <= 2 ? 2 : (g.co <= 4 ? 4 : 8);
+    if (pass == MRI3D_PASS_DGRAD) return p;
+    // bf16: 8 channels per lane when the channel count and pitch allow 16-byte loads; one vector load of dy when it is dense
+    const bool v8 = g.dtype == MRI3D_BF16 && g.ci % 8 == 0 && g.x_ld % 8 == 0 && 256 % (g.ci / 8) == 0 && align16(ax) && p.co <= 4;
+    p.vx = v8 ? 8 : 4;
+    p.dv = g.co == p.co && g.y_ld == p.co && align16(ay);
+    p.blocks = pw_blocks(g);
+    p.ws_bytes = (size_t)p.blocks * (g.co * g.ci + g.co) * sizeof(double);
+    p.smem = (size_t)256 * (p.vx + 1) * p.co * sizeof(double);
+    return p;
+}
+
 size_t conv_pointwise_workspace_bytes(const Mri3dConvGeom& g, int pass) {
-    if (pass != MRI3D_PASS_WGRAD) return 0;
-    return (size_t)pw_blocks(g) * (g.co * g.ci + g.co) * sizeof(double);
+    return pass == MRI3D_PASS_WGRAD ? pw_plan(g, pass, 16, 16).ws_bytes : 0;   // (the partials do not depend on the alignment)
+}
+
+bool conv_pointwise_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax, int ay, char* name, size_t name_bytes) {
+    const PointwisePlan p = pw_plan(g, pass, ax, ay);
+    int len;
+    if (pass == MRI3D_PASS_WGRAD) len = snprintf(name, name_bytes, "pointwise co%d vx%d dv%d", p.co, p.vx, p.dv ? 1 : 0);
+    else len = snprintf(name, name_bytes, "pointwise co%d%s", p.co, (bias && pass == MRI3D_PASS_DGRAD) ? " bias" : "");
+    return len > 0 && (size_t)len < name_bytes;
 }
 
 int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx,
                          hipStream_t s) {
     MRI3D_REQUIRE(aligned_vec4(g.dtype, dx), MRI3D_EINVAL, "conv3d_dgrad(pointwise): dx must be aligned to 4 elements");
+    const PointwisePlan p = pw_plan(g, MRI3D_PASS_DGRAD, ptr_align(dx), ptr_align(dy));
     const int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
     const int VL = 256 / (g.ci >> 2);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(nvox, (int64_t)VL * 4), 2048));
@@ -250,8 +283,8 @@ int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w,
     hipLaunchKernelGGL((pw_dgrad_kernel<T, CO>), dim3(grid), dim3(256), 0, s, (const T*)dy, w, bias, (T*)dx, nvox, g.ci, g.co, \
                        g.x_ld, g.y_ld)
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (g.co <= 2) PW_DGRAD(2);
-        else if (g.co <= 4) PW_DGRAD(4);
+        if (p.co == 2) PW_DGRAD(2);
+        else if (p.co == 4) PW_DGRAD(4);
         else PW_DGRAD(8);
     });
 #undef PW_DGRAD
@@ -260,6 +293,7 @@ int conv_pointwise_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w,
 
 int conv_pointwise_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, hipStream_t s) {
     MRI3D_REQUIRE(aligned_vec4(g.dtype, x), MRI3D_EINVAL, "conv3d_fwd(pointwise): x must be aligned to 4 elements");
+    const PointwisePlan p = pw_plan(g, MRI3D_PASS_FWD, ptr_align(x), ptr_align(y));
     const int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
     const int VL = 256 / (g.ci >> 2);
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv64(nvox, (int64_t)VL * 4), 2048));
@@ -267,7 +301,7 @@ int conv_pointwise_fwd(const Mri3dConvGeom& g, const void* x, const float* w, co
     hipLaunchKernelGGL((pw_fwd_kernel<T, CO>), dim3(grid), dim3(256), 0, s, (const T*)x, w, bias, (T*)y, nvox, g.ci, g.co,     \
                        g.x_ld, g.y_ld)
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (g.co <= 2) PW_FWD(2);
+        if (p.co == 2) PW_FWD(2);
         else PW_FWD(4);
     });
 #undef PW_FWD
@@ -276,19 +310,18 @@ int conv_pointwise_fwd(const Mri3dConvGeom& g, const void* x, const float* w, co
 
 int conv_pointwise_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                          size_t ws_bytes, hipStream_t s) {
-    const int nb = pw_blocks(g);
-    const size_t need = conv_pointwise_workspace_bytes(g, MRI3D_PASS_WGRAD);
+    const PointwisePlan p = pw_plan(g, MRI3D_PASS_WGRAD, ptr_align(x), ptr_align(dy));
+    const int nb = p.blocks;
+    const size_t need = p.ws_bytes;
     MRI3D_REQUIRE(ws && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad(pointwise): workspace %zu < %zu", ws_bytes, need);
     MRI3D_REQUIRE(aligned_vec4(g.dtype, x) && (reinterpret_cast<uintptr_t>(ws) & 7) == 0, MRI3D_EINVAL,
                   "conv3d_wgrad(pointwise): x must be aligned to 4 elements");
     double* part = static_cast<double*>(ws);
     double* bias_part = dbias ? part + (size_t)nb * g.co * g.ci : nullptr;
     const int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
-    const int CO = g.co <= 2 ? 2 : (g.co <= 4 ? 4 : 8);
-    // bf16: 8 channels per lane when the channel count and pitch allow 16-byte loads; one vector load of dy when it is dense
-    const bool v8 = g.dtype == MRI3D_BF16 && g.ci % 8 == 0 && g.x_ld % 8 == 0 && 256 % (g.ci / 8) == 0 && aligned16(x) && CO <= 4;
-    const bool dyv = g.co == CO && g.y_ld == CO && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-    const size_t smem = (size_t)256 * ((v8 ? 8 : 4) + 1) * CO * sizeof(double);
+    const int CO = p.co;
+    const bool v8 = p.vx == 8, dyv = p.dv;
+    const size_t smem = p.smem;
 #define PW_WGRAD(CO_, VX_, DV_)                                                                                        \
     do {                                                                                                               \
         auto kern = pw_wgrad_kernel<T, CO_, VX_, DV_>;                                                                 \

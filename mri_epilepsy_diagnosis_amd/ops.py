@@ -350,12 +350,14 @@ def _ptr_align(*ts):
     return bits & -bits
 
 
-def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16):
+def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16, x_align=None, y_align=None):
     """Name of the kernel the C ABI launches for geometry `g` (a ConvGeom from `_conv_geom`) in pass `pass_` (PASS_*): host only,
-    nothing is launched and no device is needed.  split > 0: the *_cat entry points; align: `_ptr_align` of the tensors involved (16:
-    what the allocator gives).  The vocabulary of names is documented at mri3d_conv3d_route in include/mri3d.h."""
+    nothing is launched and no device is needed.  split > 0: the *_cat entry points.  x_align / y_align: `_ptr_align` of the x-side
+    tensor (x, or dx in the data gradient) and of the y-side tensor (y, or dy); `align` is the shorthand for both (16: what the
+    allocator gives).  The vocabulary of names is documented at mri3d_conv3d_route in include/mri3d.h."""
     name = ctypes.create_string_buffer(64)
-    check(_lib.lib().mri3d_conv3d_route(ctypes.byref(g), pass_, int(bool(stats)), int(bool(bias)), split, second_ld, align, name, 64),
+    xa, ya = align if x_align is None else x_align, align if y_align is None else y_align
+    check(_lib.lib().mri3d_conv3d_route(ctypes.byref(g), pass_, int(bool(stats)), int(bool(bias)), split, second_ld, xa, ya, name, 64),
           "conv3d_route")
     return name.value.decode()
 
@@ -363,21 +365,39 @@ def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16
 def conv3d_routes(xshape, wshape, stride=1, padding=0, dilation=1, dtype=F32, x_ld=None, dy_ld=None, bias=True, bn_stats=False,
                   x_align=16, dy_align=16):
     """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv3d(x, w, b, ...)` and its backward launch, from the
-    geometries `_Conv3dFn` builds: x a slice of pitch x_ld, the incoming gradient one of pitch dy_ld, y and dx fresh dense tensors,
-    no bias in the data gradient, the stride-2 weight gradient on the stride-1 kernels where `_stuffed_wgrad_ok`.  *_align:
-    `_ptr_align` of x / of the incoming gradient.  With bn_stats the forward name is that of the fused-statistics entry point
+    geometries `_Conv3dFn` builds: x a slice of pitch x_ld, the incoming gradient one of pitch dy_ld, y and dx fresh dense tensors
+    (16-byte aligned), no bias in the data gradient, the stride-2 weight gradient on the stride-1 kernels where `_stuffed_wgrad_ok`.
+    *_align: `_ptr_align` of x / of the incoming gradient.  With bn_stats the forward name is that of the fused-statistics entry point
     where it serves the geometry (as `conv3d(bn_stats=True)` asks first)."""
     stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
     g = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=x_ld, dtype=dtype)
-    fwd = conv_route(g, PASS_FWD, bn_stats, bias, align=x_align) if bn_stats else "none"
+    fwd = conv_route(g, PASS_FWD, bn_stats, bias, x_align=x_align, y_align=16) if bn_stats else "none"
     if fwd == "none":
-        fwd = conv_route(g, PASS_FWD, False, bias, align=x_align)
+        fwd = conv_route(g, PASS_FWD, False, bias, x_align=x_align, y_align=16)
     gd = _conv_geom(xshape, wshape, stride, padding, dilation, y_ld=dy_ld, dtype=dtype)
     gw = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=g.x_ld, y_ld=dy_ld, dtype=dtype)
-    w_align = min(x_align, dy_align)
+    wy_align = dy_align
     if _stuffed_wgrad_ok(g):
-        gw, w_align = _conv_geom(xshape, wshape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=dtype), x_align
-    return {"fwd": fwd, "dgrad": conv_route(gd, PASS_DGRAD, align=dy_align), "wgrad": conv_route(gw, PASS_WGRAD, align=w_align)}
+        gw, wy_align = _conv_geom(xshape, wshape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=dtype), 16
+    return {"fwd": fwd, "dgrad": conv_route(gd, PASS_DGRAD, x_align=16, y_align=dy_align),
+            "wgrad": conv_route(gw, PASS_WGRAD, x_align=x_align, y_align=wy_align)}
+
+
+def conv_transpose3d_routes(xshape, wshape, stride=1, padding=0, output_padding=0, dilation=1, dtype=F32, bias=True, x_align=16,
+                            dy_align=16):
+    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv_transpose3d(x, w, b, ...)` and its backward launch, from
+    the mirrored geometry `_ConvTranspose3dFn` builds (dense tensors): the forward is the mirrored convolution's data gradient with
+    the bias, dx its forward without one, dw its weight gradient with the operands swapped.  *_align: `_ptr_align` of x / of the
+    incoming gradient."""
+    stride, padding, output_padding, dilation = _triple(stride), _triple(padding), _triple(output_padding), _triple(dilation)
+    n = xshape[0]
+    out = tuple((i - 1) * s - 2 * p + d * (k - 1) + op + 1 for i, s, p, d, k, op in zip(xshape[2:], stride, padding, dilation, wshape[2:], output_padding))
+    g = _conv_geom((n, wshape[1]) + out, wshape, stride, padding, dilation, dtype=dtype)
+    if (g.dout, g.ho, g.wo) != tuple(xshape[2:]):
+        raise RuntimeError("conv_transpose3d: inconsistent output_padding")
+    return {"fwd": conv_route(g, PASS_DGRAD, False, bias, x_align=16, y_align=x_align),
+            "dgrad": conv_route(g, PASS_FWD, x_align=dy_align, y_align=16),
+            "wgrad": conv_route(g, PASS_WGRAD, x_align=dy_align, y_align=x_align)}
 
 
 def _conv_fwd(g, x, w, b):

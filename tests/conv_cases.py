@@ -7,7 +7,8 @@ same route with the real pointers before they launch.  A threshold that moves ma
 moving the cases to another kernel.
 
 `expect[dtype][pass]` is a route name or the leading words of one ("tiled" matches "tiled nt2 stats", not "tiled_n8"); a tuple
-holds one entry per case for tables that span several kernels on purpose.  Passes: "fwd", "dgrad", "wgrad", and "stats" (the
+holds one entry per case for tables that span several kernels on purpose (the first word of a name is the kernel file: "generic"
+matches every kernel of conv_generic.hip).  Passes: "fwd", "dgrad", "wgrad", and "stats" (the
 forward with fused BatchNorm statistics) where the test uses it.  Route names: include/mri3d.h at mri3d_conv3d_route.
 """
 import numpy as np
@@ -45,7 +46,9 @@ class Table:
 
     def expected(self, case, dtype):
         """[(pass, expected route)]: what the table is there for (`expect`), then the case's own row of PER_CASE."""
-        out = list(self.expect[dtype].items())
+        out = []
+        for p, e in self.expect[dtype].items():      # (a tuple: one entry per case of this dtype, in table order)
+            out.append((p, e[[c for c, dt in pairs(self) if dt == dtype].index(case)] if isinstance(e, tuple) else e))
         row = PER_CASE[(self.name, dtype)][self.ids(case)].split(" | ")
         assert len(row) == len(ORDER[self.kind]), (self.name, dtype, self.ids(case))
         return out + list(zip(ORDER[self.kind], row))
@@ -55,8 +58,11 @@ class Table:
         of freshly allocated buffers."""
         return ROUTES[self.kind](self, case, dtype, x_align, dy_align)
 
-    def shape(self, case):
-        """(n, d, h, w) of the input volume."""
+    def shape(self, case, pass_="fwd"):
+        """(n, d, h, w) of the input volume ("transpose": of the volume the pass's kernel walks — the output in the forward, the
+        input in the gradients)."""
+        if self.kind == "transpose" and pass_ != "fwd":
+            return (case[0],) + tuple(case[3])
         return SHAPES[self.kind](case)
 
     def check(self, case, dtype, x=None, dy=None):
@@ -145,13 +151,57 @@ def _stats_fwd_routes(t, case, dtype, x_align, dy_align):
     return {"stats": _stats_routes(t, case, dtype, x_align, dy_align)["stats"]}
 
 
+# ---- "geom": (n, ci, co, (d, h, w), k, stride, padding, dilation, bias, pad_in, pad_out) of tests/test_conv_variants_gpu.py — any filter;
+# x is channels [pad_in, pad_in + ci) of a buffer of pitch ci + pad_in, the incoming gradient channels [pad_out, pad_out + co) of one
+# of pitch co + pad_out (pads 0 / 0: dense); the other channels of both buffers hold a sentinel
+def _geom_routes(t, case, dtype, x_align, dy_align):
+    n, ci, co, sp, k, s, p, dil, bias, pad_in, pad_out = case
+    if x_align is None:
+        x_align = align_of(pad_in * ESIZE[dtype])
+    if dy_align is None:
+        dy_align = align_of(pad_out * ESIZE[dtype])
+    return ops.conv3d_routes((n, ci) + tuple(sp), (co, ci) + tuple(k), s, p, dil, DTYPES[dtype], x_ld=ci + pad_in, dy_ld=co + pad_out, bias=bias,
+                             x_align=x_align, dy_align=dy_align)
+
+
+# ---- "transpose": (n, ci, co, (d, h, w), k, stride, padding, output_padding, bias) of ConvTranspose3d(ci, co, ...) on dense tensors.  The
+# routes are those of the mirrored convolution `_ConvTranspose3dFn` builds: "fwd" is its data gradient WITH the bias, "dgrad" its
+# forward without one, "wgrad" its weight gradient with the operands swapped.  The volume a case counts as ragged by is the
+# transposed convolution's OUTPUT (what the forward's data-gradient kernel walks)
+def _transpose_routes(t, case, dtype, x_align, dy_align):
+    n, ci, co, sp, k, s, p, op, bias = case
+    return ops.conv_transpose3d_routes((n, ci) + tuple(sp), (ci, co) + tuple(k), s, p, op, 1, DTYPES[dtype], bias,
+                                       x_align=16 if x_align is None else x_align, dy_align=16 if dy_align is None else dy_align)
+
+
+# ---- "ws_wgrad": (id, dtype, "geom" case, channel offset of the incoming gradient in its buffer, seed, kernel-name pattern) of the
+# exact-workspace test in test_buffer_contracts_gpu: as "geom", but the incoming gradient is channels [dy_off, dy_off + co) of its
+# buffer of pitch co + pad_out, so that it can be misaligned under a pitch that is a multiple of 4
+def _ws_wgrad_routes(t, case, dtype, x_align, dy_align):
+    if dy_align is None:
+        dy_align = align_of(case[3] * ESIZE[dtype])
+    return _geom_routes(t, case[2], dtype, x_align, dy_align)
+
+
+# pass of the mirrored convolution whose kernel runs in each pass of the transposed one
+KERNEL_PASS = {"transpose": {"fwd": "dgrad", "dgrad": "fwd", "wgrad": "wgrad"}}
+
+
+def transpose_out(case):
+    n, ci, co, sp, k, s, p, op, bias = case
+    return tuple((i - 1) * ss - 2 * pp + (kk - 1) + oo + 1 for i, ss, pp, kk, oo in zip(sp, s, p, k, op))
+
+
 ORDER = {"slice": ("fwd", "dgrad", "wgrad"), "first": ("fwd", "dgrad", "wgrad"), "dense": ("fwd", "dgrad", "wgrad"),
-         "stats": ("fwd", "dgrad", "wgrad", "stats"), "cat": ("fwd", "stats", "dgrad", "wgrad"), "capi_stats": ("stats",), "stats_fwd": ("stats",)}
+         "stats": ("fwd", "dgrad", "wgrad", "stats"), "cat": ("fwd", "stats", "dgrad", "wgrad"), "capi_stats": ("stats",), "stats_fwd": ("stats",),
+         "geom": ("fwd", "dgrad", "wgrad"), "transpose": ("fwd", "dgrad", "wgrad"), "ws_wgrad": ("fwd", "dgrad", "wgrad")}
 ROUTES = {"slice": _slice_routes, "first": _first_routes, "dense": _dense_routes, "stats": _stats_routes, "cat": _cat_routes,
-          "capi_stats": _capi_stats_routes, "stats_fwd": _stats_fwd_routes}
+          "capi_stats": _capi_stats_routes, "stats_fwd": _stats_fwd_routes, "geom": _geom_routes, "transpose": _transpose_routes,
+          "ws_wgrad": _ws_wgrad_routes}
 SHAPES = {"slice": lambda c: (c[0],) + tuple(c[3:6]), "first": lambda c: (c[0],) + tuple(c[2:5]), "dense": None,
           "stats": lambda c: (c[0],) + tuple(c[3:6]), "cat": lambda c: (c[0],) + tuple(c[4]), "capi_stats": lambda c: (c[2],) + tuple(c[7]),
-          "stats_fwd": lambda c: (c[0],) + tuple(c[3:6])}
+          "stats_fwd": lambda c: (c[0],) + tuple(c[3:6]), "geom": lambda c: (c[0],) + tuple(c[3]), "transpose": lambda c: (c[0],) + transpose_out(c),
+          "ws_wgrad": lambda c: (c[2][0],) + tuple(c[2][3])}
 
 
 
@@ -289,7 +339,7 @@ class DenseTable(Table):
         self.fields, self.case_dtype = fields, case_dtype
         Table.__init__(self, name, "dense", cases, expect, **kw)
 
-    def shape(self, case):
+    def shape(self, case, pass_="fwd"):
         f = self.fields(case)
         return (f[0],) + tuple(f[3])
 
@@ -430,6 +480,167 @@ WS_CONV = DenseTable("WS_CONV", [
     ids=lambda c: c[0])
 
 
+# ================================================================== tests/test_conv_variants_gpu.py
+# Every kernel and instantiation of conv_generic.hip and conv_pointwise.hip (the route names "generic ..." / "pointwise ..."), in fp32
+# and bf16.  The case lists are a greedy cover of tests/test_conv_routes.py's MATRIX over small volumes that are ragged in d, h and w
+# (W a multiple of 4 with odd d and h for the 1 -> 1 taps kernels, which need it): separable filters of 2-6 taps along each axis with
+# stride 1 and 2, 2x2x2, 1x2x2 (four taps), 3x3x1 / stride 2 (four valid taps in the data gradient), k4s4, k4s2, 3x3x3 with stride 2,
+# one-axis strides, dilation 2 and 3, 5x5x5 and 1x1x1 on 1-72 channels, W of 33 and 65 for the slab-walk kernels; then by hand an
+# extent of 1 per axis and W = 70.  PER_CASE pins every case to its three kernels.
+def _geom_id(c):
+    j = lambda t: "".join(map(str, t))
+    return "n%d_%d-%d_%s_k%s_s%s_p%s_d%s_b%d_i%d_o%d" % (c[0], c[1], c[2], "x".join(map(str, c[3])), j(c[4]), j(c[5]), j(c[6]), j(c[7]), c[8], c[9], c[10])
+
+
+def _transpose_id(c):
+    j = lambda t: "".join(map(str, t))
+    return "n%d_%d-%d_%s_k%s_s%s_p%s_o%s_b%d" % (c[0], c[1], c[2], "x".join(map(str, c[3])), j(c[4]), j(c[5]), j(c[6]), j(c[7]), c[8])
+
+
+GENERIC_DENSE_CASES = [
+    (1, 1, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 1, 3, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 5, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0), (1, 1, 16, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 72, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 2, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 2, 3, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 2, 5, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 2, 16, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0), (1, 3, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 3, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 3, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 3, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 5, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 4, 16, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 5, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 5, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 5, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 8, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0), (1, 16, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 16, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 0, 0), (1, 16, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 1, (5, 7, 8), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 4, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 3, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 3, 4, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 5, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 5, 4, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0), (1, 16, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 16, 4, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 1, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 3, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 4, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 5, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0), (1, 1, 16, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 3, 1, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 3, 4, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 1, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 3, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 5, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0), (1, 4, 16, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 5, 1, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0), (1, 5, 4, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 16, 1, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 16, 4, (5, 7, 9), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 1, (5, 7, 8), (4, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 4, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 3, 4, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 1, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 3, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 4, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 5, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0), (1, 4, 16, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 5, 4, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), False, 0, 0), (1, 16, 4, (5, 7, 9), (5, 1, 1), (1, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 1, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 3, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 1, 4, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 5, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 1, 16, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 3, 4, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 1, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 3, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 4, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 5, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 4, 16, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 5, 4, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 16, 4, (5, 7, 9), (2, 2, 2), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 1, 4, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0),
+    (1, 3, 4, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0), (1, 4, 1, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 3, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0), (1, 4, 5, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), False, 0, 0),
+    (1, 4, 16, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0), (1, 5, 4, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), False, 0, 0),
+    (1, 16, 4, (5, 7, 9), (3, 3, 1), (2, 2, 1), (1, 1, 0), (1, 1, 1), True, 0, 0), (1, 1, 4, (5, 7, 9), (4, 4, 4), (2, 2, 2), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 3, 4, (5, 7, 9), (4, 4, 4), (2, 2, 2), (1, 1, 1), (1, 1, 1), True, 0, 0), (1, 5, 4, (5, 7, 9), (4, 4, 4), (2, 2, 2), (1, 1, 1), (1, 1, 1), False, 0, 0),
+    (1, 16, 4, (5, 7, 9), (4, 4, 4), (2, 2, 2), (1, 1, 1), (1, 1, 1), True, 0, 0), (1, 1, 1, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 1, 4, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0), (1, 1, 8, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), False, 0, 0),
+    (1, 1, 16, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0), (1, 3, 4, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 5, 4, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), False, 0, 0), (1, 16, 4, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 1, 4, (5, 7, 9), (3, 3, 3), (2, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0), (1, 3, 4, (5, 7, 9), (3, 3, 3), (2, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 5, 4, (5, 7, 9), (3, 3, 3), (2, 1, 1), (1, 1, 1), (1, 1, 1), False, 0, 0), (1, 16, 4, (5, 7, 9), (3, 3, 3), (2, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0),
+    (1, 4, 1, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 2, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 4, 3, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 4, 4, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 4, 5, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0), (1, 4, 8, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 8, 1, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0), (1, 8, 2, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0),
+    (1, 8, 3, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 0, 0), (1, 8, 4, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), False, 0, 0),
+    (1, 8, 8, (1, 7, 9), (1, 3, 1), (1, 1, 1), (0, 1, 0), (1, 1, 1), True, 0, 0), (2, 16, 8, (3, 5, 70), (1, 1, 6), (1, 1, 2), (0, 0, 2), (1, 1, 1), True, 0, 0),
+    (1, 1, 1, (5, 1, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 0), (3, 4, 4, (5, 7, 1), (2, 2, 2), (1, 1, 1), (1, 1, 1), (1, 1, 1), False, 0, 0),
+    (1, 8, 16, (9, 1, 33), (6, 1, 1), (2, 1, 1), (2, 0, 0), (1, 1, 1), True, 0, 0),
+]
+GENERIC_PITCHED_CASES = [
+    (1, 1, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 4, 4), (1, 1, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 4, 4),
+    (1, 1, 4, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 4, 4), (1, 1, 72, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 4, 4),
+    (1, 2, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 4, 4), (1, 1, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 4, 4),
+    (1, 1, 4, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 4, 4), (1, 1, 1, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 4, 4),
+    (1, 1, 8, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), False, 4, 4), (1, 1, 16, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 4, 4),
+    (1, 4, 1, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 4, 4), (1, 1, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 1, 1),
+    (1, 1, 2, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 1, 1), (1, 1, 72, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), True, 1, 1),
+    (1, 2, 1, (5, 7, 9), (2, 1, 1), (1, 1, 1), (1, 0, 0), (1, 1, 1), False, 1, 1), (1, 1, 1, (5, 7, 9), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 1, 1), True, 1, 1),
+    (1, 1, 1, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 1, 1), (1, 1, 8, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), False, 1, 1),
+    (1, 4, 1, (5, 7, 9), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 1, 1), (1, 1, 16, (5, 7, 9), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 1, 0),
+    (1, 8, 8, (5, 7, 70), (1, 1, 3), (1, 1, 1), (0, 0, 1), (1, 1, 1), True, 4, 4), (2, 1, 8, (1, 9, 13), (3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), True, 0, 4),
+    (1, 16, 2, (3, 1, 11), (1, 1, 1), (1, 1, 1), (0, 0, 0), (1, 1, 1), True, 4, 0),
+]
+TRANSPOSE_CASES = [
+    (1, 1, 1, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 1, 3, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 1, 5, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 1, 16, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 2, 1, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 2, 3, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 2, 5, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 2, 16, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 1, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 3, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 5, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 16, (2, 3, 17), (2, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (2, 1, 1, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True), (2, 1, 3, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True),
+    (2, 1, 5, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True), (2, 1, 16, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True),
+    (2, 4, 1, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True), (2, 4, 3, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True),
+    (2, 4, 5, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True), (2, 4, 16, (3, 5, 7), (2, 1, 1), (2, 1, 1), (0, 0, 0), (1, 0, 0), True),
+    (1, 1, 1, (5, 7, 8), (3, 1, 1), (1, 1, 1), (1, 0, 0), (0, 0, 0), True), (1, 1, 1, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 1, 3, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 1, 5, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 1, 16, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 1, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 3, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 5, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 16, (2, 3, 17), (4, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (2, 4, 1, (3, 5, 7), (5, 1, 1), (1, 1, 1), (2, 0, 0), (0, 0, 0), True),
+    (2, 4, 3, (3, 5, 7), (5, 1, 1), (1, 1, 1), (2, 0, 0), (0, 0, 0), True), (2, 4, 5, (3, 5, 7), (5, 1, 1), (1, 1, 1), (2, 0, 0), (0, 0, 0), True),
+    (2, 4, 16, (3, 5, 7), (5, 1, 1), (1, 1, 1), (2, 0, 0), (0, 0, 0), True), (1, 1, 1, (5, 7, 8), (5, 1, 1), (1, 1, 1), (2, 0, 0), (0, 0, 0), True),
+    (2, 1, 1, (3, 5, 7), (3, 3, 3), (1, 1, 1), (1, 1, 1), (0, 0, 0), True), (2, 4, 1, (3, 5, 7), (3, 3, 3), (1, 1, 1), (1, 1, 1), (0, 0, 0), True),
+    (2, 4, 3, (3, 5, 7), (3, 3, 3), (1, 1, 1), (1, 1, 1), (0, 0, 0), True), (2, 4, 5, (3, 5, 7), (3, 3, 3), (1, 1, 1), (1, 1, 1), (0, 0, 0), True),
+    (2, 4, 16, (3, 5, 7), (3, 3, 3), (1, 1, 1), (1, 1, 1), (0, 0, 0), True), (1, 4, 1, (4, 6, 8), (2, 2, 2), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 3, (4, 6, 8), (2, 2, 2), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 5, (4, 6, 8), (2, 2, 2), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 4, 16, (4, 6, 8), (2, 2, 2), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (1, 4, 1, (3, 4, 5), (3, 3, 1), (2, 2, 1), (1, 1, 0), (0, 0, 0), True),
+    (1, 4, 3, (3, 4, 5), (3, 3, 1), (2, 2, 1), (1, 1, 0), (0, 0, 0), True), (1, 4, 5, (3, 4, 5), (3, 3, 1), (2, 2, 1), (1, 1, 0), (0, 0, 0), True),
+    (1, 4, 16, (3, 4, 5), (3, 3, 1), (2, 2, 1), (1, 1, 0), (0, 0, 0), True), (1, 4, 1, (4, 6, 8), (3, 3, 3), (2, 2, 2), (1, 1, 1), (0, 0, 0), True),
+    (1, 4, 3, (4, 6, 8), (3, 3, 3), (2, 2, 2), (1, 1, 1), (0, 0, 0), True), (1, 4, 5, (4, 6, 8), (3, 3, 3), (2, 2, 2), (1, 1, 1), (0, 0, 0), True),
+    (1, 4, 16, (4, 6, 8), (3, 3, 3), (2, 2, 2), (1, 1, 1), (0, 0, 0), True), (1, 4, 1, (4, 6, 8), (5, 5, 5), (2, 2, 2), (2, 2, 2), (0, 0, 0), True),
+    (1, 4, 3, (4, 6, 8), (5, 5, 5), (2, 2, 2), (2, 2, 2), (0, 0, 0), True), (1, 4, 5, (4, 6, 8), (5, 5, 5), (2, 2, 2), (2, 2, 2), (0, 0, 0), True),
+    (1, 4, 16, (4, 6, 8), (5, 5, 5), (2, 2, 2), (2, 2, 2), (0, 0, 0), True), (2, 1, 4, (3, 5, 7), (1, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (2, 3, 4, (3, 5, 7), (1, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True), (2, 5, 4, (3, 5, 7), (1, 1, 1), (1, 1, 1), (0, 0, 0), (0, 0, 0), True),
+    (1, 6, 6, (5, 6, 7), (2, 2, 2), (2, 2, 2), (0, 0, 0), (0, 0, 0), True), (2, 1, 1, (3, 4, 5), (4, 4, 4), (4, 4, 4), (0, 0, 0), (0, 0, 0), True),
+    (1, 8, 4, (5, 5, 6), (4, 4, 4), (2, 2, 2), (1, 1, 1), (0, 0, 0), True), (1, 4, 8, (4, 5, 3), (3, 3, 3), (2, 2, 2), (1, 1, 1), (1, 1, 1), True),
+    (1, 8, 8, (3, 4, 5), (4, 4, 4), (4, 4, 4), (0, 0, 0), (0, 0, 0), True), (1, 16, 16, (2, 3, 5), (4, 4, 4), (4, 4, 4), (0, 0, 0), (0, 0, 0), True),
+    (1, 1, 1, (3, 5, 7), (4, 4, 4), (4, 4, 4), (0, 0, 0), (0, 0, 0), True), (2, 8, 8, (3, 5, 7), (4, 4, 4), (2, 2, 2), (1, 1, 1), (0, 0, 0), True),
+    (2, 4, 8, (3, 5, 7), (3, 3, 3), (2, 2, 2), (1, 1, 1), (1, 1, 1), True), (1, 8, 8, (1, 5, 7), (2, 2, 2), (2, 2, 2), (0, 0, 0), (0, 0, 0), False),
+]
+
+# dense tensors
+GENERIC_DENSE = Table("GENERIC_DENSE", "geom", GENERIC_DENSE_CASES, {"f32": {}, "bf16": {}}, ids=_geom_id)
+# pitched channel slices: pads of 4 (fp32: the slice stays 16-byte aligned and keeps its vector loads; bf16: 8 bytes), 1 (neither
+# alignment nor a pitch that is a multiple of 4) and 2 (fp32: 8 bytes), on one side or both — at least one per kernel family and pass
+# wherever the family's precondition allows the pitch
+GENERIC_PITCHED = Table("GENERIC_PITCHED", "geom", GENERIC_PITCHED_CASES, {"f32": {}, "bf16": {}}, ids=_geom_id)
+# ConvTranspose3d: the only way to the data gradient WITH a bias of every generic and pointwise data-gradient kernel; then the four
+# cases of test_ops_gpu's test_conv_transpose3d, the shipped layers (AE_model.py:71: k = s = 4 on 8 -> 8 and 16 -> 16; :128: 1 -> 1
+# k4 s4), k4 s2 p1, output_padding on odd extents, an extent of 1 without a bias
+TRANSPOSE = Table("TRANSPOSE", "transpose", TRANSPOSE_CASES, {"f32": {}, "bf16": {}}, ids=_transpose_id)
+
+# one exact-workspace case per weight-gradient family of conv_generic.hip / conv_pointwise.hip: every family lays its partials out
+# differently and conv_generic_workspace_bytes sizes them from the plan the launch reads.  The launched-kernel pattern doubles as the
+# check that a route name means the kernel it says.  quads_dy_misaligned: an 8 -> 8 (1,3,1) layer is the channel-quad kernel's by
+# geometry (gradient pitch 12), but its gradient starts 8 bytes into the voxel, so the launch falls through to `small`
+_1, _0 = (1, 1, 1), (0, 0, 0)
+WS_WGRAD = Table("WS_WGRAD", "ws_wgrad", [
+    ("wgrad_c1c1", "f32", (2, 1, 1, (5, 7, 9), (3, 3, 3), _1, _1, _1, True, 0, 0), 0, 50, r"conv_c1c1_wgrad_kernel"),
+    ("wgrad_c1taps", "f32", (2, 1, 1, (5, 7, 12), (1, 1, 3), _1, (0, 0, 1), _1, True, 0, 0), 0, 51, r"conv_c1_taps_wgrad_kernel"),
+    ("wgrad_cin1", "f32", (2, 1, 8, (5, 7, 9), (3, 3, 3), _1, _1, _1, True, 0, 0), 0, 52, r"conv_cin1_wgrad_kernel"),
+    ("wgrad_cin1_bf16", "bf16", (1, 1, 16, (5, 7, 9), (3, 3, 3), _1, _1, _1, True, 0, 4), 4, 53, r"conv_cin1_wgrad_kernel"),
+    ("wgrad_co1", "f32", (2, 8, 1, (5, 7, 9), (3, 1, 1), _1, (1, 0, 0), _1, True, 0, 0), 0, 54, r"conv_wgrad_co1_kernel"),
+    ("wgrad_quads", "f32", (2, 8, 8, (5, 7, 9), (1, 3, 1), _1, (0, 1, 0), _1, True, 0, 0), 0, 55, r"conv_wgrad_quads_kernel"),
+    ("wgrad_quads_bf16", "bf16", (2, 8, 16, (5, 7, 33), (1, 1, 6), (1, 1, 2), (0, 0, 2), _1, True, 4, 0), 0, 56, r"conv_wgrad_quads_kernel"),
+    ("wgrad_quads_dy_misaligned", "f32", (2, 8, 8, (5, 7, 9), (1, 3, 1), _1, (0, 1, 0), _1, True, 0, 4), 2, 57, r"conv_wgrad_small_kernel"),
+    ("wgrad_small", "f32", (2, 3, 5, (5, 7, 9), (1, 1, 3), _1, (0, 0, 1), _1, True, 0, 0), 0, 58, r"conv_wgrad_small_kernel"),
+    ("wgrad_lds", "f32", (1, 3, 5, (7, 9, 11), (3, 3, 3), _1, (2, 2, 2), (2, 2, 2), True, 1, 0), 0, 59, r"conv_wgrad_generic_kernel"),
+    ("wgrad_pointwise", "f32", (2, 16, 2, (5, 7, 9), _1, _1, _0, _1, True, 0, 0), 0, 60, r"pw_wgrad_kernel"),
+    ("wgrad_pointwise_bf16", "bf16", (2, 32, 4, (5, 7, 9), _1, _1, _0, _1, True, 0, 0), 0, 61, r"pw_wgrad_kernel"),
+], {"f32": {"wgrad": ("generic c1c1", "generic c1taps nt3", "generic cin1 co8", "generic co1 ci8", "generic quads nt4 civ4", "generic small",
+                      "generic small", "generic lds", "pointwise co2 vx4 dv1")},
+    "bf16": {"wgrad": ("generic cin1 co16", "generic quads nt6 civ4", "pointwise co4 vx8 dv1")}}, oracle=False, ids=lambda c: c[0])
+WS_WGRAD.case_dtype = lambda c: c[1]
+
+
 def pairs(table):
     """(case, dtype) of everything the table's test runs."""
     cd = getattr(table, "case_dtype", None)
@@ -477,18 +688,18 @@ PER_CASE.update({
         'n2_16-64_6x7x23_p8_8': "tiled nt2 | tiled nt1 | bf16",
     },
     ("MISALIGNED", "f32"): {
-        'n1_16-16_5x9x20_p2_0': "generic | direct nt1 mode0 split1 | generic",
-        'n2_8-16_4x8x16_p2_2': "generic | generic | generic",
+        'n1_16-16_5x9x20_p2_0': "generic gather tl16 vec0 | direct nt1 mode0 split1 | generic lds",
+        'n2_8-16_4x8x16_p2_2': "generic gather tl16 vec0 | generic gather tl8 vec0 | generic lds",
         'n1_48-16_3x8x17_p4_4': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
-        'n1_16-32_6x10x18_p6_0': "generic | direct nt1 mode0 split1 | generic",
-        'n1_32-32_2x3x5_p1_3': "generic | generic | generic",
+        'n1_16-32_6x10x18_p6_0': "generic gather tl16 vec0 | direct nt1 mode0 split1 | generic lds",
+        'n1_32-32_2x3x5_p1_3': "generic gather tl16 vec0 | generic gather tl16 vec0 | generic lds",
     },
     ("MISALIGNED", "bf16"): {
-        'n1_16-16_5x9x20_p2_0': "generic | tiled nt1 | generic",
-        'n2_8-16_4x8x16_p2_2': "generic | generic | generic",
-        'n1_48-16_3x8x17_p4_4': "generic | generic | generic",
-        'n1_16-32_6x10x18_p6_0': "generic | tiled nt1 | generic",
-        'n1_32-32_2x3x5_p1_3': "generic | generic | generic",
+        'n1_16-16_5x9x20_p2_0': "generic gather tl16 vec0 | tiled nt1 | generic lds",
+        'n2_8-16_4x8x16_p2_2': "generic gather tl16 vec0 | generic gather tl8 vec0 | generic lds",
+        'n1_48-16_3x8x17_p4_4': "generic gather tl16 vec1 | generic gather tl16 vec1 | generic lds",
+        'n1_16-32_6x10x18_p6_0': "generic gather tl16 vec0 | tiled nt1 | generic lds",
+        'n1_32-32_2x3x5_p1_3': "generic gather tl16 vec0 | generic gather tl16 vec0 | generic lds",
     },
     ("TILED_F32", "f32"): {
         'n64_16-16_5x9x19_p0_0': "tiled nt1 | tiled nt1 | wgrad6",
@@ -610,16 +821,16 @@ PER_CASE.update({
         'n1_8-64_81x81x81_p0_0': "direct nt4 mode0 split0 | direct nt1 mode1 split0 | bf16",
     },
     ("STRIDE3", "f32"): {
-        'n1_16-32_10x11x13_p0_0': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | generic",
-        'n2_8-16_7x8x19_p8_0': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | generic",
+        'n1_16-32_10x11x13_p0_0': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | generic lds",
+        'n2_8-16_7x8x19_p8_0': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | generic lds",
     },
     ("BF16_WGRAD_QUADS", "bf16"): {
-        'n2_16-12_5x13x37_p0_0': "tiled nt1 | generic | wgrad4",
-        'n2_16-20_5x9x17_p8_0': "tiled nt2 | generic | wgrad4",
-        'n2_32-12_7x13x33_p0_0': "tiled nt1 | generic | wgrad4",
-        'n2_16-16_5x13x37_p0_4': "tiled nt1 | generic | wgrad4",
-        'n2_8-12_5x13x37_p0_0': "tiled nt1 | generic | wgrad3",
-        'n2_24-20_5x9x17_p0_0': "tiled nt2 | generic | wgrad3",
+        'n2_16-12_5x13x37_p0_0': "tiled nt1 | generic gather tl16 vec1 | wgrad4",
+        'n2_16-20_5x9x17_p8_0': "tiled nt2 | generic gather tl16 vec1 | wgrad4",
+        'n2_32-12_7x13x33_p0_0': "tiled nt1 | generic gather tl16 vec1 | wgrad4",
+        'n2_16-16_5x13x37_p0_4': "tiled nt1 | generic gather tl16 vec1 | wgrad4",
+        'n2_8-12_5x13x37_p0_0': "tiled nt1 | generic gather tl8 vec1 | wgrad3",
+        'n2_24-20_5x9x17_p0_0': "tiled nt2 | generic gather tl16 vec1 | wgrad3",
     },
     ("MARCH_BF16", "bf16"): {
         'n48_16-16_41x5x9_p0_0': "march bias | march | bf16",
@@ -643,37 +854,37 @@ PER_CASE.update({
         'n48_8-16_41x5x9_b0': "march stats",
     },
     ("FIRST", "f32"): {
-        'n2_1-8_9x13x37_b1_p0': "generic | generic | generic",
-        'n1_1-16_8x16x32_b0_p0': "generic | generic | cin1",
-        'n1_1-8_4x8x32_b0_p8': "generic | generic | generic",
-        'n3_1-16_5x7x19_b1_p0': "generic | generic | cin1",
-        'n1_1-8_1x1x1_b1_p0': "generic | generic | generic",
-        'n1_1-8_17x9x70_b1_p8': "generic | generic | generic",
-        'n2_1-16_6x20x33_b1_p16': "generic | generic | cin1",
-        'n1_1-8_12x24x64_b0_p0': "generic | generic | generic",
+        'n2_1-8_9x13x37_b1_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_8x16x32_b0_p0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_4x8x32_b0_p8': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n3_1-16_5x7x19_b1_p0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_1x1x1_b1_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-8_17x9x70_b1_p8': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n2_1-16_6x20x33_b1_p16': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_12x24x64_b0_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
     },
     ("FIRST", "bf16"): {
-        'n2_1-8_9x13x37_b1_p0': "generic | generic | generic",
-        'n1_1-16_8x16x32_b0_p0': "generic | generic | cin1",
-        'n1_1-8_4x8x32_b0_p8': "generic | generic | generic",
-        'n3_1-16_5x7x19_b1_p0': "generic | generic | cin1",
-        'n1_1-8_1x1x1_b1_p0': "generic | generic | generic",
-        'n1_1-8_17x9x70_b1_p8': "generic | generic | generic",
-        'n2_1-16_6x20x33_b1_p16': "generic | generic | cin1",
-        'n1_1-8_12x24x64_b0_p0': "generic | generic | generic",
+        'n2_1-8_9x13x37_b1_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_8x16x32_b0_p0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_4x8x32_b0_p8': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n3_1-16_5x7x19_b1_p0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_1x1x1_b1_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-8_17x9x70_b1_p8': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n2_1-16_6x20x33_b1_p16': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_12x24x64_b0_p0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
     },
     ("ONE_OUT", "f32"): {
-        'n2_8-1_k3x1x1_s111_9x13x37': "generic | generic | generic",
-        'n1_1-1_k1x3x1_s111_4x8x32': "generic | generic | generic",
-        'n1_1-1_k1x1x3_s111_5x7x19': "generic | generic | generic",
-        'n2_4-1_k1x6x1_s121_6x20x9': "generic | generic | generic",
-        'n1_16-1_k1x1x3_s111_3x5x70': "generic | generic | generic",
-        'n2_1-1_k3x3x3_s111_9x13x37': "generic | generic | generic",
-        'n1_1-1_k3x3x3_s111_1x1x1': "generic | generic | generic",
-        'n1_8-1_k6x1x1_s211_12x6x10': "generic | generic | generic",
+        'n2_8-1_k3x1x1_s111_9x13x37': "generic taps tl2 nt3 cv4 | generic taps tl8 nt3 cv1 | generic co1 ci8",
+        'n1_1-1_k1x3x1_s111_4x8x32': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'n1_1-1_k1x1x3_s111_5x7x19': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n2_4-1_k1x6x1_s121_6x20x9': "generic taps tl2 nt6 cv4 | generic strided tl4 vec0 | generic co1 ci4",
+        'n1_16-1_k1x1x3_s111_3x5x70': "generic taps tl2 nt3 cv4 | generic taps tl16 nt3 cv1 | generic co1 ci16",
+        'n2_1-1_k3x3x3_s111_9x13x37': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-1_k3x3x3_s111_1x1x1': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_8-1_k6x1x1_s211_12x6x10': "generic taps tl2 nt6 cv4 | generic strided tl8 vec0 | generic co1 ci8",
     },
     ("OPS_CONV", "f32"): {
-        'unet_1_8': "generic | generic | generic",
+        'unet_1_8': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
         'unet_8_16': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad3",
         'unet_16_16': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'unet_16_32': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
@@ -681,37 +892,37 @@ PER_CASE.update({
         'unet_32_64': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'unet_96_32': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'unet_48_16': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
-        'unet_cls_16_2': "pointwise | pointwise | pointwise",
-        'pw_32_2': "pointwise | pointwise | pointwise",
-        'pw_64_8': "generic | pointwise | pointwise",
-        'pw_16_5': "generic | pointwise | pointwise",
-        'pw_128_64': "generic | generic | generic",
-        'pw_8_3': "pointwise | pointwise | pointwise",
-        'pw_4_1': "pointwise | pointwise | pointwise",
-        'pw_64_4': "pointwise | pointwise | pointwise",
+        'unet_cls_16_2': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+        'pw_32_2': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+        'pw_64_8': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv1",
+        'pw_16_5': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv0",
+        'pw_128_64': "generic taps tl16 nt3 cv4 | generic taps tl16 nt3 cv4 | generic lds",
+        'pw_8_3': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv0",
+        'pw_4_1': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'pw_64_4': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv1",
         'mfma_24_40': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad3",
         'mfma_64_128_ragged': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'ragged_3x3x3': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'tiny_1voxel': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad3",
-        'sepx_k6s2p2': "generic | generic | generic",
-        'sepy_k6s2p2': "generic | generic | generic",
-        'sepz_k6s2p2': "generic | generic | generic",
-        'sepx_k3p0': "generic | generic | generic",
-        'sepz_k3p1': "generic | generic | generic",
+        'sepx_k6s2p2': "generic taps tl8 nt6 cv1 | generic staps tl2 nt3 | generic quads nt8 civ1",
+        'sepy_k6s2p2': "generic taps tl8 nt6 cv4 | generic staps tl8 nt3 | generic quads nt6 civ4",
+        'sepz_k6s2p2': "generic taps tl16 nt6 cv4 | generic staps tl8 nt3 | generic quads nt6 civ4",
+        'sepx_k3p0': "generic taps tl16 nt3 cv4 | generic taps tl16 nt3 cv4 | generic small",
+        'sepz_k3p1': "generic taps tl8 nt3 cv4 | generic taps tl16 nt3 cv4 | generic quads nt4 civ4",
         'stride2_m3d': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | wgrad3",
         'stride2_odd': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | wgrad6",
-        'dilated_s2': "generic | generic | generic",
-        'dilated_p3': "generic | generic | generic",
-        'reduce_k4s4': "generic | generic | generic",
-        'vox_1_1': "generic | generic | generic",
-        'c1_sepy': "generic | generic | generic",
-        'c1_sepz': "generic | generic | generic",
-        'c1_sepx_nobias': "generic | generic | generic",
-        'c1_sepz_k6_p2': "generic | generic | generic",
-        'c1_sepz_k5_p2_dil2': "generic | generic | generic",
-        'c1_sepy_k2': "generic | generic | generic",
-        'c1_sepz_ragged': "generic | generic | generic",
-        'odd_channels': "generic | generic | generic",
+        'dilated_s2': "generic gather tl4 vec0 | generic gather tl2 vec1 | generic lds",
+        'dilated_p3': "generic gather tl4 vec1 | generic gather tl4 vec1 | generic lds",
+        'reduce_k4s4': "generic gather tl2 vec0 | generic strided tl2 vec0 | generic lds",
+        'vox_1_1': "generic c1c1 | generic c1c1 | generic c1c1",
+        'c1_sepy': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'c1_sepz': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'c1_sepx_nobias': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'c1_sepz_k6_p2': "generic taps tl2 nt6 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'c1_sepz_k5_p2_dil2': "generic c1taps nt8 | generic c1taps nt8 | generic c1taps nt8",
+        'c1_sepy_k2': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'c1_sepz_ragged': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'odd_channels': "generic gather tl8 vec0 | generic gather tl4 vec0 | generic lds",
         'wide_128': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
     },
     ("OPS_STATS", "f32"): {
@@ -760,14 +971,14 @@ PER_CASE.update({
         'n1_48-16_8x16x16_k3_s1': "tiled nt1 | tiled nt1 | bf16",
         'n2_32-64_6x9x17_k3_s1': "tiled nt2 | tiled nt2 | bf16",
         'n1_96-32_5x8x16_k3_s1': "tiled nt2 | tiled nt2 | bf16",
-        'n2_1-8_10x12x14_k3_s1': "generic | generic | generic",
-        'n2_16-2_10x12x14_k1_s1': "pointwise | pointwise | pointwise",
-        'n1_32-2_9x10x11_k1_s1': "pointwise | pointwise | pointwise",
-        'n2_64-4_5x7x9_k1_s1': "pointwise | pointwise | pointwise",
-        'n1_16-5_6x7x8_k1_s1': "generic | pointwise | pointwise",
-        'n1_24-3_6x7x8_k1_s1': "generic | generic | pointwise",
+        'n2_1-8_10x12x14_k3_s1': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n2_16-2_10x12x14_k1_s1': "pointwise co2 | pointwise co2 | pointwise co2 vx8 dv1",
+        'n1_32-2_9x10x11_k1_s1': "pointwise co2 | pointwise co2 | pointwise co2 vx8 dv1",
+        'n2_64-4_5x7x9_k1_s1': "pointwise co4 | pointwise co4 | pointwise co4 vx8 dv1",
+        'n1_16-5_6x7x8_k1_s1': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv0",
+        'n1_24-3_6x7x8_k1_s1': "generic taps tl4 nt3 cv4 | generic gather tl16 vec0 | pointwise co4 vx4 dv0",
         'n1_8-16_11x12x13_k3_s2': "direct nt1 mode0 split1 | direct nt1 mode1 split1 | bf16",
-        'n1_4-6_9x10x11_k(3, 1, 1)_s(2, 1, 1)': "generic | generic | generic",
+        'n1_4-6_9x10x11_k(3, 1, 1)_s(2, 1, 1)': "generic taps tl8 nt3 cv4 | generic strided tl4 vec0 | generic small",
     },
     ("CAPI_STATS", "f32"): {
         'f32_tiled': "tiled nt2 stats",
@@ -784,8 +995,8 @@ PER_CASE.update({
         'bf16_cat_march': "march stats bias",
     },
     ("WS_CONV", "f32"): {
-        'conv_generic_odd_dilated': "generic | generic | generic",
-        'conv_pointwise': "pointwise | pointwise | pointwise",
+        'conv_generic_odd_dilated': "generic gather tl8 vec0 | generic gather tl4 vec0 | generic lds",
+        'conv_pointwise': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
         'conv_small_f32': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6",
         'conv_narrow_f32': "direct nt1 mode0 split0 | direct nt1 mode0 split0 | wgrad6",
         'conv_tiled_f32': "tiled nt1 | tiled nt1 | wgrad6",
@@ -796,5 +1007,437 @@ PER_CASE.update({
         'conv_n8_bf16': "tiled_n8 | tiled nt1 | bf16",
         'conv_march_bf16': "march bias | march | bf16",
         'conv_wgrad_bf16_march_d': "tiled nt2 | tiled nt2 | bf16t",
+    },
+    ("GENERIC_DENSE", "f32"): {
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl8 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_2-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl2 vec0 | generic small",
+        'n1_2-5_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl8 vec0 | generic gather tl2 vec0 | generic small",
+        'n1_2-16_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl16 vec0 | generic taps tl2 nt3 cv4 | generic small",
+        'n1_3-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic taps tl4 nt3 cv1 | generic small",
+        'n1_3-2_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic gather tl4 vec0 | generic small",
+        'n1_3-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt3 cv4 | generic small",
+        'n1_4-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl4 nt3 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_4-5_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv4 | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_5-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl8 nt3 cv1 | generic small",
+        'n1_5-2_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic gather tl8 vec0 | generic small",
+        'n1_5-4_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt3 cv4 | generic small",
+        'n1_8-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl8 nt3 cv1 | generic co1 ci8",
+        'n1_16-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl16 nt3 cv1 | generic co1 ci16",
+        'n1_16-2_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv4 | generic gather tl16 vec0 | generic small",
+        'n1_16-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic taps tl16 nt3 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k211_s111_p100_d111_b1_i0_o0': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic co1 ci1",
+        'n1_1-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic staps tl2 nt3 | generic quads nt8 civ1",
+        'n1_3-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic gather tl2 vec0 | generic strided tl4 vec0 | generic small",
+        'n1_3-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt3 | generic small",
+        'n1_5-1_5x7x9_k211_s211_p000_d111_b0_i0_o0': "generic gather tl2 vec0 | generic strided tl8 vec0 | generic small",
+        'n1_5-4_5x7x9_k211_s211_p000_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt3 | generic small",
+        'n1_16-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic strided tl16 vec0 | generic co1 ci16",
+        'n1_16-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic staps tl16 nt3 | generic quads nt4 civ4",
+        'n1_1-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt6 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'n1_1-3_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic taps tl2 nt4 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt6 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv1 | generic taps tl2 nt4 cv4 | generic quads nt8 civ1",
+        'n1_3-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic gather tl2 vec0 | generic taps tl4 nt8 cv1 | generic small",
+        'n1_3-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt4 cv4 | generic small",
+        'n1_4-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt4 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt4 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-5_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt4 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt4 cv4 | generic taps tl4 nt4 cv4 | generic quads nt4 civ4",
+        'n1_5-1_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl8 nt8 cv1 | generic small",
+        'n1_5-4_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt4 cv4 | generic small",
+        'n1_16-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt4 cv4 | generic taps tl16 nt8 cv1 | generic co1 ci16",
+        'n1_16-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt4 cv4 | generic taps tl16 nt4 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k411_s111_p200_d111_b1_i0_o0': "generic c1taps nt8 | generic c1taps nt8 | generic c1taps nt8",
+        'n1_1-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic taps tl2 nt6 cv4 | generic quads nt8 civ1",
+        'n1_3-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt6 cv4 | generic small",
+        'n1_4-1_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt6 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_4-5_5x7x9_k511_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt6 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv4 | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_5-4_5x7x9_k511_s111_p200_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt6 cv4 | generic small",
+        'n1_16-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic taps tl16 nt6 cv4 | generic quads nt6 civ4",
+        'n1_1-1_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl2 nt8 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'n1_1-3_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv1 | generic taps tl2 nt8 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt8 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl16 nt8 cv1 | generic taps tl2 nt8 cv4 | generic quads nt8 civ1",
+        'n1_3-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt8 cv4 | generic small",
+        'n1_4-1_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl2 nt8 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_4-5_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt8 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl16 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_5-4_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt8 cv4 | generic small",
+        'n1_16-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl16 nt8 cv4 | generic quads nt8 civ4",
+        'n1_1-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl2 nt4 | generic lds",
+        'n1_3-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt4 | generic lds",
+        'n1_4-1_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl2 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-3_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-5_5x7x9_k331_s221_p110_d111_b0_i0_o0': "generic gather tl8 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-16_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl16 vec1 | generic staps tl4 nt4 | generic lds",
+        'n1_5-4_5x7x9_k331_s221_p110_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt4 | generic lds",
+        'n1_16-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec1 | generic staps tl16 nt4 | generic lds",
+        'n1_1-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl2 nt8 | generic lds",
+        'n1_3-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt8 | generic lds",
+        'n1_5-4_5x7x9_k444_s222_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt8 | generic lds",
+        'n1_16-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic staps tl16 nt8 | generic lds",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i0_o0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_3-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl4 vec1 | generic lds",
+        'n1_5-4_5x7x9_k333_s111_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic gather tl8 vec1 | generic lds",
+        'n1_16-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic gather tl16 vec1 | wgrad6",
+        'n1_1-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic strided tl2 vec1 | generic lds",
+        'n1_3-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic strided tl4 vec1 | generic lds",
+        'n1_5-4_5x7x9_k333_s211_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic strided tl8 vec1 | generic lds",
+        'n1_16-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic strided tl16 vec1 | generic lds",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'n1_4-2_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+        'n1_4-3_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv0",
+        'n1_4-4_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv1",
+        'n1_4-5_5x7x9_k111_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv0",
+        'n1_4-8_5x7x9_k111_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv1",
+        'n1_8-1_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'n1_8-2_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+        'n1_8-3_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv0",
+        'n1_8-4_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv1",
+        'n1_8-8_1x7x9_k131_s111_p010_d111_b1_i0_o0': "generic taps tl8 nt3 cv4 | generic taps tl8 nt3 cv4 | generic quads nt4 civ4",
+        'n2_16-8_3x5x70_k116_s112_p002_d111_b1_i0_o0': "generic taps tl8 nt6 cv4 | generic staps tl16 nt3 | generic quads nt6 civ4",
+        'n1_1-1_5x1x9_k333_s111_p111_d111_b1_i0_o0': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n3_4-4_5x7x1_k222_s111_p111_d111_b0_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_8-16_9x1x33_k611_s211_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv4 | generic staps tl8 nt3 | generic quads nt6 civ4",
+    },
+    ("GENERIC_DENSE", "bf16"): {
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl8 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_2-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl2 vec0 | generic small",
+        'n1_2-5_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl8 vec0 | generic gather tl2 vec0 | generic small",
+        'n1_2-16_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl16 vec0 | generic taps tl2 nt3 cv4 | generic small",
+        'n1_3-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic taps tl4 nt3 cv1 | generic small",
+        'n1_3-2_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic gather tl4 vec0 | generic small",
+        'n1_3-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt3 cv4 | generic small",
+        'n1_4-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl4 nt3 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_4-5_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl16 nt3 cv4 | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_5-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl8 nt3 cv1 | generic small",
+        'n1_5-2_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic gather tl2 vec0 | generic gather tl8 vec0 | generic small",
+        'n1_5-4_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt3 cv4 | generic small",
+        'n1_8-1_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl8 nt3 cv1 | generic co1 ci8",
+        'n1_16-1_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic taps tl16 nt3 cv1 | generic co1 ci16",
+        'n1_16-2_5x7x9_k211_s111_p100_d111_b0_i0_o0': "generic taps tl2 nt3 cv4 | generic gather tl16 vec0 | generic small",
+        'n1_16-4_5x7x9_k211_s111_p100_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic taps tl16 nt3 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k211_s111_p100_d111_b1_i0_o0': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic co1 ci1",
+        'n1_1-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl4 nt3 cv1 | generic staps tl2 nt3 | generic quads nt8 civ1",
+        'n1_3-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic gather tl2 vec0 | generic strided tl4 vec0 | generic small",
+        'n1_3-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt3 | generic small",
+        'n1_5-1_5x7x9_k211_s211_p000_d111_b0_i0_o0': "generic gather tl2 vec0 | generic strided tl8 vec0 | generic small",
+        'n1_5-4_5x7x9_k211_s211_p000_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt3 | generic small",
+        'n1_16-1_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl2 nt3 cv4 | generic strided tl16 vec0 | generic co1 ci16",
+        'n1_16-4_5x7x9_k211_s211_p000_d111_b1_i0_o0': "generic taps tl4 nt3 cv4 | generic staps tl16 nt3 | generic quads nt4 civ4",
+        'n1_1-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt6 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'n1_1-3_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic taps tl2 nt4 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt6 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv1 | generic taps tl2 nt4 cv4 | generic quads nt8 civ1",
+        'n1_3-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic gather tl2 vec0 | generic taps tl4 nt8 cv1 | generic small",
+        'n1_3-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt4 cv4 | generic small",
+        'n1_4-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt4 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt4 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-5_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt4 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt4 cv4 | generic taps tl4 nt4 cv4 | generic quads nt4 civ4",
+        'n1_5-1_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic gather tl2 vec0 | generic taps tl8 nt8 cv1 | generic small",
+        'n1_5-4_5x7x9_k411_s111_p200_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt4 cv4 | generic small",
+        'n1_16-1_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt4 cv4 | generic taps tl16 nt8 cv1 | generic co1 ci16",
+        'n1_16-4_5x7x9_k411_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt4 cv4 | generic taps tl16 nt4 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k411_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt6 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'n1_1-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv1 | generic taps tl2 nt6 cv4 | generic quads nt8 civ1",
+        'n1_3-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt6 cv4 | generic small",
+        'n1_4-1_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl2 nt6 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_4-5_5x7x9_k511_s111_p200_d111_b0_i0_o0': "generic taps tl8 nt6 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv4 | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_5-4_5x7x9_k511_s111_p200_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt6 cv4 | generic small",
+        'n1_16-4_5x7x9_k511_s111_p200_d111_b1_i0_o0': "generic taps tl4 nt6 cv4 | generic taps tl16 nt6 cv4 | generic quads nt6 civ4",
+        'n1_1-1_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl2 nt8 cv1 | generic taps tl2 nt8 cv1 | generic co1 ci1",
+        'n1_1-3_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv1 | generic taps tl2 nt8 cv4 | generic quads nt8 civ1",
+        'n1_1-5_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt8 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-16_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl16 nt8 cv1 | generic taps tl2 nt8 cv4 | generic quads nt8 civ1",
+        'n1_3-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic gather tl4 vec0 | generic taps tl4 nt8 cv4 | generic small",
+        'n1_4-1_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl2 nt8 cv4 | generic taps tl4 nt8 cv1 | generic co1 ci4",
+        'n1_4-3_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_4-5_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt8 cv4 | generic gather tl4 vec0 | generic small",
+        'n1_4-16_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl16 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_5-4_5x7x9_k222_s111_p000_d111_b0_i0_o0': "generic gather tl4 vec0 | generic taps tl8 nt8 cv4 | generic small",
+        'n1_16-4_5x7x9_k222_s111_p000_d111_b1_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl16 nt8 cv4 | generic quads nt8 civ4",
+        'n1_1-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl2 nt4 | generic lds",
+        'n1_3-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt4 | generic lds",
+        'n1_4-1_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl2 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-3_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-5_5x7x9_k331_s221_p110_d111_b0_i0_o0': "generic gather tl8 vec1 | generic strided tl4 vec0 | generic lds",
+        'n1_4-16_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl16 vec1 | generic staps tl4 nt4 | generic lds",
+        'n1_5-4_5x7x9_k331_s221_p110_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt4 | generic lds",
+        'n1_16-4_5x7x9_k331_s221_p110_d111_b1_i0_o0': "generic gather tl4 vec1 | generic staps tl16 nt4 | generic lds",
+        'n1_1-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl2 nt8 | generic lds",
+        'n1_3-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic staps tl4 nt8 | generic lds",
+        'n1_5-4_5x7x9_k444_s222_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic staps tl8 nt8 | generic lds",
+        'n1_16-4_5x7x9_k444_s222_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic staps tl16 nt8 | generic lds",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl2 vec1 | cin1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i0_o0': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_3-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic gather tl4 vec1 | generic lds",
+        'n1_5-4_5x7x9_k333_s111_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic gather tl8 vec1 | generic lds",
+        'n1_16-4_5x7x9_k333_s111_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic gather tl16 vec1 | wgrad4",
+        'n1_1-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic strided tl2 vec1 | generic lds",
+        'n1_3-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec0 | generic strided tl4 vec1 | generic lds",
+        'n1_5-4_5x7x9_k333_s211_p111_d111_b0_i0_o0': "generic gather tl4 vec0 | generic strided tl8 vec1 | generic lds",
+        'n1_16-4_5x7x9_k333_s211_p111_d111_b1_i0_o0': "generic gather tl4 vec1 | generic strided tl16 vec1 | generic lds",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'n1_4-2_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+        'n1_4-3_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv0",
+        'n1_4-4_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx4 dv1",
+        'n1_4-5_5x7x9_k111_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv0",
+        'n1_4-8_5x7x9_k111_s111_p000_d111_b0_i0_o0': "generic taps tl8 nt3 cv4 | pointwise co8 | pointwise co8 vx4 dv1",
+        'n1_8-1_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx8 dv0",
+        'n1_8-2_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx8 dv1",
+        'n1_8-3_5x7x9_k111_s111_p000_d111_b1_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx8 dv0",
+        'n1_8-4_5x7x9_k111_s111_p000_d111_b0_i0_o0': "pointwise co4 | pointwise co4 | pointwise co4 vx8 dv1",
+        'n1_8-8_1x7x9_k131_s111_p010_d111_b1_i0_o0': "generic taps tl8 nt3 cv4 | generic taps tl8 nt3 cv4 | generic quads nt4 civ4",
+        'n2_16-8_3x5x70_k116_s112_p002_d111_b1_i0_o0': "generic taps tl8 nt6 cv4 | generic staps tl16 nt3 | generic quads nt6 civ4",
+        'n1_1-1_5x1x9_k333_s111_p111_d111_b1_i0_o0': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n3_4-4_5x7x1_k222_s111_p111_d111_b0_i0_o0': "generic taps tl4 nt8 cv4 | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_8-16_9x1x33_k611_s211_p200_d111_b1_i0_o0': "generic taps tl16 nt6 cv4 | generic staps tl8 nt3 | generic quads nt6 civ4",
+    },
+    ("GENERIC_PITCHED", "f32"): {
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i4_o4': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl4 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i4_o4': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i4_o4': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic co1 ci1",
+        'n1_1-4_5x7x9_k211_s211_p000_d111_b1_i4_o4': "generic taps tl4 nt3 cv1 | generic staps tl2 nt3 | generic quads nt8 civ1",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i4_o4': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i4_o4': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i4_o4': "generic cin1 co16 | generic gather tl2 vec1 | cin1",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i4_o4': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i1_o1': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i1_o1': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i1_o1': "generic taps tl16 nt3 cv1 | generic gather tl2 vec0 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i1_o1': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i1_o1': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic small",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i1_o1': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i1_o1': "generic cin1 co8 | generic gather tl2 vec0 | generic lds",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i1_o1': "generic gather tl2 vec0 | pointwise co2 | generic small",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i1_o0': "generic cin1 co16 | generic gather tl2 vec1 | generic cin1 co16",
+        'n1_8-8_5x7x70_k113_s111_p001_d111_b1_i4_o4': "generic taps tl8 nt3 cv4 | generic taps tl8 nt3 cv4 | generic quads nt4 civ4",
+        'n2_1-8_1x9x13_k333_s111_p111_d111_b1_i0_o4': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_16-2_3x1x11_k111_s111_p000_d111_b1_i4_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+    },
+    ("GENERIC_PITCHED", "bf16"): {
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i4_o4': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-4_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl4 nt3 cv1 | generic taps tl2 nt3 cv4 | generic quads nt8 civ1",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i4_o4': "generic taps tl16 nt3 cv1 | generic taps tl2 nt3 cv4 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i4_o4': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i4_o4': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic co1 ci1",
+        'n1_1-4_5x7x9_k211_s211_p000_d111_b1_i4_o4': "generic taps tl4 nt3 cv1 | generic staps tl2 nt3 | generic quads nt8 civ1",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i4_o4': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i4_o4': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i4_o4': "generic cin1 co16 | generic gather tl2 vec1 | generic cin1 co16",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i4_o4': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv0",
+        'n1_1-1_5x7x9_k211_s111_p100_d111_b1_i1_o1': "generic taps tl2 nt3 cv1 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-2_5x7x9_k211_s111_p100_d111_b0_i1_o1': "generic taps tl2 nt3 cv1 | generic gather tl2 vec0 | generic small",
+        'n1_1-72_5x7x9_k211_s111_p100_d111_b1_i1_o1': "generic taps tl16 nt3 cv1 | generic gather tl2 vec0 | generic lds",
+        'n1_2-1_5x7x9_k211_s111_p100_d111_b0_i1_o1': "generic gather tl2 vec0 | generic taps tl2 nt3 cv1 | generic small",
+        'n1_1-1_5x7x9_k211_s211_p000_d111_b1_i1_o1': "generic taps tl2 nt3 cv1 | generic strided tl2 vec0 | generic small",
+        'n1_1-1_5x7x9_k333_s111_p111_d111_b1_i1_o1': "generic c1c1 | generic c1c1 | generic c1c1",
+        'n1_1-8_5x7x9_k333_s111_p111_d111_b0_i1_o1': "generic cin1 co8 | generic gather tl2 vec0 | generic lds",
+        'n1_4-1_5x7x9_k111_s111_p000_d111_b1_i1_o1': "generic gather tl2 vec0 | pointwise co2 | generic small",
+        'n1_1-16_5x7x9_k333_s111_p111_d111_b1_i1_o0': "generic cin1 co16 | generic gather tl2 vec1 | generic cin1 co16",
+        'n1_8-8_5x7x70_k113_s111_p001_d111_b1_i4_o4': "generic taps tl8 nt3 cv4 | generic taps tl8 nt3 cv4 | generic quads nt4 civ4",
+        'n2_1-8_1x9x13_k333_s111_p111_d111_b1_i0_o4': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'n1_16-2_3x1x11_k111_s111_p000_d111_b1_i4_o0': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+    },
+    ("TRANSPOSE", "f32"): {
+        'n1_1-1_2x3x17_k211_s111_p000_o000_b1': "generic taps tl2 nt3 cv1 bias | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-3_2x3x17_k211_s111_p000_o000_b1': "generic taps tl4 nt3 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-5_2x3x17_k211_s111_p000_o000_b1': "generic taps tl8 nt3 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-16_2x3x17_k211_s111_p000_o000_b1': "generic taps tl16 nt3 cv1 bias | generic taps tl2 nt3 cv4 | generic co1 ci16",
+        'n1_2-1_2x3x17_k211_s111_p000_o000_b1': "generic gather tl2 vec0 bias | generic taps tl2 nt3 cv1 | generic small",
+        'n1_2-3_2x3x17_k211_s111_p000_o000_b1': "generic gather tl4 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n1_2-5_2x3x17_k211_s111_p000_o000_b1': "generic gather tl8 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n1_2-16_2x3x17_k211_s111_p000_o000_b1': "generic gather tl16 vec0 bias | generic taps tl2 nt3 cv4 | generic small",
+        'n1_4-1_2x3x17_k211_s111_p000_o000_b1': "generic taps tl2 nt3 cv4 bias | generic taps tl4 nt3 cv1 | generic quads nt8 civ1",
+        'n1_4-3_2x3x17_k211_s111_p000_o000_b1': "generic taps tl4 nt3 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_2x3x17_k211_s111_p000_o000_b1': "generic taps tl8 nt3 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_2x3x17_k211_s111_p000_o000_b1': "generic taps tl16 nt3 cv4 bias | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n2_1-1_3x5x7_k211_s211_p000_o100_b1': "generic strided tl2 vec0 bias | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n2_1-3_3x5x7_k211_s211_p000_o100_b1': "generic strided tl4 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n2_1-5_3x5x7_k211_s211_p000_o100_b1': "generic strided tl8 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n2_1-16_3x5x7_k211_s211_p000_o100_b1': "generic strided tl16 vec0 bias | generic taps tl2 nt3 cv4 | generic co1 ci16",
+        'n2_4-1_3x5x7_k211_s211_p000_o100_b1': "generic staps tl2 nt3 bias | generic taps tl4 nt3 cv1 | generic quads nt8 civ1",
+        'n2_4-3_3x5x7_k211_s211_p000_o100_b1': "generic staps tl4 nt3 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-5_3x5x7_k211_s211_p000_o100_b1': "generic staps tl8 nt3 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-16_3x5x7_k211_s211_p000_o100_b1': "generic staps tl16 nt3 bias | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k311_s111_p100_o000_b1': "generic c1taps nt3 bias | generic c1taps nt3 | generic c1taps nt3",
+        'n1_1-1_2x3x17_k411_s111_p000_o000_b1': "generic taps tl2 nt8 cv1 bias | generic taps tl2 nt6 cv1 | generic co1 ci1",
+        'n1_1-3_2x3x17_k411_s111_p000_o000_b1': "generic taps tl4 nt8 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-5_2x3x17_k411_s111_p000_o000_b1': "generic taps tl8 nt8 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-16_2x3x17_k411_s111_p000_o000_b1': "generic taps tl16 nt8 cv1 bias | generic taps tl2 nt4 cv4 | generic co1 ci16",
+        'n1_4-1_2x3x17_k411_s111_p000_o000_b1': "generic taps tl2 nt4 cv4 bias | generic taps tl4 nt6 cv1 | generic quads nt8 civ1",
+        'n1_4-3_2x3x17_k411_s111_p000_o000_b1': "generic taps tl4 nt4 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_2x3x17_k411_s111_p000_o000_b1': "generic taps tl8 nt4 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_2x3x17_k411_s111_p000_o000_b1': "generic taps tl16 nt4 cv4 bias | generic taps tl4 nt4 cv4 | generic quads nt4 civ4",
+        'n2_4-1_3x5x7_k511_s111_p200_o000_b1': "generic taps tl2 nt6 cv4 bias | generic taps tl4 nt6 cv1 | generic quads nt8 civ1",
+        'n2_4-3_3x5x7_k511_s111_p200_o000_b1': "generic taps tl4 nt6 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-5_3x5x7_k511_s111_p200_o000_b1': "generic taps tl8 nt6 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-16_3x5x7_k511_s111_p200_o000_b1': "generic taps tl16 nt6 cv4 bias | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_1-1_5x7x8_k511_s111_p200_o000_b1': "generic c1taps nt8 bias | generic c1taps nt8 | generic c1taps nt8",
+        'n2_1-1_3x5x7_k333_s111_p111_o000_b1': "generic c1c1 bias | generic c1c1 | generic c1c1",
+        'n2_4-1_3x5x7_k333_s111_p111_o000_b1': "generic gather tl2 vec1 bias | generic gather tl4 vec0 | cin1",
+        'n2_4-3_3x5x7_k333_s111_p111_o000_b1': "generic gather tl4 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n2_4-5_3x5x7_k333_s111_p111_o000_b1': "generic gather tl8 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n2_4-16_3x5x7_k333_s111_p111_o000_b1': "generic gather tl16 vec1 bias | generic gather tl4 vec1 | wgrad6",
+        'n1_4-1_4x6x8_k222_s111_p000_o000_b1': "generic taps tl2 nt8 cv4 bias | generic taps tl4 nt8 cv1 | generic quads nt8 civ1",
+        'n1_4-3_4x6x8_k222_s111_p000_o000_b1': "generic taps tl4 nt8 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_4x6x8_k222_s111_p000_o000_b1': "generic taps tl8 nt8 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_4x6x8_k222_s111_p000_o000_b1': "generic taps tl16 nt8 cv4 bias | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_4-1_3x4x5_k331_s221_p110_o000_b1': "generic staps tl2 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_3x4x5_k331_s221_p110_o000_b1': "generic staps tl4 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_3x4x5_k331_s221_p110_o000_b1': "generic staps tl8 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_3x4x5_k331_s221_p110_o000_b1': "generic staps tl16 nt4 bias | generic gather tl4 vec1 | generic lds",
+        'n1_4-1_4x6x8_k333_s222_p111_o000_b1': "generic staps tl2 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_4x6x8_k333_s222_p111_o000_b1': "generic staps tl4 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_4x6x8_k333_s222_p111_o000_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_4x6x8_k333_s222_p111_o000_b1': "generic staps tl16 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_4-1_4x6x8_k555_s222_p222_o000_b1': "generic strided tl2 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_4x6x8_k555_s222_p222_o000_b1': "generic strided tl4 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_4x6x8_k555_s222_p222_o000_b1': "generic strided tl8 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_4x6x8_k555_s222_p222_o000_b1': "generic strided tl16 vec1 bias | generic gather tl4 vec1 | generic lds",
+        'n2_1-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co2 bias | pointwise co2 | pointwise co2 vx4 dv0",
+        'n2_3-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co4 bias | pointwise co4 | pointwise co4 vx4 dv0",
+        'n2_5-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co8 bias | generic taps tl8 nt3 cv4 | pointwise co8 vx4 dv0",
+        'n1_6-6_5x6x7_k222_s222_p000_o000_b1': "generic strided tl8 vec0 bias | generic gather tl8 vec0 | generic small",
+        'n2_1-1_3x4x5_k444_s444_p000_o000_b1': "generic strided tl2 vec0 bias | generic gather tl2 vec0 | generic lds",
+        'n1_8-4_5x5x6_k444_s222_p111_o000_b1': "generic staps tl4 nt8 bias | generic gather tl8 vec1 | generic lds",
+        'n1_4-8_4x5x3_k333_s222_p111_o111_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_8-8_3x4x5_k444_s444_p000_o000_b1': "generic staps tl8 nt3 bias | generic gather tl8 vec1 | generic lds",
+        'n1_16-16_2x3x5_k444_s444_p000_o000_b1': "generic staps tl16 nt3 bias | generic gather tl16 vec1 | generic lds",
+        'n1_1-1_3x5x7_k444_s444_p000_o000_b1': "generic strided tl2 vec0 bias | generic gather tl2 vec0 | generic lds",
+        'n2_8-8_3x5x7_k444_s222_p111_o000_b1': "generic staps tl8 nt8 bias | generic gather tl8 vec1 | generic lds",
+        'n2_4-8_3x5x7_k333_s222_p111_o111_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_8-8_1x5x7_k222_s222_p000_o000_b0': "generic staps tl8 nt3 | generic taps tl8 nt8 cv4 | generic quads nt8 civ4",
+    },
+    ("TRANSPOSE", "bf16"): {
+        'n1_1-1_2x3x17_k211_s111_p000_o000_b1': "generic taps tl2 nt3 cv1 bias | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-3_2x3x17_k211_s111_p000_o000_b1': "generic taps tl4 nt3 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-5_2x3x17_k211_s111_p000_o000_b1': "generic taps tl8 nt3 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-16_2x3x17_k211_s111_p000_o000_b1': "generic taps tl16 nt3 cv1 bias | generic taps tl2 nt3 cv4 | generic co1 ci16",
+        'n1_2-1_2x3x17_k211_s111_p000_o000_b1': "generic gather tl2 vec0 bias | generic taps tl2 nt3 cv1 | generic small",
+        'n1_2-3_2x3x17_k211_s111_p000_o000_b1': "generic gather tl4 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n1_2-5_2x3x17_k211_s111_p000_o000_b1': "generic gather tl8 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n1_2-16_2x3x17_k211_s111_p000_o000_b1': "generic gather tl16 vec0 bias | generic taps tl2 nt3 cv4 | generic small",
+        'n1_4-1_2x3x17_k211_s111_p000_o000_b1': "generic taps tl2 nt3 cv4 bias | generic taps tl4 nt3 cv1 | generic quads nt8 civ1",
+        'n1_4-3_2x3x17_k211_s111_p000_o000_b1': "generic taps tl4 nt3 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_2x3x17_k211_s111_p000_o000_b1': "generic taps tl8 nt3 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_2x3x17_k211_s111_p000_o000_b1': "generic taps tl16 nt3 cv4 bias | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n2_1-1_3x5x7_k211_s211_p000_o100_b1': "generic strided tl2 vec0 bias | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n2_1-3_3x5x7_k211_s211_p000_o100_b1': "generic strided tl4 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n2_1-5_3x5x7_k211_s211_p000_o100_b1': "generic strided tl8 vec0 bias | generic gather tl2 vec0 | generic small",
+        'n2_1-16_3x5x7_k211_s211_p000_o100_b1': "generic strided tl16 vec0 bias | generic taps tl2 nt3 cv4 | generic co1 ci16",
+        'n2_4-1_3x5x7_k211_s211_p000_o100_b1': "generic staps tl2 nt3 bias | generic taps tl4 nt3 cv1 | generic quads nt8 civ1",
+        'n2_4-3_3x5x7_k211_s211_p000_o100_b1': "generic staps tl4 nt3 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-5_3x5x7_k211_s211_p000_o100_b1': "generic staps tl8 nt3 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-16_3x5x7_k211_s211_p000_o100_b1': "generic staps tl16 nt3 bias | generic taps tl4 nt3 cv4 | generic quads nt4 civ4",
+        'n1_1-1_5x7x8_k311_s111_p100_o000_b1': "generic taps tl2 nt3 cv1 bias | generic taps tl2 nt3 cv1 | generic co1 ci1",
+        'n1_1-1_2x3x17_k411_s111_p000_o000_b1': "generic taps tl2 nt8 cv1 bias | generic taps tl2 nt6 cv1 | generic co1 ci1",
+        'n1_1-3_2x3x17_k411_s111_p000_o000_b1': "generic taps tl4 nt8 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-5_2x3x17_k411_s111_p000_o000_b1': "generic taps tl8 nt8 cv1 bias | generic gather tl2 vec0 | generic small",
+        'n1_1-16_2x3x17_k411_s111_p000_o000_b1': "generic taps tl16 nt8 cv1 bias | generic taps tl2 nt4 cv4 | generic co1 ci16",
+        'n1_4-1_2x3x17_k411_s111_p000_o000_b1': "generic taps tl2 nt4 cv4 bias | generic taps tl4 nt6 cv1 | generic quads nt8 civ1",
+        'n1_4-3_2x3x17_k411_s111_p000_o000_b1': "generic taps tl4 nt4 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_2x3x17_k411_s111_p000_o000_b1': "generic taps tl8 nt4 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_2x3x17_k411_s111_p000_o000_b1': "generic taps tl16 nt4 cv4 bias | generic taps tl4 nt4 cv4 | generic quads nt4 civ4",
+        'n2_4-1_3x5x7_k511_s111_p200_o000_b1': "generic taps tl2 nt6 cv4 bias | generic taps tl4 nt6 cv1 | generic quads nt8 civ1",
+        'n2_4-3_3x5x7_k511_s111_p200_o000_b1': "generic taps tl4 nt6 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-5_3x5x7_k511_s111_p200_o000_b1': "generic taps tl8 nt6 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n2_4-16_3x5x7_k511_s111_p200_o000_b1': "generic taps tl16 nt6 cv4 bias | generic taps tl4 nt6 cv4 | generic quads nt6 civ4",
+        'n1_1-1_5x7x8_k511_s111_p200_o000_b1': "generic taps tl2 nt8 cv1 bias | generic taps tl2 nt6 cv1 | generic co1 ci1",
+        'n2_1-1_3x5x7_k333_s111_p111_o000_b1': "generic c1c1 bias | generic c1c1 | generic c1c1",
+        'n2_4-1_3x5x7_k333_s111_p111_o000_b1': "generic gather tl2 vec1 bias | generic gather tl4 vec0 | cin1",
+        'n2_4-3_3x5x7_k333_s111_p111_o000_b1': "generic gather tl4 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n2_4-5_3x5x7_k333_s111_p111_o000_b1': "generic gather tl8 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n2_4-16_3x5x7_k333_s111_p111_o000_b1': "generic gather tl16 vec1 bias | generic gather tl4 vec1 | wgrad4",
+        'n1_4-1_4x6x8_k222_s111_p000_o000_b1': "generic taps tl2 nt8 cv4 bias | generic taps tl4 nt8 cv1 | generic quads nt8 civ1",
+        'n1_4-3_4x6x8_k222_s111_p000_o000_b1': "generic taps tl4 nt8 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-5_4x6x8_k222_s111_p000_o000_b1': "generic taps tl8 nt8 cv4 bias | generic gather tl4 vec0 | generic small",
+        'n1_4-16_4x6x8_k222_s111_p000_o000_b1': "generic taps tl16 nt8 cv4 bias | generic taps tl4 nt8 cv4 | generic quads nt8 civ4",
+        'n1_4-1_3x4x5_k331_s221_p110_o000_b1': "generic staps tl2 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_3x4x5_k331_s221_p110_o000_b1': "generic staps tl4 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_3x4x5_k331_s221_p110_o000_b1': "generic staps tl8 nt4 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_3x4x5_k331_s221_p110_o000_b1': "generic staps tl16 nt4 bias | generic gather tl4 vec1 | generic lds",
+        'n1_4-1_4x6x8_k333_s222_p111_o000_b1': "generic staps tl2 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_4x6x8_k333_s222_p111_o000_b1': "generic staps tl4 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_4x6x8_k333_s222_p111_o000_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_4x6x8_k333_s222_p111_o000_b1': "generic staps tl16 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_4-1_4x6x8_k555_s222_p222_o000_b1': "generic strided tl2 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-3_4x6x8_k555_s222_p222_o000_b1': "generic strided tl4 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-5_4x6x8_k555_s222_p222_o000_b1': "generic strided tl8 vec1 bias | generic gather tl4 vec0 | generic lds",
+        'n1_4-16_4x6x8_k555_s222_p222_o000_b1': "generic strided tl16 vec1 bias | generic gather tl4 vec1 | generic lds",
+        'n2_1-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co2 bias | pointwise co2 | pointwise co2 vx4 dv0",
+        'n2_3-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co4 bias | pointwise co4 | pointwise co4 vx4 dv0",
+        'n2_5-4_3x5x7_k111_s111_p000_o000_b1': "pointwise co8 bias | generic taps tl8 nt3 cv4 | pointwise co8 vx4 dv0",
+        'n1_6-6_5x6x7_k222_s222_p000_o000_b1': "generic strided tl8 vec0 bias | generic gather tl8 vec0 | generic small",
+        'n2_1-1_3x4x5_k444_s444_p000_o000_b1': "generic strided tl2 vec0 bias | generic gather tl2 vec0 | generic lds",
+        'n1_8-4_5x5x6_k444_s222_p111_o000_b1': "generic staps tl4 nt8 bias | generic gather tl8 vec1 | generic lds",
+        'n1_4-8_4x5x3_k333_s222_p111_o111_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_8-8_3x4x5_k444_s444_p000_o000_b1': "generic staps tl8 nt3 bias | generic gather tl8 vec1 | generic lds",
+        'n1_16-16_2x3x5_k444_s444_p000_o000_b1': "generic staps tl16 nt3 bias | generic gather tl16 vec1 | generic lds",
+        'n1_1-1_3x5x7_k444_s444_p000_o000_b1': "generic strided tl2 vec0 bias | generic gather tl2 vec0 | generic lds",
+        'n2_8-8_3x5x7_k444_s222_p111_o000_b1': "generic staps tl8 nt8 bias | generic gather tl8 vec1 | generic lds",
+        'n2_4-8_3x5x7_k333_s222_p111_o111_b1': "generic staps tl8 nt8 bias | generic gather tl4 vec1 | generic lds",
+        'n1_8-8_1x5x7_k222_s222_p000_o000_b0': "generic staps tl8 nt3 | generic taps tl8 nt8 cv4 | generic quads nt8 civ4",
+    },
+    ("WS_WGRAD", "f32"): {
+        'wgrad_c1c1': "generic c1c1 | generic c1c1 | generic c1c1",
+        'wgrad_c1taps': "generic c1taps nt3 | generic c1taps nt3 | generic c1taps nt3",
+        'wgrad_cin1': "generic cin1 co8 | generic gather tl2 vec1 | generic cin1 co8",
+        'wgrad_co1': "generic taps tl2 nt3 cv4 | generic taps tl8 nt3 cv1 | generic co1 ci8",
+        'wgrad_quads': "generic taps tl8 nt3 cv4 | generic taps tl8 nt3 cv4 | generic quads nt4 civ4",
+        'wgrad_quads_dy_misaligned': "generic taps tl8 nt3 cv4 | generic gather tl8 vec0 | generic small",
+        'wgrad_small': "generic gather tl8 vec0 | generic gather tl4 vec0 | generic small",
+        'wgrad_lds': "generic gather tl8 vec0 | generic gather tl4 vec0 | generic lds",
+        'wgrad_pointwise': "pointwise co2 | pointwise co2 | pointwise co2 vx4 dv1",
+    },
+    ("WS_WGRAD", "bf16"): {
+        'wgrad_cin1_bf16': "generic cin1 co16 | generic gather tl2 vec1 | generic cin1 co16",
+        'wgrad_quads_bf16': "generic taps tl16 nt6 cv4 | generic staps tl8 nt3 | generic quads nt6 civ4",
+        'wgrad_pointwise_bf16': "pointwise co4 | pointwise co4 | pointwise co4 vx8 dv1",
     },
 })

@@ -59,19 +59,21 @@ int main() {
                                 ++checked;
                                 // the route query names a kernel for every pass, alignment and bias; only a request for fused
                                 // statistics can be refused ("none"), and a misaligned tensor never reaches the 16-byte MFMA kernels
+                                // (every name fits the 32-byte minimum buffer; the two tensors' alignments are independent)
                                 for (int align : {16, 8, 4})
-                                    for (int bias = 0; bias < 2; ++bias) {
-                                        memset(name, 0x7f, sizeof(name));
-                                        EXPECT(mri3d_conv3d_route(&g, pass, 0, bias, 0, 0, align, name, sizeof(name)) == MRI3D_OK);
-                                        EXPECT(memchr(name, 0, sizeof(name)) != nullptr && name[0] != 0 && strcmp(name, "none") != 0);
-                                        if (align < 16) EXPECT(strcmp(name, "generic") == 0 || strcmp(name, "pointwise") == 0);
-                                        ++routes;
-                                    }
+                                    for (int align_y : {16, 4})
+                                        for (int bias = 0; bias < 2; ++bias) {
+                                            memset(name, 0x7f, sizeof(name));
+                                            EXPECT(mri3d_conv3d_route(&g, pass, 0, bias, 0, 0, align, align_y, name, sizeof(name)) == MRI3D_OK);
+                                            EXPECT(memchr(name, 0, sizeof(name)) != nullptr && name[0] != 0 && strcmp(name, "none") != 0);
+                                            if (align < 16 || align_y < 16) EXPECT(strncmp(name, "generic ", 8) == 0 || strncmp(name, "pointwise ", 10) == 0);
+                                            ++routes;
+                                        }
                             }
                             // statistics: served exactly where the block query promises them
-                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 16, name, sizeof(name)) == MRI3D_OK);
+                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 16, 16, name, sizeof(name)) == MRI3D_OK);
                             EXPECT((strcmp(name, "none") != 0) == (mri3d_conv3d_fwd_stats_blocks(&g) > 0));
-                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 8, name, sizeof(name)) == MRI3D_OK && strcmp(name, "none") == 0);
+                            EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_FWD, 1, 1, 0, 0, 8, 8, name, sizeof(name)) == MRI3D_OK && strcmp(name, "none") == 0);
                             // where the query promises fused statistics, the launch path reaches the same route: with a 16-byte
                             // workspace it stops at the packed-weight image (always larger), neither "not served" nor a launch
                             if (mri3d_conv3d_fwd_stats_blocks(&g) > 0) {
@@ -112,13 +114,13 @@ int main() {
     EXPECT(mri3d_conv3d_fwd(&bad, P, P, P, P, P, 0, nullptr) == MRI3D_EINVAL);
 
     // ---- route query: argument validation
-    EXPECT(mri3d_conv3d_route(nullptr, 0, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);
-    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, nullptr, sizeof(name)) == MRI3D_EINVAL);
-    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, name, 8) == MRI3D_EINVAL);                  // name buffer too small
-    EXPECT(mri3d_conv3d_route(&g, 3, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);       // no such pass
-    EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_WGRAD, 1, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);   // statistics outside the forward
-    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, -16, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);
-    EXPECT(mri3d_conv3d_route(&bad, 0, 0, 0, 0, 0, 16, name, sizeof(name)) == MRI3D_EINVAL);     // (bad.pd = -1)
+    EXPECT(mri3d_conv3d_route(nullptr, 0, 0, 0, 0, 0, 16, 16, name, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, 16, nullptr, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, 0, 0, 16, 16, name, 8) == MRI3D_EINVAL);                  // name buffer too small
+    EXPECT(mri3d_conv3d_route(&g, 3, 0, 0, 0, 0, 16, 16, name, sizeof(name)) == MRI3D_EINVAL);       // no such pass
+    EXPECT(mri3d_conv3d_route(&g, MRI3D_PASS_WGRAD, 1, 0, 0, 0, 16, 16, name, sizeof(name)) == MRI3D_EINVAL);   // statistics outside the forward
+    EXPECT(mri3d_conv3d_route(&g, 0, 0, 0, -16, 0, 16, 16, name, sizeof(name)) == MRI3D_EINVAL);
+    EXPECT(mri3d_conv3d_route(&bad, 0, 0, 0, 0, 0, 16, 16, name, sizeof(name)) == MRI3D_EINVAL);     // (bad.pd = -1)
 
     // ---- split operands (conv over cat((x, x2))): the support query over a sweep, refusals without a launch
     {
@@ -142,7 +144,7 @@ int main() {
                             for (int extra : {0, 4, 8, 12}) {
                                 EXPECT(cat_agrees(c, ca, cb + extra, pass));
                                 // the route query names a kernel exactly where the split entry point is served
-                                EXPECT(mri3d_conv3d_route(&c, pass, 0, 1, ca, cb + extra, 16, name, sizeof(name)) == MRI3D_OK);
+                                EXPECT(mri3d_conv3d_route(&c, pass, 0, 1, ca, cb + extra, 16, 16, name, sizeof(name)) == MRI3D_OK);
                                 EXPECT((strcmp(name, "none") != 0) == (mri3d_conv3d_cat_supported(&c, ca, cb + extra, pass) == 1));
                             }
                         }

@@ -47,33 +47,23 @@ def test_conv3d_bf16(case):
     x = _rb(torch.randn(n, ci, *size))
     conv = torch.nn.Conv3d(ci, co, k, stride=stride, padding=pad, dilation=dil)
     w, b = conv.weight.detach(), conv.bias.detach()
-    wq = _rb(w)                                  # the kernels round weights to bf16 for the MFMA operands
+    xg = _dev(x).requires_grad_(True)
+    wg = w.cuda().requires_grad_(True)
+    bg = b.cuda().requires_grad_(True)
+    routes = cc.BF16_CONV.check(case, "bf16", x=xg)
+    # the MFMA kernels round the weights to bf16 for their operands; the kernels of conv_generic.hip / conv_pointwise.hip keep them fp32
+    wref = w if routes["fwd"].split(" ")[0] in ("generic", "pointwise") else _rb(w)
     xr = x.clone().requires_grad_(True)
-    wr = wq.clone().requires_grad_(True)
+    wr = wref.clone().requires_grad_(True)
     br = b.clone().requires_grad_(True)
     yr = F.conv3d(xr, wr, br, stride=stride, padding=pad, dilation=dil)
     dy = _rb(torch.randn_like(yr))
     yr.backward(dy)
 
-    xg = _dev(x).requires_grad_(True)
-    wg = w.cuda().requires_grad_(True)
-    bg = b.cuda().requires_grad_(True)
-    cc.BF16_CONV.check(case, "bf16", x=xg)
     yg = ops.conv3d(xg, wg, bg, stride=stride, padding=pad, dilation=dil)
     assert yg.dtype == BF
     yg.backward(_dev(dy))
     assert xg.grad.dtype == BF and wg.grad.dtype == torch.float32 and bg.grad.dtype == torch.float32
-    # generic (non-MFMA) kernels keep fp32 weights: compare against whichever weight rounding is closer
-    y_alt = F.conv3d(x, w, b, stride=stride, padding=pad, dilation=dil)
-    e1 = (yg.float().cpu() - yr.detach()).abs().max().item()
-    e2 = (yg.float().cpu() - y_alt).abs().max().item()
-    if e2 < e1:   # fp32-weight kernel
-        xr2 = x.clone().requires_grad_(True)
-        wr2 = w.clone().requires_grad_(True)
-        br2 = b.clone().requires_grad_(True)
-        yr2 = F.conv3d(xr2, wr2, br2, stride=stride, padding=pad, dilation=dil)
-        yr2.backward(dy)
-        yr, xr, wr, br = yr2, xr2, wr2, br2
     _close(yg, yr, "conv y")
     _close(xg.grad, xr.grad, "conv dx")
     _close(wg.grad, wr.grad, "conv dw", ulp=0.0, abs_frac=2e-3)

@@ -310,8 +310,28 @@ def _ws_conv(case):
     return cid, checked, pattern
 
 
-# (id, case, kernel that must be among the launched ones, or None); the convolutions: cc.WS_CONV
-WS_CASES = [_ws_conv(c) for c in cc.WS_CONV.cases] + [
+def _ws_wgrad(case):
+    """A row of cc.WS_WGRAD as (id, run, kernel pattern): x and the incoming gradient are channel slices of wider buffers; the routes
+    the row declares are asserted with the real tensors before the passes run."""
+    cid, dtype_id, (n, ci, co, sp, k, s, p, dil, bias, pad_in, pad_out), dy_off, seed, pattern = case
+    dtype = DT[dtype_id]
+
+    def run():
+        x = _rand(seed, (n, ci + pad_in) + sp, dtype)[:, pad_in:].detach().requires_grad_(True)
+        g = torch.Generator().manual_seed(seed + 1)
+        w = (torch.randn(co, ci, *k, generator=g) / np.sqrt(k[0] * k[1] * k[2] * ci)).cuda().requires_grad_(True)
+        b = torch.randn(co, generator=g).cuda().requires_grad_(True)
+        geom = ops._conv_geom(tuple(x.shape), w.shape, s, p, dil)
+        dy = _rand(seed + 2, (n, co + pad_out, geom.dout, geom.ho, geom.wo), dtype)[:, dy_off:dy_off + co]
+        cc.WS_WGRAD.check(case, dtype_id, x=x, dy=dy)
+        y = ops.conv3d(x, w, b, s, p, dil)
+        y.backward(dy)
+        return [y.detach(), x.grad, w.grad, b.grad]
+    return cid, run, pattern
+
+
+# (id, case, kernel that must be among the launched ones, or None); the convolutions: cc.WS_CONV, cc.WS_WGRAD
+WS_CASES = [_ws_conv(c) for c in cc.WS_CONV.cases] + [_ws_wgrad(c) for c in cc.WS_WGRAD.cases] + [
     ("conv_transpose3d", _convt_case(), None),
     ("upsample_conv3d", _upconv_case(), r"upconv"),
     ("conv3d_pair", _pair_case(), r"convpair|sepconv|pair"),
