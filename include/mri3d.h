@@ -431,6 +431,40 @@ int mri3d_convert_channels(const void* src, int32_t src_dtype, void* dst, int32_
                            int32_t src_ld, int32_t dst_ld, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * BayesConv3d (variational dropout) — segmentation/models/3d_bayes_layers.py:195-232, used by 3d_bayes_unet.py::UNet3D(bayes=True).
+ * The layer is a mean convolution, a variance convolution over x^2 and one Gaussian sample per output element; the two
+ * convolutions and their gradients are mri3d_conv3d_* calls, the passes around them are below.  The noise `eps` is an INPUT
+ * (fp32, drawn by the caller): nothing here is random, every entry is deterministic.
+ *   weights (fp32 parameters, n elements, any layout):
+ *     raw = logsigma - log(mu^2 + 1e-8)    log_alpha = clamp(raw, -5, 5)    v = mu^2 exp(log_alpha)
+ *     eval == 0:  w_var = v                 (w_mean = mu: w_mean is not written and may be NULL)
+ *     eval != 0:  m = [log_alpha < threshold]    w_mean = mu m    w_var = v m
+ *     bwd: dmu, dlogsigma from the gradients of w_mean, w_var, log_alpha (each may be NULL = no gradient), with the clamp passing
+ *     the gradient on the closed interval and the mask m carrying none; pass d_w_mean also in train mode (w_mean = mu there).
+ *     mu = 0 gives finite values and gradients.
+ *   volume passes (NDHWC, one voxel pitch per tensor, dtype = storage of every tensor except eps, which is always fp32):
+ *     square:      x2 = x^2
+ *     sample_fwd:  y = mu_out + eps sqrt(1e-4 + var_out)              y == mu_out (same pitch) is allowed
+ *     sample_bwd:  dvar = dy eps / (2 sqrt(1e-4 + var_out))
+ *     dx:          dx = dx_mean + 2 x dx_var                          dx == dx_mean (same pitch) is allowed
+ *     16 bytes per lane when c and every pitch are multiples of 4 (fp32) / 8 (bf16) and every pointer is 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int mri3d_bayes_weights_fwd(const float* mu, const float* logsigma, int64_t n, int32_t eval, float threshold, float* w_mean,
+                            float* w_var, float* log_alpha, mri3d_stream_t stream);
+int mri3d_bayes_weights_bwd(const float* mu, const float* logsigma, int64_t n, int32_t eval, float threshold,
+                            const float* d_w_mean, const float* d_w_var, const float* d_log_alpha, float* dmu,
+                            float* dlogsigma, mri3d_stream_t stream);
+int mri3d_bayes_square(const void* x, void* x2, int64_t nvox, int32_t c, int32_t x_ld, int32_t x2_ld, int32_t dtype,
+                       mri3d_stream_t stream);
+int mri3d_bayes_sample_fwd(const void* mu_out, const void* var_out, const float* eps, void* y, int64_t nvox, int32_t c,
+                           int32_t mu_ld, int32_t var_ld, int32_t eps_ld, int32_t y_ld, int32_t dtype, mri3d_stream_t stream);
+int mri3d_bayes_sample_bwd(const void* dy, const void* var_out, const float* eps, void* dvar, int64_t nvox, int32_t c,
+                           int32_t dy_ld, int32_t var_ld, int32_t eps_ld, int32_t dvar_ld, int32_t dtype,
+                           mri3d_stream_t stream);
+int mri3d_bayes_dx(const void* dx_mean, const void* dx_var, const void* x, void* dx, int64_t nvox, int32_t c,
+                   int32_t dx_mean_ld, int32_t dx_var_ld, int32_t x_ld, int32_t dx_ld, int32_t dtype, mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * AdamW / Adam on one flat fp32 buffer — torch.optim.AdamW (segmentation/routine.py:358) and
  * torch.optim.Adam with L2 weight_decay (classification/routine.py:271,275).
  * grad_scale multiplies the gradient first (1/world_size after the RCCL sum all-reduce).

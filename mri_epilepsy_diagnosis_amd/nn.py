@@ -7,6 +7,8 @@ conv -> BatchNorm3d -> PReLU blocks of ``unet.UNet`` and the (MaxPool ->) BatchN
 ``AE_model.DownBlock`` (classification/models/AE_model.py:27-36) — and ``FusedSequential`` does that pairing
 automatically for ``nn.Sequential``-style reference models (classification/models/cnn_model.py:104-175).
 """
+import math
+
 import torch
 import torch.nn as tnn
 
@@ -26,6 +28,68 @@ class ConvTranspose3d(tnn.ConvTranspose3d):
             raise NotImplementedError("mri3d ConvTranspose3d supports groups=1, zero padding, no output_size")
         return ops.conv_transpose3d(x, self.weight, self.bias, self.stride, self.padding, self.output_padding,
                                     self.dilation)
+
+
+class BayesConv3d(tnn.Module):
+    """Variational-dropout convolution (segmentation/models/3d_bayes_layers.py:85-116,195-232): same constructor, parameters
+    (`mu_weight`, `logsigma_weight`, `mu_bias`, `logsigma_bias`), initialisation and state_dict keys; `forward` is
+    `ops.bayes_conv3d` and leaves `self.log_alpha` behind for a KL regulariser, as the reference does.
+
+    `noise`: None (the operator draws the standard normals from torch's device generator) or a callable
+    `(shape, device) -> eps`, eps a float32 tensor of the output's (N, Co, D, H, W) shape — how a test, or a caller that wants
+    the same sample twice, supplies the noise.  A plain attribute, not part of the state_dict."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
+                 zero_mean=False, threshold=3):
+        super().__init__()
+        if in_channels % groups != 0 or out_channels % groups != 0:
+            raise ValueError("in_channels and out_channels must be divisible by groups")
+        self.in_channels, self.out_channels, self.groups = in_channels, out_channels, groups
+        self.kernel_size, self.stride, self.dilation = ops._triple(kernel_size), ops._triple(stride), ops._triple(dilation)
+        self.padding = padding if isinstance(padding, str) else ops._triple(padding)
+        self.zero_mean, self.threshold = zero_mean, threshold
+        self.noise = None
+        self.log_alpha = None
+        shape = (out_channels, in_channels // groups) + self.kernel_size
+        self.mu_weight = tnn.Parameter(torch.empty(shape))
+        self.logsigma_weight = tnn.Parameter(torch.empty(shape))
+        if bias:
+            self.mu_bias = tnn.Parameter(torch.empty(out_channels))
+            self.logsigma_bias = tnn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("mu_bias", None)
+            self.register_parameter("logsigma_bias", None)
+        self.reset_parameters()
+        if zero_mean:
+            self.mu_weight = tnn.Parameter(torch.zeros_like(self.mu_weight))
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            self.mu_weight.normal_(0, 0.02)
+            self.logsigma_weight.fill_(-5)
+            if self.mu_bias is not None:
+                fan_in = self.mu_weight[0].numel()
+                bound = 1 / math.sqrt(fan_in)
+                self.mu_bias.uniform_(-bound, bound)
+                self.logsigma_bias.uniform_(-bound, bound)
+
+    def output_shape(self, x):
+        """(N, Co, D, H, W) of forward(x): what `noise` is asked for."""
+        return (x.shape[0], self.out_channels) + tuple(
+            (i + 2 * p - d * (k - 1) - 1) // s + 1
+            for i, p, d, k, s in zip(x.shape[2:], self.padding, self.dilation, self.kernel_size, self.stride))
+
+    def extra_repr(self):
+        return "%d, %d, kernel_size=%s, stride=%s, padding=%s%s" % (self.in_channels, self.out_channels, self.kernel_size, self.stride,
+                                                                    self.padding, "" if self.mu_bias is not None else ", bias=False")
+
+    def forward(self, x):
+        if self.groups != 1 or isinstance(self.padding, str):
+            raise NotImplementedError("mri3d BayesConv3d supports groups=1, numeric padding")
+        eps = self.noise(self.output_shape(x), x.device) if self.noise is not None else None
+        y, self.log_alpha = ops.bayes_conv3d(x, self.mu_weight, self.logsigma_weight, self.mu_bias, self.logsigma_bias, self.stride,
+                                             self.padding, self.dilation, self.training, self.threshold, eps)
+        return y
 
 
 def _act_spec(act):

@@ -12,6 +12,7 @@ Reference operators replaced (file:line in /root/reference):
   upsample3d           nn.Upsample / F.interpolate   modified_3dunet.py:13; AE_model.py:70-73,119
   softmax_dice_loss    F.softmax + get_dice_loss + mean   segmentation/routine.py:239-253,272-274
   cat_channels / add   torch.cat(dim=1) / residual adds   modified_3dunet.py:108,158
+  bayes_conv3d         BayesConv3d          3d_bayes_layers.py:195-232 (3d_bayes_unet.py::UNet3D(bayes=True))
 """
 import ctypes
 import math
@@ -507,6 +508,19 @@ def _stuffed_wgrad_ok(g):
             and (g.dd, g.dh, g.dw) == (1, 1, 1) and g.ci % 8 == 0 and g.co % 4 == 0 and g.x_ld % 4 == 0)
 
 
+def _stuffed_wgrad(g, gw, x, dy, w):
+    """(geometry, incoming gradient) the weight gradient of forward geometry `g` runs on: (gw, dy) as given, except where
+    `_stuffed_wgrad_ok`."""
+    if not (_stuffed_wgrad_ok(g) and dy.dtype == x.dtype):
+        return gw, dy
+    # 3x3x3 / stride 2 / pad 1 (modified_3dunet.py:23-38): dW[tap] = sum_o X[2o - 1 + tap] dY[o] is the STRIDE-1 weight
+    # gradient of X against dY spread onto the even voxels of a zero volume — 8x the arithmetic, but on the MFMA
+    # weight-gradient kernel (~100 TFLOP/s) instead of the generic one (4.6 TFLOP/s on the 8 -> 16 layer at 80x96x80)
+    dyw = torch.empty((g.n, g.co, g.di, g.hi, g.wi), dtype=dy.dtype, device=dy.device, memory_format=CL3D).zero_()
+    dyw[:, :, ::2, ::2, ::2].copy_(dy)
+    return _conv_geom(x.shape, w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=g.dtype), dyw
+
+
 class _Conv3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, dilation, stats_holder=None):
@@ -554,15 +568,8 @@ class _Conv3dFn(torch.autograd.Function):
             want_b = ctx.has_bias and ctx.needs_input_grad[2]
             dw_out = _sink_take(wp) if ctx.needs_input_grad[1] else None
             db_out = _sink_take(bp) if want_b else None
-            xw, dyw = x, dy
-            if (_stuffed_wgrad_ok(g) and dy.dtype == x.dtype):
-                # 3x3x3 / stride 2 / pad 1 (modified_3dunet.py:23-38): dW[tap] = sum_o X[2o - 1 + tap] dY[o] is the STRIDE-1 weight
-                # gradient of X against dY spread onto the even voxels of a zero volume — 8x the arithmetic, but on the MFMA
-                # weight-gradient kernel (~100 TFLOP/s) instead of the generic one (4.6 TFLOP/s on the 8 -> 16 layer at 80x96x80)
-                dyw = torch.empty((g.n, g.co, g.di, g.hi, g.wi), dtype=dy.dtype, device=dy.device, memory_format=CL3D).zero_()
-                dyw[:, :, ::2, ::2, ::2].copy_(dy)
-                gw = _conv_geom(x.shape, w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=g.dtype)
-            dw, db = _conv_wgrad(gw, xw, dyw, w, ctx.has_bias, dw_out, db_out)
+            gw, dyw = _stuffed_wgrad(g, gw, x, dy, w)
+            dw, db = _conv_wgrad(gw, x, dyw, w, ctx.has_bias, dw_out, db_out)
             dw = _sink_done(wp, dw, dw_out) if ctx.needs_input_grad[1] else None
             db = _sink_done(bp, db, db_out) if want_b else None
         return dx, dw, db, None, None, None, None
@@ -672,6 +679,145 @@ def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, bn_stats=False
     if holder:
         y._mri3d_bn_stats = holder[0]
     return y
+
+
+# ----------------------------------------------------------------------------------------------- BayesConv3d
+# 3d_bayes_layers.py:195-232.  Two autograd nodes: the weight transform (parameters only, one small kernel each way) and the layer
+# itself — two convolutions on the convolution kernels plus the streaming passes of csrc/bayes.hip.
+
+
+class _BayesWeightsFn(torch.autograd.Function):
+    """(mu, logsigma) -> (w_var, log_alpha) in train mode, (w_mean, w_var, log_alpha) in eval mode (mri3d_bayes_weights_*)."""
+
+    @staticmethod
+    def forward(ctx, mu, logsigma, evaluate, threshold):
+        _require_param(mu, logsigma)
+        if mu.shape != logsigma.shape:
+            raise RuntimeError("bayes_conv3d: mu_weight %s and logsigma_weight %s differ in shape" % (tuple(mu.shape), tuple(logsigma.shape)))
+        mu, logsigma = mu.contiguous(), logsigma.contiguous()
+        w_var, log_alpha = torch.empty_like(mu), torch.empty_like(mu)
+        w_mean = torch.empty_like(mu) if evaluate else None
+        check(_lib.lib().mri3d_bayes_weights_fwd(_ptr(mu), _ptr(logsigma), mu.numel(), int(evaluate), float(threshold), _ptr(w_mean),
+                                                 _ptr(w_var), _ptr(log_alpha), _stream()), "bayes_weights_fwd")
+        ctx.save_for_backward(mu, logsigma)
+        ctx.evaluate, ctx.threshold = bool(evaluate), float(threshold)
+        ctx.set_materialize_grads(False)      # an unused output (log_alpha without a regulariser) arrives as None -> NULL
+        return (w_mean, w_var, log_alpha) if evaluate else (w_var, log_alpha)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        mu, logsigma = ctx.saved_tensors
+        d_w_mean, d_w_var, d_log_alpha = grads if ctx.evaluate else (None,) + grads
+        d_w_mean, d_w_var, d_log_alpha = (None if g is None else g.contiguous() for g in (d_w_mean, d_w_var, d_log_alpha))
+        dmu, dls = torch.empty_like(mu), torch.empty_like(mu)
+        check(_lib.lib().mri3d_bayes_weights_bwd(_ptr(mu), _ptr(logsigma), mu.numel(), int(ctx.evaluate), ctx.threshold, _ptr(d_w_mean),
+                                                 _ptr(d_w_var), _ptr(d_log_alpha), _ptr(dmu), _ptr(dls), _stream()),
+              "bayes_weights_bwd")
+        return dmu, dls, None, None
+
+
+def _stream_work(n_tensors, like, eps_numel=0):
+    return {"flops": 0.0, "bytes": _esz(like) * n_tensors * like.numel() + 4.0 * eps_numel}
+
+
+def _bayes_square(x, x_ld):
+    n, c, d, h, w = x.shape
+    x2 = _new(x.shape, x)
+    with _timed(lambda: "bayes_square %d @%dx%dx%d n%d" % (c, d, h, w, n), lambda: _stream_work(2, x)):
+        check(_lib.lib().mri3d_bayes_square(_ptr(x), _ptr(x2), n * d * h * w, c, x_ld, c, _dt(x), _stream()), "bayes_square")
+    return x2
+
+
+class _BayesConv3dFn(torch.autograd.Function):
+    """y = conv3d(x, w_mean, mu_bias) + eps * sqrt(1e-4 + conv3d(x^2, w_var, logsigma_bias^2)).  eps: float32, logical
+    (N, Co, D, H, W), no gradient.  Backward (dvar = dy eps / (2 sqrt(1e-4 + var_out))):
+        dx = dgrad(dy, w_mean) + 2 x dgrad(dvar, w_var)      dw_mean = wgrad(x, dy)      dw_var = wgrad(x^2, dvar)
+        dmu_bias = sum dy      dlogsigma_bias = 2 logsigma_bias sum dvar
+    x^2 is recomputed in the backward (one streaming pass) rather than kept alive between the passes."""
+
+    @staticmethod
+    def forward(ctx, x, w_mean, w_var, mu_bias, logsigma_bias, eps, stride, padding, dilation):
+        _require_device(x)
+        _require_param(w_mean, w_var, mu_bias, logsigma_bias, eps)
+        L = _lib.lib()
+        x, x_ld = _nd(x)
+        w_mean, w_var = w_mean.contiguous(), w_var.contiguous()
+        g = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, x_ld=x_ld, dtype=_dt(x))
+        y = _conv_fwd(g, x, w_mean, mu_bias)
+        g2 = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=_dt(x))
+        var_bias = logsigma_bias * logsigma_bias if logsigma_bias is not None else None
+        var_out = _conv_fwd(g2, _bayes_square(x, x_ld), w_var, var_bias)
+        if tuple(eps.shape) != tuple(y.shape):
+            raise RuntimeError("bayes_conv3d: eps has shape %s, the output %s" % (tuple(eps.shape), tuple(y.shape)))
+        eps, eps_ld = _nd(eps)
+        nvox = g.n * g.dout * g.ho * g.wo
+        with _timed(lambda: "bayes_sample_fwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n), lambda: _stream_work(3, y, eps.numel())):
+            check(L.mri3d_bayes_sample_fwd(_ptr(y), _ptr(var_out), _ptr(eps), _ptr(y), nvox, g.co, g.co, g.co, eps_ld, g.co, g.dtype,
+                                           _stream()), "bayes_sample_fwd")
+        ctx.save_for_backward(x, w_mean, w_var, var_out, eps, logsigma_bias)
+        ctx.geom, ctx.eps_ld, ctx.has_bias = g, eps_ld, mu_bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _lib.lib()
+        x, w_mean, w_var, var_out, eps, logsigma_bias = ctx.saved_tensors
+        g = ctx.geom
+        stride, padding, dilation = (g.sd, g.sh, g.sw), (g.pd, g.ph, g.pw), (g.dd, g.dh, g.dw)
+        dy, y_ld = _nd(dy)
+        nvox = g.n * g.dout * g.ho * g.wo
+        dvar = _new(dy.shape, dy)
+        with _timed(lambda: "bayes_sample_bwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n), lambda: _stream_work(3, dy, eps.numel())):
+            check(L.mri3d_bayes_sample_bwd(_ptr(dy), _ptr(var_out), _ptr(eps), _ptr(dvar), nvox, g.co, y_ld, g.co, ctx.eps_ld, g.co,
+                                           g.dtype, _stream()), "bayes_sample_bwd")
+        dx = dw_mean = dw_var = dmb = dlb = None
+        if ctx.needs_input_grad[0]:
+            gd = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, y_ld=y_ld, dtype=g.dtype)
+            dx = _conv_dgrad(gd, dy, w_mean, None, x)
+            gdv = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=g.dtype)
+            dx_var = _conv_dgrad(gdv, dvar, w_var, None, x)
+            with _timed(lambda: "bayes_dx %d @%dx%dx%d n%d" % (g.ci, g.di, g.hi, g.wi, g.n), lambda: _stream_work(4, x)):
+                check(L.mri3d_bayes_dx(_ptr(dx), _ptr(dx_var), _ptr(x), _ptr(dx), g.n * g.di * g.hi * g.wi, g.ci, g.ci, g.ci, g.x_ld,
+                                       g.ci, g.dtype, _stream()), "bayes_dx")
+        want_b = ctx.has_bias and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or want_b:
+            gw = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, x_ld=g.x_ld, y_ld=y_ld, dtype=g.dtype)
+            gw, dyw = _stuffed_wgrad(g, gw, x, dy, w_mean)
+            dw_mean, dmb = _conv_wgrad(gw, x, dyw, w_mean, ctx.has_bias)
+            g2 = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=g.dtype)
+            gw2, dvw = _stuffed_wgrad(g2, g2, x, dvar, w_var)
+            dw_var, dvb = _conv_wgrad(gw2, _bayes_square(x, g.x_ld), dvw, w_var, ctx.has_bias)
+            if ctx.has_bias:
+                dlb = 2.0 * logsigma_bias * dvb
+        return dx, dw_mean, dw_var, dmb, dlb, None, None, None, None
+
+
+def bayes_conv3d(x, mu_weight, logsigma_weight, mu_bias=None, logsigma_bias=None, stride=1, padding=0, dilation=1, training=True,
+                 threshold=3, eps=None, groups=1):
+    """BayesConv3d.forward (3d_bayes_layers.py:210-232) -> (y, log_alpha).  `eps`: the standard-normal noise as a float32 device tensor
+    of y's logical shape (N, Co, D, H, W); None draws it from torch's default device generator in y's NDHWC memory order, as
+    `dropout3d` draws its mask.  The noise is sampled in train AND eval mode; eval mode masks the weights with
+    log_alpha < threshold.  Under `autocast` x is converted like `conv3d` converts it, eps stays float32."""
+    if groups != 1:
+        raise NotImplementedError("bayes_conv3d: groups != 1 is not supported")
+    if isinstance(padding, str):
+        raise NotImplementedError("bayes_conv3d: string padding is not supported")
+    if (mu_bias is None) != (logsigma_bias is None):
+        raise RuntimeError("bayes_conv3d: mu_bias and logsigma_bias come together")
+    _require_device(x)
+    if _autocast_dtype is not None and x.dtype != _autocast_dtype:
+        x = convert(x, _autocast_dtype)
+    stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
+    g = _conv_geom(x.shape, mu_weight.shape, stride, padding, dilation)
+    if training:
+        w_mean = mu_weight
+        w_var, log_alpha = _BayesWeightsFn.apply(mu_weight, logsigma_weight, False, threshold)
+    else:
+        w_mean, w_var, log_alpha = _BayesWeightsFn.apply(mu_weight, logsigma_weight, True, threshold)
+    if eps is None:
+        eps = torch.empty((g.n, g.dout, g.ho, g.wo, g.co), dtype=torch.float32, device=x.device).normal_().permute(0, 4, 1, 2, 3)
+    y = _BayesConv3dFn.apply(x, w_mean, w_var, mu_bias, logsigma_bias, eps.detach(), stride, padding, dilation)
+    return y, log_alpha
 
 
 class _ConvPairFn(torch.autograd.Function):
