@@ -32,21 +32,27 @@ int conv_mfma_fwd(const Mri3dConvGeom& g, const void* x, const float* w, const f
                   size_t ws_bytes, hipStream_t s);
 int conv_mfma_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, const float* bias, void* dx, void* ws,
                     size_t ws_bytes, hipStream_t s);
-int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
-                    size_t ws_bytes, hipStream_t s);
 int conv_mfma_fwd_stat_blocks(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);
 bool conv_mfma_cat_supported(const Mri3dConvGeom& g, int split, int second_ld, int pass);
 int conv_mfma_fwd_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const float* w, const float* bias,
                       void* y, double* stat_part, void* ws, size_t ws_bytes, hipStream_t s);
 int conv_mfma_dgrad_cat(const Mri3dConvGeom& g, const void* dy, const float* w, void* dx, void* dx2, int split, int dx2_ld, void* ws,
                         size_t ws_bytes, hipStream_t s);
-int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
-                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
 int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, const float* bias, void* y, double* stat_part,
                         void* ws, size_t ws_bytes, hipStream_t s);
 // name of the kernel instantiation the pass launches (mri3d_conv3d_route; the vocabulary is in include/mri3d.h), written from the
-// same fwd_route / mfma_wgrad_plan answer the launch reads.  false: this file does not serve the pass.
+// same fwd_route answer (weight gradient: the same plan, below) the launch reads.  false: the pass is not served.
 bool conv_mfma_route_name(const Mri3dConvGeom& g, int pass, bool stats, bool bias, const ConvSplit& sp, char* name, size_t name_bytes);
+
+// conv_mfma_wgrad.hip: the weight gradient of the 3x3x3 MFMA path.  The three queries are what conv_mfma.hip's queries over all
+// passes answer with for MRI3D_PASS_WGRAD; all read the one plan the launch reads.
+bool conv_mfma_wgrad_supported(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);   // split > 0: ... with that split operand
+size_t conv_mfma_wgrad_workspace_bytes(const Mri3dConvGeom& g);                             // 0: not served
+bool conv_mfma_wgrad_route_name(const Mri3dConvGeom& g, char* name, size_t name_bytes);     // false: not served
+int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
+                    size_t ws_bytes, hipStream_t s);
+int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,
+                        float* dbias, void* ws, size_t ws_bytes, hipStream_t s);
 
 // conv_march.hip: forward / data gradient marching along d.  `force` = the explicit entry points (every geometry the kernel can
 // compute); otherwise the dispatcher's own choice of the layers where it is the faster kernel.

@@ -1,7 +1,7 @@
 // conv_generic.hip — direct NDHWC Conv3d forward / data-gradient / weight-gradient for ANY kernel size,
 // stride, padding and dilation (separable (k,1,1) convs of AE_model.py:9-26, strided convs of
 // modified_3dunet.py:23-38, dilated convs of cnn_model.py:212-240, 1x1x1 classifier of unet.UNet).
-// The 3x3x3 stride-1 hot layers take the MFMA implicit-GEMM path in conv_mfma.hip instead.
+// The 3x3x3 stride-1 hot layers take the MFMA implicit-GEMM path in conv_mfma.hip / conv_mfma_wgrad.hip instead.
 //
 // Roofline: these layers have arithmetic intensity of a few FLOP/byte (separable convs AI~6) and are
 // HBM-bound; the design goal is one coalesced pass over x and y with weights on the scalar path.

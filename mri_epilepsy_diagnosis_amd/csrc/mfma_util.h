@@ -1,4 +1,4 @@
-// mfma_util.h — device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv_march.hip); gfx950 only.
+// mfma_util.h — device helpers shared by the MFMA convolution kernels (conv_mfma.hip, conv_mfma_wgrad.hip, conv_march.hip); gfx950 only.
 #pragma once
 #include "common.h"
 

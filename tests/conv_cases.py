@@ -264,7 +264,7 @@ LARGE_BATCH = Table("LARGE_BATCH", "slice", [(64, 16, 16, 9, 13, 21, 0, 0, 41), 
                                              (128, 32, 64, 8, 8, 8, 0, 0, 46), (70, 16, 24, 5, 7, 6, 8, 0, 47), (300, 64, 64, 8, 8, 8, 0, 0, 48)],
                     {"f32": {"wgrad": "wgrad6"}, "bf16": {"fwd": "tiled"}})
 
-# bf16 weight gradient marching along d (conv_mfma_wgrad_bf16t_kernel, LDS-DMA rows + transposing reads: taken when columns x
+# bf16 weight gradient marching along d (conv_mfma_wgrad_bf16t_kernel in conv_mfma_wgrad.hip, LDS-DMA rows + transposing reads: taken when columns x
 # segments >= 3 tasks per workgroup): a last segment of 5 / 3 / 1 planes, a last row tile of one row, a last column tile of 5 voxels,
 # an 8-channel input tile (upper half empty) read from a pitched buffer, 24 output channels (half-empty second block) written from
 # a pitched gradient
@@ -317,6 +317,14 @@ MARCH_BF16 = Table("MARCH_BF16", "slice", [(48, 16, 16, 41, 5, 9, 0, 0, 131), (4
                    {"bf16": {"dgrad": "march"}}, dtypes=("bf16",))
 MARCH_BF16_NOBIAS = Table("MARCH_BF16_NOBIAS", "slice", [(48, 8, 16, 41, 5, 9, 0, 0, 141)], {"bf16": {"fwd": "march", "dgrad": "march"}},
                           dtypes=("bf16",), bias=False)
+
+# The weight-gradient kernels reserve the dbias accumulator only in their BIAS instantiations, and the partial layout they share
+# (TGA = tap groups + 1) changes with it: the bias-less twins of rows above that no other table reaches — the same small ragged
+# geometries as in BF16_WGRAD_QUADS (8 -> 12, 16 -> 12), N8 (8 -> 8 pitched, 32 -> 8) and MARCH_WGRAD (8 -> 128 marching along d)
+WGRAD_NOBIAS = Table("WGRAD_NOBIAS", "slice", [(2, 8, 12, 5, 13, 37, 0, 0, 151), (2, 16, 12, 5, 13, 37, 0, 0, 152), (1, 8, 8, 7, 13, 33, 8, 8, 153),
+                                               (1, 32, 8, 11, 19, 37, 0, 0, 154), (24, 8, 128, 23, 9, 33, 8, 0, 155)],
+                     {"f32": {"wgrad": ("wgrad3", "wgrad6", "wgrad6 ci8 co8", "wgrad6 co8", "wgrad3")},
+                      "bf16": {"wgrad": ("wgrad3", "wgrad4", "bf16", "bf16", "bf16t")}}, bias=False)
 
 # the forward with fused BatchNorm statistics against the CPU reference (y and the statistics): the tiled kernel with 1 and 2
 # N-tiles per wave, the marching kernel with and without a bias (bf16; fp32 takes it from 4 Mi voxels up only)
@@ -837,6 +845,20 @@ PER_CASE.update({
         'n48_16-16_41x9x17_p0_0': "march bias | march | bf16",
         'n48_32-16_41x5x9_p8_8': "march bias | march | bf16",
         'n48_16-48_41x5x9_p0_0': "tiled nt1 | march | bf16",
+    },
+    ("WGRAD_NOBIAS", "f32"): {
+        'n2_8-12_5x13x37_p0_0': "direct nt1 mode0 split1 | generic gather tl8 vec1 | wgrad3",
+        'n2_16-12_5x13x37_p0_0': "direct nt1 mode0 split1 | generic gather tl16 vec1 | wgrad6",
+        'n1_8-8_7x13x33_p8_8': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6 ci8 co8",
+        'n1_32-8_11x19x37_p0_0': "direct nt1 mode0 split1 | direct nt1 mode0 split1 | wgrad6 co8",
+        'n24_8-128_23x9x33_p8_0': "tiled nt2 | tiled_n8 | wgrad3",
+    },
+    ("WGRAD_NOBIAS", "bf16"): {
+        'n2_8-12_5x13x37_p0_0': "tiled nt1 | generic gather tl8 vec1 | wgrad3",
+        'n2_16-12_5x13x37_p0_0': "tiled nt1 | generic gather tl16 vec1 | wgrad4",
+        'n1_8-8_7x13x33_p8_8': "tiled_n8 | tiled_n8 | bf16",
+        'n1_32-8_11x19x37_p0_0': "tiled_n8 | tiled nt2 | bf16",
+        'n24_8-128_23x9x33_p8_0': "tiled nt2 | tiled_n8 | bf16t",
     },
     ("MARCH_BF16_NOBIAS", "bf16"): {
         'n48_8-16_41x5x9_p0_0': "march | march | bf16",

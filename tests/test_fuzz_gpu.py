@@ -110,6 +110,12 @@ def test_bf16_marching_kernel_by_choice_without_a_bias(case):
     _run_conv_case(case, torch.bfloat16, cc.MARCH_BF16_NOBIAS)
 
 
+@pytest.mark.parametrize(**_BOTH)
+@pytest.mark.parametrize(**_params(cc.WGRAD_NOBIAS))
+def test_weight_gradient_kernels_without_a_bias(case, dtype):
+    _run_conv_case(case, dtype, cc.WGRAD_NOBIAS)
+
+
 def _dtype_id(dtype):
     return "f32" if dtype == torch.float32 else "bf16"
 

@@ -50,7 +50,7 @@ def test_march_kernels_keep_hipcc_off_the_named_accumulators(tmp_path):
 
 
 def test_bf16_weight_gradient_stages_by_dma_and_reads_transposed(tmp_path):
-    """conv_mfma_wgrad_bf16t_kernel (csrc/conv_mfma.hip): what makes it fast is visible in the generated code and easy to lose —
+    """conv_mfma_wgrad_bf16t_kernel (csrc/conv_mfma_wgrad.hip): what makes it fast is visible in the generated code and easy to lose —
     the data's way in is LDS-DMA only (`buffer_load_dwordx4 ... lds`: no vector register staging, so no v_perm transposes and no
     ds_write of tensor data in the step loop), the K = voxel operands come from `ds_read_b64_tr_b16`, nothing is spilled (a scratch
     access is a vector-memory operation and would break the counted `s_waitcnt vmcnt`), and two workgroups fit a CU (<= 256
@@ -58,8 +58,8 @@ def test_bf16_weight_gradient_stages_by_dma_and_reads_transposed(tmp_path):
     from mri_epilepsy_diagnosis_amd import build
     if not os.path.exists(build.HIPCC):
         pytest.skip("no hipcc in this environment")
-    src = os.path.join(build.CSRC, "conv_mfma.hip")
-    out = tmp_path / "conv_mfma.s"
+    src = os.path.join(build.CSRC, "conv_mfma_wgrad.hip")
+    out = tmp_path / "conv_mfma_wgrad.s"
     cmd = [build.HIPCC] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-S", "--cuda-device-only", src, "-o", str(out)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-2000:]

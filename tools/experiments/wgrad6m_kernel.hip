@@ -1,5 +1,5 @@
 // NOT part of the library: the fp32 counterpart of conv_mfma_wgrad_bf16m_kernel (weight gradient marching along d), as it was
-// built, tested (fuzz + operator suites green) and measured in round 2 inside csrc/conv_mfma.hip (it uses that file's
+// built, tested (fuzz + operator suites green) and measured in round 2 inside csrc/conv_mfma.hip (now csrc/conv_mfma_wgrad.hip; it uses that file's
 // constants MTH, MXP, MXS, MYP, MYS, MHP, FTW, DLS, rot_slot, ldg4, g_zero16, TileWalk).  Result against the tile kernel (v6), same box:
 //   16 -> 16 @160x192x160 x2   1.204 -> 1.249 ms        48 -> 16 (cat)   3.354 -> 3.399 ms       96 -> 32 (cat) @80x96x80  1.834 -> 1.806 ms
 //   32 -> 32 @80x96x80 x2      0.619 -> 0.673 ms        16 -> 16 @32^3 x512   2.206 -> 2.030 ms

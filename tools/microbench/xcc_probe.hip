@@ -1,4 +1,4 @@
-// Which XCD does workgroup (x, y, z) of a 3-D grid land on?  (tile_walk in conv_mfma.hip assumes linear id % 8.)
+// Which XCD does workgroup (x, y, z) of a 3-D grid land on?  (tile_walk in conv_mfma_wgrad.hip assumes linear id % 8.)
 //   hipcc --offload-arch=gfx950 -O2 tools/microbench/xcc_probe.hip -o tools/microbench/xcc_probe && tools/microbench/xcc_probe 170 3 1
 #include <hip/hip_runtime.h>
 #include <cstdio>
