@@ -26,27 +26,33 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
 }
 
 // ------------------------------------------------------------------ weight repack
-// torch (Co, Ci, kd, kh, kw)  ->  fwd  Wf[tap][ci][coP]   (coP = Co rounded up to the cout tile)
-//                             ->  dgrad Wd[tap][co][ciP]
-__global__ void repack_w_fwd_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Ci, int taps,
-                                    int CoP) {
-    int total = taps * Ci * CoP;
+// torch (Co, Ci, kd, kh, kw)  ->  forward (dgrad = 0)        Wf[tap][ci][coP]   (P = coP: Co rounded up to the cout tile)
+//                             ->  data gradient (dgrad = 1)  Wd[tap][co][ciP]   (P = ciP)
+__global__ void repack_w_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Ci, int taps, int P, int dgrad) {
+    const int M = dgrad ? Co : Ci, N = dgrad ? Ci : Co;   // channels summed over, channels tiled (N padded to P)
+    int total = taps * M * P;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        int co = i % CoP;
-        int ci = (i / CoP) % Ci;
-        int tap = i / (CoP * Ci);
-        wp[i] = (co < Co) ? w[((size_t)co * Ci + ci) * taps + tap] : 0.f;
+        int p = i % P;
+        int m = (i / P) % M;
+        int tap = i / (P * M);
+        const int co = dgrad ? m : p, ci = dgrad ? p : m;
+        wp[i] = (p < N) ? w[((size_t)co * Ci + ci) * taps + tap] : 0.f;
     }
 }
-__global__ void repack_w_dgrad_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Ci, int taps,
-                                      int CiP) {
-    int total = taps * Co * CiP;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        int ci = i % CiP;
-        int co = (i / CiP) % Co;
-        int tap = i / (CiP * Co);
-        wp[i] = (ci < Ci) ? w[((size_t)co * Ci + ci) * taps + tap] : 0.f;
-    }
+
+// ------------------------------------------------------------------ index arithmetic the kernels share
+// Shared is what leaves every kernel's gfx950 code instruction-identical to the same text written out in place: the two index
+// decodes (here and decode_tile below).  A helper that takes a thread's arrays by reference (acc[], the tap tables) changes the
+// code of the kernels that use it, so those pieces stay written out in each kernel, marked "written out".
+
+// flat voxel index -> (n, d, h, w) of n volumes of D x H x W
+__device__ __forceinline__ void decode_voxel(int64_t v, int D, int H, int W, int& n, int& d, int& h, int& w) {
+    w = (int)(v % W);
+    int64_t t = v / W;
+    h = (int)(t % H);
+    t /= H;
+    d = (int)(t % D);
+    n = (int)(t / D);
 }
 
 // ------------------------------------------------------------------ forward
@@ -58,12 +64,9 @@ conv_fwd_generic_kernel(Mri3dConvGeom g, const T* __restrict__ x, const float* _
     const int cot = blockIdx.y * COT;
     const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * blockDim.x) {
-        int ow = (int)(v % g.wo);
-        int64_t t = v / g.wo;
-        int oh = (int)(t % g.ho);
-        t /= g.ho;
-        int od = (int)(t % g.dout);
-        int n = (int)(t / g.dout);
+        int n, od, oh, ow;
+        decode_voxel(v, g.dout, g.ho, g.wo, n, od, oh, ow);
+        // (bias initialisation, tap FMAs and tile store are written out in each of the six kernels of this kind: shared, the code changed)
         float acc[COT];
 #pragma unroll
         for (int j = 0; j < COT; ++j) acc[j] = (bias != nullptr && cot + j < g.co) ? bias[cot + j] : 0.f;
@@ -122,7 +125,8 @@ conv_fwd_taps_kernel(Mri3dConvGeom g, const T* __restrict__ x, const float* __re
                      T* __restrict__ y, int CoP, int hch) {
     const int taps = g.kd * g.kh * g.kw;
     const int cot = blockIdx.y * COT;
-    int tdd[NTAPS], tdh[NTAPS], tdw[NTAPS];   // tap offsets in voxels per axis, and as one element offset (all wave-uniform)
+    int tdd[NTAPS], tdh[NTAPS], tdw[NTAPS];   // tap offsets in voxels per axis, and as one element offset (all wave-uniform; the table of
+                                              // conv_wgrad_quads_kernel, written out in both: shared, the code changed)
     int64_t tdelta[NTAPS];
 #pragma unroll
     for (int t = 0; t < NTAPS; ++t) {
@@ -154,6 +158,7 @@ conv_fwd_taps_kernel(Mri3dConvGeom g, const T* __restrict__ x, const float* __re
                 okm |= ok ? (1u << t) : 0u;
                 off[t] = ok ? base + tdelta[t] : 0;
             }
+            // (bias initialisation, batched tap FMAs and tile store are written out: shared with the other few-taps kernel, the code changed)
             float acc[COT];
 #pragma unroll
             for (int j = 0; j < COT; ++j) acc[j] = (bias != nullptr && cot + j < g.co) ? bias[cot + j] : 0.f;
@@ -204,12 +209,9 @@ conv_dgrad_generic_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float
     const int cit = blockIdx.y * CIT;
     const int64_t nvox = (int64_t)g.n * g.di * g.hi * g.wi;
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (int64_t)gridDim.x * blockDim.x) {
-        int iw = (int)(v % g.wi);
-        int64_t t = v / g.wi;
-        int ih = (int)(t % g.hi);
-        t /= g.hi;
-        int id = (int)(t % g.di);
-        int n = (int)(t / g.di);
+        int n, id, ih, iw;
+        decode_voxel(v, g.di, g.hi, g.wi, n, id, ih, iw);
+        // (bias initialisation, tap FMAs and tile store are written out in each of the six kernels of this kind: shared, the code changed)
         float acc[CIT];
 #pragma unroll
         for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
@@ -299,6 +301,7 @@ conv_dgrad_taps_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* _
                 const int cd = min(max(od, 0), g.dout - 1), chh = min(max(oh, 0), g.ho - 1), cw = min(max(ow, 0), g.wo - 1);
                 off[t] = (((int64_t)cd * g.ho + chh) * g.wo + cw) * g.y_ld;
             }
+            // (bias initialisation, batched tap FMAs and tile store are written out: shared with the other few-taps kernel, the code changed)
             float acc[CIT];
 #pragma unroll
             for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
@@ -336,6 +339,171 @@ conv_dgrad_taps_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* _
                 for (int j = 0; j < CIT; ++j)
                     if (cit + j < g.ci) stf(xp + j, acc[j]);
             }
+        }
+    }
+}
+
+// ------------------------------------------------------------------ data gradient, strided convs
+// Data gradient of a STRIDED convolution (dilation 1): only the taps with k = (i + pad) mod stride reach an input voxel i, i.e.
+// 1 .. 8 of the 27 taps of a 3x3x3 / stride-2 layer (modified_3dunet.py:23-38, cnn_model.py:49-81).  The gather kernel above
+// walks all taps and masks (8x wasted FMAs: 6 TFLOP/s on the 8 -> 16 stride-2 layer at 80x96x80).  Here one WAVE owns one
+// (n, id, ih, w-parity) row segment: the valid tap set is wave-uniform, so the tap loops just step by the stride, the weights
+// stay on the scalar path and nothing is masked except the volume border.
+template <typename T, int CIT, bool VEC4>
+__global__ void __launch_bounds__(64)
+conv_dgrad_strided_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* __restrict__ wp,
+                          const float* __restrict__ bias, T* __restrict__ dx, int CiP) {
+    int u = blockIdx.x;
+    const int rw = u % g.sw;   // residue of iw modulo the W stride handled by this wave
+    u /= g.sw;
+    const int ih = u % g.hi;
+    u /= g.hi;
+    const int id = u % g.di;
+    const int n = u / g.di;
+    const int cit = blockIdx.y * CIT;
+    const int kd0 = (id + g.pd) % g.sd, kh0 = (ih + g.ph) % g.sh, kw0 = (rw + g.pw) % g.sw;
+    for (int iw = rw + (int)threadIdx.x * g.sw; iw < g.wi; iw += 64 * g.sw) {
+        // (bias initialisation, tap FMAs and tile store are written out in each of the six kernels of this kind: shared, the code changed)
+        float acc[CIT];
+#pragma unroll
+        for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
+        for (int kd = kd0; kd < g.kd; kd += g.sd) {
+            const int nd = id + g.pd - kd;
+            if (nd < 0) break;
+            const int od = nd / g.sd;
+            if (od >= g.dout) continue;
+            for (int kh = kh0; kh < g.kh; kh += g.sh) {
+                const int nh = ih + g.ph - kh;
+                if (nh < 0) break;
+                const int oh = nh / g.sh;
+                if (oh >= g.ho) continue;
+                for (int kw = kw0; kw < g.kw; kw += g.sw) {
+                    const int nw = iw + g.pw - kw;
+                    const int ow = nw / g.sw;
+                    const bool valid = nw >= 0 && ow < g.wo;
+                    const T* yp = dy + ((((int64_t)n * g.dout + od) * g.ho + oh) * g.wo + (valid ? ow : 0)) * g.y_ld;
+                    const float* wt = wp + (size_t)((kd * g.kh + kh) * g.kw + kw) * g.co * CiP + cit;
+                    if (VEC4) {
+                        for (int co = 0; co < g.co; co += 4) {
+                            const float4 gv = valid ? ldf4(yp + co) : make_float4(0.f, 0.f, 0.f, 0.f);
+                            const float* w0 = wt + (size_t)co * CiP;
+#pragma unroll
+                            for (int j = 0; j < CIT; ++j) {
+                                acc[j] = fmaf(gv.x, w0[j], acc[j]);
+                                acc[j] = fmaf(gv.y, w0[CiP + j], acc[j]);
+                                acc[j] = fmaf(gv.z, w0[2 * CiP + j], acc[j]);
+                                acc[j] = fmaf(gv.w, w0[3 * CiP + j], acc[j]);
+                            }
+                        }
+                    } else {
+                        for (int co = 0; co < g.co; ++co) {
+                            const float gv = valid ? ldf(yp + co) : 0.f;
+                            const float* w0 = wt + (size_t)co * CiP;
+#pragma unroll
+                            for (int j = 0; j < CIT; ++j) acc[j] = fmaf(gv, w0[j], acc[j]);
+                        }
+                    }
+                }
+            }
+        }
+        T* xp = dx + ((((int64_t)n * g.di + id) * g.hi + ih) * g.wi + iw) * g.x_ld + cit;
+#pragma unroll
+        for (int j = 0; j < CIT; ++j)
+            if (cit + j < g.ci) stf(xp + j, acc[j]);
+    }
+}
+
+// The same wave-per-(n, id, ih, w-residue) decomposition with the valid taps ENUMERATED first (they are wave-uniform: at most NT of
+// them) and, per output-channel quad, their dy loads issued together before the FMAs — in the kernel above every tap's load sits in
+// a run-time loop behind `valid ? load : 0` and gets its own wait (6 serial round trips per voxel of the (1,6,1) stride-2 layer).
+// Slots past the last valid tap re-read slot 0 (cached) and are masked: no branch around a load.
+template <typename T, int CIT, int NT>
+__global__ void __launch_bounds__(64)
+conv_dgrad_strided_taps_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* __restrict__ wp,
+                               const float* __restrict__ bias, T* __restrict__ dx, int CiP) {
+    int u = blockIdx.x;
+    const int rw = u % g.sw;
+    u /= g.sw;
+    const int ih = u % g.hi;
+    u /= g.hi;
+    const int id = u % g.di;
+    const int n = u / g.di;
+    const int cit = blockIdx.y * CIT;
+    const int kd0 = (id + g.pd) % g.sd, kh0 = (ih + g.ph) % g.sh, kw0 = (rw + g.pw) % g.sw;
+    // enumerate the taps that reach this row (uniform): dy row base, kw, packed-weight tap index
+    int64_t rowoff[NT];
+    int tkw[NT], ttap[NT];
+    int ntap = 0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { rowoff[t] = 0; tkw[t] = kw0; ttap[t] = 0; }
+    for (int kd = kd0; kd < g.kd; kd += g.sd) {
+        const int nd = id + g.pd - kd;
+        if (nd < 0) break;
+        const int od = nd / g.sd;
+        if (od >= g.dout) continue;
+        for (int kh = kh0; kh < g.kh; kh += g.sh) {
+            const int nh = ih + g.ph - kh;
+            if (nh < 0) break;
+            const int oh = nh / g.sh;
+            if (oh >= g.ho) continue;
+            for (int kw = kw0; kw < g.kw; kw += g.sw) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (t == ntap) {
+                        rowoff[t] = ((((int64_t)n * g.dout + od) * g.ho + oh) * g.wo) * g.y_ld;
+                        tkw[t] = kw;
+                        ttap[t] = (kd * g.kh + kh) * g.kw + kw;
+                    }
+                ++ntap;   // host guarantees <= NT
+            }
+        }
+    }
+    // input voxel iw = rw + k * sw: its tap kw (kw = (rw + pw) mod sw, enumerated above) reaches output voxel k + (rw + pw - kw) / sw —
+    // an exact, wave-uniform quotient per tap, so the voxel loop has no integer division
+    int tq[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) tq[t] = (rw + g.pw - tkw[t]) / g.sw;
+    int k = (int)threadIdx.x;
+    for (int iw = rw + (int)threadIdx.x * g.sw; iw < g.wi; iw += 64 * g.sw, k += 64) {
+        // (bias initialisation, tap FMAs and tile store are written out in each of the six kernels of this kind: shared, the code changed)
+        float acc[CIT];
+#pragma unroll
+        for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
+        int64_t off[NT];
+        unsigned okm = 0;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int ow = k + tq[t];
+            const bool ok = t < ntap && (unsigned)ow < (unsigned)g.wo;
+            okm |= ok ? (1u << t) : 0u;
+            off[t] = rowoff[t] + (int64_t)(ok ? ow : 0) * g.y_ld;
+        }
+        for (int co = 0; co < g.co; co += 4) {
+            float4 gv[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) gv[t] = ldf4(dy + off[t] + co);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bool ok = (okm >> t) & 1u;
+                const float g0 = ok ? gv[t].x : 0.f, g1 = ok ? gv[t].y : 0.f, g2 = ok ? gv[t].z : 0.f, g3 = ok ? gv[t].w : 0.f;
+                const float* w0 = wp + ((size_t)ttap[t] * g.co + co) * CiP + cit;
+#pragma unroll
+                for (int j = 0; j < CIT; ++j) {
+                    acc[j] = fmaf(g0, w0[j], acc[j]);
+                    acc[j] = fmaf(g1, w0[CiP + j], acc[j]);
+                    acc[j] = fmaf(g2, w0[2 * CiP + j], acc[j]);
+                    acc[j] = fmaf(g3, w0[3 * CiP + j], acc[j]);
+                }
+            }
+        }
+        T* xp = dx + ((((int64_t)n * g.di + id) * g.hi + ih) * g.wi + iw) * g.x_ld + cit;
+        if (CIT % 4 == 0 && cit + CIT <= g.ci && (g.x_ld & 3) == 0) {
+#pragma unroll
+            for (int j = 0; j < CIT; j += 4) stf4(xp + j, make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]));
+        } else {
+#pragma unroll
+            for (int j = 0; j < CIT; ++j)
+                if (cit + j < g.ci) stf(xp + j, acc[j]);
         }
     }
 }
@@ -396,12 +564,8 @@ conv_wgrad_generic_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __r
             int64_t v = v0 + tid;
             int64_t off = -1;
             if (v < nvox) {
-                int ow = (int)(v % g.wo);
-                int64_t t = v / g.wo;
-                int oh = (int)(t % g.ho);
-                t /= g.ho;
-                int od = (int)(t % g.dout);
-                int n = (int)(t / g.dout);
+                int n, od, oh, ow;
+                decode_voxel(v, g.dout, g.ho, g.wo, n, od, oh, ow);
                 int id = od * g.sd - g.pd + kd_ * g.dd;
                 int ih = oh * g.sh - g.ph + kh_ * g.dh;
                 int iw = ow * g.sw - g.pw + kw_ * g.dw;
@@ -547,7 +711,7 @@ conv_wgrad_small_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __res
     const int64_t per_n = (int64_t)g.dout * g.ho * g.wo;
     const int64_t nvox = (int64_t)g.n * per_n;
     for (int64_t v = (int64_t)blockIdx.x * VL + vl; v < nvox; v += (int64_t)gridDim.x * VL) {
-        const int n = (int)(v / per_n);
+        const int n = (int)(v / per_n);   // (this decode is written out here and in the other per-sample walk: shared, the code changed)
         unsigned r = (unsigned)(v - (int64_t)n * per_n);
         const int ow = r % g.wo;
         r /= g.wo;
@@ -642,6 +806,7 @@ conv_wgrad_quads_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __res
             for (int b = 0; b < 4; ++b) acc[t][a][b] = 0.f;
     // tap offsets in voxels per axis and as ONE element offset (all wave-uniform): a tap's address is the voxel's base offset plus
     // a scalar — no clamps, no multiplications per tap (they were 230 of the 330 instructions per voxel of the 8 -> 8 layer)
+    // (the table of conv_fwd_taps_kernel, written out in both: shared, the code changed)
     int tdd[NTAPS], tdh[NTAPS], tdw[NTAPS];
     int64_t tdelta[NTAPS];
 #pragma unroll
@@ -767,7 +932,7 @@ conv_wgrad_co1_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __restr
     const int64_t per_n = (int64_t)g.dout * g.ho * g.wo;
     const int64_t nvox = (int64_t)g.n * per_n;
     for (int64_t v = (int64_t)blockIdx.x * 256 + tid; v < nvox; v += (int64_t)gridDim.x * 256) {
-        const int n = (int)(v / per_n);
+        const int n = (int)(v / per_n);   // (this decode is written out here and in the other per-sample walk: shared, the code changed)
         unsigned r = (unsigned)(v - (int64_t)n * per_n);
         const int ow = r % g.wo;
         r /= g.wo;
@@ -843,7 +1008,15 @@ constexpr int C1D = 4, C1H = 8, C1WQ = 8;   // tile: 4 x 8 x (8*VPT) voxels, 256
 template <int CO> struct Cin1 { static constexpr int VPT = CO <= 8 ? 4 : 2; };
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-
+// tile index -> sample and origin of a C1D x C1H x TW voxel tile
+__device__ __forceinline__ void decode_tile(int t, int tilesD, int tilesH, int tilesW, int TW, int& n, int& d0, int& h0, int& w0) {
+    w0 = (t % tilesW) * TW;
+    t /= tilesW;
+    h0 = (t % tilesH) * C1H;
+    t /= tilesH;
+    d0 = (t % tilesD) * C1D;
+    n = t / tilesD;
+}
 
 // stage rows [dlo, dlo+ND) x (C1H+2) x (TW+2) of the zero-padded input around tile origin (d0, h0, w0) into LDS
 template <typename T, int TW, int ND, int NTHR = 256>
@@ -878,13 +1051,8 @@ conv_cin1_fwd_kernel(Mri3dConvGeom g, const T* __restrict__ x, const float* __re
 #pragma unroll
     for (int c = 0; c < CO; ++c) bv[c] = bias ? bias[c] : 0.f;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int t = tile;
-        const int w0 = (t % tilesW) * TW;
-        t /= tilesW;
-        const int h0 = (t % tilesH) * C1H;
-        t /= tilesH;
-        const int d0 = (t % tilesD) * C1D;
-        const int n = t / tilesD;
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
         __syncthreads();
         cin1_stage<T, TW, C1D + 2>(xs, x + (int64_t)n * g.di * g.hi * g.wi * g.x_ld, g, d0 - 1, h0, w0, tid);
         __syncthreads();
@@ -965,13 +1133,8 @@ conv_cin1_wgrad_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __rest
 #pragma unroll
     for (int c = 0; c < CO; ++c) bsum[c] = 0.f;
     for (int tile = share; tile < ntiles; tile += nshares) {
-        int t = tile;
-        const int w0 = (t % tilesW) * TW;
-        t /= tilesW;
-        const int h0 = (t % tilesH) * C1H;
-        t /= tilesH;
-        const int d0 = (t % tilesD) * C1D;
-        const int n = t / tilesD;
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
         __syncthreads();
         cin1_stage<T, TW, C1D + 2, 768>(xs, x + (int64_t)n * g.di * g.hi * g.wi * g.x_ld, g, d0 - 1, h0, w0, (int)threadIdx.x);
         // this lane's VPT output voxels of dy (zero outside the volume)
@@ -1060,13 +1223,8 @@ conv_c1c1_stencil_kernel(Mri3dConvGeom g, const T* __restrict__ x, int x_ld, con
     Mri3dConvGeom gs = g;
     gs.x_ld = x_ld;   // cin1_stage reads its source pitch from the geometry
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int t = tile;
-        const int w0 = (t % tilesW) * TW;
-        t /= tilesW;
-        const int h0 = (t % tilesH) * C1H;
-        t /= tilesH;
-        const int d0 = (t % tilesD) * C1D;
-        const int n = t / tilesD;
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
         __syncthreads();
         cin1_stage<T, TW, C1D + 2>(xs, x + (int64_t)n * g.di * g.hi * g.wi * x_ld, gs, d0 - 1, h0, w0, tid);
         __syncthreads();
@@ -1111,13 +1269,8 @@ conv_c1c1_wgrad_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __rest
 #pragma unroll
     for (int t = 0; t < 27; ++t) acc[t] = 0.f;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        int t = tile;
-        const int w0 = (t % tilesW) * TW;
-        t /= tilesW;
-        const int h0 = (t % tilesH) * C1H;
-        t /= tilesH;
-        const int d0 = (t % tilesD) * C1D;
-        const int n = t / tilesD;
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
         __syncthreads();
         cin1_stage<T, TW, C1D + 2>(xs, x + (int64_t)n * g.di * g.hi * g.wi * g.x_ld, g, d0 - 1, h0, w0, tid);
         const int od = d0 + dl, oh = h0 + hl;
@@ -1290,20 +1443,41 @@ static bool c1_taps_ok(const Mri3dConvGeom& g) {
            (int64_t)g.n * g.dout * g.ho * g.wo < 0x7fffffffLL && (int64_t)g.n * g.di * g.hi * g.wi < 0x7fffffffLL;
 }
 
+// forward (sign +1: src = x) and stride-1 data gradient (sign -1: src = dy) of the 1 -> 1 few-taps stencil
+static void launch_c1_taps(const Mri3dConvGeom& g, int nt, const float* src, const float* w, const float* bias, float* dst, int sign,
+                           hipStream_t s) {
+    const int sD = sign > 0 ? g.di : g.dout, sH = sign > 0 ? g.hi : g.ho, sW = sign > 0 ? g.wi : g.wo;
+    const int oD = sign > 0 ? g.dout : g.di, oH = sign > 0 ? g.ho : g.hi, oW = sign > 0 ? g.wo : g.wi;
+    const int64_t items = (int64_t)g.n * oD * oH * (oW / 4);
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256), 8192));
+    if (nt == 3)
+        hipLaunchKernelGGL(conv_c1_taps_kernel<3>, dim3(grid), dim3(256), 0, s, g, src, w, bias, dst, sign, sD, sH, sW, oD, oH, oW);
+    else
+        hipLaunchKernelGGL(conv_c1_taps_kernel<kSmTaps>, dim3(grid), dim3(256), 0, s, g, src, w, bias, dst, sign, sD, sH, sW, oD, oH, oW);
+}
+
+// the 4 x 8 x (8*vpt) voxel tiles of the cin1 / c1c1 kernels over n volumes of D x H x W (the count in 64 bits: the _ok tests bound it)
+struct C1Tiles { int tilesD, tilesH, tilesW; int64_t ntiles; };
+static C1Tiles c1_tiles(int n, int D, int H, int W, int vpt) {
+    C1Tiles t;
+    t.tilesD = cdiv(D, C1D), t.tilesH = cdiv(H, C1H), t.tilesW = cdiv(W, C1WQ * vpt);
+    t.ntiles = (int64_t)n * t.tilesD * t.tilesH * t.tilesW;
+    return t;
+}
+
 static bool c1c1_ok(const Mri3dConvGeom& g) {
     static const int off = tuning_knob("MRI3D_C1C1_OFF", 0);   // tuning aid (A/B)
     return !off && g.ci == 1 && g.co == 1 && g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 && g.sh == 1 && g.sw == 1 &&
            g.dd == 1 && g.dh == 1 && g.dw == 1 && g.pd == 1 && g.ph == 1 && g.pw == 1 &&
-           (int64_t)g.n * cdiv(g.dout, C1D) * cdiv(g.ho, C1H) * cdiv(g.wo, C1WQ * 4) < 0x7fffffffLL;
+           c1_tiles(g.n, g.dout, g.ho, g.wo, 4).ntiles < 0x7fffffffLL;
 }
 
 template <typename T>
 static void launch_c1c1_stencil(const Mri3dConvGeom& g, const T* src, int src_ld, const float* w, const float* bias, int flip,
                                 T* dst, int dst_ld, hipStream_t s) {
-    const int tilesD = cdiv(g.di, C1D), tilesH = cdiv(g.hi, C1H), tilesW = cdiv(g.wi, C1WQ * 4);
-    const int ntiles = g.n * tilesD * tilesH * tilesW;
-    hipLaunchKernelGGL(conv_c1c1_stencil_kernel<T>, dim3(std::min(ntiles, 256 * 8)), dim3(256), 0, s, g, src, src_ld, w, bias, flip,
-                       dst, dst_ld, tilesD, tilesH, tilesW, ntiles);
+    const C1Tiles t = c1_tiles(g.n, g.di, g.hi, g.wi, 4);
+    hipLaunchKernelGGL(conv_c1c1_stencil_kernel<T>, dim3(std::min((int)t.ntiles, 256 * 8)), dim3(256), 0, s, g, src, src_ld, w, bias, flip,
+                       dst, dst_ld, t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles);
 }
 
 static const int g_cin1_off = tuning_knob("MRI3D_CIN1_OFF", 0);   // tuning aid (A/B)
@@ -1312,8 +1486,9 @@ constexpr int kCin1Shares = 256;   // 3 * 256 = 768 workgroups = 3 per CU
 static bool cin1_ok(const Mri3dConvGeom& g) {
     return !g_cin1_off && g.ci == 1 && (g.co == 8 || g.co == 16) && g.kd == 3 && g.kh == 3 && g.kw == 3 && g.sd == 1 &&
            g.sh == 1 && g.sw == 1 && g.dd == 1 && g.dh == 1 && g.dw == 1 && g.pd == 1 && g.ph == 1 && g.pw == 1 &&
-           g.y_ld % 4 == 0 && (int64_t)g.n * cdiv(g.dout, C1D) * cdiv(g.ho, C1H) * cdiv(g.wo, C1WQ * 2) < 0x7fffffffLL;
+           g.y_ld % 4 == 0 && c1_tiles(g.n, g.dout, g.ho, g.wo, 2).ntiles < 0x7fffffffLL;   // (the Co = 16 tiles: the larger count)
 }
+static C1Tiles cin1_tiles(const Mri3dConvGeom& g) { return c1_tiles(g.n, g.dout, g.ho, g.wo, g.co <= 8 ? 4 : 2); }   // Cin1<CO>::VPT
 
 static bool wgrad_small_ok(const Mri3dConvGeom& g) {
     const int taps = g.kd * g.kh * g.kw;
@@ -1331,87 +1506,45 @@ static bool wgrad_quads_ok(const Mri3dConvGeom& g) {
            g.x_ld % 4 == 0 && g.y_ld % 4 == 0 && (int64_t)g.ho * g.wo < 0x7fffffffLL &&
            (int64_t)g.n * g.dout * g.ho < 0x7fffffffLL;
 }
-struct WgradQuadsPlan { int QI, QO, hch, gx, CiP, CoP; size_t part_floats, bias_floats; };
-static WgradQuadsPlan wgrad_quads_plan(const Mri3dConvGeom& g) {
-    WgradQuadsPlan p;
-    p.QI = g.ci == 1 ? 1 : g.ci / 4, p.QO = g.co / 4, p.CiP = g.ci, p.CoP = g.co;
-    const int VL = 256 / (p.QI * p.QO);
-    // ~16 voxels per lane and slab
-    p.hch = (int)std::max<int64_t>(1, std::min<int64_t>(g.ho, (int64_t)16 * VL / std::max(g.wo, 1)));
-    const int64_t slabs = (int64_t)g.n * g.dout * cdiv(g.ho, p.hch);
-    // one resident round: 4 / 3 / 2 workgroups per CU with 4 / 6 / 8 accumulator slots (112 / 161 / 209 VGPRs)
-    const int taps = g.kd * g.kh * g.kw;
-    const int resident = 256 * (taps <= 4 ? 4 : (taps <= 6 ? 3 : 2));
-    p.gx = (int)std::max<int64_t>(1, std::min<int64_t>(slabs, resident));
-    p.part_floats = (size_t)p.gx * g.kd * g.kh * g.kw * p.CiP * p.CoP;
-    p.bias_floats = (size_t)p.gx * g.co;
-    return p;
-}
-
-struct WgradSmallPlan { int CiL, gz, gy, gx, CiP, CoP; size_t part_floats, bias_floats; };
-static WgradSmallPlan wgrad_small_plan(const Mri3dConvGeom& g) {
-    WgradSmallPlan p;
-    int cil = 1;
-    while (cil < g.ci && cil < 16) cil <<= 1;
-    p.CiL = cil;
-    p.gz = cdiv(g.ci, cil);
-    p.gy = cdiv(g.co, kSmCo);
-    p.CiP = cdiv(g.ci, 4) * 4;
-    p.CoP = cdiv(g.co, 4) * 4;
-    const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
-    int64_t want = cdiv64(nvox, (int64_t)(256 / cil) * 8);
-    int cap = 2048 / (p.gy * p.gz);
-    if (cap < 8) cap = 8;
-    p.gx = (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
-    p.part_floats = (size_t)p.gx * g.kd * g.kh * g.kw * p.CiP * p.CoP;
-    p.bias_floats = (size_t)p.gx * g.co;
-    return p;
-}
 
 // ------------------------------------------------------------------ host side
 static int pick_tile(int c) { return c >= 16 ? 16 : (c > 4 ? 8 : (c > 2 ? 4 : 2)); }
-
-struct WgradPlan {
-    int Ci4, Co4, nitems, vsplit, gx, gz, taps;
-    size_t part_floats, bias_floats, smem;
-};
-static WgradPlan wgrad_plan(const Mri3dConvGeom& g) {
-    WgradPlan p;
-    p.Ci4 = cdiv(g.ci, 4);
-    p.Co4 = cdiv(g.co, 4);
-    p.nitems = p.Ci4 * p.Co4;
-    p.taps = g.kd * g.kh * g.kw;
-    p.vsplit = p.nitems >= 256 ? 1 : (256 / p.nitems);
-    if (p.vsplit > kWgCH) p.vsplit = kWgCH;
-    p.gz = p.vsplit > 1 ? 1 : cdiv(p.nitems, 256 * kWgIPT);
-    int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
-    int64_t nchunks = cdiv64(nvox, kWgCH);
-    int gx = 2048 / (p.taps * p.gz);
-    if (gx < 8) gx = 8;
-    if (gx > 256) gx = 256;
-    if (gx > nchunks) gx = (int)nchunks;
-    if (gx < 1) gx = 1;
-    p.gx = gx;
-    p.part_floats = (size_t)gx * p.taps * p.Ci4 * 4 * p.Co4 * 4;
-    p.bias_floats = (size_t)gx * g.co;
-    p.smem = (size_t)kWgCH * (p.Ci4 + p.Co4) * 4 * sizeof(float) + kWgCH * sizeof(int64_t) +
-             (p.vsplit > 1 ? 256 * 16 * sizeof(float) : 0);
-    return p;
+static int pad_to_tile(int c) { return cdiv(c, pick_tile(c)) * pick_tile(c); }
+// forward / data gradient: the repacked weights [tap][channels summed over][tiled channels, padded to the tile], in the workspace
+static size_t packed_w_bytes(const Mri3dConvGeom& g, int pass) {
+    const int taps = g.kd * g.kh * g.kw;
+    return pass == MRI3D_PASS_FWD ? (size_t)taps * g.ci * pad_to_tile(g.co) * sizeof(float)
+                                  : (size_t)taps * g.co * pad_to_tile(g.ci) * sizeof(float);
 }
 
 // ------------------------------------------------------------------ THE decision of each pass
 // Which kernel and instantiation a pass launches, from the geometry and the alignment (ptr_align) of its two activation tensors:
 // ax = that of x (forward, weight gradient) / dx (data gradient), ay = that of y / dy.  conv_generic_fwd / _dgrad / _wgrad launch
-// from it, conv_generic_route_name prints it and conv_generic_workspace_bytes sizes the weight gradient's partials by it.
+// from it and conv_generic_route_name prints it.  The plan of a weight gradient also OWNS the layout of its workspace — where the
+// partials of dw end and those of the bias begin, how wgrad_reduce_kernel strides through them, the grid that fills them: the
+// launch carves the workspace by the plan and conv_generic_workspace_bytes sizes it by the plan, neither has a size of its own.
 enum class GenKernel { c1c1, c1taps, cin1, taps, gather, strided_taps, strided, co1, quads, small, lds };
 struct GenericPlan {
     GenKernel kernel = GenKernel::gather;
     int tl = 0;           // taps / gather / strided_taps / strided: channel tile of a thread, the padding of the packed weights
     int nt = 0;           // tap slots: c1taps 3 | 8, taps 3 | 4 | 6 | 8, strided_taps 3 | 4 | 8, quads 4 | 6 | 8
-    int cv = 0;           // taps: channels per load (4 | 1); gather / strided: vector loads (1 | 0); quads: CIV (4 | 1); cin1: Co (8 | 16);
-                          // co1: the CI instance (1 | 4 | 8 | 16)
+    int cv = 0;           // taps: channels per load (4 | 1)
+    int vec = 0;          // gather / strided: 16-byte loads (1 | 0)
+    int civ = 0;          // quads: input channels per lane, the kernel's CIV (4 | 1)
+    int co_inst = 0;      // cin1: the CO instance (8 | 16)
+    int ci_inst = 0;      // co1: the CI instance (1 | 4 | 8 | 16)
     int cp = 0;           // taps / gather / strided*: channels of the packed weights (Co or Ci rounded up to tl)
-    size_t ws_bytes = 0;  // workspace the launch requires
+    size_t ws_bytes = 0;  // workspace the launch requires: the packed weights, or (part_floats + bias_floats) floats
+    // weight gradient: the workspace is part[slots][taps][CiP][CoP] (c1taps and co1: [slots][slot of their widest instance]), then
+    // bias_part[slots][Co]; a launch fills the first nb <= slots of each and wgrad_reduce_kernel sums those
+    int slots = 0;                              // partials the workspace holds = the most workgroups (x) a launch may use
+    size_t part_floats = 0, bias_floats = 0;    // part_floats is also the offset of bias_part
+    int CiP = 0, CoP = 0;                       // channel pitches of a partial (taps, Ci, Co: the geometry's)
+    // the family's own grid data (grid x = slots in all three)
+    struct { int QI = 0, QO = 0, hch = 0; } quads;          // channel quads per voxel, output rows per slab
+    struct { int CiL = 0, gy = 1, gz = 1; } small;          // input channels per workgroup; grid (slots, gy, gz)
+    struct { int Ci4 = 0, Co4 = 0, nitems = 0, vsplit = 0, gz = 1; size_t smem = 0; } lds;   // channel quads, 4x4 items, voxel split
+                                                            // of a small item set; grid (slots, taps, gz); dynamic LDS bytes
 };
 
 static GenericPlan generic_fwd_plan(const Mri3dConvGeom& g, int ax, int ay) {
@@ -1419,12 +1552,9 @@ static GenericPlan generic_fwd_plan(const Mri3dConvGeom& g, int ax, int ay) {
     const int taps = g.kd * g.kh * g.kw;
     if (c1c1_ok(g)) { p.kernel = GenKernel::c1c1; return p; }
     if (c1_taps_ok(g) && align16(ay)) { p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps; return p; }
-    if (cin1_ok(g) && align_vec4(g.dtype, ay)) {
-        p.kernel = GenKernel::cin1, p.cv = g.co == 8 ? 8 : 16, p.ws_bytes = (size_t)27 * g.co * sizeof(float);
-        return p;
-    }
-    p.tl = pick_tile(g.co), p.cp = cdiv(g.co, p.tl) * p.tl;
-    p.ws_bytes = (size_t)taps * g.ci * p.cp * sizeof(float);
+    p.ws_bytes = packed_w_bytes(g, MRI3D_PASS_FWD);
+    if (cin1_ok(g) && align_vec4(g.dtype, ay)) { p.kernel = GenKernel::cin1, p.co_inst = g.co == 8 ? 8 : 16; return p; }   // [27][1][Co]: the tile of 8 | 16 pads nothing
+    p.tl = pick_tile(g.co), p.cp = pad_to_tile(g.co);
     const bool vec = (g.ci % 4 == 0) && (g.x_ld % 4 == 0) && align_vec4(g.dtype, ax);
     if ((vec || g.ci == 1) && taps <= 8 && align_vec4(g.dtype, ay) && (int64_t)g.ho * g.wo < 0x7fffffffLL && (int64_t)g.n * g.dout * g.ho < 0x7fffffffLL) {
         // tap slots = the filter's taps where an instance exists (3: the decoder's k = 3 filters, 6: the encoder's k = 6 ones): a
@@ -1433,7 +1563,7 @@ static GenericPlan generic_fwd_plan(const Mri3dConvGeom& g, int ax, int ay) {
         p.nt = vec ? (taps <= 3 ? 3 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8))) : (taps <= 3 ? 3 : (taps <= 6 ? 6 : 8));
         return p;
     }
-    p.kernel = GenKernel::gather, p.cv = vec ? 1 : 0;
+    p.kernel = GenKernel::gather, p.vec = vec ? 1 : 0;
     return p;
 }
 
@@ -1443,8 +1573,8 @@ static GenericPlan generic_dgrad_plan(const Mri3dConvGeom& g, int ax, int ay) {
     const int taps = g.kd * g.kh * g.kw;
     if (c1c1_ok(g)) { p.kernel = GenKernel::c1c1; return p; }
     if (c1_taps_ok(g) && align16(ax)) { p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps; return p; }
-    p.tl = pick_tile(g.ci), p.cp = cdiv(g.ci, p.tl) * p.tl;
-    p.ws_bytes = (size_t)taps * g.co * p.cp * sizeof(float);
+    p.tl = pick_tile(g.ci), p.cp = pad_to_tile(g.ci);
+    p.ws_bytes = packed_w_bytes(g, MRI3D_PASS_DGRAD);
     const bool vec = (g.co % 4 == 0) && (g.y_ld % 4 == 0) && align_vec4(g.dtype, ay);
     const bool unit_stride = g.sd == 1 && g.sh == 1 && g.sw == 1;   // strided layers: the wave-uniform tap sets below are faster (0.29 vs 0.33 ms)
     if ((vec || g.co == 1) && unit_stride && taps <= 8 && align_vec4(g.dtype, ax) && (int64_t)g.hi * g.wi < 0x7fffffffLL && (int64_t)g.n * g.di * g.hi < 0x7fffffffLL) {
@@ -1460,37 +1590,91 @@ static GenericPlan generic_dgrad_plan(const Mri3dConvGeom& g, int ax, int ay) {
             p.kernel = GenKernel::strided_taps, p.nt = vt <= 3 ? 3 : (vt <= 4 ? 4 : 8);
             return p;
         }
-        p.kernel = GenKernel::strided, p.cv = vec ? 1 : 0;
+        p.kernel = GenKernel::strided, p.vec = vec ? 1 : 0;
         return p;
     }
-    p.kernel = GenKernel::gather, p.cv = vec ? 1 : 0;
+    p.kernel = GenKernel::gather, p.vec = vec ? 1 : 0;
     return p;
+}
+
+// the three families whose grid follows the volume: each sets its slots (grid x), channel pitches and grid data
+static void wgrad_quads_plan(const Mri3dConvGeom& g, GenericPlan& p) {
+    const int taps = g.kd * g.kh * g.kw;
+    auto& q = p.quads;
+    p.civ = g.ci == 1 ? 1 : 4, p.nt = g.ci == 1 ? 8 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8));
+    q.QI = g.ci == 1 ? 1 : g.ci / 4, q.QO = g.co / 4;
+    const int VL = 256 / (q.QI * q.QO);
+    // ~16 voxels per lane and slab
+    q.hch = (int)std::max<int64_t>(1, std::min<int64_t>(g.ho, (int64_t)16 * VL / std::max(g.wo, 1)));
+    const int64_t slabs = (int64_t)g.n * g.dout * cdiv(g.ho, q.hch);
+    // one resident round: 4 / 3 / 2 workgroups per CU with 4 / 6 / 8 accumulator slots (112 / 161 / 209 VGPRs)
+    const int resident = 256 * (taps <= 4 ? 4 : (taps <= 6 ? 3 : 2));
+    p.slots = (int)std::max<int64_t>(1, std::min<int64_t>(slabs, resident));
+}
+
+static void wgrad_small_plan(const Mri3dConvGeom& g, GenericPlan& p) {
+    auto& q = p.small;
+    int cil = 1;
+    while (cil < g.ci && cil < 16) cil <<= 1;
+    q.CiL = cil;
+    q.gz = cdiv(g.ci, cil);
+    q.gy = cdiv(g.co, kSmCo);
+    p.CiP = cdiv(g.ci, 4) * 4;
+    p.CoP = cdiv(g.co, 4) * 4;
+    const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
+    int64_t want = cdiv64(nvox, (int64_t)(256 / cil) * 8);
+    int cap = 2048 / (q.gy * q.gz);
+    if (cap < 8) cap = 8;
+    p.slots = (int)std::max<int64_t>(1, std::min<int64_t>(want, cap));
+}
+
+static void wgrad_lds_plan(const Mri3dConvGeom& g, GenericPlan& p) {
+    const int taps = g.kd * g.kh * g.kw;
+    auto& q = p.lds;
+    q.Ci4 = cdiv(g.ci, 4);
+    q.Co4 = cdiv(g.co, 4);
+    p.CiP = q.Ci4 * 4, p.CoP = q.Co4 * 4;
+    q.nitems = q.Ci4 * q.Co4;
+    q.vsplit = q.nitems >= 256 ? 1 : (256 / q.nitems);
+    if (q.vsplit > kWgCH) q.vsplit = kWgCH;
+    q.gz = q.vsplit > 1 ? 1 : cdiv(q.nitems, 256 * kWgIPT);
+    int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
+    int64_t nchunks = cdiv64(nvox, kWgCH);
+    int gx = 2048 / (taps * q.gz);
+    if (gx < 8) gx = 8;
+    if (gx > 256) gx = 256;
+    if (gx > nchunks) gx = (int)nchunks;
+    if (gx < 1) gx = 1;
+    p.slots = gx;
+    q.smem = (size_t)kWgCH * (q.Ci4 + q.Co4) * 4 * sizeof(float) + kWgCH * sizeof(int64_t) +
+             (q.vsplit > 1 ? 256 * 16 * sizeof(float) : 0);
 }
 
 // (ax: x, ay: dy)
 static GenericPlan generic_wgrad_plan(const Mri3dConvGeom& g, int ax, int ay) {
     GenericPlan p;
     const int taps = g.kd * g.kh * g.kw;
+    p.CiP = g.ci, p.CoP = g.co;   // small and lds round them up to quads
+    size_t slot_floats = 0;       // floats of one partial of dw; 0: taps * CiP * CoP
     if (c1c1_ok(g)) {
-        p.kernel = GenKernel::c1c1, p.ws_bytes = (size_t)kC1C1Blocks * 28 * sizeof(float);
+        p.kernel = GenKernel::c1c1, p.slots = kC1C1Blocks;
     } else if (c1_taps_ok(g) && align16(ay)) {
-        p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps, p.ws_bytes = (size_t)kC1TBlocks * (kSmTaps + 1) * sizeof(float);
+        p.kernel = GenKernel::c1taps, p.nt = taps <= 3 ? 3 : kSmTaps, p.slots = kC1TBlocks, slot_floats = kSmTaps;
     } else if (cin1_ok(g) && align_vec4(g.dtype, ay)) {
-        p.kernel = GenKernel::cin1, p.cv = g.co == 8 ? 8 : 16, p.ws_bytes = (size_t)kCin1Shares * (27 + 1) * g.co * sizeof(float);
+        p.kernel = GenKernel::cin1, p.co_inst = g.co == 8 ? 8 : 16, p.slots = kCin1Shares;
     } else if (wgrad_co1_ok(g) && align_vec4(g.dtype, ax)) {
-        p.kernel = GenKernel::co1, p.cv = (g.ci == 1 || g.ci == 4 || g.ci == 8) ? g.ci : 16;
-        p.ws_bytes = (size_t)kCo1Blocks * (kSmTaps * 16 + 1) * sizeof(float);
+        p.kernel = GenKernel::co1, p.ci_inst = (g.ci == 1 || g.ci == 4 || g.ci == 8) ? g.ci : 16;
+        p.slots = kCo1Blocks, slot_floats = kSmTaps * 16;
     } else if (wgrad_quads_ok(g) && align_vec4(g.dtype, ay) && (g.ci == 1 || align_vec4(g.dtype, ax))) {
-        const WgradQuadsPlan q = wgrad_quads_plan(g);
-        p.kernel = GenKernel::quads, p.cv = g.ci == 1 ? 1 : 4, p.nt = g.ci == 1 ? 8 : (taps <= 4 ? 4 : (taps <= 6 ? 6 : 8));
-        p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+        p.kernel = GenKernel::quads, wgrad_quads_plan(g, p);
     } else if (wgrad_small_ok(g)) {
-        const WgradSmallPlan q = wgrad_small_plan(g);
-        p.kernel = GenKernel::small, p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+        p.kernel = GenKernel::small, wgrad_small_plan(g, p);
     } else {
-        const WgradPlan q = wgrad_plan(g);
-        p.kernel = GenKernel::lds, p.ws_bytes = (q.part_floats + q.bias_floats) * sizeof(float);
+        p.kernel = GenKernel::lds, wgrad_lds_plan(g, p);
     }
+    p.part_floats = (size_t)p.slots * (slot_floats ? slot_floats : (size_t)taps * p.CiP * p.CoP);
+    p.bias_floats = (size_t)p.slots * g.co;
+    p.ws_bytes = (p.part_floats + p.bias_floats) * sizeof(float);
     return p;
 }
 
@@ -1503,13 +1687,13 @@ bool conv_generic_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax
     switch (p.kernel) {
     case GenKernel::c1c1: len = snprintf(name, name_bytes, "generic c1c1%s", b); break;
     case GenKernel::c1taps: len = snprintf(name, name_bytes, "generic c1taps nt%d%s", p.nt, b); break;
-    case GenKernel::cin1: len = snprintf(name, name_bytes, "generic cin1 co%d", p.cv); break;
+    case GenKernel::cin1: len = snprintf(name, name_bytes, "generic cin1 co%d", p.co_inst); break;
     case GenKernel::taps: len = snprintf(name, name_bytes, "generic taps tl%d nt%d cv%d%s", p.tl, p.nt, p.cv, b); break;
-    case GenKernel::gather: len = snprintf(name, name_bytes, "generic gather tl%d vec%d%s", p.tl, p.cv, b); break;
+    case GenKernel::gather: len = snprintf(name, name_bytes, "generic gather tl%d vec%d%s", p.tl, p.vec, b); break;
     case GenKernel::strided_taps: len = snprintf(name, name_bytes, "generic staps tl%d nt%d%s", p.tl, p.nt, b); break;
-    case GenKernel::strided: len = snprintf(name, name_bytes, "generic strided tl%d vec%d%s", p.tl, p.cv, b); break;
-    case GenKernel::co1: len = snprintf(name, name_bytes, "generic co1 ci%d", p.cv); break;
-    case GenKernel::quads: len = snprintf(name, name_bytes, "generic quads nt%d civ%d", p.nt, p.cv); break;
+    case GenKernel::strided: len = snprintf(name, name_bytes, "generic strided tl%d vec%d%s", p.tl, p.vec, b); break;
+    case GenKernel::co1: len = snprintf(name, name_bytes, "generic co1 ci%d", p.ci_inst); break;
+    case GenKernel::quads: len = snprintf(name, name_bytes, "generic quads nt%d civ%d", p.nt, p.civ); break;
     case GenKernel::small: len = snprintf(name, name_bytes, "generic small"); break;
     case GenKernel::lds: len = snprintf(name, name_bytes, "generic lds"); break;
     }
@@ -1517,15 +1701,8 @@ bool conv_generic_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax
 }
 
 size_t conv_generic_workspace_bytes(const Mri3dConvGeom& g, int pass) {
-    const int taps = g.kd * g.kh * g.kw;
-    if (pass == MRI3D_PASS_FWD) {
-        int t = pick_tile(g.co);
-        return (size_t)taps * g.ci * cdiv(g.co, t) * t * sizeof(float);
-    }
-    if (pass == MRI3D_PASS_DGRAD) {
-        int t = pick_tile(g.ci);
-        return (size_t)taps * g.co * cdiv(g.ci, t) * t * sizeof(float);
-    }
+    // forward / data gradient: the packed weights, also where the plan ends at a kernel that reads the weights as they are
+    if (pass != MRI3D_PASS_WGRAD) return packed_w_bytes(g, pass);
     // the weight gradient falls through a chain of `geometry && alignment` tests whose kernels lay their partials out differently:
     // the largest need of the kernels the chain can end at, over the alignments x and dy may have
     size_t a = 0;
@@ -1554,7 +1731,7 @@ static void launch_fwd(const Mri3dConvGeom& g, const GenericPlan& p, const void*
         return;
     }
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (p.cv)
+        if (p.vec)
             hipLaunchKernelGGL((conv_fwd_generic_kernel<T, TL, true>), grid, dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y, CoP);
         else
             hipLaunchKernelGGL((conv_fwd_generic_kernel<T, TL, false>), grid, dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y, CoP);
@@ -1569,43 +1746,29 @@ int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, cons
         return check_launch("conv3d_fwd(1->1 stencil)");
     }
     if (p.kernel == GenKernel::c1taps) {
-        const int64_t items = (int64_t)g.n * g.dout * g.ho * (g.wo / 4);
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256), 8192));
-        if (p.nt == 3)
-            hipLaunchKernelGGL(conv_c1_taps_kernel<3>, dim3(grid), dim3(256), 0, s, g, (const float*)x, w, bias, (float*)y, 1, g.di, g.hi,
-                               g.wi, g.dout, g.ho, g.wo);
-        else
-            hipLaunchKernelGGL(conv_c1_taps_kernel<kSmTaps>, dim3(grid), dim3(256), 0, s, g, (const float*)x, w, bias, (float*)y, 1, g.di,
-                               g.hi, g.wi, g.dout, g.ho, g.wo);
+        launch_c1_taps(g, p.nt, (const float*)x, w, bias, (float*)y, 1, s);
         return check_launch("conv3d_fwd(1->1 taps)");
     }
+    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, MRI3D_EWORKSPACE, "conv3d_fwd: workspace %zu < %zu", ws_bytes, p.ws_bytes);
+    float* wp = static_cast<float*>(ws);
+    const int taps = g.kd * g.kh * g.kw;
     if (p.kernel == GenKernel::cin1) {
-        const size_t need1 = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need1, MRI3D_EWORKSPACE, "conv3d_fwd: workspace %zu < %zu", ws_bytes, need1);
-        float* wp = static_cast<float*>(ws);
-        hipLaunchKernelGGL(repack_w_fwd_kernel, dim3(1), dim3(256), 0, s, w, wp, g.co, 1, 27, g.co);
-        const int vpt = g.co <= 8 ? 4 : 2;
-        const int tilesD = cdiv(g.dout, C1D), tilesH = cdiv(g.ho, C1H), tilesW = cdiv(g.wo, C1WQ * vpt);
-        const int ntiles = g.n * tilesD * tilesH * tilesW;
-        const int grid = std::min(ntiles, 256 * 8);
+        hipLaunchKernelGGL(repack_w_kernel, dim3(1), dim3(256), 0, s, w, wp, g.co, 1, 27, g.co, 0);
+        const C1Tiles t = cin1_tiles(g);
+        const int grid = std::min((int)t.ntiles, 256 * 8);
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (p.cv == 8)
+            if (p.co_inst == 8)
                 hipLaunchKernelGGL((conv_cin1_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y,
-                                   tilesD, tilesH, tilesW, ntiles);
+                                   t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles);
             else
                 hipLaunchKernelGGL((conv_cin1_fwd_kernel<T, 16>), dim3(grid), dim3(256), 0, s, g, (const T*)x, wp, bias, (T*)y,
-                                   tilesD, tilesH, tilesW, ntiles);
+                                   t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles);
         });
         return check_launch("conv3d_fwd(cin1)");
     }
-    const int taps = g.kd * g.kh * g.kw;
     const int TL = p.tl, CoP = p.cp;
-    size_t need = p.ws_bytes;
-    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_fwd: workspace %zu < %zu", ws_bytes, need);
-    float* wp = static_cast<float*>(ws);
     int total = taps * g.ci * CoP;
-    hipLaunchKernelGGL(repack_w_fwd_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co, g.ci,
-                       taps, CoP);
+    hipLaunchKernelGGL(repack_w_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co, g.ci, taps, CoP, 0);
     switch (TL) {
         case 16: launch_fwd<16>(g, p, x, wp, bias, y, s); break;
         case 8: launch_fwd<8>(g, p, x, wp, bias, y, s); break;
@@ -1613,168 +1776,6 @@ int conv_generic_fwd(const Mri3dConvGeom& g, const void* x, const float* w, cons
         default: launch_fwd<2>(g, p, x, wp, bias, y, s); break;
     }
     return check_launch("conv3d_fwd(generic)");
-}
-
-// Data gradient of a STRIDED convolution (dilation 1): only the taps with k = (i + pad) mod stride reach an input voxel i, i.e.
-// 1 .. 8 of the 27 taps of a 3x3x3 / stride-2 layer (modified_3dunet.py:23-38, cnn_model.py:49-81).  The gather kernel above
-// walks all taps and masks (8x wasted FMAs: 6 TFLOP/s on the 8 -> 16 stride-2 layer at 80x96x80).  Here one WAVE owns one
-// (n, id, ih, w-parity) row segment: the valid tap set is wave-uniform, so the tap loops just step by the stride, the weights
-// stay on the scalar path and nothing is masked except the volume border.
-template <typename T, int CIT, bool VEC4>
-__global__ void __launch_bounds__(64)
-conv_dgrad_strided_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* __restrict__ wp,
-                          const float* __restrict__ bias, T* __restrict__ dx, int CiP) {
-    int u = blockIdx.x;
-    const int rw = u % g.sw;   // residue of iw modulo the W stride handled by this wave
-    u /= g.sw;
-    const int ih = u % g.hi;
-    u /= g.hi;
-    const int id = u % g.di;
-    const int n = u / g.di;
-    const int cit = blockIdx.y * CIT;
-    const int kd0 = (id + g.pd) % g.sd, kh0 = (ih + g.ph) % g.sh, kw0 = (rw + g.pw) % g.sw;
-    for (int iw = rw + (int)threadIdx.x * g.sw; iw < g.wi; iw += 64 * g.sw) {
-        float acc[CIT];
-#pragma unroll
-        for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
-        for (int kd = kd0; kd < g.kd; kd += g.sd) {
-            const int nd = id + g.pd - kd;
-            if (nd < 0) break;
-            const int od = nd / g.sd;
-            if (od >= g.dout) continue;
-            for (int kh = kh0; kh < g.kh; kh += g.sh) {
-                const int nh = ih + g.ph - kh;
-                if (nh < 0) break;
-                const int oh = nh / g.sh;
-                if (oh >= g.ho) continue;
-                for (int kw = kw0; kw < g.kw; kw += g.sw) {
-                    const int nw = iw + g.pw - kw;
-                    const int ow = nw / g.sw;
-                    const bool valid = nw >= 0 && ow < g.wo;
-                    const T* yp = dy + ((((int64_t)n * g.dout + od) * g.ho + oh) * g.wo + (valid ? ow : 0)) * g.y_ld;
-                    const float* wt = wp + (size_t)((kd * g.kh + kh) * g.kw + kw) * g.co * CiP + cit;
-                    if (VEC4) {
-                        for (int co = 0; co < g.co; co += 4) {
-                            const float4 gv = valid ? ldf4(yp + co) : make_float4(0.f, 0.f, 0.f, 0.f);
-                            const float* w0 = wt + (size_t)co * CiP;
-#pragma unroll
-                            for (int j = 0; j < CIT; ++j) {
-                                acc[j] = fmaf(gv.x, w0[j], acc[j]);
-                                acc[j] = fmaf(gv.y, w0[CiP + j], acc[j]);
-                                acc[j] = fmaf(gv.z, w0[2 * CiP + j], acc[j]);
-                                acc[j] = fmaf(gv.w, w0[3 * CiP + j], acc[j]);
-                            }
-                        }
-                    } else {
-                        for (int co = 0; co < g.co; ++co) {
-                            const float gv = valid ? ldf(yp + co) : 0.f;
-                            const float* w0 = wt + (size_t)co * CiP;
-#pragma unroll
-                            for (int j = 0; j < CIT; ++j) acc[j] = fmaf(gv, w0[j], acc[j]);
-                        }
-                    }
-                }
-            }
-        }
-        T* xp = dx + ((((int64_t)n * g.di + id) * g.hi + ih) * g.wi + iw) * g.x_ld + cit;
-#pragma unroll
-        for (int j = 0; j < CIT; ++j)
-            if (cit + j < g.ci) stf(xp + j, acc[j]);
-    }
-}
-
-// The same wave-per-(n, id, ih, w-residue) decomposition with the valid taps ENUMERATED first (they are wave-uniform: at most NT of
-// them) and, per output-channel quad, their dy loads issued together before the FMAs — in the kernel above every tap's load sits in
-// a run-time loop behind `valid ? load : 0` and gets its own wait (6 serial round trips per voxel of the (1,6,1) stride-2 layer).
-// Slots past the last valid tap re-read slot 0 (cached) and are masked: no branch around a load.
-template <typename T, int CIT, int NT>
-__global__ void __launch_bounds__(64)
-conv_dgrad_strided_taps_kernel(Mri3dConvGeom g, const T* __restrict__ dy, const float* __restrict__ wp,
-                               const float* __restrict__ bias, T* __restrict__ dx, int CiP) {
-    int u = blockIdx.x;
-    const int rw = u % g.sw;
-    u /= g.sw;
-    const int ih = u % g.hi;
-    u /= g.hi;
-    const int id = u % g.di;
-    const int n = u / g.di;
-    const int cit = blockIdx.y * CIT;
-    const int kd0 = (id + g.pd) % g.sd, kh0 = (ih + g.ph) % g.sh, kw0 = (rw + g.pw) % g.sw;
-    // enumerate the taps that reach this row (uniform): dy row base, kw, packed-weight tap index
-    int64_t rowoff[NT];
-    int tkw[NT], ttap[NT];
-    int ntap = 0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) { rowoff[t] = 0; tkw[t] = kw0; ttap[t] = 0; }
-    for (int kd = kd0; kd < g.kd; kd += g.sd) {
-        const int nd = id + g.pd - kd;
-        if (nd < 0) break;
-        const int od = nd / g.sd;
-        if (od >= g.dout) continue;
-        for (int kh = kh0; kh < g.kh; kh += g.sh) {
-            const int nh = ih + g.ph - kh;
-            if (nh < 0) break;
-            const int oh = nh / g.sh;
-            if (oh >= g.ho) continue;
-            for (int kw = kw0; kw < g.kw; kw += g.sw) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    if (t == ntap) {
-                        rowoff[t] = ((((int64_t)n * g.dout + od) * g.ho + oh) * g.wo) * g.y_ld;
-                        tkw[t] = kw;
-                        ttap[t] = (kd * g.kh + kh) * g.kw + kw;
-                    }
-                ++ntap;   // host guarantees <= NT
-            }
-        }
-    }
-    // input voxel iw = rw + k * sw: its tap kw (kw = (rw + pw) mod sw, enumerated above) reaches output voxel k + (rw + pw - kw) / sw —
-    // an exact, wave-uniform quotient per tap, so the voxel loop has no integer division
-    int tq[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) tq[t] = (rw + g.pw - tkw[t]) / g.sw;
-    int k = (int)threadIdx.x;
-    for (int iw = rw + (int)threadIdx.x * g.sw; iw < g.wi; iw += 64 * g.sw, k += 64) {
-        float acc[CIT];
-#pragma unroll
-        for (int j = 0; j < CIT; ++j) acc[j] = (bias != nullptr && cit + j < g.ci) ? bias[cit + j] : 0.f;
-        int64_t off[NT];
-        unsigned okm = 0;
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int ow = k + tq[t];
-            const bool ok = t < ntap && (unsigned)ow < (unsigned)g.wo;
-            okm |= ok ? (1u << t) : 0u;
-            off[t] = rowoff[t] + (int64_t)(ok ? ow : 0) * g.y_ld;
-        }
-        for (int co = 0; co < g.co; co += 4) {
-            float4 gv[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) gv[t] = ldf4(dy + off[t] + co);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const bool ok = (okm >> t) & 1u;
-                const float g0 = ok ? gv[t].x : 0.f, g1 = ok ? gv[t].y : 0.f, g2 = ok ? gv[t].z : 0.f, g3 = ok ? gv[t].w : 0.f;
-                const float* w0 = wp + ((size_t)ttap[t] * g.co + co) * CiP + cit;
-#pragma unroll
-                for (int j = 0; j < CIT; ++j) {
-                    acc[j] = fmaf(g0, w0[j], acc[j]);
-                    acc[j] = fmaf(g1, w0[CiP + j], acc[j]);
-                    acc[j] = fmaf(g2, w0[2 * CiP + j], acc[j]);
-                    acc[j] = fmaf(g3, w0[3 * CiP + j], acc[j]);
-                }
-            }
-        }
-        T* xp = dx + ((((int64_t)n * g.di + id) * g.hi + ih) * g.wi + iw) * g.x_ld + cit;
-        if (CIT % 4 == 0 && cit + CIT <= g.ci && (g.x_ld & 3) == 0) {
-#pragma unroll
-            for (int j = 0; j < CIT; j += 4) stf4(xp + j, make_float4(acc[j], acc[j + 1], acc[j + 2], acc[j + 3]));
-        } else {
-#pragma unroll
-            for (int j = 0; j < CIT; ++j)
-                if (cit + j < g.ci) stf(xp + j, acc[j]);
-        }
-    }
 }
 
 template <int TL>
@@ -1810,7 +1811,7 @@ static void launch_dgrad(const Mri3dConvGeom& g, const GenericPlan& p, const voi
             return;
         }
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (p.cv)
+            if (p.vec)
                 hipLaunchKernelGGL((conv_dgrad_strided_kernel<T, TL, true>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
             else
                 hipLaunchKernelGGL((conv_dgrad_strided_kernel<T, TL, false>), sgrid, dim3(64), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
@@ -1818,7 +1819,7 @@ static void launch_dgrad(const Mri3dConvGeom& g, const GenericPlan& p, const voi
         return;
     }
     MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        if (p.cv)
+        if (p.vec)
             hipLaunchKernelGGL((conv_dgrad_generic_kernel<T, TL, true>), grid, dim3(256), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
         else
             hipLaunchKernelGGL((conv_dgrad_generic_kernel<T, TL, false>), grid, dim3(256), 0, s, g, (const T*)dy, wp, bias, (T*)dx, CiP);
@@ -1834,25 +1835,15 @@ int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, c
         return check_launch("conv3d_dgrad(1->1 stencil)");
     }
     if (p.kernel == GenKernel::c1taps) {
-        const int64_t items = (int64_t)g.n * g.di * g.hi * (g.wi / 4);
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256), 8192));
-        if (p.nt == 3)
-            hipLaunchKernelGGL(conv_c1_taps_kernel<3>, dim3(grid), dim3(256), 0, s, g, (const float*)dy, w, bias, (float*)dx, -1, g.dout,
-                           g.ho, g.wo, g.di, g.hi, g.wi);
-        else
-            hipLaunchKernelGGL(conv_c1_taps_kernel<kSmTaps>, dim3(grid), dim3(256), 0, s, g, (const float*)dy, w, bias, (float*)dx, -1, g.dout,
-                           g.ho, g.wo, g.di, g.hi, g.wi);
+        launch_c1_taps(g, p.nt, (const float*)dy, w, bias, (float*)dx, -1, s);
         return check_launch("conv3d_dgrad(1->1 taps)");
     }
     const int taps = g.kd * g.kh * g.kw;
     const int TL = p.tl, CiP = p.cp;
-    size_t need = p.ws_bytes;
-    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_dgrad: workspace %zu < %zu", ws_bytes,
-                  need);
+    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, MRI3D_EWORKSPACE, "conv3d_dgrad: workspace %zu < %zu", ws_bytes, p.ws_bytes);
     float* wp = static_cast<float*>(ws);
     int total = taps * g.co * CiP;
-    hipLaunchKernelGGL(repack_w_dgrad_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co,
-                       g.ci, taps, CiP);
+    hipLaunchKernelGGL(repack_w_kernel, dim3(std::min(cdiv(total, 256), 1024)), dim3(256), 0, s, w, wp, g.co, g.ci, taps, CiP, 1);
     switch (TL) {
         case 16: launch_dgrad<16>(g, p, dy, wp, bias, dx, s); break;
         case 8: launch_dgrad<8>(g, p, dy, wp, bias, dx, s); break;
@@ -1865,68 +1856,51 @@ int conv_generic_dgrad(const Mri3dConvGeom& g, const void* dy, const float* w, c
 int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                        size_t ws_bytes, hipStream_t s) {
     const GenericPlan p = generic_wgrad_plan(g, ptr_align(x), ptr_align(dy));
-    if (p.kernel == GenKernel::c1c1) {
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        const int tilesD = cdiv(g.dout, C1D), tilesH = cdiv(g.ho, C1H), tilesW = cdiv(g.wo, C1WQ * 4);
-        const int ntiles = g.n * tilesD * tilesH * tilesW;
-        const int nb = std::min(ntiles, kC1C1Blocks);
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + (size_t)kC1C1Blocks * 27 : nullptr;
+    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, p.ws_bytes);
+    float* part = static_cast<float*>(ws);
+    float* bias_part = dbias ? part + p.part_floats : nullptr;
+    const int taps = g.kd * g.kh * g.kw;
+    const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
+    int nb = p.slots;   // workgroups (x) = partials written; c1c1, c1taps and co1 use fewer on small volumes
+    const char* what = "conv3d_wgrad(generic)";
+    switch (p.kernel) {
+    case GenKernel::c1c1: {
+        const C1Tiles t = c1_tiles(g.n, g.dout, g.ho, g.wo, 4);
+        nb = std::min((int)t.ntiles, kC1C1Blocks), what = "conv3d_wgrad(1->1 stencil)";
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
             hipLaunchKernelGGL(conv_c1c1_wgrad_kernel<T>, dim3(nb), dim3(256), 0, s, g, (const T*)x, (const T*)dy, part, bias_part,
-                               tilesD, tilesH, tilesW, ntiles);
+                               t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles);
         });
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(27 + 1, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb, 27, 1, 1, 1, 1);
-        return check_launch("conv3d_wgrad(1->1 stencil)");
+        break;
     }
-    if (p.kernel == GenKernel::c1taps) {
-        const int taps = g.kd * g.kh * g.kw;
+    case GenKernel::c1taps: {
         const int64_t items = (int64_t)g.n * g.dout * g.ho * (g.wo / 4);
-        const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256 * 4), kC1TBlocks));
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + (size_t)kC1TBlocks * kSmTaps : nullptr;
+        nb = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(items, 256 * 4), kC1TBlocks)), what = "conv3d_wgrad(1->1 taps)";
         if (p.nt == 3)
             hipLaunchKernelGGL(conv_c1_taps_wgrad_kernel<3>, dim3(nb), dim3(256), 0, s, g, (const float*)x, (const float*)dy, part, bias_part);
         else
             hipLaunchKernelGGL(conv_c1_taps_wgrad_kernel<kSmTaps>, dim3(nb), dim3(256), 0, s, g, (const float*)x, (const float*)dy, part, bias_part);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(taps + 1, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb, taps, 1, 1, 1, 1);
-        return check_launch("conv3d_wgrad(1->1 taps)");
+        break;
     }
-    if (p.kernel == GenKernel::cin1) {
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        const int vpt = g.co <= 8 ? 4 : 2;
-        const int tilesD = cdiv(g.dout, C1D), tilesH = cdiv(g.ho, C1H), tilesW = cdiv(g.wo, C1WQ * vpt);
-        const int ntiles = g.n * tilesD * tilesH * tilesW;
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + (size_t)kCin1Shares * 27 * g.co : nullptr;
+    case GenKernel::cin1: {
+        const C1Tiles t = cin1_tiles(g);
+        what = "conv3d_wgrad(cin1)";
         // every (share, kd) workgroup writes its slots, also when its share of the tiles is empty (zeros)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (p.cv == 8)
-                hipLaunchKernelGGL((conv_cin1_wgrad_kernel<T, 8>), dim3(kCin1Shares), dim3(768), 0, s, g, (const T*)x,
-                                   (const T*)dy, part, bias_part, tilesD, tilesH, tilesW, ntiles, kCin1Shares);
+            if (p.co_inst == 8)
+                hipLaunchKernelGGL((conv_cin1_wgrad_kernel<T, 8>), dim3(nb), dim3(768), 0, s, g, (const T*)x,
+                                   (const T*)dy, part, bias_part, t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles, nb);
             else
-                hipLaunchKernelGGL((conv_cin1_wgrad_kernel<T, 16>), dim3(kCin1Shares), dim3(768), 0, s, g, (const T*)x,
-                                   (const T*)dy, part, bias_part, tilesD, tilesH, tilesW, ntiles, kCin1Shares);
+                hipLaunchKernelGGL((conv_cin1_wgrad_kernel<T, 16>), dim3(nb), dim3(768), 0, s, g, (const T*)x,
+                                   (const T*)dy, part, bias_part, t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles, nb);
         });
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(27 * g.co + g.co, 8)), dim3(256), 0, s, part, bias_part, dw, dbias,
-                           kCin1Shares, 27, 1, g.co, 1, g.co);
-        return check_launch("conv3d_wgrad(cin1)");
+        break;
     }
-    if (p.kernel == GenKernel::co1) {
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        const int taps = g.kd * g.kh * g.kw;
-        const int64_t nvox = (int64_t)g.n * g.dout * g.ho * g.wo;
-        const int nb = (int)std::min<int64_t>(cdiv64(nvox, 256), kCo1Blocks);
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + (size_t)kCo1Blocks * kSmTaps * 16 : nullptr;
+    case GenKernel::co1: {
+        nb = (int)std::min<int64_t>(cdiv64(nvox, 256), kCo1Blocks), what = "conv3d_wgrad(co1)";
 #define MRI3D_CO1(CIv) hipLaunchKernelGGL((conv_wgrad_co1_kernel<T, CIv>), dim3(nb), dim3(256), 0, s, g, (const T*)x, (const T*)dy, part, bias_part)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            switch (p.cv) {
+            switch (p.ci_inst) {
                 case 1: MRI3D_CO1(1); break;
                 case 4: MRI3D_CO1(4); break;
                 case 8: MRI3D_CO1(8); break;
@@ -1934,69 +1908,50 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
             }
         });
 #undef MRI3D_CO1
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(taps * g.ci + 1, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb, taps,
-                           g.ci, 1, g.ci, 1);
-        return check_launch("conv3d_wgrad(co1)");
+        break;
     }
-    if (p.kernel == GenKernel::quads) {
-        WgradQuadsPlan q = wgrad_quads_plan(g);
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + q.part_floats : nullptr;
-        const int taps = g.kd * g.kh * g.kw;
+    case GenKernel::quads: {
+        what = "conv3d_wgrad(quads)";
 #define MRI3D_WGQ(NTv, CIVv)                                                                                           \
-    hipLaunchKernelGGL((conv_wgrad_quads_kernel<T, NTv, CIVv>), dim3(q.gx), dim3(256), 0, s, g, (const T*)x, (const T*)dy,  \
-                       part, bias_part, q.QI, q.QO, q.hch, q.CiP, q.CoP)
+    hipLaunchKernelGGL((conv_wgrad_quads_kernel<T, NTv, CIVv>), dim3(nb), dim3(256), 0, s, g, (const T*)x, (const T*)dy,  \
+                       part, bias_part, p.quads.QI, p.quads.QO, p.quads.hch, p.CiP, p.CoP)
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            if (p.cv == 1) MRI3D_WGQ(8, 1);
+            if (p.civ == 1) MRI3D_WGQ(8, 1);
             else if (p.nt == 4) MRI3D_WGQ(4, 4);
             else if (p.nt == 6) MRI3D_WGQ(6, 4);
             else MRI3D_WGQ(8, 4);
         });
 #undef MRI3D_WGQ
-        const int total = g.co * g.ci * taps;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total + g.co, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, q.gx, taps,
-                           g.ci, g.co, q.CiP, q.CoP);
-        return check_launch("conv3d_wgrad(quads)");
+        break;
     }
-    if (p.kernel == GenKernel::small) {
-        WgradSmallPlan q = wgrad_small_plan(g);
-        const size_t need = p.ws_bytes;
-        MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        float* part = static_cast<float*>(ws);
-        float* bias_part = dbias ? part + q.part_floats : nullptr;
-        const int taps = g.kd * g.kh * g.kw;
+    case GenKernel::small: {
+        what = "conv3d_wgrad(small)";
         // partial slots of padded channels are never written by the kernel and never read by the reduce
         MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-            hipLaunchKernelGGL(conv_wgrad_small_kernel<T>, dim3(q.gx, q.gy, q.gz), dim3(256), 0, s, g, (const T*)x,
-                               (const T*)dy, part, bias_part, q.CiL, q.CiP, q.CoP);
+            hipLaunchKernelGGL(conv_wgrad_small_kernel<T>, dim3(nb, p.small.gy, p.small.gz), dim3(256), 0, s, g, (const T*)x,
+                               (const T*)dy, part, bias_part, p.small.CiL, p.CiP, p.CoP);
         });
-        const int total = g.co * g.ci * taps;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total + g.co, 8)), dim3(256), 0, s, part, bias_part, dw,
-                           dbias, q.gx, taps, g.ci, g.co, q.CiP, q.CoP);
-        return check_launch("conv3d_wgrad(small)");
+        break;
     }
-    const WgradPlan lp = wgrad_plan(g);
-    size_t need = p.ws_bytes;
-    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= need, MRI3D_EWORKSPACE, "conv3d_wgrad: workspace %zu < %zu", ws_bytes,
-                  need);
-    MRI3D_REQUIRE(lp.smem <= 160 * 1024, MRI3D_ENOTSUP, "conv3d_wgrad: Ci=%d Co=%d needs %zu B of LDS", g.ci, g.co,
-                  lp.smem);
-    float* part = static_cast<float*>(ws);
-    float* bias_part = dbias ? part + lp.part_floats : nullptr;
-    MRI3D_DISPATCH_DTYPE(g.dtype, T, {
-        // the kernel's dynamic-LDS limit is raised once (to the CU's 160 KB), not per launch
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_generic_kernel<T>),
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)attr_;
-        hipLaunchKernelGGL(conv_wgrad_generic_kernel<T>, dim3(lp.gx, lp.taps, lp.gz), dim3(256), lp.smem, s, g, (const T*)x,
-                           (const T*)dy, part, bias_part, lp.Ci4, lp.Co4, lp.nitems, lp.vsplit);
-    });
-    int total = g.co * g.ci * lp.taps;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(total + g.co, 8)), dim3(256), 0, s, part, bias_part, dw,
-                       dbias, lp.gx, lp.taps, g.ci, g.co, lp.Ci4 * 4, lp.Co4 * 4);
-    return check_launch("conv3d_wgrad(generic)");
+    case GenKernel::lds: {
+        const auto& q = p.lds;
+        MRI3D_REQUIRE(q.smem <= 160 * 1024, MRI3D_ENOTSUP, "conv3d_wgrad: Ci=%d Co=%d needs %zu B of LDS", g.ci, g.co, q.smem);
+        MRI3D_DISPATCH_DTYPE(g.dtype, T, {
+            // the kernel's dynamic-LDS limit is raised once (to the CU's 160 KB), not per launch
+            static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_generic_kernel<T>),
+                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)attr_;
+            hipLaunchKernelGGL(conv_wgrad_generic_kernel<T>, dim3(nb, taps, q.gz), dim3(256), q.smem, s, g, (const T*)x,
+                               (const T*)dy, part, bias_part, q.Ci4, q.Co4, q.nitems, q.vsplit);
+        });
+        break;
+    }
+    case GenKernel::taps: case GenKernel::gather: case GenKernel::strided_taps: case GenKernel::strided:   // forward / data gradient only
+        MRI3D_REQUIRE(false, MRI3D_EINVAL, "conv3d_wgrad: no weight-gradient kernel in the plan");
+    }
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(g.co * g.ci * taps + g.co, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb,
+                       taps, g.ci, g.co, p.CiP, p.CoP);
+    return check_launch(what);
 }
 
 }  // namespace mri3d

@@ -626,7 +626,9 @@ GENERIC_PITCHED = Table("GENERIC_PITCHED", "geom", GENERIC_PITCHED_CASES, {"f32"
 TRANSPOSE = Table("TRANSPOSE", "transpose", TRANSPOSE_CASES, {"f32": {}, "bf16": {}}, ids=_transpose_id)
 
 # one exact-workspace case per weight-gradient family of conv_generic.hip / conv_pointwise.hip: every family lays its partials out
-# differently and conv_generic_workspace_bytes sizes them from the plan the launch reads.  The launched-kernel pattern doubles as the
+# differently.  In conv_generic.hip the plan (generic_wgrad_plan) owns that layout — part_floats, bias_floats, channel pitches — and
+# both the launch's carve and conv_generic_workspace_bytes read it; these cases check the plan against what the kernels really
+# write, with guard bands around a workspace of exactly the queried size.  The launched-kernel pattern doubles as the
 # check that a route name means the kernel it says.  quads_dy_misaligned: an 8 -> 8 (1,3,1) layer is the channel-quad kernel's by
 # geometry (gradient pitch 12), but its gradient starts 8 bytes into the voxel, so the launch falls through to `small`
 _1, _0 = (1, 1, 1), (0, 0, 0)
