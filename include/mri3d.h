@@ -266,6 +266,31 @@ int mri3d_maxpool3d_bwd(const Mri3dPoolGeom* g, const void* dy, const uint8_t* i
 int mri3d_maxpool3d_bwd_add(const Mri3dPoolGeom* g, const void* dy, const uint8_t* idx, const void* addend,
                             int32_t addend_ld, void* dx, mri3d_stream_t stream);
 
+/* norm_act followed by MaxPool3d(2) with the activation kept as the skip tensor, as ONE operator — the tail of an encoder level
+ * of `unet.UNet` (conv -> BatchNorm3d -> PReLU -> skip, MaxPool3d(2)).  _fwd reads x once and writes skip = act(norm(x)), pooled =
+ * maxpool(skip) and the pool's index bytes; _bwd takes the two gradients that meet at the activation, da = dskip + scatter(dpool),
+ * without storing da.  Results are those of mri3d_norm_act_fwd + mri3d_maxpool3d_fwd and of mri3d_maxpool3d_bwd_add +
+ * mri3d_norm_act_bwd, bit for bit in fp32 (same expressions, same per-block partial sums); in bf16 the activation and da are
+ * rounded to bf16 where the two operators would have stored them.
+ * g describes the norm_act part: batch (training != 0), running or no statistics (mean = invstd = NULL); g->x_ld = voxel pitch of
+ * x / dx, g->y_ld = voxel pitch of skip / dskip.  pg describes the pool: pg->x_ld = g->y_ld (its input is skip), pg->y_ld = voxel
+ * pitch of pooled / dpool; n, c, dtype and di*hi*wi = g->vox agree with g.
+ * mri3d_norm_act_pool_supported(g, pg) = 1 (host only): kernel 2, stride 2, padding 0 on even extents; batch-type statistics (not
+ * instance / group); c % 4 == 0 with c/4 a power of two <= 16; every pitch a multiple of 4; n * vox and the elements of one
+ * sample below 2^31; x, dx, skip, dskip, pooled, dpool and idx must be aligned to 4 elements.  Otherwise 0: keep the two
+ * operators.
+ * _bwd: dskip or dpool may be NULL (zeros); dx, dgamma, dbeta, dalpha may be NULL.  Workspace:
+ * mri3d_norm_act_pool_workspace_bytes (host only; 0 when not supported), 8-byte aligned. */
+int32_t mri3d_norm_act_pool_supported(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg);
+size_t mri3d_norm_act_pool_workspace_bytes(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg);
+int mri3d_norm_act_pool_fwd(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg, const void* x, const float* mean,
+                            const float* invstd, const float* gamma, const float* beta, const float* alpha, void* skip,
+                            void* pooled, uint8_t* idx, mri3d_stream_t stream);
+int mri3d_norm_act_pool_bwd(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg, int training, const void* x, const void* dskip,
+                            const void* dpool, const uint8_t* idx, const float* mean, const float* invstd, const float* gamma,
+                            const float* beta, const float* alpha, void* dx, float* dgamma, float* dbeta, float* dalpha,
+                            void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Upsample — nn.Upsample(scale_factor=2, mode='trilinear', align_corners=False) (unet.UNet decoder),
  * mode='nearest' (modified_3dunet.py:13, AE_model.py:70-73), F.interpolate(size=...) (AE_model.py:119).

@@ -90,7 +90,12 @@ SIGNATURES = {
     "mri3d_maxpool3d_fwd": (c_int32, [POINTER(PoolGeom), _P, _P, _P, _P]),
     "mri3d_maxpool3d_bwd": (c_int32, [POINTER(PoolGeom), _P, _P, _P, _P]),
     "mri3d_maxpool3d_bwd_add": (c_int32, [POINTER(PoolGeom), _P, _P, _P, c_int32, _P, _P]),
-    "mri3d_upsample3d_workspace_bytes": (c_size_t, [POINTER(UpGeom)]),
+    "mri3d_norm_act_pool_supported": (c_int32, [POINTER(NormGeom), POINTER(PoolGeom)]),
+    "mri3d_norm_act_pool_workspace_bytes": (c_size_t, [POINTER(NormGeom), POINTER(PoolGeom)]),
+    "mri3d_norm_act_pool_fwd": (c_int32, [POINTER(NormGeom), POINTER(PoolGeom), _P, _FP, _FP, _FP, _FP, _FP, _P, _P, _P, _P]),
+    "mri3d_norm_act_pool_bwd": (c_int32, [POINTER(NormGeom), POINTER(PoolGeom), c_int32, _P, _P, _P, _P, _FP, _FP, _FP, _FP,
+                                          _FP, _P, _FP, _FP, _FP, _P, c_size_t, _P]),
+    "mri3d_upsample3d_workspace_bytes":(c_size_t, [POINTER(UpGeom)]),
     "mri3d_upsample3d_fwd": (c_int32, [POINTER(UpGeom), _P, _P, _P]),
     "mri3d_upsample3d_bwd": (c_int32, [POINTER(UpGeom), _P, _P, _P, c_size_t, _P]),
     "mri3d_softmax_dice_workspace_bytes": (c_size_t, [POINTER(DiceGeom)]),

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <stdlib.h>
+#include <algorithm>
 #include "../../include/mri3d.h"
 
 namespace mri3d {
@@ -110,6 +111,23 @@ inline bool align16(int align) { return align >= 16; }
             __VA_ARGS__                      \
         }                                    \
     } while (0)
+
+// ---------------------------------------------------------------- pooling plans shared by resample.hip and norm.hip
+// slab kernels: a block walks (n, depth, h-chunk) slabs of about 2048 (w, channel-vector) elements times hch rows
+inline void slab_plan(int nd, int h, int w, int cv, int& hch, int& grid) {
+    int64_t per_row = (int64_t)w * cv;
+    hch = (int)std::max<int64_t>(1, std::min<int64_t>(h, 2048 / std::max<int64_t>(per_row, 1)));
+    int64_t slabs = (int64_t)nd * ((h + hch - 1) / hch);
+    grid = (int)std::min<int64_t>(slabs, 8192);
+}
+
+// MaxPool3d(2) on even extents, one sample below 2^31 elements: what the line-contiguous pool kernels serve
+inline bool pool2_ok(const Mri3dPoolGeom& g, int vec) {
+    const int cv = g.c / vec;
+    return g.kd == 2 && g.kh == 2 && g.kw == 2 && g.sd == 2 && g.sh == 2 && g.sw == 2 && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
+           g.di == 2 * g.dout && g.hi == 2 * g.ho && g.wi == 2 * g.wo && cv >= 1 && cv <= 32 && (cv & (cv - 1)) == 0 &&
+           (int64_t)g.di * g.hi * g.wi * g.x_ld < ((int64_t)1 << 31);
+}
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float wave_sum(float v) {

@@ -599,9 +599,10 @@ __device__ __forceinline__ float through_storage(float v) {
 }
 
 // per-lane constants of the forward: y = act(x * sc + sh), as norm_act_fwd_kernel forms them
-__device__ __forceinline__ void nap_fwd_consts(const NapArgs& p, int c0, float (&sc)[4], float (&sh)[4], float (&al)[4]) {
+template <int VEC>
+__device__ __forceinline__ void nap_fwd_consts(const NapArgs& p, int c0, float (&sc)[VEC], float (&sh)[VEC], float (&al)[VEC]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < VEC; ++j) {
         int c = c0 + j;
         float gm = p.gamma ? p.gamma[c] : 1.f;
         float bt = p.beta ? p.beta[c] : 0.f;
@@ -674,7 +675,9 @@ struct PwHeadGrad {
         const float* w;
         int Co, ld;
     };
-    static constexpr int kCo = CO;         // gradient values loaded per voxel
+    struct Val {                           // what a lane loads per voxel row
+        float g[CO];
+    };
     static constexpr int kSide = 5 * CO;   // doubles per lane: dw[4][CO], dbias[CO]
     const T* dout;
     int Co, ld;
@@ -692,12 +695,13 @@ struct PwHeadGrad {
             for (int j = 0; j < 4; ++j) dw[j][co] = 0.0;
         }
     }
-    __device__ __forceinline__ void load(int64_t v, float (&gv)[CO]) const {
+    __device__ __forceinline__ void load(int64_t v, Val& val) const {
 #pragma unroll
-        for (int co = 0; co < CO; ++co) gv[co] = co < Co ? ldf(dout + v * ld + co) : 0.f;
+        for (int co = 0; co < CO; ++co) val.g[co] = co < Co ? ldf(dout + v * ld + co) : 0.f;
     }
     // pw_dgrad_kernel's order; the two-operator path stores da in the activation's storage type
-    __device__ __forceinline__ void grad(const float (&gv)[CO], float (&da)[4]) const {
+    __device__ __forceinline__ void grad(const Val& val, float (&da)[4]) const {
+        const float (&gv)[CO] = val.g;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
@@ -710,7 +714,8 @@ struct PwHeadGrad {
         da[2] = through_storage<T>(acc.z), da[3] = through_storage<T>(acc.w);
     }
     // a = the forward's activation of this lane's quad (pw_wgrad_kernel: float product, double sum)
-    __device__ __forceinline__ void side(const float (&a)[4], const float (&gv)[CO], bool lead) {
+    __device__ __forceinline__ void side(const float (&a)[4], const Val& val, bool lead) {
+        const float (&gv)[CO] = val.g;
 #pragma unroll
         for (int co = 0; co < CO; ++co) {
 #pragma unroll
@@ -746,12 +751,12 @@ struct PwHeadGrad {
 // SUMS: the per-block partials of (sum du, sum du*xhat, sum da*u*[u<=0]) as norm_act_bwd_reduce_kernel forms them, plus the
 // source's side sums.  DX: dx = k0*du - k1 - xhat*k2 as norm_act_bwd_apply_kernel writes it.  Training statistics take two
 // launches (<true, false>, then <false, true> once the sums are combined); with frozen statistics k1 = k2 = 0 and <true, true>
-// does both in one pass.
+// does both in one pass.  The body is shared by one entry point per gradient source.
 template <typename T, class SRC, bool SUMS, bool DX>
-__global__ void __launch_bounds__(256)
-norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SRC::Args sa, NapArgs p,
-                        const float* __restrict__ sums, int training, double* __restrict__ part, double* __restrict__ spart,
-                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dalpha) {
+__device__ __forceinline__ void
+norm_act_src_bwd_body(const T* __restrict__ x, T* __restrict__ dx, const typename SRC::Args& sa, const NapArgs& p,
+                      const float* __restrict__ sums, int training, double* __restrict__ part, double* __restrict__ spart,
+                      float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dalpha) {
     constexpr int kRed = SUMS ? (SRC::kSide > 12 ? SRC::kSide : 12) : 1;
     __shared__ double red[256 * kRed];
     // the parameter gradients ride on the first workgroup of the dx pass that follows the combined sums (uniform branch)
@@ -782,13 +787,13 @@ norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SR
         }
     }
     float sc[4], sh[4], af[4];   // the forward's constants: the side sums want the activation exactly as the forward formed it
-    if constexpr (SUMS) nap_fwd_consts(p, c0, sc, sh, af);
+    if constexpr (SUMS && SRC::kSide > 0) nap_fwd_consts(p, c0, sc, sh, af);
     SRC src;
     src.init(sa, p.C, q);
     double s0[4], s1[4], s2[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) { s0[j] = 0.0; s1[j] = 0.0; s2[j] = 0.0; }
-    auto row = [&](const float (&xv)[4], const float (&gv)[SRC::kCo], int64_t v) {
+    auto row = [&](const float (&xv)[4], const typename SRC::Val& gv, int64_t v) {
         float da[4], ov[4];
         src.grad(gv, da);
 #pragma unroll
@@ -804,7 +809,7 @@ norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SR
             }
             if constexpr (DX) ov[j] = fmaf(k0[j], du, -k1[j]) - xh * k2[j];
         }
-        if constexpr (SUMS) {
+        if constexpr (SUMS && SRC::kSide > 0) {
             float a[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = through_storage<T>(apply_act(fmaf(xv[j], sc[j], sh[j]), p.act, af[j]));
@@ -816,7 +821,8 @@ norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SR
     const int64_t step = (int64_t)gridDim.x * VT;
     int64_t v = (int64_t)blockIdx.x * VT + vt;
     for (; v + step < p.nvox; v += 2 * step) {
-        float xa[4], xb[4], ga[SRC::kCo], gb[SRC::kCo];
+        float xa[4], xb[4];
+        typename SRC::Val ga, gb;
         Ld<4>::load(x + v * p.x_ld + c0, xa);
         src.load(v, ga);
         Ld<4>::load(x + (v + step) * p.x_ld + c0, xb);
@@ -825,7 +831,8 @@ norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SR
         row(xb, gb, v + step);
     }
     for (; v < p.nvox; v += step) {
-        float xv[4], gv[SRC::kCo];
+        float xv[4];
+        typename SRC::Val gv;
         Ld<4>::load(x + v * p.x_ld + c0, xv);
         src.load(v, gv);
         row(xv, gv, v);
@@ -853,9 +860,19 @@ norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SR
                 o[2] = d;
             }
         }
-        __syncthreads();
-        src.flush(red, spart, p.C, QC, VT);
+        if constexpr (SRC::kSide > 0) {
+            __syncthreads();
+            src.flush(red, spart, p.C, QC, VT);
+        }
     }
+}
+
+template <typename T, class SRC, bool SUMS, bool DX>
+__global__ void __launch_bounds__(256)
+norm_act_src_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename SRC::Args sa, NapArgs p,
+                        const float* __restrict__ sums, int training, double* __restrict__ part, double* __restrict__ spart,
+                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dalpha) {
+    norm_act_src_bwd_body<T, SRC, SUMS, DX>(x, dx, sa, p, sums, training, part, spart, dgamma, dbeta, dalpha);
 }
 
 // dw[co][c], dbias[co] = fixed-order double sums of the per-block side partials: 256 threads = 8 elements x 32 partial lanes
@@ -880,6 +897,154 @@ norm_act_pw_wsum_kernel(const double* __restrict__ spart, float* __restrict__ dw
             dbias[i - nw] = (float)t;
         }
     }
+}
+
+// ------------------------------------------------------------------ norm + activation + MaxPool3d(2), fused
+// An encoder level of unet.UNet ends conv -> BatchNorm -> PReLU -> (skip, MaxPool3d(2)).  Forward: one pass reads the conv output
+// and writes the activation (the skip tensor), the pooled tensor and the arg-max bytes — the pool does not read the activation
+// back.  Lane mapping and selection rule are maxpool2_fwd_kernel's (resample.hip): a lane owns one input column x VEC channels,
+// takes its four (kd, kh) taps and meets its kw partner, CV lanes away, in one shuffle; the first maximum in raster order wins,
+// NaN propagates with the later NaN's index.  The activation is formed as norm_act_fwd_kernel forms it and, in bf16, rounded
+// through storage before it is compared: skip, pooled and index bytes are those of the two operators.
+template <typename T, int VEC>
+__global__ void __launch_bounds__(256)
+norm_act_pool_fwd_kernel(Mri3dPoolGeom g, const T* __restrict__ x, T* __restrict__ skip, T* __restrict__ y,
+                         uint8_t* __restrict__ idx, int hch, NapArgs p) {
+    const unsigned CV = g.c / VEC;            // lanes per voxel: a power of two <= 16 (host)
+    const int hchunks = (g.ho + hch - 1) / hch;
+    const int slabs = g.n * g.dout * hchunks;
+    // element strides of x (pitch p.x_ld) and of skip (pitch g.x_ld): one sample of either is below 2^31 elements (host)
+    const unsigned xrow = (unsigned)g.wi * p.x_ld, xplane = (unsigned)g.hi * xrow;
+    const unsigned srow = (unsigned)g.wi * g.x_ld, splane = (unsigned)g.hi * srow;
+    const unsigned cv = threadIdx.x % CV;     // 256 % CV == 0: a lane keeps its channels
+    float sc[VEC], sh[VEC], al[VEC];
+    nap_fwd_consts(p, (int)cv * VEC, sc, sh, al);
+    for (int slab = blockIdx.x; slab < slabs; slab += gridDim.x) {
+        const int hc = slab % hchunks, nd = slab / hchunks;
+        const int n = nd / g.dout, od = nd - n * g.dout;
+        const int h0 = hc * hch, hn = min(hch, g.ho - h0);
+        const unsigned inner = (unsigned)hn * g.wi * CV;   // lanes walk (oh, input column iw, channel vector)
+        const int64_t sample = ((int64_t)n * g.di + 2 * od) * g.hi * g.wi;
+        const T* xs = x + sample * p.x_ld;
+        T* ss = skip + sample * g.x_ld;
+        const int64_t obase = ((int64_t)nd * g.ho + h0) * g.wo;
+        for (unsigned e0 = 0; e0 < inner; e0 += blockDim.x) {   // whole block iterates together: the shuffle needs both kw lanes
+            const unsigned e = e0 + threadIdx.x;
+            const bool live = e < inner;
+            const unsigned col = (live ? e : 0) / CV;
+            const unsigned iw = col % g.wi, ohl = col / g.wi;
+            const unsigned kw = iw & 1, ow = iw >> 1, oh = h0 + ohl;
+            const T* xp = xs + (2 * oh) * xrow + iw * (unsigned)p.x_ld + cv * VEC;
+            T* sp = ss + (2 * oh) * srow + iw * (unsigned)g.x_ld + cv * VEC;
+            float v[4][VEC];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) Ld<VEC>::load(xp + (t >> 1) * xplane + (t & 1) * xrow, v[t]);
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+#pragma unroll
+                for (int j = 0; j < VEC; ++j) v[t][j] = through_storage<T>(apply_act(fmaf(v[t][j], sc[j], sh[j]), p.act, al[j]));
+                if (live) Ld<VEC>::store(sp + (t >> 1) * splane + (t & 1) * srow, v[t]);
+            }
+            float best[VEC];
+            int bi[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) { best[j] = v[0][j]; bi[j] = (int)kw; }
+#pragma unroll
+            for (int t = 1; t < 4; ++t)
+#pragma unroll
+                for (int j = 0; j < VEC; ++j)
+                    if (v[t][j] > best[j] || v[t][j] != v[t][j]) { best[j] = v[t][j]; bi[j] = 2 * t + (int)kw; }
+            // merge with the other kw lane (CV lanes away; wi is even and CV | 64, so both are in the same wave and both live)
+            float o[VEC];
+            int oi[VEC];
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) {
+                const float pb = __shfl_xor(best[j], (int)CV, 64);
+                const int pi = __shfl_xor(bi[j], (int)CV, 64);
+                const bool mine_nan = best[j] != best[j], his_nan = pb != pb;
+                bool take_his;
+                if (mine_nan || his_nan) take_his = his_nan && (!mine_nan || pi > bi[j]);     // the LAST NaN in raster order
+                else take_his = pb > best[j] || (pb == best[j] && pi < bi[j]);                  // the FIRST maximum
+                o[j] = take_his ? pb : best[j];
+                oi[j] = take_his ? pi : bi[j];
+            }
+            if (live && kw == 0) {
+                const int64_t ov = obase + (int64_t)ohl * g.wo + ow;
+                Ld<VEC>::store(y + ov * g.y_ld + cv * VEC, o);
+                uint8_t* ip = idx + ov * g.c + cv * VEC;
+                if constexpr (VEC == 8) {
+                    uint2 pk;
+                    pk.x = (uint32_t)oi[0] | ((uint32_t)oi[1] << 8) | ((uint32_t)oi[2] << 16) | ((uint32_t)oi[3] << 24);
+                    pk.y = (uint32_t)oi[4] | ((uint32_t)oi[5] << 8) | ((uint32_t)oi[6] << 16) | ((uint32_t)oi[7] << 24);
+                    *reinterpret_cast<uint2*>(ip) = pk;
+                } else {
+                    *reinterpret_cast<uint32_t*>(ip) = (uint32_t)oi[0] | ((uint32_t)oi[1] << 8) | ((uint32_t)oi[2] << 16) | ((uint32_t)oi[3] << 24);
+                }
+            }
+        }
+    }
+}
+
+// Gradient source of the encoder tail: da = dskip + scatter(dpool), the sum maxpool_bwd_kernel forms with the skip gradient as
+// its addend (addend first, one add where the window's arg-max is this voxel; in bf16 rounded through storage as the stored da
+// was).  Either gradient may be absent (NULL = zeros).  No side sums.  A lane finds its window from the flat voxel index with
+// 32-bit arithmetic: v = (n*di + d)*hi*wi + h*wi + w below 2^31 (host), extents even, so the pooled row is (nd/2)*ho + h/2.
+template <typename T>
+struct PoolSkipGrad {
+    struct Args {
+        const T *dskip, *dpool;
+        const uint8_t* idx;
+        int s_ld, p_ld;          // voxel pitch of dskip and of dpool
+        unsigned wi, hi;         // input extents (wo = wi/2, ho = hi/2)
+    };
+    struct Val {
+        float ds[4], dp[4];
+        uint32_t ib, tap;        // the window's four index bytes; this voxel's tap
+    };
+    static constexpr int kSide = 0;
+    Args a;
+    int C, c0;
+
+    __device__ __forceinline__ void init(const Args& args, int C_, int q) { a = args, C = C_, c0 = 4 * q; }
+    __device__ __forceinline__ void load(int64_t v, Val& val) const {
+        if (a.dskip != nullptr) {
+            Ld<4>::load(a.dskip + v * a.s_ld + c0, val.ds);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) val.ds[j] = 0.f;
+        }
+        val.ib = 0, val.tap = 0xff;   // no tap is 255: without dpool nothing is added
+        if (a.dpool != nullptr) {
+            const unsigned u = (unsigned)v;
+            const unsigned r = u / a.wi, w = u - r * a.wi;   // r = (n*di + d)*hi + h
+            const unsigned nd = r / a.hi, h = r - nd * a.hi;
+            const int64_t pv = ((int64_t)(nd >> 1) * (a.hi >> 1) + (h >> 1)) * (a.wi >> 1) + (w >> 1);
+            Ld<4>::load(a.dpool + pv * a.p_ld + c0, val.dp);
+            val.ib = *reinterpret_cast<const uint32_t*>(a.idx + pv * C + c0);
+            val.tap = ((nd & 1) * 2 + (h & 1)) * 2 + (w & 1);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) val.dp[j] = 0.f;
+        }
+    }
+    __device__ __forceinline__ void grad(const Val& val, float (&da)[4]) const {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float acc = val.ds[j];
+            if (((val.ib >> (8 * j)) & 0xff) == val.tap) acc += val.dp[j];
+            da[j] = through_storage<T>(acc);
+        }
+    }
+    __device__ __forceinline__ void side(const float (&)[4], const Val&, bool) {}
+    __device__ __forceinline__ void flush(double*, double* __restrict__, int, int, int) const {}
+};
+
+template <typename T, bool SUMS, bool DX>
+__global__ void __launch_bounds__(256)
+norm_act_pool_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename PoolSkipGrad<T>::Args sa, NapArgs p,
+                         const float* __restrict__ sums, int training, double* __restrict__ part,
+                         float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dalpha) {
+    norm_act_src_bwd_body<T, PoolSkipGrad<T>, SUMS, DX>(x, dx, sa, p, sums, training, part, nullptr, dgamma, dbeta, dalpha);
 }
 
 struct NapPlan {
@@ -1191,4 +1356,115 @@ extern "C" int mri3d_norm_act_pw_bwd(const Mri3dNormGeom* g, int32_t co, int tra
                                  s);
     });
     return check_launch("norm_act_pw_bwd");
+}
+
+// ------------------------------------------------------------------ norm + activation + MaxPool3d(2): host side
+// g: the norm_act part (x_ld = pitch of x / dx, y_ld = pitch of skip / dskip); pg: the pool (x_ld = its input = skip, y_ld = pooled).
+static bool napool_supported(const Mri3dNormGeom& g, const Mri3dPoolGeom& pg) {
+    if (!nap_supported(g, 1) || g.y_ld < g.c || g.y_ld % 4 != 0) return false;   // co = 1: the head's width plays no part here
+    if (pg.dtype != g.dtype || pg.n != g.n || pg.c != g.c || pg.x_ld != g.y_ld || pg.y_ld < g.c || pg.y_ld % 4 != 0) return false;
+    if (pg.di <= 0 || pg.hi <= 0 || pg.wi <= 0 || (int64_t)pg.di * pg.hi * pg.wi != g.vox) return false;
+    if (!pool2_ok(pg, 4)) return false;
+    const int64_t ld = g.x_ld > g.y_ld ? g.x_ld : g.y_ld;
+    if (g.vox * ld >= ((int64_t)1 << 31)) return false;           // 32-bit element offsets inside one sample (forward)
+    if ((int64_t)g.n * g.vox >= ((int64_t)1 << 31)) return false;  // 32-bit decode of the flat voxel index (backward)
+    return true;
+}
+
+extern "C" int32_t mri3d_norm_act_pool_supported(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg) {
+    return (g != nullptr && pg != nullptr && napool_supported(*g, *pg)) ? 1 : 0;
+}
+
+extern "C" size_t mri3d_norm_act_pool_workspace_bytes(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg) {
+    if (g == nullptr || pg == nullptr || !napool_supported(*g, *pg)) return 0;
+    return nap_plan(*g, 0).bytes;
+}
+
+extern "C" int mri3d_norm_act_pool_fwd(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg, const void* x, const float* mean,
+                                       const float* invstd, const float* gamma, const float* beta, const float* alpha,
+                                       void* skip, void* pooled, uint8_t* idx, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(g != nullptr && pg != nullptr, MRI3D_EINVAL, "norm_act_pool_fwd: null geometry");
+    MRI3D_REQUIRE(napool_supported(*g, *pg), MRI3D_ENOTSUP,
+                  "norm_act_pool_fwd: c=%d x_ld=%d y_ld=%d instance=%d pool %dx%dx%d/%d -> %dx%dx%d not served", g->c, g->x_ld,
+                  g->y_ld, g->instance, pg->di, pg->hi, pg->wi, pg->kd, pg->dout, pg->ho, pg->wo);
+    MRI3D_REQUIRE(x && skip && pooled && idx, MRI3D_EINVAL, "norm_act_pool_fwd: null pointer");
+    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pool_fwd: mean/invstd must both be set");
+    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pool_fwd: PReLU needs alpha");
+    MRI3D_REQUIRE(aligned_vec4(g->dtype, x, skip, pooled) && (reinterpret_cast<uintptr_t>(idx) & 3) == 0, MRI3D_EINVAL,
+                  "norm_act_pool_fwd: x, skip, pooled and idx must be aligned to 4 elements");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
+    // bf16: 16-byte accesses where the layout allows them, as norm_act_fwd_kernel and maxpool2_fwd_kernel choose
+    const bool v8 = g->dtype == MRI3D_BF16 && g->c % 8 == 0 && g->x_ld % 8 == 0 && g->y_ld % 8 == 0 && pg->y_ld % 8 == 0 &&
+                    aligned16(x, skip, pooled) && (reinterpret_cast<uintptr_t>(idx) & 7) == 0;
+    int hch, grid;
+    slab_plan(pg->n * pg->dout, pg->ho, pg->wi, pg->c / (v8 ? 8 : 4), hch, grid);
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, {
+        if constexpr (sizeof(T) == 2) {
+            if (v8)
+                hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip,
+                                   (T*)pooled, idx, hch, a);
+        }
+        if (!v8)
+            hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip, (T*)pooled,
+                               idx, hch, a);
+    });
+    return check_launch("norm_act_pool_fwd");
+}
+
+template <typename T>
+static void napool_bwd_launch(const Mri3dNormGeom& g, const Mri3dPoolGeom& pg, int training, const T* x, const T* dskip,
+                              const T* dpool, const uint8_t* idx, T* dx, float* dgamma, float* dbeta, float* dalpha,
+                              const NapArgs& a, const NapPlan& p, char* ws, hipStream_t s) {
+    const typename PoolSkipGrad<T>::Args sa = {dskip, dpool, idx, g.y_ld, pg.y_ld, (unsigned)pg.wi, (unsigned)pg.hi};
+    double* part = reinterpret_cast<double*>(ws + p.part_off);
+    float* sums = reinterpret_cast<float*>(ws + p.sums_off);
+    const dim3 grid(p.nblk), blk(256);
+    const bool params = dgamma || dbeta || dalpha;
+    const bool need_sums = training || params;
+    if (need_sums) {
+        if (training || dx == nullptr)
+            hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, true, false>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
+                               dgamma, dbeta, dalpha);
+        else   // frozen statistics: dx does not wait for the sums
+            hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, true, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
+                               dgamma, dbeta, dalpha);
+        hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(g.c, 256 / kFinQL)), dim3(256), 0, s, part, sums, g.c, p.nblk, 1);
+        if (params && !(training && dx != nullptr))
+            hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g.alpha_n, g.c,
+                               1);
+    }
+    if (dx != nullptr && (training || !need_sums))
+        hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, false, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part, dgamma,
+                           dbeta, dalpha);
+}
+
+extern "C" int mri3d_norm_act_pool_bwd(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg, int training, const void* x,
+                                       const void* dskip, const void* dpool, const uint8_t* idx, const float* mean,
+                                       const float* invstd, const float* gamma, const float* beta, const float* alpha, void* dx,
+                                       float* dgamma, float* dbeta, float* dalpha, void* workspace, size_t ws_bytes,
+                                       mri3d_stream_t stream) {
+    MRI3D_REQUIRE(g != nullptr && pg != nullptr, MRI3D_EINVAL, "norm_act_pool_bwd: null geometry");
+    MRI3D_REQUIRE(napool_supported(*g, *pg), MRI3D_ENOTSUP,
+                  "norm_act_pool_bwd: c=%d x_ld=%d y_ld=%d instance=%d pool %dx%dx%d/%d -> %dx%dx%d not served", g->c, g->x_ld,
+                  g->y_ld, g->instance, pg->di, pg->hi, pg->wi, pg->kd, pg->dout, pg->ho, pg->wo);
+    MRI3D_REQUIRE(x != nullptr, MRI3D_EINVAL, "norm_act_pool_bwd: null pointer");
+    MRI3D_REQUIRE(dpool == nullptr || idx != nullptr, MRI3D_EINVAL, "norm_act_pool_bwd: dpool needs the index bytes");
+    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pool_bwd: mean/invstd must both be set");
+    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "norm_act_pool_bwd: training mode needs statistics");
+    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pool_bwd: PReLU needs alpha");
+    MRI3D_REQUIRE(aligned_vec4(g->dtype, x, dx) && aligned_vec4(g->dtype, dskip, dpool) &&
+                      (reinterpret_cast<uintptr_t>(idx) & 3) == 0,
+                  MRI3D_EINVAL, "norm_act_pool_bwd: x, dx, dskip, dpool and idx must be aligned to 4 elements");
+    const NapPlan p = nap_plan(*g, 0);
+    MRI3D_REQUIRE(workspace && ws_bytes >= p.bytes && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, MRI3D_EWORKSPACE,
+                  "norm_act_pool_bwd: workspace %zu < %zu (or not 8-byte aligned)", ws_bytes, p.bytes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
+    char* ws = static_cast<char*>(workspace);
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, {
+        napool_bwd_launch<T>(*g, *pg, training, (const T*)x, (const T*)dskip, (const T*)dpool, idx, (T*)dx, dgamma, dbeta, dalpha, a,
+                             p, ws, s);
+    });
+    return check_launch("norm_act_pool_bwd");
 }

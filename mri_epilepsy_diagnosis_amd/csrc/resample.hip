@@ -256,13 +256,6 @@ maxpool2_fwd_kernel(Mri3dPoolGeom g, const T* __restrict__ x, T* __restrict__ y,
     }
 }
 
-static inline bool pool2_ok(const Mri3dPoolGeom& g, int vec) {
-    const int cv = g.c / vec;
-    return g.kd == 2 && g.kh == 2 && g.kw == 2 && g.sd == 2 && g.sh == 2 && g.sw == 2 && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
-           g.di == 2 * g.dout && g.hi == 2 * g.ho && g.wi == 2 * g.wo && cv >= 1 && cv <= 32 && (cv & (cv - 1)) == 0 &&
-           (int64_t)g.di * g.hi * g.wi * g.x_ld < ((int64_t)1 << 31);
-}
-
 // ------------------------------------------------------------------ upsample coordinate helpers (torch semantics)
 struct Lin { int i0, i1; float l0, l1; };
 __device__ __forceinline__ Lin lin_src(int o, float r, int in_size, int align_corners) {
@@ -849,13 +842,6 @@ static inline bool up2x_fast_ok(const Mri3dUpGeom& g) {
 }
 
 // rows of H per slab so that one slab is ~8 passes of a 256-thread block, and the resulting grid size
-static inline void slab_plan(int nd, int h, int w, int cv, int& hch, int& grid) {
-    int64_t per_row = (int64_t)w * cv;
-    hch = (int)std::max<int64_t>(1, std::min<int64_t>(h, 2048 / std::max<int64_t>(per_row, 1)));
-    int64_t slabs = (int64_t)nd * ((h + hch - 1) / hch);
-    grid = (int)std::min<int64_t>(slabs, 8192);
-}
-
 static inline bool vec_ok(int dtype, int c, int a_ld, int b_ld, const void* a, const void* b) {
     return c % 4 == 0 && a_ld % 4 == 0 && b_ld % 4 == 0 && aligned_vec4(dtype, a, b);
 }

@@ -140,29 +140,36 @@ def _plain_pointwise(head):
             and not isinstance(head.padding, str) and tuple(head.padding) == (0, 0, 0))
 
 
+def _local_stats_spec(norm, act):
+    """(mode, leading arguments of the fused operators, activation kind, alpha, slope) for `norm` a BatchNorm3d with local batch or
+    running statistics, or None (activation only); None for every other normalisation (instance, group, synchronised)."""
+    kind, alpha, slope = _act_spec(act)
+    if norm is None:
+        return "none", (None, None, alpha, None, None, "none", 0.1, 0.0), kind, alpha, slope
+    if not isinstance(norm, tnn.modules.batchnorm._BatchNorm) or norm.momentum is None:
+        return None
+    use_batch = norm.training or norm.running_mean is None
+    if use_batch and norm.training and ops.sync_batchnorm_reducer() is not None:
+        return None
+    mode = "batch" if use_batch else "running"
+    args = (norm.weight, norm.bias, alpha, norm.running_mean if norm.track_running_stats else None,
+            norm.running_var if norm.track_running_stats else None, mode, norm.momentum, norm.eps)
+    return mode, args, kind, alpha, slope
+
+
 def fused_norm_act_head(norm, act, x, head):
     """head(act(norm(x))) as ONE operator (ops.norm_act_pointwise) where that is served: `head` a plain 1x1x1 Conv3d with at most
     four output channels, `norm` a BatchNorm3d with local batch or running statistics (or None), channels and layout as the native
     predicate asks.  Returns None — with nothing run and no counter touched — where it is not: the caller keeps the two operators."""
     if not _plain_pointwise(head):
         return None
-    kind, alpha, slope = _act_spec(act)
     cast = ops.autocast_dtype()
     if cast is not None and x.dtype != cast:   # the head's conv3d would convert its input first
         return None
-    if norm is None:
-        mode, args = "none", (None, None, alpha, None, None, "none", 0.1, 0.0)
-    elif isinstance(norm, tnn.modules.batchnorm._BatchNorm):
-        use_batch = norm.training or norm.running_mean is None
-        if use_batch and norm.training and ops.sync_batchnorm_reducer() is not None:
-            return None
-        if norm.momentum is None:
-            return None
-        mode = "batch" if use_batch else "running"
-        args = (norm.weight, norm.bias, alpha, norm.running_mean if norm.track_running_stats else None,
-                norm.running_var if norm.track_running_stats else None, mode, norm.momentum, norm.eps)
-    else:
+    spec = _local_stats_spec(norm, act)
+    if spec is None:
         return None
+    mode, args, kind, alpha, slope = spec
     if not ops.norm_act_pointwise_supported(x, head.weight, mode, kind, alpha):
         return None
     if mode != "none" and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
@@ -170,12 +177,36 @@ def fused_norm_act_head(norm, act, x, head):
     return ops.norm_act_pointwise(x, head.weight, head.bias, *args, act=kind, slope=slope)
 
 
-def conv_norm_act(conv, norm, act, x, out=None, head=None):
+def fused_norm_act_pool(norm, act, x, pool):
+    """(pool(a), a) with a = act(norm(x)) as ONE operator (ops.norm_act_pool) where that is served: `pool` a MaxPool3d(2) in floor
+    mode, `norm` a BatchNorm3d with local batch or running statistics (or None), fp32 activations, extents, channels and layout as
+    the native predicate asks.  Returns None — with nothing run and no counter touched — where it is not: the caller keeps the two operators."""
+    if (not isinstance(pool, tnn.MaxPool3d) or pool.ceil_mode or pool.return_indices or pool.dilation not in (1, (1, 1, 1))
+            or not x.is_cuda):
+        return None
+    if x.dtype != torch.float32:
+        # bf16 activations keep the two operators: measured on the bench step the fold is no faster there (DESIGN §4.6 — the
+        # backward sums pass is bound by its float64 accumulation, not by the bytes the fold removes); ops.norm_act_pool serves bf16
+        return None
+    spec = _local_stats_spec(norm, act)
+    if spec is None:
+        return None
+    mode, args, kind, alpha, slope = spec
+    if not ops.norm_act_pool_supported(x, pool.kernel_size, pool.stride, pool.padding, mode, kind, alpha):
+        return None
+    if mode != "none" and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
+        norm.num_batches_tracked.add_(1)
+    return ops.norm_act_pool(x, *args, act=kind, slope=slope)
+
+
+def conv_norm_act(conv, norm, act, x, out=None, head=None, pool=None):
     """act(norm(conv(x))) for a Conv3d module followed by a normalisation (`unet.UNet`'s ConvolutionalBlock, the conv -> BN ->
     ReLU stems of cnn_model.py).  When `norm` is a BatchNorm3d that will use BATCH statistics (training mode, local statistics)
     the convolution is asked to accumulate them in its epilogue, which saves the statistics pass over its output.
     head: a Conv3d module applied to the result (`unet.UNet`'s 1x1x1 classifier); the return value is then head(act(norm(conv(x)))),
-    computed without storing the activation where `fused_norm_act_head` serves the case."""
+    computed without storing the activation where `fused_norm_act_head` serves the case.
+    pool: a MaxPool3d module applied to the result, which is also kept (`unet.UNet`'s encoder levels); the return value is then
+    (pool(a), a) for a = act(norm(conv(x))), from one operator where `fused_norm_act_pool` serves the case."""
     wants = (isinstance(norm, tnn.modules.batchnorm._BatchNorm) and (norm.training or norm.running_mean is None)
              and ops.sync_batchnorm_reducer() is None and isinstance(conv, Conv3d) and conv.padding_mode == "zeros"
              and conv.groups == 1 and not isinstance(conv.padding, str))
@@ -195,6 +226,9 @@ def conv_norm_act(conv, norm, act, x, out=None, head=None):
     if head is not None:
         logits = fused_norm_act_head(norm, act, y, head) if out is None else None
         return logits if logits is not None else head(fused_norm_act(norm, act, y, out))
+    if pool is not None:
+        both = fused_norm_act_pool(norm, act, y, pool) if out is None else None
+        return both if both is not None else pool.forward_with_skip(fused_norm_act(norm, act, y, out))
     return fused_norm_act(norm, act, y, out)
 
 

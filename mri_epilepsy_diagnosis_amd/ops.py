@@ -1281,6 +1281,158 @@ def norm_act_pointwise(x, weight, bias=None, gamma=None, beta=None, alpha=None, 
                                      act, slope, fused)
 
 
+def _pool_tail_geoms(x, x_ld, s_ld, p_ld, kernel, stride, padding, act_code, alpha, slope, eps):
+    """(NormGeom, PoolGeom, pooled extents) of act(norm(x)) followed by a max pool: pitches x_ld (x / dx), s_ld (skip / dskip),
+    p_ld (pooled / dpool)."""
+    n, c, d, h, w = x.shape
+    do, ho, wo = (_pool_out(i, k, s, p, False) for i, k, s, p in zip((d, h, w), kernel, stride, padding))
+    alpha_n = alpha.numel() if (act_code == ACT_PRELU and alpha is not None) else 1
+    g = NormGeom(n, d * h * w, c, x_ld, s_ld, 0, act_code, alpha_n, float(slope), float(eps), 0, _dt(x))
+    pg = PoolGeom(n, d, h, w, do, ho, wo, c, *kernel, *stride, *padding, s_ld, c if p_ld is None else p_ld, _dt(x))
+    return g, pg, (do, ho, wo)
+
+
+def norm_act_pool_supported(x, kernel_size=2, stride=None, padding=0, stats_mode="batch", act=None, alpha=None):
+    """True when `norm_act_pool` serves act(norm(x)) followed by max_pool3d_skip as one operator: the native predicate on the two
+    geometries (a host-only decision: x may live anywhere), plus what only the caller can see (statistics mode, memory layout)."""
+    if stats_mode not in ("batch", "running", "none") or act not in _ACT_CODES:
+        return False
+    if not (x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    k = _triple(kernel_size)
+    s = _triple(stride) if stride is not None else k
+    x_ld = _pitch_of(x)
+    if x_ld is None:
+        x_ld = x.shape[1]          # _nd makes a dense copy
+    elif x.data_ptr() % (4 * x.element_size()):
+        return False
+    g, pg, out = _pool_tail_geoms(x, x_ld, x.shape[1], None, k, s, _triple(padding), _ACT_CODES[act], alpha, 0.0, 0.0)
+    if min(out) <= 0:
+        return False
+    return bool(_lib.lib().mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)))
+
+
+class _NormActPoolFn(torch.autograd.Function):
+    """(pooled, skip) = (max_pool3d(a, 2), a) with a = act(gamma * (x - mean) / sqrt(var + eps) + beta), batch, running or no
+    statistics: one forward pass writes a, the pooled tensor and the index bytes; the backward takes dskip + scatter(dpool) inside
+    the norm_act backward passes and never stores it (mri3d_norm_act_pool_*)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, alpha, running_mean, running_var, stats_mode, momentum, eps, act, slope, fused_stats=None):
+        _require_device(x)
+        _require_param(gamma, beta, alpha)
+        ctx.params = (gamma, beta, alpha)
+        L = _lib.lib()
+        x, x_ld = _nd(x)
+        n, c, d, h, w = x.shape
+        act_code = _ACT_CODES[act]
+        two = (2, 2, 2)
+        g, pg, (do, ho, wo) = _pool_tail_geoms(x, x_ld, c, c, two, two, (0, 0, 0), act_code, alpha, slope, eps)
+        if not L.mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)):
+            raise RuntimeError("norm_act_pool: c=%d pitch %d extents %s is not served (ask norm_act_pool_supported first)"
+                               % (c, x_ld, (d, h, w)))
+        mean = invstd = None
+        gn = _head_geom(x, x_ld, x_ld, act_code, alpha, slope, eps)   # the statistics entry points
+        if stats_mode == "batch":
+            mean = torch.empty(c, dtype=torch.float32, device=x.device)
+            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+            upd = running_mean is not None
+            if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
+                part, blocks, shift = fused_stats
+                with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
+                    check(L.mri3d_norm_stats_from_partials(ctypes.byref(gn), _ptr(part), blocks, _ptr(shift), _ptr(mean),
+                                                           _ptr(invstd), _ptr(running_mean) if upd else None,
+                                                           _ptr(running_var) if upd else None, float(momentum), _stream()),
+                          "norm_stats_from_partials")
+            else:
+                ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(gn)), x.device)
+                with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
+                    check(L.mri3d_norm_stats(ctypes.byref(gn), _ptr(x), _ptr(mean), _ptr(invstd),
+                                             _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None,
+                                             float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
+        elif stats_mode == "running":
+            mean = running_mean.detach().to(torch.float32).contiguous()
+            invstd = torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous()
+        elif stats_mode != "none":
+            raise RuntimeError("norm_act_pool: statistics mode %r is not served" % (stats_mode,))
+        skip = _new(x.shape, x)
+        pooled = _new((n, c, do, ho, wo), x)
+        idx = torch.empty(pooled.numel(), dtype=torch.uint8, device=x.device)
+        # read x; write skip, pooled and one index byte per pooled element
+        with _timed(lambda: "norm_act_pool_fwd c%d" % c,
+                    lambda: {"flops": 0.0, "bytes": _esz(x) * 2 * x.numel() + (_esz(x) + 1) * pooled.numel()}):
+            check(L.mri3d_norm_act_pool_fwd(ctypes.byref(g), ctypes.byref(pg), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma),
+                                            _ptr(beta), _ptr(alpha) if act_code == ACT_PRELU else None, _ptr(skip), _ptr(pooled),
+                                            _ptr(idx), _stream()), "norm_act_pool_fwd")
+        ctx.save_for_backward(x, idx, mean, invstd, gamma, beta, alpha)
+        ctx.geom = g
+        ctx.pooled_shape = tuple(pooled.shape)
+        ctx.training_stats = stats_mode == "batch"
+        ctx.set_materialize_grads(False)   # an unused output arrives as None and is not read as zeros
+        return pooled, skip
+
+    @staticmethod
+    def backward(ctx, dpool, dskip):
+        L = _lib.lib()
+        if dpool is None and dskip is None:
+            return (None,) * 12
+        x, idx, mean, invstd, gamma, beta, alpha = ctx.saved_tensors
+        g0 = ctx.geom
+        n, c, d, h, w = x.shape
+        s_ld = p_ld = c
+        for name, t, shape in (("pooled", dpool, ctx.pooled_shape), ("skip", dskip, tuple(x.shape))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != x.dtype):
+                raise RuntimeError("norm_act_pool backward: %s gradient %s %s does not match %s %s"
+                                   % (name, tuple(t.shape), t.dtype, shape, x.dtype))
+        if dskip is not None:
+            dskip, s_ld = _nd(dskip)
+            if s_ld % 4 or dskip.data_ptr() % (4 * dskip.element_size()):
+                dskip, s_ld = dskip.contiguous(memory_format=CL3D), c
+        if dpool is not None:
+            dpool, p_ld = _nd(dpool)
+            if p_ld % 4 or dpool.data_ptr() % (4 * dpool.element_size()):
+                dpool, p_ld = dpool.contiguous(memory_format=CL3D), c
+        if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
+            x = x.contiguous(memory_format=CL3D)
+        two = (2, 2, 2)
+        g, pg, _ = _pool_tail_geoms(x, c, s_ld, p_ld, two, two, (0, 0, 0), g0.act, alpha, g0.slope, g0.eps)
+        pg_, pb_, pa_ = ctx.params
+        prelu = g.act == ACT_PRELU
+        need = ctx.needs_input_grad
+        want = (gamma is not None and need[1], beta is not None and need[2], prelu and need[3])
+        srcs = (gamma, beta, alpha)
+        sinks = [_sink_take(p) if wt else None for p, wt in zip(ctx.params, want)]
+        grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
+                 for sk, t, wt in zip(sinks, srcs, want)]
+        dx = _new(x.shape, x) if need[0] else None
+        ws = _workspace(L.mri3d_norm_act_pool_workspace_bytes(ctypes.byref(g), ctypes.byref(pg)), x.device)
+        # per pass: x and dskip read, dpool and the index bytes read once (each is shared by a window's eight voxels); training
+        # statistics take the sums pass and the dx pass, frozen statistics one pass; dx written once
+        passes = 2 if ctx.training_stats else 1
+        npool = idx.numel()
+        with _timed(lambda: "norm_act_pool_bwd c%d" % c,
+                    lambda: {"flops": 0.0,
+                             "bytes": passes * (_esz(x) * (x.numel() + (x.numel() if dskip is not None else 0))
+                                                + ((_esz(x) + 1) * npool if dpool is not None else 0))
+                                      + (_esz(x) * x.numel() if dx is not None else 0)}):
+            check(L.mri3d_norm_act_pool_bwd(ctypes.byref(g), ctypes.byref(pg), 1 if ctx.training_stats else 0, _ptr(x),
+                                            _ptr(dskip), _ptr(dpool), _ptr(idx), _ptr(mean), _ptr(invstd), _ptr(gamma),
+                                            _ptr(beta), _ptr(alpha) if prelu else None, _ptr(dx), _ptr(grads[0]), _ptr(grads[1]),
+                                            _ptr(grads[2]), _ptr(ws), ws.numel(), _stream()), "norm_act_pool_bwd")
+        outs = [_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks)]
+        return (dx, outs[0], outs[1], outs[2], None, None, None, None, None, None, None, None)
+
+
+def norm_act_pool(x, gamma=None, beta=None, alpha=None, running_mean=None, running_var=None, stats_mode="batch",
+                  momentum=0.1, eps=1e-5, act=None, slope=0.01):
+    """(max_pool3d(a, 2), a) for a = norm_act(x, ...) as one operator (see `norm_act_pool_supported`): the second output is the
+    skip connection's tensor.  The producer's fused BatchNorm statistics are picked up from x as `norm_act` does."""
+    if momentum is None:
+        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
+    fused = getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+    return _NormActPoolFn.apply(x, gamma, beta, alpha, running_mean, running_var, stats_mode, momentum, eps, act, slope, fused)
+
+
 def activation(x, act, alpha=None, slope=0.01):
     return norm_act(x, None, None, alpha, None, None, "none", 0.1, 0.0, act, slope)
 

@@ -44,9 +44,10 @@ class ConvolutionalBlock(tnn.Module):
         self.dropout_layer = None
         self.block = tnn.Sequential(*[m for m in (conv, norm, act) if m is not None])
 
-    def forward(self, x, out=None, head=None):
+    def forward(self, x, out=None, head=None, pool=None):
         # head: the classifier's 1x1x1 Conv3d, applied to this block's result (mnn.conv_norm_act)
-        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out, head)
+        # pool: the encoder level's MaxPool3d; the result is then (pooled, this block's result)
+        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out, head, pool)
 
 
 class EncodingBlock(tnn.Module):
@@ -68,10 +69,13 @@ class EncodingBlock(tnn.Module):
                 raise NotImplementedError("only max pooling is used by the reference")
             self.downsample = mnn.MaxPool3d(kernel_size=2)
 
-    def forward(self, x, skip_out=None, head=None):
+    def forward(self, x, skip_out=None, head=None, fused_pool=True):
         # skip_out = (concat buffer, 0): the block's output is written straight into the decoder's concat buffer
         if self.downsample is None:
             return self.conv2(self.conv1(x), skip_out, head)
+        if fused_pool and skip_out is None and isinstance(self.downsample, mnn.MaxPool3d):
+            # (pooled, skip) from conv2's BatchNorm + activation pass itself where ops.norm_act_pool serves the level
+            return self.conv2(self.conv1(x), pool=self.downsample)
         x = self.conv2(self.conv1(x), skip_out)
         # (pooled, skip) from one autograd node: the two gradients of x are summed inside the pool-backward kernel
         return self.downsample.forward_with_skip(x)
@@ -98,10 +102,10 @@ class Encoder(tnn.Module):
             if self.dilation is not None:
                 self.dilation *= 2
 
-    def forward(self, x, cat_bufs=None):
+    def forward(self, x, cat_bufs=None, fused_pool=True):
         skips = []
         for i, blk in enumerate(self.encoding_blocks):
-            x, skip = blk(x, None if cat_bufs is None else (cat_bufs[i], 0))
+            x, skip = blk(x, None if cat_bufs is None else (cat_bufs[i], 0), fused_pool=fused_pool)
             skips.append(skip)
         return skips, x
 
@@ -192,6 +196,10 @@ class UNet(tnn.Module):
         # the classifier's 1x1x1 convolution runs inside the last block's BatchNorm + activation pass (A/B switch; not part of the
         # reference's API): same logits bit for bit in fp32, without the full-resolution activation in between
         self.fused_head = True
+        # each encoder level's MaxPool3d(2) runs inside that level's last BatchNorm + activation passes (A/B switch; not part of
+        # the reference's API): same tensors and gradients bit for bit in fp32, without re-reading the activation or storing the
+        # summed gradient of the skip connection and the pool
+        self.fused_pool = True
         self.classifier = ConvolutionalBlock(dimensions, 2 * out_channels_first_layer, out_classes, kernel_size=1,
                                              activation=None)
 
@@ -213,7 +221,7 @@ class UNet(tnn.Module):
         clf = self.classifier
         head = clf.conv_layer if (self.fused_head and x.is_cuda and clf.norm_layer is None and clf.activation_layer is None
                                   and clf.dropout_layer is None) else None
-        skips, enc = self.encoder(x, cat_bufs)
+        skips, enc = self.encoder(x, cat_bufs, self.fused_pool)
         if not skips:
             return self.bottom_block(enc, head=head) if head is not None else self.classifier(self.bottom_block(enc))
         enc = self.bottom_block(enc)
