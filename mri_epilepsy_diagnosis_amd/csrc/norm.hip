@@ -13,6 +13,7 @@
 // the workspace.  A finalize kernel sums the partials in a fixed order in double precision (deterministic).
 #include "common.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace mri3d {
 
@@ -57,6 +58,17 @@ size_t norm_workspace_floats(const Mri3dNormGeom& g) {
     part += (size_t)groups * g.c * 3;                           // bwd per-(group,channel) sums
     return part;
 }
+
+// Run `body` with `VEC` bound to a plan's channels per lane: 4 or 1, and 8 where `with8` (a constant expression: the bf16
+// forward) allows it.  Only the branches written here are instantiated.
+#define MRI3D_DISPATCH_VEC(vec, with8, VEC, ...)                      \
+    do {                                                              \
+        if constexpr (with8) {                                        \
+            if ((vec) == 8) { constexpr int VEC = 8; __VA_ARGS__ }    \
+        }                                                             \
+        if ((vec) == 4) { constexpr int VEC = 4; __VA_ARGS__ }        \
+        else if ((vec) == 1) { constexpr int VEC = 1; __VA_ARGS__ }   \
+    } while (0)
 
 template <int VEC>
 struct Ld {
@@ -1049,7 +1061,11 @@ norm_act_pool_bwd_kernel(const T* __restrict__ x, T* __restrict__ dx, typename P
 
 struct NapPlan {
     int QC, VT, nblk;
-    size_t part_off, sums_off, side_off, bytes;   // byte offsets into the workspace
+    size_t sums_off, side_off, bytes;   // byte offsets into the workspace (the norm partials start it)
+    // the regions of a workspace of `bytes` bytes: per-block norm partials, combined sums, per-block side partials of the source
+    double* part(void* ws) const { return static_cast<double*>(ws); }
+    float* sums(void* ws) const { return reinterpret_cast<float*>(static_cast<char*>(ws) + sums_off); }
+    double* spart(void* ws) const { return reinterpret_cast<double*>(static_cast<char*>(ws) + side_off); }
 };
 
 static bool nap_supported(const Mri3dNormGeom& g, int co) {
@@ -1072,7 +1088,6 @@ static NapPlan nap_plan(const Mri3dNormGeom& g, int co) {
     const int64_t want = cdiv64(nvox, (int64_t)p.VT * 8);   // >= 8 voxel rows per thread, as norm_plan
     p.nblk = (int)(want < kNormMaxBlocks ? want : kNormMaxBlocks);
     if (p.nblk < 1) p.nblk = 1;
-    p.part_off = 0;
     p.sums_off = (size_t)p.nblk * g.c * 3 * sizeof(double);
     p.side_off = p.sums_off + align_up((size_t)g.c * 3 * sizeof(float), sizeof(double));
     p.bytes = p.side_off + (size_t)p.nblk * (co * g.c + co) * sizeof(double);
@@ -1101,6 +1116,15 @@ static int norm_check(const Mri3dNormGeom* g, const char* who) {
     return MRI3D_OK;
 }
 
+// what every norm_act entry point asks of its statistics and activation arguments (the forward ones pass training = 0)
+static int norm_act_args_check(const Mri3dNormGeom* g, int training, const float* mean, const float* invstd, const float* alpha,
+                               const char* who) {
+    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "%s: mean/invstd must both be set", who);
+    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "%s: training mode needs statistics", who);
+    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "%s: PReLU needs alpha", who);
+    return MRI3D_OK;
+}
+
 extern "C" int mri3d_norm_stats(const Mri3dNormGeom* g, const void* x, float* mean, float* invstd, float* running_mean,
                                 float* running_var, float momentum, void* workspace, size_t ws_bytes,
                                 mri3d_stream_t stream) {
@@ -1118,10 +1142,9 @@ extern "C" int mri3d_norm_stats(const Mri3dNormGeom* g, const void* x, float* me
     const int tot = p.groups * g->c;
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
         const T* xf = static_cast<const T*>(x);
-        if (p.vec == 4)
-            hipLaunchKernelGGL((norm_stats_kernel<T, 4>), grid, dim3(256), 0, s, xf, part, g->c, g->x_ld, p.gvox, p.CL, p.VT);
-        else if (p.vec == 1)
-            hipLaunchKernelGGL((norm_stats_kernel<T, 1>), grid, dim3(256), 0, s, xf, part, g->c, g->x_ld, p.gvox, p.CL, p.VT);
+        MRI3D_DISPATCH_VEC(p.vec, false, VEC, {
+            hipLaunchKernelGGL((norm_stats_kernel<T, VEC>), grid, dim3(256), 0, s, xf, part, g->c, g->x_ld, p.gvox, p.CL, p.VT);
+        });
         hipLaunchKernelGGL(norm_stats_finalize_kernel<T>, dim3(cdiv(tot, 256 / kFinQL)), dim3(256), 0, s, xf, part, mean,
                            invstd, running_mean, running_var, momentum, g->eps, g->c, g->x_ld, p.gvox, p.nblk, p.groups);
         if (g->group_c > 0) {
@@ -1155,24 +1178,17 @@ extern "C" int mri3d_norm_act_fwd(const Mri3dNormGeom* g, const void* x, const f
     int rc = norm_check(g, "norm_act_fwd");
     if (rc) return rc;
     MRI3D_REQUIRE(x && y, MRI3D_EINVAL, "norm_act_fwd: null pointer");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_fwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_fwd: PReLU needs alpha");
+    if ((rc = norm_act_args_check(g, 0, mean, invstd, alpha, "norm_act_fwd"))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     NormPlan p = norm_plan(*g, aligned_vec4(g->dtype, x, y), aligned16(x, y));
     dim3 grid(p.nblk, p.cy, p.groups);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
         const T* xf = static_cast<const T*>(x);
         T* yf = static_cast<T*>(y);
-        if constexpr (sizeof(T) == 2) {
-            if (p.vec == 8) hipLaunchKernelGGL((norm_act_fwd_kernel<T, 8>), grid, dim3(256), 0, s, xf, yf, mean, invstd, gamma, beta, alpha,
+        MRI3D_DISPATCH_VEC(p.vec, sizeof(T) == 2, VEC, {
+            hipLaunchKernelGGL((norm_act_fwd_kernel<T, VEC>), grid, dim3(256), 0, s, xf, yf, mean, invstd, gamma, beta, alpha,
                                g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL, p.VT);
-        }
-        if (p.vec == 4)
-            hipLaunchKernelGGL((norm_act_fwd_kernel<T, 4>), grid, dim3(256), 0, s, xf, yf, mean, invstd, gamma, beta, alpha,
-                               g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL, p.VT);
-        else if (p.vec == 1)
-            hipLaunchKernelGGL((norm_act_fwd_kernel<T, 1>), grid, dim3(256), 0, s, xf, yf, mean, invstd, gamma, beta, alpha,
-                               g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL, p.VT);
+        });
     });
     return check_launch("norm_act_fwd");
 }
@@ -1184,9 +1200,7 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
     int rc = norm_check(g, "norm_act_bwd");
     if (rc) return rc;
     MRI3D_REQUIRE(x && dy && dx, MRI3D_EINVAL, "norm_act_bwd: null pointer");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_bwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "norm_act_bwd: training mode needs statistics");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_bwd: PReLU needs alpha");
+    if ((rc = norm_act_args_check(g, training, mean, invstd, alpha, "norm_act_bwd"))) return rc;
     MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_norm_workspace_bytes(g), MRI3D_EWORKSPACE,
                   "norm_act_bwd: workspace %zu < %zu", ws_bytes, mri3d_norm_workspace_bytes(g));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1203,14 +1217,11 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
         T* of = static_cast<T*>(dx);
         if (need_reduce && !training) {
             // nothing in dx depends on the sums: one pass writes dx and the per-block partials, then the two small kernels
-            if (p.vec == 4)
-                hipLaunchKernelGGL((norm_act_bwd_frozen_kernel<T, 4>), grid, dim3(256), 0, s, xf, df, of, part, mean, invstd,
+            MRI3D_DISPATCH_VEC(p.vec, false, VEC, {
+                hipLaunchKernelGGL((norm_act_bwd_frozen_kernel<T, VEC>), grid, dim3(256), 0, s, xf, df, of, part, mean, invstd,
                                    gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
                                    p.VT);
-            else if (p.vec == 1)
-                hipLaunchKernelGGL((norm_act_bwd_frozen_kernel<T, 1>), grid, dim3(256), 0, s, xf, df, of, part, mean, invstd,
-                                   gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
-                                   p.VT);
+            });
             hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(p.groups * g->c, 256 / kFinQL)), dim3(256), 0, s, part,
                                sums, g->c, p.nblk, p.groups);
             hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g->alpha_n,
@@ -1218,14 +1229,11 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
             return check_launch("norm_act_bwd");
         }
         if (need_reduce) {
-            if (p.vec == 4)
-                hipLaunchKernelGGL((norm_act_bwd_reduce_kernel<T, 4>), grid, dim3(256), 0, s, xf, df, part, mean, invstd,
+            MRI3D_DISPATCH_VEC(p.vec, false, VEC, {
+                hipLaunchKernelGGL((norm_act_bwd_reduce_kernel<T, VEC>), grid, dim3(256), 0, s, xf, df, part, mean, invstd,
                                    gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
                                    p.VT);
-            else if (p.vec == 1)
-                hipLaunchKernelGGL((norm_act_bwd_reduce_kernel<T, 1>), grid, dim3(256), 0, s, xf, df, part, mean, invstd,
-                                   gamma, beta, alpha, g->alpha_n, g->act, g->slope, g->c, g->x_ld, g->y_ld, p.gvox, p.CL,
-                                   p.VT);
+            });
             hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(p.groups * g->c, 256 / kFinQL)), dim3(256), 0, s, part,
                                sums, g->c, p.nblk, p.groups);
             if ((dgamma || dbeta || dalpha) && g->group_c > 0) {   // GroupNorm: before the combine step rewrites `sums`
@@ -1242,14 +1250,11 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
         float* pg = params_done ? nullptr : dgamma;
         float* pb = params_done ? nullptr : dbeta;
         float* pa = params_done ? nullptr : dalpha;
-        if (p.vec == 4)
-            hipLaunchKernelGGL((norm_act_bwd_apply_kernel<T, 4>), grid, dim3(256), 0, s, xf, df, of, sums, mean, invstd,
+        MRI3D_DISPATCH_VEC(p.vec, false, VEC, {
+            hipLaunchKernelGGL((norm_act_bwd_apply_kernel<T, VEC>), grid, dim3(256), 0, s, xf, df, of, sums, mean, invstd,
                                gamma, beta, alpha, g->alpha_n, g->act, g->slope, training, g->c, g->x_ld, g->y_ld, p.gvox,
                                p.CL, p.VT, g->group_c, pg, pb, pa);
-        else if (p.vec == 1)
-            hipLaunchKernelGGL((norm_act_bwd_apply_kernel<T, 1>), grid, dim3(256), 0, s, xf, df, of, sums, mean, invstd,
-                               gamma, beta, alpha, g->alpha_n, g->act, g->slope, training, g->c, g->x_ld, g->y_ld, p.gvox,
-                               p.CL, p.VT, g->group_c, pg, pb, pa);
+        });
     });
     return check_launch("norm_act_bwd");
 }
@@ -1279,8 +1284,7 @@ extern "C" int mri3d_norm_act_pw_fwd(const Mri3dNormGeom* g, int32_t co, const v
     MRI3D_REQUIRE(nap_supported(*g, co), MRI3D_ENOTSUP, "norm_act_pw_fwd: c=%d co=%d x_ld=%d y_ld=%d instance=%d not served",
                   g->c, co, g->x_ld, g->y_ld, g->instance);
     MRI3D_REQUIRE(x && w && out, MRI3D_EINVAL, "norm_act_pw_fwd: null pointer");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pw_fwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pw_fwd: PReLU needs alpha");
+    if (int rc = norm_act_args_check(g, 0, mean, invstd, alpha, "norm_act_pw_fwd")) return rc;
     MRI3D_REQUIRE(aligned_vec4(g->dtype, x), MRI3D_EINVAL, "norm_act_pw_fwd: x must be aligned to 4 elements");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
@@ -1297,36 +1301,44 @@ extern "C" int mri3d_norm_act_pw_fwd(const Mri3dNormGeom* g, int32_t co, const v
     return check_launch("norm_act_pw_fwd");
 }
 
-template <typename T, int CO>
-static void nap_bwd_launch(const Mri3dNormGeom& g, int co, int training, const T* x, const T* dout, const float* w, T* dx,
-                           float* dgamma, float* dbeta, float* dalpha, float* dw, float* dbias, const NapArgs& a,
-                           const NapPlan& p, char* ws, hipStream_t s) {
-    using SRC = PwHeadGrad<T, CO>;
-    const typename SRC::Args sa = {dout, w, co, g.y_ld};
-    double* part = reinterpret_cast<double*>(ws + p.part_off);
-    float* sums = reinterpret_cast<float*>(ws + p.sums_off);
-    double* spart = reinterpret_cast<double*>(ws + p.side_off);
+// The launch sequence of a gradient-source backward (PwHeadGrad, PoolSkipGrad), decided by (training statistics, dx wanted,
+// parameter gradients wanted, side sums wanted).  Training statistics: a sums pass, the combined sums, then the dx pass, whose
+// first workgroup writes the parameter gradients.  Frozen statistics: one pass does both (or only one of them is wanted), and
+// the parameter kernel follows the combined sums.  dw / dbias: the side sums of a source with kSide > 0 (co rows of c).
+template <typename T, class SRC>
+static void nap_bwd_launch(const Mri3dNormGeom& g, const NapPlan& p, void* ws, hipStream_t s, int training, const T* x, T* dx,
+                           const typename SRC::Args& sa, const NapArgs& a, float* dgamma, float* dbeta, float* dalpha,
+                           int co = 0, float* dw = nullptr, float* dbias = nullptr) {
+    double* part = p.part(ws);
+    float* sums = p.sums(ws);
+    double* spart = p.spart(ws);
     const dim3 grid(p.nblk), blk(256);
+    auto pass = [&](auto sums_pass, auto dx_pass) {
+        constexpr bool SUMS = decltype(sums_pass)::value, DX = decltype(dx_pass)::value;
+        if constexpr (std::is_same_v<SRC, PoolSkipGrad<T>>)   // its entry point has no side-partials parameter
+            hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, SUMS, DX>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
+                               dgamma, dbeta, dalpha);
+        else
+            hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, SUMS, DX>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
+                               spart, dgamma, dbeta, dalpha);
+    };
     const bool params = dgamma || dbeta || dalpha;
-    const bool need_sums = training || params || dw || dbias;
+    const bool side = SRC::kSide > 0 && (dw || dbias);
+    const bool need_sums = training || params || side;
     if (need_sums) {
         if (training || dx == nullptr)
-            hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, true, false>), grid, blk, 0, s, x, dx, sa, a, sums, training,
-                               part, spart, dgamma, dbeta, dalpha);
+            pass(std::true_type{}, std::false_type{});
         else   // frozen statistics: dx does not wait for the sums
-            hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, true, true>), grid, blk, 0, s, x, dx, sa, a, sums, training,
-                               part, spart, dgamma, dbeta, dalpha);
+            pass(std::true_type{}, std::true_type{});
         hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(g.c, 256 / kFinQL)), dim3(256), 0, s, part, sums, g.c, p.nblk, 1);
-        if (dw || dbias)
+        if (side)
             hipLaunchKernelGGL(norm_act_pw_wsum_kernel, dim3(cdiv(co * g.c + co, 8)), dim3(256), 0, s, spart, dw, dbias, p.nblk,
                                co * g.c, co);
         if (params && !(training && dx != nullptr))
             hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g.alpha_n, g.c,
                                1);
     }
-    if (dx != nullptr && (training || !need_sums))
-        hipLaunchKernelGGL((norm_act_src_bwd_kernel<T, SRC, false, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
-                           spart, dgamma, dbeta, dalpha);
+    if (dx != nullptr && (training || !need_sums)) pass(std::false_type{}, std::true_type{});
 }
 
 extern "C" int mri3d_norm_act_pw_bwd(const Mri3dNormGeom* g, int32_t co, int training, const void* x, const void* dout,
@@ -1337,23 +1349,20 @@ extern "C" int mri3d_norm_act_pw_bwd(const Mri3dNormGeom* g, int32_t co, int tra
     MRI3D_REQUIRE(nap_supported(*g, co), MRI3D_ENOTSUP, "norm_act_pw_bwd: c=%d co=%d x_ld=%d y_ld=%d instance=%d not served",
                   g->c, co, g->x_ld, g->y_ld, g->instance);
     MRI3D_REQUIRE(x && dout && w, MRI3D_EINVAL, "norm_act_pw_bwd: null pointer");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pw_bwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "norm_act_pw_bwd: training mode needs statistics");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pw_bwd: PReLU needs alpha");
+    if (int rc = norm_act_args_check(g, training, mean, invstd, alpha, "norm_act_pw_bwd")) return rc;
     MRI3D_REQUIRE(aligned_vec4(g->dtype, x, dx), MRI3D_EINVAL, "norm_act_pw_bwd: x and dx must be aligned to 4 elements");
     const NapPlan p = nap_plan(*g, co);
     MRI3D_REQUIRE(workspace && ws_bytes >= p.bytes && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, MRI3D_EWORKSPACE,
                   "norm_act_pw_bwd: workspace %zu < %zu (or not 8-byte aligned)", ws_bytes, p.bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
-    char* ws = static_cast<char*>(workspace);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
         if (co <= 2)
-            nap_bwd_launch<T, 2>(*g, co, training, (const T*)x, (const T*)dout, w, (T*)dx, dgamma, dbeta, dalpha, dw, dbias, a, p, ws,
-                                 s);
+            nap_bwd_launch<T, PwHeadGrad<T, 2>>(*g, p, workspace, s, training, (const T*)x, (T*)dx, {(const T*)dout, w, co, g->y_ld},
+                                                a, dgamma, dbeta, dalpha, co, dw, dbias);
         else
-            nap_bwd_launch<T, 4>(*g, co, training, (const T*)x, (const T*)dout, w, (T*)dx, dgamma, dbeta, dalpha, dw, dbias, a, p, ws,
-                                 s);
+            nap_bwd_launch<T, PwHeadGrad<T, 4>>(*g, p, workspace, s, training, (const T*)x, (T*)dx, {(const T*)dout, w, co, g->y_ld},
+                                                a, dgamma, dbeta, dalpha, co, dw, dbias);
     });
     return check_launch("norm_act_pw_bwd");
 }
@@ -1388,8 +1397,7 @@ extern "C" int mri3d_norm_act_pool_fwd(const Mri3dNormGeom* g, const Mri3dPoolGe
                   "norm_act_pool_fwd: c=%d x_ld=%d y_ld=%d instance=%d pool %dx%dx%d/%d -> %dx%dx%d not served", g->c, g->x_ld,
                   g->y_ld, g->instance, pg->di, pg->hi, pg->wi, pg->kd, pg->dout, pg->ho, pg->wo);
     MRI3D_REQUIRE(x && skip && pooled && idx, MRI3D_EINVAL, "norm_act_pool_fwd: null pointer");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pool_fwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pool_fwd: PReLU needs alpha");
+    if (int rc = norm_act_args_check(g, 0, mean, invstd, alpha, "norm_act_pool_fwd")) return rc;
     MRI3D_REQUIRE(aligned_vec4(g->dtype, x, skip, pooled) && (reinterpret_cast<uintptr_t>(idx) & 3) == 0, MRI3D_EINVAL,
                   "norm_act_pool_fwd: x, skip, pooled and idx must be aligned to 4 elements");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1412,33 +1420,6 @@ extern "C" int mri3d_norm_act_pool_fwd(const Mri3dNormGeom* g, const Mri3dPoolGe
     return check_launch("norm_act_pool_fwd");
 }
 
-template <typename T>
-static void napool_bwd_launch(const Mri3dNormGeom& g, const Mri3dPoolGeom& pg, int training, const T* x, const T* dskip,
-                              const T* dpool, const uint8_t* idx, T* dx, float* dgamma, float* dbeta, float* dalpha,
-                              const NapArgs& a, const NapPlan& p, char* ws, hipStream_t s) {
-    const typename PoolSkipGrad<T>::Args sa = {dskip, dpool, idx, g.y_ld, pg.y_ld, (unsigned)pg.wi, (unsigned)pg.hi};
-    double* part = reinterpret_cast<double*>(ws + p.part_off);
-    float* sums = reinterpret_cast<float*>(ws + p.sums_off);
-    const dim3 grid(p.nblk), blk(256);
-    const bool params = dgamma || dbeta || dalpha;
-    const bool need_sums = training || params;
-    if (need_sums) {
-        if (training || dx == nullptr)
-            hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, true, false>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
-                               dgamma, dbeta, dalpha);
-        else   // frozen statistics: dx does not wait for the sums
-            hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, true, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part,
-                               dgamma, dbeta, dalpha);
-        hipLaunchKernelGGL(norm_act_bwd_sums_kernel, dim3(cdiv(g.c, 256 / kFinQL)), dim3(256), 0, s, part, sums, g.c, p.nblk, 1);
-        if (params && !(training && dx != nullptr))
-            hipLaunchKernelGGL(norm_act_bwd_params_kernel, dim3(1), dim3(256), 0, s, sums, dgamma, dbeta, dalpha, g.alpha_n, g.c,
-                               1);
-    }
-    if (dx != nullptr && (training || !need_sums))
-        hipLaunchKernelGGL((norm_act_pool_bwd_kernel<T, false, true>), grid, blk, 0, s, x, dx, sa, a, sums, training, part, dgamma,
-                           dbeta, dalpha);
-}
-
 extern "C" int mri3d_norm_act_pool_bwd(const Mri3dNormGeom* g, const Mri3dPoolGeom* pg, int training, const void* x,
                                        const void* dskip, const void* dpool, const uint8_t* idx, const float* mean,
                                        const float* invstd, const float* gamma, const float* beta, const float* alpha, void* dx,
@@ -1450,9 +1431,7 @@ extern "C" int mri3d_norm_act_pool_bwd(const Mri3dNormGeom* g, const Mri3dPoolGe
                   g->y_ld, g->instance, pg->di, pg->hi, pg->wi, pg->kd, pg->dout, pg->ho, pg->wo);
     MRI3D_REQUIRE(x != nullptr, MRI3D_EINVAL, "norm_act_pool_bwd: null pointer");
     MRI3D_REQUIRE(dpool == nullptr || idx != nullptr, MRI3D_EINVAL, "norm_act_pool_bwd: dpool needs the index bytes");
-    MRI3D_REQUIRE((mean == nullptr) == (invstd == nullptr), MRI3D_EINVAL, "norm_act_pool_bwd: mean/invstd must both be set");
-    MRI3D_REQUIRE(!(training && mean == nullptr), MRI3D_EINVAL, "norm_act_pool_bwd: training mode needs statistics");
-    MRI3D_REQUIRE(g->act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "norm_act_pool_bwd: PReLU needs alpha");
+    if (int rc = norm_act_args_check(g, training, mean, invstd, alpha, "norm_act_pool_bwd")) return rc;
     MRI3D_REQUIRE(aligned_vec4(g->dtype, x, dx) && aligned_vec4(g->dtype, dskip, dpool) &&
                       (reinterpret_cast<uintptr_t>(idx) & 3) == 0,
                   MRI3D_EINVAL, "norm_act_pool_bwd: x, dx, dskip, dpool and idx must be aligned to 4 elements");
@@ -1461,10 +1440,10 @@ extern "C" int mri3d_norm_act_pool_bwd(const Mri3dNormGeom* g, const Mri3dPoolGe
                   "norm_act_pool_bwd: workspace %zu < %zu (or not 8-byte aligned)", ws_bytes, p.bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
-    char* ws = static_cast<char*>(workspace);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-        napool_bwd_launch<T>(*g, *pg, training, (const T*)x, (const T*)dskip, (const T*)dpool, idx, (T*)dx, dgamma, dbeta, dalpha, a,
-                             p, ws, s);
+        const typename PoolSkipGrad<T>::Args sa = {(const T*)dskip, (const T*)dpool, idx, g->y_ld, pg->y_ld, (unsigned)pg->wi,
+                                                   (unsigned)pg->hi};
+        nap_bwd_launch<T, PoolSkipGrad<T>>(*g, p, workspace, s, training, (const T*)x, (T*)dx, sa, a, dgamma, dbeta, dalpha);
     });
     return check_launch("norm_act_pool_bwd");
 }

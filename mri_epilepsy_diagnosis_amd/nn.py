@@ -105,6 +105,20 @@ def _act_spec(act):
     raise NotImplementedError("unsupported activation module %r" % (act,))
 
 
+def _batchnorm_spec(norm, alpha):
+    """(mode, leading arguments of ops.norm_act and the fused operators) for a BatchNorm3d: "batch" or "running" statistics, or
+    "sync" where a training layer takes them over all ranks."""
+    use_batch = norm.training or norm.running_mean is None
+    mode = "running" if not use_batch else ("sync" if norm.training and ops.sync_batchnorm_reducer() is not None else "batch")
+    running = (norm.running_mean, norm.running_var) if norm.track_running_stats else (None, None)
+    return mode, (norm.weight, norm.bias, alpha, *running, mode, norm.momentum, norm.eps)
+
+
+def _count_batch(norm):
+    if norm is not None and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
+        norm.num_batches_tracked.add_(1)
+
+
 def fused_norm_act(norm, act, x, out=None):
     """act(norm(x)) in one pass.  `norm` is a BatchNorm3d / InstanceNorm3d module or None; `act` an activation or None.
     `out=(buffer, channel_offset)` makes the kernel write straight into a channel slice of a wider NDHWC buffer (a
@@ -115,15 +129,8 @@ def fused_norm_act(norm, act, x, out=None):
             return x
         return ops.norm_act(x, None, None, alpha, None, None, "none", 0.1, 0.0, kind, slope, out)
     if isinstance(norm, tnn.modules.batchnorm._BatchNorm):
-        use_batch = norm.training or norm.running_mean is None
-        if norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
-            norm.num_batches_tracked.add_(1)
-        return ops.norm_act(x, norm.weight, norm.bias, alpha,
-                            norm.running_mean if norm.track_running_stats else None,
-                            norm.running_var if norm.track_running_stats else None,
-                            ("sync" if (norm.training and ops.sync_batchnorm_reducer() is not None) else "batch")
-                            if use_batch else "running",
-                            norm.momentum, norm.eps, kind, slope, out)
+        _count_batch(norm)
+        return ops.norm_act(x, *_batchnorm_spec(norm, alpha)[1], kind, slope, out)
     if isinstance(norm, tnn.modules.instancenorm._InstanceNorm):
         if norm.track_running_stats:
             raise NotImplementedError("InstanceNorm3d(track_running_stats=True) is not supported")
@@ -148,13 +155,21 @@ def _local_stats_spec(norm, act):
         return "none", (None, None, alpha, None, None, "none", 0.1, 0.0), kind, alpha, slope
     if not isinstance(norm, tnn.modules.batchnorm._BatchNorm) or norm.momentum is None:
         return None
-    use_batch = norm.training or norm.running_mean is None
-    if use_batch and norm.training and ops.sync_batchnorm_reducer() is not None:
+    mode, args = _batchnorm_spec(norm, alpha)
+    return None if mode == "sync" else (mode, args, kind, alpha, slope)
+
+
+def _fused_tail(norm, act, supported, asked, run, given):
+    """The shared end of the two folds below: run(*given, ...) where supported(*asked, ...) serves the layer, after counting the
+    batch as the layer's own forward would; None, with nothing touched, where it does not."""
+    spec = _local_stats_spec(norm, act)
+    if spec is None:
         return None
-    mode = "batch" if use_batch else "running"
-    args = (norm.weight, norm.bias, alpha, norm.running_mean if norm.track_running_stats else None,
-            norm.running_var if norm.track_running_stats else None, mode, norm.momentum, norm.eps)
-    return mode, args, kind, alpha, slope
+    mode, args, kind, alpha, slope = spec
+    if not supported(*asked, mode, kind, alpha):
+        return None
+    _count_batch(norm)
+    return run(*given, *args, act=kind, slope=slope)
 
 
 def fused_norm_act_head(norm, act, x, head):
@@ -166,15 +181,8 @@ def fused_norm_act_head(norm, act, x, head):
     cast = ops.autocast_dtype()
     if cast is not None and x.dtype != cast:   # the head's conv3d would convert its input first
         return None
-    spec = _local_stats_spec(norm, act)
-    if spec is None:
-        return None
-    mode, args, kind, alpha, slope = spec
-    if not ops.norm_act_pointwise_supported(x, head.weight, mode, kind, alpha):
-        return None
-    if mode != "none" and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
-        norm.num_batches_tracked.add_(1)
-    return ops.norm_act_pointwise(x, head.weight, head.bias, *args, act=kind, slope=slope)
+    return _fused_tail(norm, act, ops.norm_act_pointwise_supported, (x, head.weight), ops.norm_act_pointwise,
+                       (x, head.weight, head.bias))
 
 
 def fused_norm_act_pool(norm, act, x, pool):
@@ -188,15 +196,8 @@ def fused_norm_act_pool(norm, act, x, pool):
         # bf16 activations keep the two operators: measured on the bench step the fold is no faster there (DESIGN §4.6 — the
         # backward sums pass is bound by its float64 accumulation, not by the bytes the fold removes); ops.norm_act_pool serves bf16
         return None
-    spec = _local_stats_spec(norm, act)
-    if spec is None:
-        return None
-    mode, args, kind, alpha, slope = spec
-    if not ops.norm_act_pool_supported(x, pool.kernel_size, pool.stride, pool.padding, mode, kind, alpha):
-        return None
-    if mode != "none" and norm.training and norm.track_running_stats and norm.num_batches_tracked is not None:
-        norm.num_batches_tracked.add_(1)
-    return ops.norm_act_pool(x, *args, act=kind, slope=slope)
+    return _fused_tail(norm, act, ops.norm_act_pool_supported, (x, pool.kernel_size, pool.stride, pool.padding), ops.norm_act_pool,
+                       (x,))
 
 
 def conv_norm_act(conv, norm, act, x, out=None, head=None, pool=None):

@@ -989,6 +989,131 @@ def sync_batchnorm_reducer():
     return _sync_bn_reducer
 
 
+def _sync_statistics(reducer, g, x, running_mean, running_var, momentum, eps):
+    """(mean, invstd, count) over the global batch: local moments with the statistics kernel, summed over the ranks as
+    (count, sum x, sum x^2) in float64; updates the running buffers with the reduced statistics."""
+    c = g.c
+    mean_l, invstd_l = _norm_statistics("norm_act", g, x, 1, "batch", None, None, momentum, eps, None)
+    # Wire format: (count, sum(x - s), sum((x - s)^2)) per channel in float64, with the shift s = running_mean (the same on
+    # every rank: the buffers start equal and are only ever updated by this code with the reduced statistics) or 0
+    # without running statistics.  The local variance comes from the statistics kernel's own shifted float64 sums, so
+    # nothing here subtracts two large numbers once s has followed the mean (|mean| >> std: a raw E[x^2] - mean^2
+    # across ranks would lose mean^2/var digits).
+    cnt_l = float(g.n * g.vox)
+    shift = running_mean.detach().double() if running_mean is not None else torch.zeros(c, dtype=torch.float64, device=x.device)
+    m64 = mean_l.double() - shift
+    var_l = (1.0 / invstd_l.double() ** 2 - float(eps)).clamp_(min=0.0)
+    pack = torch.cat([torch.full((1,), cnt_l, dtype=torch.float64, device=x.device), cnt_l * m64,
+                      cnt_l * (var_l + m64 * m64)])
+    pack = reducer.all_reduce(pack)
+    cnt = pack[0]
+    gm_s = pack[1:1 + c] / cnt
+    gmean = gm_s + shift
+    gvar = (pack[1 + c:] / cnt - gm_s * gm_s).clamp_(min=0.0)
+    mean = gmean.to(torch.float32).contiguous()
+    invstd = torch.rsqrt(gvar + float(eps)).to(torch.float32).contiguous()
+    if running_mean is not None:
+        with torch.no_grad():
+            unb = gvar * (cnt / torch.clamp(cnt - 1.0, min=1.0))
+            running_mean.mul_(1.0 - momentum).add_(momentum * gmean.to(running_mean.dtype))
+            running_var.mul_(1.0 - momentum).add_(momentum * unb.to(running_var.dtype))
+    return mean, invstd, cnt
+
+
+def _sync_correct_dx(reducer, g, x, mean, invstd, gamma, dbeta, dgamma, cnt, dx):
+    """dx += the two mean-subtraction terms of the BatchNorm gradient over the global batch.  The two batch sums (sum dy',
+    sum dy' * xhat) are exactly what the kernel reported as d(beta), d(gamma) of the frozen-statistics formula: sum them over
+    the ranks, then apply the terms as one more per-channel affine pass over x."""
+    L = _lib.lib()
+    tot = reducer.all_reduce(torch.cat([dbeta.double(), dgamma.double()]))
+    gam = gamma.double() if gamma is not None else torch.ones(g.c, dtype=torch.float64, device=x.device)
+    a0 = (-gam * invstd.double() * tot[:g.c] / cnt).to(torch.float32).contiguous()
+    b1 = (-gam * invstd.double() ** 2 * tot[g.c:] / cnt).to(torch.float32).contiguous()
+    ones = torch.ones(g.c, dtype=torch.float32, device=x.device)
+    corr = _new(x.shape, x)
+    ga = NormGeom(g.n, g.vox, g.c, g.c, g.c, 0, ACT_NONE, 1, 0.0, 0.0, 0, g.dtype)
+    # corr = b1 * (x - mean) + a0, then dx += corr
+    check(L.mri3d_norm_act_fwd(ctypes.byref(ga), _ptr(x), _ptr(mean), _ptr(ones), _ptr(b1), _ptr(a0), None, _ptr(corr),
+                               _stream()), "norm_act_fwd")
+    check(L.mri3d_add_channels(_ptr(dx), _ptr(corr), _ptr(dx), g.n * g.vox, g.c, g.c, g.c, g.c, g.dtype, _stream()),
+          "add_channels")
+
+
+def _norm_geom(x, x_ld, y_ld, act_code, alpha, slope, eps, instance=0, group_c=0):
+    """NormGeom of act(norm(x)): voxel pitches x_ld (x / dx) and y_ld (the output / its gradient).  alpha_n counts PReLU's
+    slopes; 0, which nothing serves, when PReLU comes without them."""
+    n, c, d, h, w = x.shape
+    alpha_n = 1 if act_code != ACT_PRELU else (alpha.numel() if alpha is not None else 0)
+    return NormGeom(n, d * h * w, c, x_ld, y_ld, instance, act_code, alpha_n, float(slope), float(eps), group_c, _dt(x))
+
+
+def _repitched(g, x_ld, y_ld):
+    return NormGeom(g.n, g.vox, g.c, x_ld, y_ld, g.instance, g.act, g.alpha_n, g.slope, g.eps, g.group_c, g.dtype)
+
+
+def _norm_statistics(who, g, x, groups, mode, running_mean, running_var, momentum, eps, fused_stats):
+    """(mean, invstd) per (group, channel) for mode "batch" (computed here; running buffers, where given, are updated), "running"
+    (from the buffers) or "none" (None, None).  groups: 1, or the batch size for instance / group statistics; fused_stats: None,
+    or the partials of the producing conv's epilogue."""
+    if mode == "none":
+        return None, None
+    if mode == "running":
+        return (running_mean.detach().to(torch.float32).contiguous(),
+                torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous())
+    if mode != "batch":
+        raise RuntimeError("%s: statistics mode %r is not served" % (who, mode))
+    L = _lib.lib()
+    c = g.c
+    g = _repitched(g, g.x_ld, g.x_ld)   # the statistics entry points: y_ld is a pitch of c channels
+    mean = torch.empty(groups * c, dtype=torch.float32, device=x.device)
+    invstd = torch.empty(groups * c, dtype=torch.float32, device=x.device)
+    if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
+        # the producing conv's epilogue already summed (y - bias), (y - bias)^2 per channel: only the finalize kernel runs
+        part, blocks, shift = fused_stats
+        with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
+            check(L.mri3d_norm_stats_from_partials(ctypes.byref(g), _ptr(part), blocks, _ptr(shift), _ptr(mean), _ptr(invstd),
+                                                   _ptr(running_mean), _ptr(running_var), float(momentum), _stream()),
+                  "norm_stats_from_partials")
+    else:
+        ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(g)), x.device)
+        with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, g.n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
+            check(L.mri3d_norm_stats(ctypes.byref(g), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(running_mean), _ptr(running_var),
+                                     float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
+    return mean, invstd
+
+
+def _fused_stats_of(x, stats_mode, momentum):
+    """Prologue of the public wrappers: the fused BatchNorm statistics of x's producing conv, where x carries them."""
+    if momentum is None:
+        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
+    return getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+
+
+def _backward_x(who, x, g0, *grads):
+    """x as the backward kernels read it, after checking the incoming gradients' dtype."""
+    for t in grads:
+        if t is not None and t.dtype != x.dtype:
+            raise RuntimeError("%s backward: gradient dtype %s does not match activation dtype %s" % (who, t.dtype, x.dtype))
+    if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
+        x = x.contiguous(memory_format=CL3D)
+    return x
+
+
+def _grad_slots(ctx, saved):
+    """(sinks, grads) for the parameter gradients a backward kernel writes.  saved: what forward kept of ctx.params, inputs 1..
+    of the function, None where a gradient cannot exist.  A wanted gradient goes to its fresh sink view, else to a new tensor."""
+    params, want = ctx.params, [t is not None and ctx.needs_input_grad[1 + i] for i, t in enumerate(saved)]
+    sinks = [_sink_take(p) if wt else None for p, wt in zip(params, want)]
+    grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
+             for sk, t, wt in zip(sinks, saved, want)]
+    return sinks, grads
+
+
+def _grad_slots_done(ctx, grads, sinks):
+    """What backward returns for the parameters of `_grad_slots`."""
+    return tuple(_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks))
+
+
 class _NormActFn(torch.autograd.Function):
     """y = act(gamma * (x - mean) / sqrt(var + eps) + beta) with batch, instance, running or no statistics."""
 
@@ -1004,7 +1129,6 @@ class _NormActFn(torch.autograd.Function):
         x, x_ld = _nd(x)
         n, c, d, h, w = x.shape
         act_code = _ACT_CODES[act]
-        alpha_n = alpha.numel() if (act_code == ACT_PRELU) else 1
         instance = 1 if stats_mode in ("instance", "group") else 0
         if stats_mode == "group" and (group_c <= 0 or c % group_c):
             raise RuntimeError("group norm: channels per group %d must divide C=%d" % (group_c, c))
@@ -1019,73 +1143,23 @@ class _NormActFn(torch.autograd.Function):
                 raise RuntimeError("norm_act(out=): buffer %s cannot hold a %s slice at channel %d"
                                    % (tuple(buf.shape), tuple(x.shape), y_off))
             y = _slice_view(buf, y_off, c)
-        g = NormGeom(n, d * h * w, c, x_ld, y_ld, instance, act_code, alpha_n, float(slope), float(eps), group_c, _dt(x))
-        mean = invstd = None
-        if stats_mode in ("batch", "instance", "group"):
-            groups = n if instance else 1
-            mean = torch.empty(groups * c, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(groups * c, dtype=torch.float32, device=x.device)
-            upd = stats_mode == "batch" and running_mean is not None
-            if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
-                # the producing conv's epilogue already summed (y - bias), (y - bias)^2 per channel: only the finalize kernel runs
-                part, blocks, shift = fused_stats
-                with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
-                    check(L.mri3d_norm_stats_from_partials(ctypes.byref(g), _ptr(part), blocks, _ptr(shift), _ptr(mean),
-                                                           _ptr(invstd), _ptr(running_mean) if upd else None,
-                                                           _ptr(running_var) if upd else None, float(momentum), _stream()),
-                          "norm_stats_from_partials")
-            else:
-                ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(g)), x.device)
-                with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
-                    check(L.mri3d_norm_stats(ctypes.byref(g), _ptr(x), _ptr(mean), _ptr(invstd),
-                                             _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None,
-                                             float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
-        elif stats_mode == "sync":
-            # local moments with the statistics kernel, summed over the ranks as (count, sum x, sum x^2) in float64
-            reducer = _sync_bn_reducer
-            if reducer is None:
+        g = _norm_geom(x, x_ld, y_ld, act_code, alpha, slope, eps, instance, group_c)
+        ctx.training_stats = stats_mode in ("batch", "instance", "group")
+        ctx.sync = _sync_bn_reducer if stats_mode == "sync" else None
+        if stats_mode == "sync":
+            if ctx.sync is None:
                 raise RuntimeError("norm_act(stats_mode='sync') needs ops.set_sync_batchnorm(reducer)")
-            mean_l = torch.empty(c, dtype=torch.float32, device=x.device)
-            invstd_l = torch.empty(c, dtype=torch.float32, device=x.device)
-            ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(g)), x.device)
-            with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
-                check(L.mri3d_norm_stats(ctypes.byref(g), _ptr(x), _ptr(mean_l), _ptr(invstd_l), None, None, float(momentum),
-                                         _ptr(ws), ws.numel(), _stream()), "norm_stats")
-            # Wire format: (count, sum(x - s), sum((x - s)^2)) per channel in float64, with the shift s = running_mean (the same on
-            # every rank: the buffers start equal and are only ever updated by this code with the reduced statistics) or 0
-            # without running statistics.  The local variance comes from the statistics kernel's own shifted float64 sums, so
-            # nothing here subtracts two large numbers once s has followed the mean (|mean| >> std: a raw E[x^2] - mean^2
-            # across ranks would lose mean^2/var digits).
-            cnt_l = float(n * g.vox)
-            shift = running_mean.detach().double() if running_mean is not None else torch.zeros(c, dtype=torch.float64, device=x.device)
-            m64 = mean_l.double() - shift
-            var_l = (1.0 / invstd_l.double() ** 2 - float(eps)).clamp_(min=0.0)
-            pack = torch.cat([torch.full((1,), cnt_l, dtype=torch.float64, device=x.device), cnt_l * m64,
-                              cnt_l * (var_l + m64 * m64)])
-            pack = reducer.all_reduce(pack)
-            cnt = pack[0]
-            gm_s = pack[1:1 + c] / cnt
-            gmean = gm_s + shift
-            gvar = (pack[1 + c:] / cnt - gm_s * gm_s).clamp_(min=0.0)
-            mean = gmean.to(torch.float32).contiguous()
-            invstd = torch.rsqrt(gvar + float(eps)).to(torch.float32).contiguous()
-            if running_mean is not None:
-                with torch.no_grad():
-                    unb = gvar * (cnt / torch.clamp(cnt - 1.0, min=1.0))
-                    running_mean.mul_(1.0 - momentum).add_(momentum * gmean.to(running_mean.dtype))
-                    running_var.mul_(1.0 - momentum).add_(momentum * unb.to(running_var.dtype))
-            ctx.sync_count = cnt
-        elif stats_mode == "running":
-            mean = running_mean.detach().to(torch.float32).contiguous()
-            invstd = torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous()
+            mean, invstd, ctx.sync_count = _sync_statistics(ctx.sync, g, x, running_mean, running_var, momentum, eps)
+        else:   # instance and group: batch statistics of n groups, without running buffers
+            mode = "batch" if ctx.training_stats else (stats_mode if stats_mode == "running" else "none")
+            mean, invstd = _norm_statistics("norm_act", g, x, n if instance else 1, mode, None if instance else running_mean,
+                                            None if instance else running_var, momentum, eps, fused_stats)
         with _timed(lambda: "norm_act_fwd c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": 2 * _esz(x) * x.numel()}):
             check(L.mri3d_norm_act_fwd(ctypes.byref(g), _ptr(x), _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
                                        _ptr(alpha) if act_code == ACT_PRELU else None, _ptr(y), _stream()),
                   "norm_act_fwd")
         ctx.save_for_backward(x, mean, invstd, gamma, beta, alpha)
         ctx.geom = g
-        ctx.training_stats = stats_mode in ("batch", "instance", "group")
-        ctx.sync = _sync_bn_reducer if stats_mode == "sync" else None
         return y
 
     @staticmethod
@@ -1094,34 +1168,17 @@ class _NormActFn(torch.autograd.Function):
         x, mean, invstd, gamma, beta, alpha = ctx.saved_tensors
         g0 = ctx.geom
         dy, dy_ld = _nd(dy)
-        dx = _new(x.shape, x) if g0.x_ld == g0.c else None
-        if dx is None:  # dx shares x's pitch in the kernel: give it a dense x instead
-            x = x.contiguous(memory_format=CL3D)
-            dx = _new(x.shape, x)
-        if dy.dtype != x.dtype:
-            raise RuntimeError("norm_act backward: gradient dtype %s does not match activation dtype %s" % (dy.dtype, x.dtype))
-        g = NormGeom(g0.n, g0.vox, g0.c, g0.c, dy_ld, g0.instance, g0.act, g0.alpha_n, g0.slope, g0.eps, g0.group_c, g0.dtype)
-        pg, pb, pa = ctx.params
+        x = _backward_x("norm_act", x, g0, dy)
+        dx = _new(x.shape, x)
+        g = _repitched(g0, g0.c, dy_ld)
         prelu = g.act == ACT_PRELU
-        want = (gamma is not None and ctx.needs_input_grad[1], beta is not None and ctx.needs_input_grad[2],
-                prelu and ctx.needs_input_grad[3])
-        sg = _sink_take(pg) if want[0] else None
-        sb = _sink_take(pb) if want[1] else None
-        sa = _sink_take(pa) if want[2] else None
-        dgamma = (sg if sg is not None else torch.empty_like(gamma)) if want[0] else None
-        dbeta = (sb if sb is not None else torch.empty_like(beta)) if want[1] else None
-        dalpha = (sa if sa is not None else torch.empty_like(alpha)) if want[2] else None
+        sinks, grads = _grad_slots(ctx, (gamma, beta, alpha if prelu else None))
+        dgamma_k, dbeta_k, dalpha = grads
         sync = ctx.sync
         if sync is not None:
-            # the two batch sums of the BatchNorm gradient (sum dy', sum dy' * xhat) are exactly what the kernel reports as
-            # d(beta), d(gamma) of the frozen-statistics formula: take them locally, sum them over the ranks, then apply the
-            # two mean-subtraction terms as one more per-channel affine pass over x
-            c_ = g.c
-            s1 = dbeta if dbeta is not None else torch.empty(c_, dtype=torch.float32, device=x.device)
-            s2 = dgamma if dgamma is not None else torch.empty(c_, dtype=torch.float32, device=x.device)
-            dbeta_k, dgamma_k = s1, s2
-        else:
-            dbeta_k, dgamma_k = dbeta, dgamma
+            # the kernel's d(gamma), d(beta) double as the batch sums of _sync_correct_dx: it writes them even where unwanted
+            dbeta_k = dbeta_k if dbeta_k is not None else torch.empty(g.c, dtype=torch.float32, device=x.device)
+            dgamma_k = dgamma_k if dgamma_k is not None else torch.empty(g.c, dtype=torch.float32, device=x.device)
         ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(g)), x.device)
         with _timed(lambda: "norm_act_bwd c%d vox%d n%d" % (g.c, g.vox, g.n), lambda: {"flops": 0.0, "bytes": 5 * _esz(x) * x.numel()}):
             check(L.mri3d_norm_act_bwd(ctypes.byref(g), 1 if ctx.training_stats else 0, _ptr(x), _ptr(dy), _ptr(mean),
@@ -1129,53 +1186,39 @@ class _NormActFn(torch.autograd.Function):
                                        _ptr(dgamma_k), _ptr(dbeta_k), _ptr(dalpha), _ptr(ws), ws.numel(), _stream()),
                   "norm_act_bwd")
         if sync is not None:
-            tot = sync.all_reduce(torch.cat([dbeta_k.double(), dgamma_k.double()]))
-            cnt = ctx.sync_count
-            gam = gamma.double() if gamma is not None else torch.ones(g.c, dtype=torch.float64, device=x.device)
-            a0 = (-gam * invstd.double() * tot[:g.c] / cnt).to(torch.float32).contiguous()
-            b1 = (-gam * invstd.double() ** 2 * tot[g.c:] / cnt).to(torch.float32).contiguous()
-            ones = torch.ones(g.c, dtype=torch.float32, device=x.device)
-            corr = _new(x.shape, x)
-            ga = NormGeom(g.n, g.vox, g.c, g.c, g.c, 0, ACT_NONE, 1, 0.0, 0.0, 0, g.dtype)
-            # corr = b1 * (x - mean) + a0, then dx += corr
-            check(L.mri3d_norm_act_fwd(ctypes.byref(ga), _ptr(x), _ptr(mean), _ptr(ones), _ptr(b1), _ptr(a0), None, _ptr(corr),
-                                       _stream()), "norm_act_fwd")
-            check(L.mri3d_add_channels(_ptr(dx), _ptr(corr), _ptr(dx), g.n * g.vox, g.c, g.c, g.c, g.c, g.dtype, _stream()),
-                  "add_channels")
-        return (dx, _sink_done(pg, dgamma, sg), _sink_done(pb, dbeta, sb), _sink_done(pa, dalpha, sa), None, None, None, None,
-                None, None, None, None, None, None)
+            _sync_correct_dx(sync, g, x, mean, invstd, gamma, dbeta_k, dgamma_k, ctx.sync_count, dx)
+        return (dx, *_grad_slots_done(ctx, grads, sinks), None, None, None, None, None, None, None, None, None, None)
 
 
 def norm_act(x, gamma=None, beta=None, alpha=None, running_mean=None, running_var=None, stats_mode="batch",
              momentum=0.1, eps=1e-5, act=None, slope=0.01, out=None, group_c=0):
-    if momentum is None:
-        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
-    fused = getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+    fused = _fused_stats_of(x, stats_mode, momentum)
     return _NormActFn.apply(x, gamma, beta, alpha, running_mean, running_var, stats_mode, momentum, eps, act, slope, out,
                             group_c, fused)
 
 
-def _head_geom(x, x_ld, o_ld, act_code, alpha, slope, eps):
-    n, c, d, h, w = x.shape
-    alpha_n = alpha.numel() if act_code == ACT_PRELU else 1
-    return NormGeom(n, d * h * w, c, x_ld, o_ld, 0, act_code, alpha_n, float(slope), float(eps), 0, _dt(x))
+def _fusable_x_ld(x, stats_mode, act):
+    """What the two `*_supported` predicates ask of x, the statistics and the activation before their native predicate: the
+    pitch x will be read with, or None where the fused operators do not serve the call."""
+    if stats_mode not in ("batch", "running", "none") or act not in _ACT_CODES:
+        return None
+    if not (x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)):
+        return None
+    x_ld = _pitch_of(x)
+    if x_ld is None:
+        return x.shape[1]          # _nd makes a dense copy
+    return None if x.data_ptr() % (4 * x.element_size()) else x_ld
 
 
 def norm_act_pointwise_supported(x, weight, stats_mode="batch", act=None, alpha=None):
     """True when `norm_act_pointwise` serves act(norm(x)) followed by the 1x1x1 convolution `weight` (co, c, 1, 1, 1) as one
     operator: the native predicate on the geometry, plus what only the caller can see (statistics mode, memory layout)."""
-    if stats_mode not in ("batch", "running", "none") or act not in _ACT_CODES:
-        return False
-    if not (x.is_cuda and x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)):
+    x_ld = _fusable_x_ld(x, stats_mode, act) if x.is_cuda else None
+    if x_ld is None:
         return False
     if weight.dim() != 5 or tuple(weight.shape[2:]) != (1, 1, 1) or weight.shape[1] != x.shape[1] or weight.dtype != torch.float32:
         return False
-    x_ld = _pitch_of(x)
-    if x_ld is None:
-        x_ld = x.shape[1]          # _nd makes a dense copy
-    elif x.data_ptr() % (4 * x.element_size()):
-        return False
-    g = _head_geom(x, x_ld, weight.shape[0], _ACT_CODES[act], alpha if alpha is not None else weight, 0.0, 0.0)
+    g = _norm_geom(x, x_ld, weight.shape[0], _ACT_CODES[act], alpha, 0.0, 0.0)
     return bool(_lib.lib().mri3d_norm_act_pw_supported(ctypes.byref(g), weight.shape[0]))
 
 
@@ -1195,34 +1238,12 @@ class _NormActPointwiseFn(torch.autograd.Function):
         co = weight.shape[0]
         act_code = _ACT_CODES[act]
         wm = weight.contiguous()
-        g = _head_geom(x, x_ld, co, act_code, alpha, slope, eps)
+        g = _norm_geom(x, x_ld, co, act_code, alpha, slope, eps)
         if not L.mri3d_norm_act_pw_supported(ctypes.byref(g), co):
             raise RuntimeError("norm_act_pointwise: c=%d co=%d pitch %d is not served (ask norm_act_pointwise_supported first)"
                                % (c, co, x_ld))
-        mean = invstd = None
-        gn = _head_geom(x, x_ld, x_ld, act_code, alpha, slope, eps)   # the statistics entry points: y_ld is a pitch of c channels
-        if stats_mode == "batch":
-            mean = torch.empty(c, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-            upd = running_mean is not None
-            if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
-                part, blocks, shift = fused_stats
-                with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
-                    check(L.mri3d_norm_stats_from_partials(ctypes.byref(gn), _ptr(part), blocks, _ptr(shift), _ptr(mean),
-                                                           _ptr(invstd), _ptr(running_mean) if upd else None,
-                                                           _ptr(running_var) if upd else None, float(momentum), _stream()),
-                          "norm_stats_from_partials")
-            else:
-                ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(gn)), x.device)
-                with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
-                    check(L.mri3d_norm_stats(ctypes.byref(gn), _ptr(x), _ptr(mean), _ptr(invstd),
-                                             _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None,
-                                             float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
-        elif stats_mode == "running":
-            mean = running_mean.detach().to(torch.float32).contiguous()
-            invstd = torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous()
-        elif stats_mode != "none":
-            raise RuntimeError("norm_act_pointwise: statistics mode %r is not served" % (stats_mode,))
+        mean, invstd = _norm_statistics("norm_act_pointwise", g, x, 1, stats_mode, running_mean, running_var, momentum, eps,
+                                        fused_stats)
         out = _new((n, co, d, h, w), x)
         with _timed(lambda: "norm_act_pw_fwd c%d->%d vox%d n%d" % (c, co, g.vox, n),
                     lambda: {"flops": 2.0 * co * c * n * g.vox, "bytes": _esz(x) * (x.numel() + out.numel())}):
@@ -1241,21 +1262,11 @@ class _NormActPointwiseFn(torch.autograd.Function):
         g0 = ctx.geom
         co = wm.shape[0]
         dout, o_ld = _nd(dout)
-        if dout.dtype != x.dtype:
-            raise RuntimeError("norm_act_pointwise backward: gradient dtype %s does not match activation dtype %s" % (dout.dtype, x.dtype))
-        if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
-            x = x.contiguous(memory_format=CL3D)
-        g = NormGeom(g0.n, g0.vox, g0.c, g0.c, o_ld, 0, g0.act, g0.alpha_n, g0.slope, g0.eps, 0, g0.dtype)
-        pg, pb, pa, pw, pbias = ctx.params
+        x = _backward_x("norm_act_pointwise", x, g0, dout)
+        g = _repitched(g0, g0.c, o_ld)
         prelu = g.act == ACT_PRELU
-        need = ctx.needs_input_grad
-        want = (gamma is not None and need[1], beta is not None and need[2], prelu and need[3], need[4],
-                pbias is not None and need[5])
-        srcs = (gamma, beta, alpha, wm, pbias)
-        sinks = [_sink_take(p) if wt else None for p, wt in zip(ctx.params, want)]
-        grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
-                 for sk, t, wt in zip(sinks, srcs, want)]
-        dx = _new(x.shape, x) if need[0] else None
+        sinks, grads = _grad_slots(ctx, (gamma, beta, alpha if prelu else None, wm, ctx.params[4]))
+        dx = _new(x.shape, x) if ctx.needs_input_grad[0] else None
         ws = _workspace(L.mri3d_norm_act_pw_workspace_bytes(ctypes.byref(g), co), x.device)
         # training statistics: x and dout are read twice and dx written once; frozen statistics: one read
         reads = 2 if ctx.training_stats else 1
@@ -1266,47 +1277,37 @@ class _NormActPointwiseFn(torch.autograd.Function):
                                           _ptr(invstd), _ptr(gamma), _ptr(beta), _ptr(alpha) if prelu else None, _ptr(wm),
                                           _ptr(dx), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), _ptr(grads[3]),
                                           _ptr(grads[4]), _ptr(ws), ws.numel(), _stream()), "norm_act_pw_bwd")
-        outs = [_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks)]
-        return (dx, outs[0], outs[1], outs[2], outs[3], outs[4], None, None, None, None, None, None, None, None)
+        return (dx, *_grad_slots_done(ctx, grads, sinks), None, None, None, None, None, None, None, None)
 
 
 def norm_act_pointwise(x, weight, bias=None, gamma=None, beta=None, alpha=None, running_mean=None, running_var=None,
                        stats_mode="batch", momentum=0.1, eps=1e-5, act=None, slope=0.01):
     """conv3d(norm_act(x, ...), weight, bias) for a 1x1x1 `weight` with at most four output channels, as one operator (see
     `norm_act_pointwise_supported`); the producer's fused BatchNorm statistics are picked up from x as `norm_act` does."""
-    if momentum is None:
-        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
-    fused = getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+    fused = _fused_stats_of(x, stats_mode, momentum)
     return _NormActPointwiseFn.apply(x, gamma, beta, alpha, weight, bias, running_mean, running_var, stats_mode, momentum, eps,
                                      act, slope, fused)
 
 
-def _pool_tail_geoms(x, x_ld, s_ld, p_ld, kernel, stride, padding, act_code, alpha, slope, eps):
-    """(NormGeom, PoolGeom, pooled extents) of act(norm(x)) followed by a max pool: pitches x_ld (x / dx), s_ld (skip / dskip),
+def _pool_tail_geom(x, s_ld, p_ld, kernel, stride, padding):
+    """(PoolGeom, pooled extents) of the max pool that follows act(norm(x)): voxel pitches s_ld (its input: skip / dskip) and
     p_ld (pooled / dpool)."""
     n, c, d, h, w = x.shape
     do, ho, wo = (_pool_out(i, k, s, p, False) for i, k, s, p in zip((d, h, w), kernel, stride, padding))
-    alpha_n = alpha.numel() if (act_code == ACT_PRELU and alpha is not None) else 1
-    g = NormGeom(n, d * h * w, c, x_ld, s_ld, 0, act_code, alpha_n, float(slope), float(eps), 0, _dt(x))
-    pg = PoolGeom(n, d, h, w, do, ho, wo, c, *kernel, *stride, *padding, s_ld, c if p_ld is None else p_ld, _dt(x))
-    return g, pg, (do, ho, wo)
+    return PoolGeom(n, d, h, w, do, ho, wo, c, *kernel, *stride, *padding, s_ld, p_ld, _dt(x)), (do, ho, wo)
 
 
 def norm_act_pool_supported(x, kernel_size=2, stride=None, padding=0, stats_mode="batch", act=None, alpha=None):
     """True when `norm_act_pool` serves act(norm(x)) followed by max_pool3d_skip as one operator: the native predicate on the two
     geometries (a host-only decision: x may live anywhere), plus what only the caller can see (statistics mode, memory layout)."""
-    if stats_mode not in ("batch", "running", "none") or act not in _ACT_CODES:
-        return False
-    if not (x.dim() == 5 and x.dtype in (torch.float32, torch.bfloat16)):
+    x_ld = _fusable_x_ld(x, stats_mode, act)
+    if x_ld is None:
         return False
     k = _triple(kernel_size)
     s = _triple(stride) if stride is not None else k
-    x_ld = _pitch_of(x)
-    if x_ld is None:
-        x_ld = x.shape[1]          # _nd makes a dense copy
-    elif x.data_ptr() % (4 * x.element_size()):
-        return False
-    g, pg, out = _pool_tail_geoms(x, x_ld, x.shape[1], None, k, s, _triple(padding), _ACT_CODES[act], alpha, 0.0, 0.0)
+    c = x.shape[1]
+    g = _norm_geom(x, x_ld, c, _ACT_CODES[act], alpha, 0.0, 0.0)
+    pg, out = _pool_tail_geom(x, c, c, k, s, _triple(padding))
     if min(out) <= 0:
         return False
     return bool(_lib.lib().mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)))
@@ -1327,34 +1328,13 @@ class _NormActPoolFn(torch.autograd.Function):
         n, c, d, h, w = x.shape
         act_code = _ACT_CODES[act]
         two = (2, 2, 2)
-        g, pg, (do, ho, wo) = _pool_tail_geoms(x, x_ld, c, c, two, two, (0, 0, 0), act_code, alpha, slope, eps)
+        g = _norm_geom(x, x_ld, c, act_code, alpha, slope, eps)
+        pg, (do, ho, wo) = _pool_tail_geom(x, c, c, two, two, (0, 0, 0))
         if not L.mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)):
             raise RuntimeError("norm_act_pool: c=%d pitch %d extents %s is not served (ask norm_act_pool_supported first)"
                                % (c, x_ld, (d, h, w)))
-        mean = invstd = None
-        gn = _head_geom(x, x_ld, x_ld, act_code, alpha, slope, eps)   # the statistics entry points
-        if stats_mode == "batch":
-            mean = torch.empty(c, dtype=torch.float32, device=x.device)
-            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
-            upd = running_mean is not None
-            if fused_stats is not None and fused_stats[0].numel() == fused_stats[1] * c * 2:
-                part, blocks, shift = fused_stats
-                with _timed(lambda: "norm_stats(from conv partials) c%d" % c, lambda: {"flops": 0.0, "bytes": 8.0 * part.numel()}):
-                    check(L.mri3d_norm_stats_from_partials(ctypes.byref(gn), _ptr(part), blocks, _ptr(shift), _ptr(mean),
-                                                           _ptr(invstd), _ptr(running_mean) if upd else None,
-                                                           _ptr(running_var) if upd else None, float(momentum), _stream()),
-                          "norm_stats_from_partials")
-            else:
-                ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(gn)), x.device)
-                with _timed(lambda: "norm_stats c%d vox%d n%d" % (c, g.vox, n), lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel()}):
-                    check(L.mri3d_norm_stats(ctypes.byref(gn), _ptr(x), _ptr(mean), _ptr(invstd),
-                                             _ptr(running_mean) if upd else None, _ptr(running_var) if upd else None,
-                                             float(momentum), _ptr(ws), ws.numel(), _stream()), "norm_stats")
-        elif stats_mode == "running":
-            mean = running_mean.detach().to(torch.float32).contiguous()
-            invstd = torch.rsqrt(running_var.detach().to(torch.float32) + eps).contiguous()
-        elif stats_mode != "none":
-            raise RuntimeError("norm_act_pool: statistics mode %r is not served" % (stats_mode,))
+        mean, invstd = _norm_statistics("norm_act_pool", g, x, 1, stats_mode, running_mean, running_var, momentum, eps,
+                                        fused_stats)
         skip = _new(x.shape, x)
         pooled = _new((n, c, do, ho, wo), x)
         idx = torch.empty(pooled.numel(), dtype=torch.uint8, device=x.device)
@@ -1381,9 +1361,8 @@ class _NormActPoolFn(torch.autograd.Function):
         n, c, d, h, w = x.shape
         s_ld = p_ld = c
         for name, t, shape in (("pooled", dpool, ctx.pooled_shape), ("skip", dskip, tuple(x.shape))):
-            if t is not None and (tuple(t.shape) != shape or t.dtype != x.dtype):
-                raise RuntimeError("norm_act_pool backward: %s gradient %s %s does not match %s %s"
-                                   % (name, tuple(t.shape), t.dtype, shape, x.dtype))
+            if t is not None and tuple(t.shape) != shape:
+                raise RuntimeError("norm_act_pool backward: %s gradient %s does not match %s" % (name, tuple(t.shape), shape))
         if dskip is not None:
             dskip, s_ld = _nd(dskip)
             if s_ld % 4 or dskip.data_ptr() % (4 * dskip.element_size()):
@@ -1392,19 +1371,13 @@ class _NormActPoolFn(torch.autograd.Function):
             dpool, p_ld = _nd(dpool)
             if p_ld % 4 or dpool.data_ptr() % (4 * dpool.element_size()):
                 dpool, p_ld = dpool.contiguous(memory_format=CL3D), c
-        if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
-            x = x.contiguous(memory_format=CL3D)
+        x = _backward_x("norm_act_pool", x, g0, dpool, dskip)
         two = (2, 2, 2)
-        g, pg, _ = _pool_tail_geoms(x, c, s_ld, p_ld, two, two, (0, 0, 0), g0.act, alpha, g0.slope, g0.eps)
-        pg_, pb_, pa_ = ctx.params
+        g = _repitched(g0, c, s_ld)
+        pg, _ = _pool_tail_geom(x, s_ld, p_ld, two, two, (0, 0, 0))
         prelu = g.act == ACT_PRELU
-        need = ctx.needs_input_grad
-        want = (gamma is not None and need[1], beta is not None and need[2], prelu and need[3])
-        srcs = (gamma, beta, alpha)
-        sinks = [_sink_take(p) if wt else None for p, wt in zip(ctx.params, want)]
-        grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
-                 for sk, t, wt in zip(sinks, srcs, want)]
-        dx = _new(x.shape, x) if need[0] else None
+        sinks, grads = _grad_slots(ctx, (gamma, beta, alpha if prelu else None))
+        dx = _new(x.shape, x) if ctx.needs_input_grad[0] else None
         ws = _workspace(L.mri3d_norm_act_pool_workspace_bytes(ctypes.byref(g), ctypes.byref(pg)), x.device)
         # per pass: x and dskip read, dpool and the index bytes read once (each is shared by a window's eight voxels); training
         # statistics take the sums pass and the dx pass, frozen statistics one pass; dx written once
@@ -1419,17 +1392,14 @@ class _NormActPoolFn(torch.autograd.Function):
                                             _ptr(dskip), _ptr(dpool), _ptr(idx), _ptr(mean), _ptr(invstd), _ptr(gamma),
                                             _ptr(beta), _ptr(alpha) if prelu else None, _ptr(dx), _ptr(grads[0]), _ptr(grads[1]),
                                             _ptr(grads[2]), _ptr(ws), ws.numel(), _stream()), "norm_act_pool_bwd")
-        outs = [_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks)]
-        return (dx, outs[0], outs[1], outs[2], None, None, None, None, None, None, None, None)
+        return (dx, *_grad_slots_done(ctx, grads, sinks), None, None, None, None, None, None, None, None)
 
 
 def norm_act_pool(x, gamma=None, beta=None, alpha=None, running_mean=None, running_var=None, stats_mode="batch",
                   momentum=0.1, eps=1e-5, act=None, slope=0.01):
     """(max_pool3d(a, 2), a) for a = norm_act(x, ...) as one operator (see `norm_act_pool_supported`): the second output is the
     skip connection's tensor.  The producer's fused BatchNorm statistics are picked up from x as `norm_act` does."""
-    if momentum is None:
-        raise RuntimeError("cumulative moving average (momentum=None) is not supported")
-    fused = getattr(x, "_mri3d_bn_stats", None) if stats_mode == "batch" else None
+    fused = _fused_stats_of(x, stats_mode, momentum)
     return _NormActPoolFn.apply(x, gamma, beta, alpha, running_mean, running_var, stats_mode, momentum, eps, act, slope, fused)
 
 

@@ -292,6 +292,111 @@ int main() {
         s3.sh = 1; s3.ho = 191;   // six taps at stride 1 reach a row through six taps: more than the kernel's three slots
         EXPECT(mri3d_convpair_supported(&first, &s3) == 0);
     }
+    {   // norm + activation and its two folds (pointwise head, max pool): every refusal below comes before a launch
+        Mri3dNormGeom ng;
+        memset(&ng, 0, sizeof(ng));
+        ng.n = 2; ng.vox = (int64_t)16 * 16 * 16; ng.c = 16; ng.x_ld = 16; ng.y_ld = 16; ng.act = MRI3D_ACT_PRELU; ng.alpha_n = 1;
+        ng.eps = 1e-5f; ng.dtype = MRI3D_F32;
+        Mri3dNormGeom nbad = ng;
+        nbad.alpha_n = 3;                                   // neither 1 nor c: refused by every predicate and entry point
+        float* F = (float*)A;                               // aligned to 4 elements, never dereferenced
+        void* odd = A + 4;                                  // off a 4-element boundary
+        const size_t big = (size_t)1 << 30;
+
+        // plain backward
+        EXPECT(mri3d_norm_act_bwd(nullptr, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(mri3d_norm_act_bwd(&nbad, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, nullptr, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_bwd: null pointer") != nullptr);
+        EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, F, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_bwd: mean/invstd must both be set") != nullptr);
+        EXPECT(mri3d_norm_act_bwd(&ng, 1, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_bwd: training mode needs statistics") != nullptr);
+        EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, nullptr, A, nullptr, nullptr, nullptr, A, big, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_bwd: PReLU needs alpha") != nullptr);
+        EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, 16, nullptr) == MRI3D_EWORKSPACE);
+        EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, nullptr, big, nullptr) == MRI3D_EWORKSPACE);
+
+        // pointwise head: co = 2
+        ng.y_ld = 2; nbad.y_ld = 2;
+        EXPECT(mri3d_norm_act_pw_supported(&ng, 2) == 1 && mri3d_norm_act_pw_supported(&nbad, 2) == 0 && mri3d_norm_act_pw_supported(&ng, 5) == 0);
+        EXPECT(mri3d_norm_act_pw_supported(nullptr, 2) == 0 && mri3d_norm_act_pw_workspace_bytes(nullptr, 2) == 0);
+        const size_t pw_need = mri3d_norm_act_pw_workspace_bytes(&ng, 2);
+        EXPECT(pw_need > 0 && pw_need % 8 == 0 && mri3d_norm_act_pw_workspace_bytes(&nbad, 2) == 0);
+        EXPECT(mri3d_norm_act_pw_fwd(nullptr, 2, A, nullptr, nullptr, nullptr, nullptr, F, F, nullptr, A, nullptr) == MRI3D_EINVAL);
+        EXPECT(mri3d_norm_act_pw_fwd(&nbad, 2, A, nullptr, nullptr, nullptr, nullptr, F, F, nullptr, A, nullptr) == MRI3D_ENOTSUP);
+        EXPECT(mri3d_norm_act_pw_fwd(&ng, 2, nullptr, nullptr, nullptr, nullptr, nullptr, F, F, nullptr, A, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pw_fwd: null pointer") != nullptr);
+        EXPECT(mri3d_norm_act_pw_fwd(&ng, 2, A, F, nullptr, nullptr, nullptr, F, F, nullptr, A, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pw_fwd: mean/invstd must both be set") != nullptr);
+        EXPECT(mri3d_norm_act_pw_fwd(&ng, 2, A, nullptr, nullptr, nullptr, nullptr, nullptr, F, nullptr, A, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pw_fwd: PReLU needs alpha") != nullptr);
+        EXPECT(mri3d_norm_act_pw_fwd(&ng, 2, odd, nullptr, nullptr, nullptr, nullptr, F, F, nullptr, A, nullptr) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "aligned") != nullptr);
+        auto pw_bwd = [&](const Mri3dNormGeom* gp, int training, const void* x, const float* mean, const float* alpha, void* dx, void* ws,
+                          size_t ws_bytes) {
+            return mri3d_norm_act_pw_bwd(gp, 2, training, x, A, mean, nullptr, nullptr, nullptr, alpha, F, dx, nullptr, nullptr, nullptr,
+                                         nullptr, nullptr, ws, ws_bytes, nullptr);
+        };
+        EXPECT(pw_bwd(nullptr, 0, A, nullptr, F, A, A, big) == MRI3D_EINVAL);
+        EXPECT(pw_bwd(&nbad, 0, A, nullptr, F, A, A, big) == MRI3D_ENOTSUP);
+        EXPECT(pw_bwd(&ng, 0, nullptr, nullptr, F, A, A, big) == MRI3D_EINVAL);
+        EXPECT(pw_bwd(&ng, 0, A, F, F, A, A, big) == MRI3D_EINVAL);                 // mean without invstd
+        EXPECT(pw_bwd(&ng, 1, A, nullptr, F, A, A, big) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pw_bwd: training mode needs statistics") != nullptr);
+        EXPECT(pw_bwd(&ng, 0, A, nullptr, nullptr, A, A, big) == MRI3D_EINVAL);     // PReLU without alpha
+        EXPECT(pw_bwd(&ng, 0, A, nullptr, F, odd, A, big) == MRI3D_EINVAL);         // dx off four elements
+        EXPECT(pw_bwd(&ng, 0, A, nullptr, F, A, A, pw_need - 1) == MRI3D_EWORKSPACE);
+        EXPECT(pw_bwd(&ng, 0, A, nullptr, F, A, A + 4, big) == MRI3D_EWORKSPACE);   // workspace off eight bytes
+        EXPECT(pw_bwd(&ng, 0, A, nullptr, F, A, nullptr, big) == MRI3D_EWORKSPACE);
+
+        // max-pool tail: 16^3 -> 8^3
+        ng.y_ld = 16; nbad.y_ld = 16;
+        Mri3dPoolGeom pl;
+        memset(&pl, 0, sizeof(pl));
+        pl.n = 2; pl.di = pl.hi = pl.wi = 16; pl.dout = pl.ho = pl.wo = 8; pl.c = 16; pl.kd = pl.kh = pl.kw = 2; pl.sd = pl.sh = pl.sw = 2;
+        pl.x_ld = 16; pl.y_ld = 16; pl.dtype = MRI3D_F32;
+        Mri3dPoolGeom pbad = pl;
+        pbad.kd = 3;
+        uint8_t* I = (uint8_t*)A;
+        EXPECT(mri3d_norm_act_pool_supported(&ng, &pl) == 1 && mri3d_norm_act_pool_supported(&nbad, &pl) == 0 &&
+               mri3d_norm_act_pool_supported(&ng, &pbad) == 0);
+        EXPECT(mri3d_norm_act_pool_supported(nullptr, &pl) == 0 && mri3d_norm_act_pool_supported(&ng, nullptr) == 0);
+        EXPECT(mri3d_norm_act_pool_workspace_bytes(nullptr, &pl) == 0 && mri3d_norm_act_pool_workspace_bytes(&ng, nullptr) == 0 &&
+               mri3d_norm_act_pool_workspace_bytes(&ng, &pbad) == 0);
+        const size_t pool_need = mri3d_norm_act_pool_workspace_bytes(&ng, &pl);
+        EXPECT(pool_need > 0 && pool_need % 8 == 0 && pool_need < pw_need);         // no side partials
+        auto pool_fwd = [&](const Mri3dNormGeom* gp, const Mri3dPoolGeom* pp, const void* x, const float* mean, const float* alpha,
+                            uint8_t* idx) {
+            return mri3d_norm_act_pool_fwd(gp, pp, x, mean, nullptr, nullptr, nullptr, alpha, A, A, idx, nullptr);
+        };
+        EXPECT(pool_fwd(nullptr, &pl, A, nullptr, F, I) == MRI3D_EINVAL && pool_fwd(&ng, nullptr, A, nullptr, F, I) == MRI3D_EINVAL);
+        EXPECT(pool_fwd(&nbad, &pl, A, nullptr, F, I) == MRI3D_ENOTSUP && pool_fwd(&ng, &pbad, A, nullptr, F, I) == MRI3D_ENOTSUP);
+        EXPECT(pool_fwd(&ng, &pl, nullptr, nullptr, F, I) == MRI3D_EINVAL && pool_fwd(&ng, &pl, A, nullptr, F, nullptr) == MRI3D_EINVAL);
+        EXPECT(pool_fwd(&ng, &pl, A, F, F, I) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pool_fwd: mean/invstd must both be set") != nullptr);
+        EXPECT(pool_fwd(&ng, &pl, A, nullptr, nullptr, I) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pool_fwd: PReLU needs alpha") != nullptr);
+        EXPECT(pool_fwd(&ng, &pl, odd, nullptr, F, I) == MRI3D_EINVAL && pool_fwd(&ng, &pl, A, nullptr, F, I + 1) == MRI3D_EINVAL);
+        auto pool_bwd = [&](const Mri3dNormGeom* gp, const Mri3dPoolGeom* pp, int training, const void* x, const void* dskip,
+                            const uint8_t* idx, const float* mean, const float* alpha, void* ws, size_t ws_bytes) {
+            return mri3d_norm_act_pool_bwd(gp, pp, training, x, dskip, A, idx, mean, nullptr, nullptr, nullptr, alpha, A, nullptr, nullptr,
+                                           nullptr, ws, ws_bytes, nullptr);
+        };
+        EXPECT(pool_bwd(nullptr, &pl, 0, A, A, I, nullptr, F, A, big) == MRI3D_EINVAL && pool_bwd(&ng, nullptr, 0, A, A, I, nullptr, F, A, big) == MRI3D_EINVAL);
+        EXPECT(pool_bwd(&nbad, &pl, 0, A, A, I, nullptr, F, A, big) == MRI3D_ENOTSUP && pool_bwd(&ng, &pbad, 0, A, A, I, nullptr, F, A, big) == MRI3D_ENOTSUP);
+        EXPECT(pool_bwd(&ng, &pl, 0, nullptr, A, I, nullptr, F, A, big) == MRI3D_EINVAL);
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, nullptr, nullptr, F, A, big) == MRI3D_EINVAL);       // dpool without the index bytes
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, I, F, F, A, big) == MRI3D_EINVAL);                   // mean without invstd
+        EXPECT(pool_bwd(&ng, &pl, 1, A, A, I, nullptr, F, A, big) == MRI3D_EINVAL);
+        EXPECT(strstr(mri3d_last_error(), "norm_act_pool_bwd: training mode needs statistics") != nullptr);
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, I, nullptr, nullptr, A, big) == MRI3D_EINVAL);       // PReLU without alpha
+        EXPECT(pool_bwd(&ng, &pl, 0, A, odd, I, nullptr, F, A, big) == MRI3D_EINVAL);           // dskip off four elements
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, I, nullptr, F, A, pool_need - 1) == MRI3D_EWORKSPACE);
+        EXPECT(pool_bwd(&ng, &pl, 1, A, A, I, nullptr, F, A, pool_need - 1) == MRI3D_EINVAL);   // the arguments are checked first
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, I, nullptr, F, A + 4, big) == MRI3D_EWORKSPACE);     // workspace off eight bytes
+        EXPECT(pool_bwd(&ng, &pl, 0, A, A, I, nullptr, F, nullptr, big) == MRI3D_EWORKSPACE);
+    }
     if (g_fail) {
         fprintf(stderr, "%d host checks failed\n", g_fail);
         return 1;

@@ -53,3 +53,16 @@ def test_argument_validation_without_a_device():
     args = (fake, fake, None, None, None, None, fake, fake, fake, None, None, None, None, None)
     assert L.mri3d_norm_act_pw_bwd(ctypes.byref(g), 2, 0, *args, fake, need - 1, None) == -4                                # workspace
     assert L.mri3d_norm_act_pw_bwd(ctypes.byref(g), 2, 1, *args, fake, need, None) == -1            # training needs statistics
+
+
+def test_ops_predicate_declines_prelu_without_alpha(monkeypatch):
+    """`act="prelu"` with `alpha=None` could never run: the predicate says so for every c and co (it is asked before any kernel, so
+    a host tensor that claims to be on the device is enough)."""
+    import torch
+    from mri_epilepsy_diagnosis_amd import ops
+    monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
+    x = torch.zeros(1, 16, 4, 6, 2).contiguous(memory_format=torch.channels_last_3d)
+    for co in (1, 2, 4, 16):        # co = 1: a weight of c elements, which used to stand in for a per-channel alpha
+        w = torch.zeros(co, 16, 1, 1, 1)
+        assert ops.norm_act_pointwise_supported(x, w, "batch", "prelu", torch.full((1,), 0.25)) == (co <= 4)
+        assert not ops.norm_act_pointwise_supported(x, w, "batch", "prelu", None)

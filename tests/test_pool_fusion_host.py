@@ -103,6 +103,7 @@ def test_ops_predicate_answers_for_host_tensors():
     assert ops.norm_act_pool_supported(x, 2, None, 0, "batch", "prelu", alpha)
     assert ops.norm_act_pool_supported(x.bfloat16(), 2, 2, 0, "running", "relu")
     assert ops.norm_act_pool_supported(x, 2, None, 0, "none", None)
+    assert not ops.norm_act_pool_supported(x, 2, None, 0, "batch", "prelu", None)      # PReLU without its alpha never runs
     assert not ops.norm_act_pool_supported(x, 3, 2, 0, "batch", "prelu", alpha)
     assert not ops.norm_act_pool_supported(x, 2, None, 1, "batch", "prelu", alpha)
     for mode in ("instance", "group", "sync"):
