@@ -201,6 +201,19 @@ typedef struct Mri3dNormGeom {
 
 size_t mri3d_norm_workspace_bytes(const Mri3dNormGeom* g);
 
+/* THE LAUNCH PLAN mri3d_norm_stats (MRI3D_NORM_PASS_STATS), mri3d_norm_act_fwd (_FWD) and mri3d_norm_act_bwd (_BWD) use for this
+ * geometry.  Host only: no device is needed, nothing is launched; the entry points take their plan from the same decision.
+ * align: the largest power of two <= 16 that divides the base address of every tensor the pass touches (x; x and y; x, dy and
+ * dx).  A 256-thread block is VT voxel rows x CL channel lanes of vec channels each (vec 8: bf16 forward only; CL * VT <= 256,
+ * the remaining threads idle); the grid is nblk blocks per group x cy channel chunks x groups, each group gvox voxels.  The
+ * statistics pass ignores y_ld.  Returns MRI3D_OK or the error the entry point gives for the geometry. */
+enum { MRI3D_NORM_PASS_STATS = 0, MRI3D_NORM_PASS_FWD = 1, MRI3D_NORM_PASS_BWD = 2 };
+typedef struct Mri3dNormPlanInfo {
+    int32_t vec, CL, VT, cy, nblk, groups;
+    int64_t gvox;
+} Mri3dNormPlanInfo;
+int32_t mri3d_norm_plan_query(const Mri3dNormGeom* g, int32_t pass, int32_t align, Mri3dNormPlanInfo* out);
+
 /* mean/invstd: [groups*c] floats where groups = instance ? n : 1.
  * If running_mean/running_var are non-NULL (batch mode only) they are updated in place:
  *   running = (1-momentum)*running + momentum*stat, with the unbiased variance, as torch does. */

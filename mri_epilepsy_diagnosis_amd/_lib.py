@@ -14,6 +14,7 @@ F32, BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU = 0, 1, 2, 3
 UP_NEAREST, UP_TRILINEAR = 0, 1
 PASS_FWD, PASS_DGRAD, PASS_WGRAD = 0, 1, 2
+NORM_PASS_STATS, NORM_PASS_FWD, NORM_PASS_BWD = 0, 1, 2
 
 
 class ConvGeom(Structure):
@@ -26,6 +27,10 @@ class NormGeom(Structure):
     _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("x_ld", c_int32), ("y_ld", c_int32),
                 ("instance", c_int32), ("act", c_int32), ("alpha_n", c_int32), ("slope", c_float),
                 ("eps", c_float), ("group_c", c_int32), ("dtype", c_int32)]
+
+
+class NormPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("vec", "CL", "VT", "cy", "nblk", "groups")] + [("gvox", c_int64)]
 
 
 class PoolGeom(Structure):
@@ -77,6 +82,7 @@ SIGNATURES = {
     "mri3d_convpair_workspace_bytes": (c_size_t, [POINTER(ConvGeom), POINTER(ConvGeom)]),
     "mri3d_convpair_wgrad_first": (c_int32, [POINTER(ConvGeom), POINTER(ConvGeom), _P, _P, _FP, _FP, _FP, _P, c_size_t, _P]),
     "mri3d_norm_workspace_bytes": (c_size_t, [POINTER(NormGeom)]),
+    "mri3d_norm_plan_query": (c_int32, [POINTER(NormGeom), c_int32, c_int32, POINTER(NormPlanInfo)]),
     "mri3d_norm_stats": (c_int32, [POINTER(NormGeom), _P, _FP, _FP, _FP, _FP, c_float, _P, c_size_t, _P]),
     "mri3d_norm_stats_from_partials": (c_int32, [POINTER(NormGeom), _P, c_int32, _FP, _FP, _FP, _FP, _FP, c_float, _P]),
     "mri3d_norm_act_fwd": (c_int32, [POINTER(NormGeom), _P, _FP, _FP, _FP, _FP, _FP, _P, _P]),

@@ -51,6 +51,18 @@ static NormPlan norm_plan(const Mri3dNormGeom& g, bool al, bool al16 = false) {
     return p;
 }
 
+// The plan of one pass (MRI3D_NORM_PASS_*) over tensors known by their ptr_align: the one decision mri3d_norm_stats,
+// mri3d_norm_act_fwd, mri3d_norm_act_bwd and the query mri3d_norm_plan_query all read.  The statistics pass reads x alone (y_ld
+// takes no part); only the bf16 forward moves 8 channels per lane (the float64 accumulators of the other two measured slower).
+static NormPlan norm_plan_for(const Mri3dNormGeom& g, int pass, int align) {
+    if (pass == MRI3D_NORM_PASS_STATS) {
+        Mri3dNormGeom gg = g;
+        gg.y_ld = gg.x_ld;
+        return norm_plan(gg, align_vec4(g.dtype, align));
+    }
+    return norm_plan(g, align_vec4(g.dtype, align), pass == MRI3D_NORM_PASS_FWD && align16(align));
+}
+
 size_t norm_workspace_floats(const Mri3dNormGeom& g) {
     // plan with worst-case (vec=1) block count is not needed: nblk <= kMaxStreamBlocks/groups always.
     int groups = g.instance ? g.n : 1;
@@ -119,6 +131,8 @@ norm_stats_kernel(const T* __restrict__ x, double* __restrict__ part, int C, int
     for (int j = 0; j < VEC; ++j) { s[j] = 0.0; ss[j] = 0.0; k[j] = 0.f; }
     if (active) {
         Ld<VEC>::load(xg + c0, k);  // shift = first voxel of the group: removes E[x^2]-E[x]^2 cancellation
+        // the differences are formed in double, where they are exact: a float subtraction rounds each by up to 2^-24 |x - k|, an
+        // error in the mean that does not shrink with |mean| and shows wherever few voxels share a statistic
         // four voxel rows per trip: the loads are independent, so four 16-byte requests per lane are in flight (one at a
         // time left this read-only pass at 4.2 TB/s); the sums still run in voxel order
         const int64_t step = (int64_t)gridDim.x * VT;
@@ -131,7 +145,7 @@ norm_stats_kernel(const T* __restrict__ x, double* __restrict__ part, int C, int
             for (int u = 0; u < 4; ++u)
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
-                    const double d = (double)(xv[u][j] - k[j]);
+                    const double d = (double)xv[u][j] - (double)k[j];
                     s[j] += d;
                     ss[j] = fma(d, d, ss[j]);
                 }
@@ -141,7 +155,7 @@ norm_stats_kernel(const T* __restrict__ x, double* __restrict__ part, int C, int
             Ld<VEC>::load(xg + v * ld + c0, xv);
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
-                const double d = (double)(xv[j] - k[j]);
+                const double d = (double)xv[j] - (double)k[j];
                 s[j] += d;
                 ss[j] = fma(d, d, ss[j]);
             }
@@ -1116,6 +1130,19 @@ static int norm_check(const Mri3dNormGeom* g, const char* who) {
     return MRI3D_OK;
 }
 
+extern "C" int32_t mri3d_norm_plan_query(const Mri3dNormGeom* g, int32_t pass, int32_t align, Mri3dNormPlanInfo* out) {
+    int rc = norm_check(g, "norm_plan_query");
+    if (rc) return rc;
+    MRI3D_REQUIRE(out != nullptr, MRI3D_EINVAL, "norm_plan_query: null result");
+    MRI3D_REQUIRE(pass == MRI3D_NORM_PASS_STATS || pass == MRI3D_NORM_PASS_FWD || pass == MRI3D_NORM_PASS_BWD, MRI3D_EINVAL,
+                  "norm_plan_query: unknown pass %d", pass);
+    MRI3D_REQUIRE(align > 0 && (align & (align - 1)) == 0, MRI3D_EINVAL, "norm_plan_query: align %d is no power of two", align);
+    const NormPlan p = norm_plan_for(*g, pass, align);
+    out->vec = p.vec, out->CL = p.CL, out->VT = p.VT, out->cy = p.cy, out->nblk = p.nblk, out->groups = p.groups;
+    out->gvox = p.gvox;
+    return MRI3D_OK;
+}
+
 // what every norm_act entry point asks of its statistics and activation arguments (the forward ones pass training = 0)
 static int norm_act_args_check(const Mri3dNormGeom* g, int training, const float* mean, const float* invstd, const float* alpha,
                                const char* who) {
@@ -1134,9 +1161,7 @@ extern "C" int mri3d_norm_stats(const Mri3dNormGeom* g, const void* x, float* me
     MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_norm_workspace_bytes(g), MRI3D_EWORKSPACE,
                   "norm_stats: workspace %zu < %zu", ws_bytes, mri3d_norm_workspace_bytes(g));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Mri3dNormGeom gg = *g;
-    gg.y_ld = gg.x_ld;
-    NormPlan p = norm_plan(gg, aligned_vec4(g->dtype, x));   // 8 channels per lane measured slower here (float64 accumulators)
+    NormPlan p = norm_plan_for(*g, MRI3D_NORM_PASS_STATS, ptr_align(x));
     double* part = static_cast<double*>(workspace);
     dim3 grid(p.nblk, p.cy, p.groups);
     const int tot = p.groups * g->c;
@@ -1180,7 +1205,7 @@ extern "C" int mri3d_norm_act_fwd(const Mri3dNormGeom* g, const void* x, const f
     MRI3D_REQUIRE(x && y, MRI3D_EINVAL, "norm_act_fwd: null pointer");
     if ((rc = norm_act_args_check(g, 0, mean, invstd, alpha, "norm_act_fwd"))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    NormPlan p = norm_plan(*g, aligned_vec4(g->dtype, x, y), aligned16(x, y));
+    NormPlan p = norm_plan_for(*g, MRI3D_NORM_PASS_FWD, ptr_align(x, y));
     dim3 grid(p.nblk, p.cy, p.groups);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
         const T* xf = static_cast<const T*>(x);
@@ -1205,7 +1230,7 @@ extern "C" int mri3d_norm_act_bwd(const Mri3dNormGeom* g, int training, const vo
                   "norm_act_bwd: workspace %zu < %zu", ws_bytes, mri3d_norm_workspace_bytes(g));
     hipStream_t s = static_cast<hipStream_t>(stream);
     // x/dx share pitch x_ld, dy has pitch y_ld
-    NormPlan p = norm_plan(*g, aligned_vec4(g->dtype, x, dy, dx));   // 8 channels per lane: reduce 66 -> 101 us, apply 74 -> 83 us (bf16 bench): not used
+    NormPlan p = norm_plan_for(*g, MRI3D_NORM_PASS_BWD, ptr_align(x, dy, dx));   // 8 channels per lane: reduce 66 -> 101 us, apply 74 -> 83 us (bf16 bench): not used
     dim3 grid(p.nblk, p.cy, p.groups);
     double* part = static_cast<double*>(workspace);
     float* sums = reinterpret_cast<float*>(part + (size_t)p.groups * p.nblk * g->c * 3);

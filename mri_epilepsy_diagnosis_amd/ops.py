@@ -20,8 +20,9 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, BF16, F32, PASS_DGRAD, PASS_FWD, PASS_WGRAD, UP_NEAREST,
-                   UP_TRILINEAR, ConvGeom, DiceGeom, NormGeom, PoolGeom, UpGeom, check)
+from ._lib import (ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, BF16, F32, NORM_PASS_BWD, NORM_PASS_FWD, NORM_PASS_STATS, PASS_DGRAD,
+                   PASS_FWD, PASS_WGRAD, UP_NEAREST, UP_TRILINEAR, ConvGeom, DiceGeom, NormGeom, NormPlanInfo, PoolGeom, UpGeom,
+                   check)
 
 CL3D = torch.channels_last_3d
 
@@ -361,6 +362,15 @@ def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16
     check(_lib.lib().mri3d_conv3d_route(ctypes.byref(g), pass_, int(bool(stats)), int(bool(bias)), split, second_ld, xa, ya, name, 64),
           "conv3d_route")
     return name.value.decode()
+
+
+def norm_plan(g, pass_, align=16):
+    """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
+    tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is
+    launched and no device is needed.  align: `_ptr_align` of the tensors the pass touches (x; x and y; x, dy and dx)."""
+    info = NormPlanInfo()
+    check(_lib.lib().mri3d_norm_plan_query(ctypes.byref(g), pass_, align, ctypes.byref(info)), "norm_plan_query")
+    return (info.vec, info.CL, info.VT, info.cy, info.nblk, info.groups, info.gvox)
 
 
 def conv3d_routes(xshape, wshape, stride=1, padding=0, dilation=1, dtype=F32, x_ld=None, dy_ld=None, bias=True, bn_stats=False,

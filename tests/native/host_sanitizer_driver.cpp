@@ -317,6 +317,49 @@ int main() {
         EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, A, 16, nullptr) == MRI3D_EWORKSPACE);
         EXPECT(mri3d_norm_act_bwd(&ng, 0, A, A, nullptr, nullptr, nullptr, nullptr, F, A, nullptr, nullptr, nullptr, nullptr, big, nullptr) == MRI3D_EWORKSPACE);
 
+        // plan query: refusals, then the sweep that contains every geometry of tests/norm_cases.py (channel counts, pitches,
+        // alignments, statistics groups and the voxel counts at which the block count changes class), with the plan's invariants
+        {
+            Mri3dNormPlanInfo info;
+            EXPECT(mri3d_norm_plan_query(nullptr, MRI3D_NORM_PASS_FWD, 16, &info) == MRI3D_EINVAL);
+            EXPECT(mri3d_norm_plan_query(&nbad, MRI3D_NORM_PASS_FWD, 16, &info) == MRI3D_EINVAL);
+            EXPECT(mri3d_norm_plan_query(&ng, MRI3D_NORM_PASS_FWD, 16, nullptr) == MRI3D_EINVAL);
+            EXPECT(mri3d_norm_plan_query(&ng, 3, 16, &info) == MRI3D_EINVAL);
+            EXPECT(mri3d_norm_plan_query(&ng, MRI3D_NORM_PASS_BWD, 12, &info) == MRI3D_EINVAL);
+            EXPECT(mri3d_norm_plan_query(&ng, MRI3D_NORM_PASS_BWD, 0, &info) == MRI3D_EINVAL);
+            long plans = 0;
+            const int extra_c[] = {128, 256, 260, 1024, 1028};
+            for (int ci = 1; ci <= 75; ++ci) {
+                const int c = ci <= 70 ? ci : extra_c[ci - 71];
+                for (int pad = 0; pad < 10; ++pad)
+                    for (int groups : {1, 3, 40, 1030})
+                        for (int dt = 0; dt < 2; ++dt)
+                            for (int al : {2, 4, 8, 16})
+                                for (int pass = 0; pass < 3; ++pass) {
+                                    Mri3dNormGeom q;
+                                    memset(&q, 0, sizeof(q));
+                                    q.n = groups; q.instance = groups > 1; q.c = c; q.x_ld = c + pad; q.y_ld = c + pad; q.alpha_n = 1;
+                                    q.eps = 1e-5f; q.dtype = dt; q.vox = 1;
+                                    EXPECT(mri3d_norm_plan_query(&q, pass, al, &info) == MRI3D_OK);
+                                    const int64_t row = (int64_t)8 * info.VT;
+                                    int64_t cap = 1024 / ((int64_t)info.groups * info.cy);
+                                    if (cap < 1) cap = 1;
+                                    for (int64_t gv : {(int64_t)1, row, row + 1, row * cap - 1, row * cap, row * cap + 1}) {
+                                        if (gv < 1) continue;
+                                        q.vox = gv;
+                                        EXPECT(mri3d_norm_plan_query(&q, pass, al, &info) == MRI3D_OK);
+                                        EXPECT(info.CL * info.VT <= 256 && info.CL >= 1 && info.VT >= 1 && info.nblk >= 1);
+                                        EXPECT((int64_t)info.cy * info.CL * info.vec >= c && c % info.vec == 0);
+                                        EXPECT(info.groups == groups && info.gvox == gv);
+                                        const size_t need = (size_t)info.groups * info.nblk * c * 3 * 8 + (size_t)info.groups * c * 3 * 4;
+                                        EXPECT(need <= mri3d_norm_workspace_bytes(&q));
+                                        ++plans;
+                                    }
+                                }
+            }
+            EXPECT(plans > 100000);
+        }
+
         // pointwise head: co = 2
         ng.y_ld = 2; nbad.y_ld = 2;
         EXPECT(mri3d_norm_act_pw_supported(&ng, 2) == 1 && mri3d_norm_act_pw_supported(&nbad, 2) == 0 && mri3d_norm_act_pw_supported(&ng, 5) == 0);

@@ -48,7 +48,7 @@ def test_version_and_error_string_without_gpu():
 def test_struct_layouts_match_header(tmp_path):
     """Compile the public header with gcc and compare sizeof/offsetof with the ctypes mirrors."""
     structs = {"Mri3dConvGeom": _lib.ConvGeom, "Mri3dNormGeom": _lib.NormGeom, "Mri3dPoolGeom": _lib.PoolGeom,
-               "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom}
+               "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom, "Mri3dNormPlanInfo": _lib.NormPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mri3d.h"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -85,6 +85,22 @@ def test_workspace_queries_are_host_only():
     assert L.mri3d_convpair_supported(ctypes.byref(first), ctypes.byref(second)) == 1
     assert L.mri3d_convpair_workspace_bytes(ctypes.byref(first), ctypes.byref(second)) > 0
     assert L.mri3d_convpair_supported(ctypes.byref(second), ctypes.byref(first)) == 0
+
+
+def test_norm_plan_query_is_declared_bound_and_host_only():
+    assert "mri3d_norm_plan_query" in _declared() and "mri3d_norm_plan_query" in _lib.SIGNATURES
+    src = open(HEADER).read()
+    for i, name in enumerate(("STATS", "FWD", "BWD")):
+        assert re.search(r"MRI3D_NORM_PASS_%s\s*=\s*%d\b" % (name, i), src) and getattr(_lib, "NORM_PASS_" + name) == i
+    L = _lib.lib()
+    g = _lib.NormGeom(2, 160 * 192 * 160, 16, 16, 16, 0, _lib.ACT_PRELU, 1, 0.0, 1e-5, 0, _lib.BF16)
+    info = _lib.NormPlanInfo()
+    assert L.mri3d_norm_plan_query(ctypes.byref(g), _lib.NORM_PASS_FWD, 16, ctypes.byref(info)) == 0
+    assert (info.vec, info.CL, info.VT, info.cy, info.nblk, info.groups, info.gvox) == (8, 2, 128, 1, 1024, 1, 2 * 160 * 192 * 160)
+    assert L.mri3d_norm_plan_query(ctypes.byref(g), _lib.NORM_PASS_BWD, 16, ctypes.byref(info)) == 0 and info.vec == 4
+    assert L.mri3d_norm_plan_query(ctypes.byref(g), 7, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_norm_plan_query(None, _lib.NORM_PASS_FWD, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_norm_plan_query(ctypes.byref(g), _lib.NORM_PASS_FWD, 16, None) == -1
 
 
 def test_host_code_is_clean_under_address_and_ub_sanitizers():

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as cc
+import norm_cases as nc
 from guard import SentinelSlice, conv3d_ref_at, gather_voxels, guarded, kernels_launched, sample_voxels
 from mri_epilepsy_diagnosis_amd import _lib, ops
 
@@ -270,6 +271,17 @@ def _norm_case(mode, dtype=F32):
     return run
 
 
+def _norm_row_case(row_id, dtype_id):
+    """A row of tests/norm_cases.py (its plans are asserted before the launch): the geometries whose block count the workspace
+    formula treats apart, groups * nblk > kNormMaxBlocks."""
+    row = nc.BY_ID[row_id]
+
+    def run():
+        res, _ = nc.run_row(row, dtype_id, nc.make_inputs(row, dtype_id))
+        return [res[k] for k in ("y", "dx", "dgamma", "dbeta", "dalpha") if res[k] is not None]
+    return run
+
+
 def _upsample_case(mode):
     def run():
         x = _rand(22, (2, 16, 6, 7, 8), F32).requires_grad_(True)
@@ -339,6 +351,7 @@ WS_CASES = [_ws_conv(c) for c in cc.WS_CONV.cases] + [_ws_wgrad(c) for c in cc.W
     ("norm_act_instance", _norm_case("instance"), None),
     ("norm_act_group", _norm_case("group"), None),
     ("norm_act_batch_bf16", _norm_case("batch", BF), None),
+] + [("norm_act_row_%s_%s" % (rid, dt), _norm_row_case(rid, dt), None) for rid in nc.WS_ROWS for dt in nc.BY_ID[rid].dtypes] + [
     ("upsample3d_nearest", _upsample_case("nearest"), None),
     ("upsample3d_trilinear", _upsample_case("trilinear"), None),
     ("softmax_dice_loss", _dice_case(), None),

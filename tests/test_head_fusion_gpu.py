@@ -106,6 +106,7 @@ def _run(p, mode, act, dtype, fused):
 
 # (n, c, co, spatial), statistics, activation, alpha_n, head bias, dtype
 S1, S2, S3, S4, S5 = (2, 16, 2, (5, 6, 7)), (1, 8, 1, (3, 5, 9)), (2, 32, 3, (4, 7, 5)), (1, 64, 4, (3, 4, 5)), (2, 16, 2, (17, 20, 23))
+S6 = (1, 64, 4, (34, 64, 62))
 CASES = [
     (S1, "batch", "prelu", 1, True, torch.float32),
     (S1, "batch", "prelu", 16, False, torch.bfloat16),
@@ -119,6 +120,8 @@ CASES = [
     (S5, "none", "relu", 1, False, torch.float32),
     (S5, "running", "prelu", 1, True, torch.bfloat16),
     (S5, "batch", "prelu", 1, True, torch.bfloat16),
+    # n * voxels > 8 * VT * 1024 with VT = 16: the fused operators' block count (nap_plan in csrc/norm.hip) at its cap of 1024
+    (S6, "batch", "prelu", 1, True, torch.float32),
 ]
 
 

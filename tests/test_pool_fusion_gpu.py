@@ -52,6 +52,9 @@ CASES = [
     ((1, 4, (2, 2, 34)), "running", "prelu", "one-", BF, False),        # bf16 with 4 channels: 8-byte accesses in the forward
     ((1, 16, (2, 2, 2)), "none", "relu", None, BF, False),
     ((3, 16, (2, 2, 34)), "batch", "prelu", "one", BF, True),
+    # n * voxels > 8 * VT * 1024 with VT = 16: the fused operators' block count (nap_plan in csrc/norm.hip) at its cap of 1024,
+    # which, unlike norm_plan's, is not divided by the groups
+    ((1, 64, (34, 64, 62)), "batch", "prelu", "one", F32, False),
 ]
 IDS = ["%dx%d_%s_%s_%s_%s_%s%s" % (s[0], s[1], "x".join(map(str, s[2])), m, a, al, "bf16" if d == BF else "f32", "_pitched" if p else "")
        for s, m, a, al, d, p in CASES]
