@@ -503,6 +503,34 @@ int mri3d_bayes_dx(const void* dx_mean, const void* dx_var, const void* x, void*
                    int32_t dx_mean_ld, int32_t dx_var_ld, int32_t x_ld, int32_t dx_ld, int32_t dtype, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Monte-Carlo predictive statistics — the read-out of the stochastic models (3d_bayes_unet.py::UNet3D(bayes=True), which samples
+ * in train and eval mode; Dropout3d in modified_3dunet.py and unet.UNet(monte_carlo_dropout=p)): T sampled forward passes become
+ * a mean prediction with its uncertainty maps.  nvox = N*D*H*W voxels of NDHWC logits (fp32 or bf16, widened on load) with
+ * 2 <= c <= 32 classes (else MRI3D_ENOTSUP) and voxel pitch ld >= c.
+ *   state: an fp32 buffer of mri3d_mc_state_bytes(nvox, c) bytes that the caller owns and only these entries read or write; it
+ *     holds, per voxel, sum_t p_c and sum_t p_c^2 for each class and sum_t sum_c p_c log p_c.  The query is host only and returns
+ *     0 for nvox <= 0 or c outside 2..32.
+ *   accumulate: adds `reps` draws in one read-modify-write of the state.  Draw r of voxel v starts at element
+ *     (r*rep_stride + v)*ld of `logits`, r = 0..reps-1 in that order, rep_stride >= nvox voxels when reps > 1 (a batch of reps*N
+ *     volumes with draw r of volume n at batch index r*N + n has rep_stride = nvox).  first != 0 overwrites the state (it need
+ *     not be initialised), first == 0 adds to it.  One call with reps = k leaves the very bits that k calls with reps = 1 leave.
+ *     Per draw:  m = max_c z_c   S = sum_c exp(z_c - m)   log p_c = z_c - m - log S   p_c = exp(z_c - m) / S;  the entropy term is
+ *     p_c * log p_c with log p_c from the logits, so a probability that underflows to 0 adds exactly 0.
+ *   finalize, with T = samples; every output is dense and may be NULL, but not all five:
+ *     mean_p[v][c] = sum p / T                        variance[v][c] = max(sum p^2 / T - mean^2, 0)   (population variance)
+ *     entropy[v] = -sum_c (mean > 0 ? mean log mean : 0)       mutual_info[v] = max(entropy + (sum_t sum_c p log p) / T, 0)
+ *     mask[v] = first maximal mean_p[v][c] (the rule of mri3d_argmax_u8, on the floats written to mean_p)
+ *   Non-finite logits are outside the contract.  No workspace, no atomics: the same inputs give the same bits.  c == 2 with dense
+ *   logits and 16-byte aligned pointers (and draws, when reps > 1) moves 16 bytes per lane and access; anything else one voxel
+ *   per lane.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mri3d_mc_state_bytes(int64_t nvox, int32_t c);
+int mri3d_mc_accumulate(const void* logits, int64_t nvox, int32_t c, int32_t ld, int32_t dtype, int32_t reps,
+                        int64_t rep_stride, int32_t first, void* state, size_t state_bytes, mri3d_stream_t stream);
+int mri3d_mc_finalize(const void* state, size_t state_bytes, int64_t nvox, int32_t c, int32_t samples, float* mean_p,
+                      float* variance, float* entropy, float* mutual_info, uint8_t* mask, mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * AdamW / Adam on one flat fp32 buffer — torch.optim.AdamW (segmentation/routine.py:358) and
  * torch.optim.Adam with L2 weight_decay (classification/routine.py:271,275).
  * grad_scale multiplies the gradient first (1/world_size after the RCCL sum all-reduce).

@@ -137,6 +137,9 @@ SIGNATURES = {
     "mri3d_bayes_sample_fwd": (c_int32, [_P, _P, _FP, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_bayes_sample_bwd": (c_int32, [_P, _P, _FP, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_bayes_dx": (c_int32, [_P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
+    "mri3d_mc_state_bytes": (c_size_t, [c_int64, c_int32]),
+    "mri3d_mc_accumulate": (c_int32, [_P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, _P, c_size_t, _P]),
+    "mri3d_mc_finalize": (c_int32, [_P, c_size_t, c_int64, c_int32, c_int32, _FP, _FP, _FP, _FP, _P, _P]),
     "mri3d_adam_step": (c_int32, [_FP, _FP, _FP, _FP, c_int64, c_float, c_float, c_float, c_float, c_float, c_int32,
                                   c_float, c_int32, _P]),
 }

@@ -12,14 +12,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libmri3d_hip.so")
-SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "elementwise.hip", "bayes.hip", "preprocess.hip", "surface.hip", "patches.hip", "augment.hip"]
+SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "surface.hip", "patches.hip", "augment.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file additions.  conv_march.hip keeps its accumulators in v160..v255 BY NAME (inline asm), above the v0..v159 that
 # `amdgpu_num_vgpr(160)` leaves to hipcc, and budgets no AGPRs at all: hipcc must never park a VGPR in an AGPR there, so its own
 # VGPR -> AGPR spilling is switched off, and tests/test_march_codegen.py checks the generated code for registers at or above
 # v160, for AGPR use and for scratch use.
-EXTRA_FLAGS = {"conv_march.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"]}
+# mc_stats.hip promises the same bits from its vector and scalar paths and from one `reps` call as from separate calls: no
+# contraction of its own choosing, the file writes fmaf where it wants one.
+EXTRA_FLAGS = {"conv_march.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mc_stats.hip": ["-ffp-contract=off"]}
 
 
 def _digest(path):

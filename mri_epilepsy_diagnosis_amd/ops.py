@@ -13,6 +13,7 @@ Reference operators replaced (file:line in /root/reference):
   softmax_dice_loss    F.softmax + get_dice_loss + mean   segmentation/routine.py:239-253,272-274
   cat_channels / add   torch.cat(dim=1) / residual adds   modified_3dunet.py:108,158
   bayes_conv3d         BayesConv3d          3d_bayes_layers.py:195-232 (3d_bayes_unet.py::UNet3D(bayes=True))
+Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd).
 """
 import ctypes
 import math
@@ -1760,6 +1761,74 @@ def argmax_mask(logits):
     out = torch.empty((n, d, h, w), dtype=torch.uint8, device=logits.device)
     check(L.mri3d_argmax_u8(_ptr(logits), _ptr(out), n * d * h * w, c, c, _dt(logits), _stream()), "argmax_u8")
     return out
+
+
+# Monte-Carlo predictive statistics (csrc/mc_stats.hip): T sampled forward passes -> mean prediction + uncertainty maps
+MC_OUTPUTS = ("mean", "variance", "entropy", "mutual_info", "mask")
+
+
+def _mc_dims(shape):
+    if len(shape) != 5:
+        raise RuntimeError("expected a 5-D (N,C,D,H,W) logits shape, got %s" % (tuple(shape),))
+    n, c, d, h, w = (int(s) for s in shape)
+    return n, c, d, h, w, n * d * h * w
+
+
+def mc_state(logits_shape, device):
+    """The accumulator of `mc_accumulate` for logits of logical shape (N, C, D, H, W): an opaque float32 tensor sized by
+    mri3d_mc_state_bytes.  It need not be cleared: the first `mc_accumulate(..., first=True)` overwrites it."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("mc_state: the Monte-Carlo statistics run only on a ROCm device (got %s); there is no CPU fallback" % device)
+    n, c, d, h, w, nvox = _mc_dims(logits_shape)
+    nbytes = _lib.lib().mri3d_mc_state_bytes(nvox, c)
+    if nbytes == 0:
+        raise RuntimeError("mc_state: unsupported logits shape %s (needs 2..32 classes and at least one voxel)" % (tuple(logits_shape),))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def mc_accumulate(state, logits, first, reps=1):
+    """Add `reps` stacked draws to `state`: `logits` is (reps*N, C, D, H, W) as the models return it (fp32 or bf16), draw r of
+    volume n at batch index r*N + n; softmax, p, p^2 and p log p per draw in one read-modify-write of the state.
+    first=True overwrites the state instead of adding to it."""
+    _require_device(logits)
+    _require_param(state)
+    if reps < 1 or logits.shape[0] % reps:
+        raise RuntimeError("mc_accumulate: batch %d is not %d stacked draws" % (logits.shape[0], reps))
+    L = _lib.lib()
+    logits, ld = _nd(logits.detach())
+    n, c, d, h, w, total = _mc_dims(logits.shape)
+    nvox = total // reps
+    check(L.mri3d_mc_accumulate(_ptr(logits), nvox, c, ld, _dt(logits), reps, nvox, 1 if first else 0, _ptr(state),
+                                state.numel() * 4, _stream()), "mc_accumulate")
+
+
+def mc_finalize(state, shape, samples, want=MC_OUTPUTS):
+    """Read `state` out after `samples` draws of logits of logical shape `shape` = (N, C, D, H, W).  Returns a dict with the
+    entries named in `want`: "mean" and "variance" (N, C, D, H, W) float32 in channels-last storage, "entropy" and "mutual_info"
+    (N, D, H, W) float32, "mask" (N, D, H, W) uint8 = arg-max of the mean (first maximum).
+    `shape` must be the shape the state was made and filled for: the state records no shape, so only its size is checked (it
+    must be exactly `mc_state(shape)`'s), and a permuted shape with the same voxel and class counts would relabel the maps
+    silently.  `MCAccumulator` keeps the two together."""
+    _require_param(state)
+    want = tuple(want)
+    if not want or any(k not in MC_OUTPUTS for k in want):
+        raise RuntimeError("mc_finalize: want must name some of %s, got %s" % (MC_OUTPUTS, want))
+    L = _lib.lib()
+    n, c, d, h, w, nvox = _mc_dims(shape)
+    if state.numel() * 4 != L.mri3d_mc_state_bytes(nvox, c):
+        raise RuntimeError("mc_finalize: a state of %d floats is not the state of logits of shape %s" % (state.numel(), tuple(shape)))
+    out = {}
+    for k in MC_OUTPUTS:
+        if k not in want:
+            out[k] = None
+        elif k in ("mean", "variance"):
+            out[k] = torch.empty((n, c, d, h, w), dtype=torch.float32, device=state.device, memory_format=CL3D)
+        else:
+            out[k] = torch.empty((n, d, h, w), dtype=torch.uint8 if k == "mask" else torch.float32, device=state.device)
+    check(L.mri3d_mc_finalize(_ptr(state), state.numel() * 4, nvox, c, int(samples), *(_ptr(out[k]) for k in MC_OUTPUTS),
+                              _stream()), "mc_finalize")
+    return {k: out[k] for k in want}
 
 
 def mask_overlap_counts(pred, gt):

@@ -110,6 +110,37 @@ def validate_dsc_asd(model, loader, surface_metrics=None):
     return dsc, asd_mean, asd_std, iou
 
 
+def _score_mask(labels, targets, surface_metrics):
+    """(dsc, asd gt->pred, asd pred->gt, iou) of the first volume's uint8 mask `labels[0]` against `targets[0][0]`, with
+    `validate_dsc_asd`'s three modes of `surface_metrics` (None = device, False = NaN, callable = host)."""
+    if (surface_metrics is None or surface_metrics is False) and targets.is_cuda:
+        gt = targets[0][0].to(torch.uint8)      # .astype(np.uint8) of the reference
+        d, i = ops.dice_iou_from_counts(ops.mask_overlap_counts(labels[0], gt))
+        if surface_metrics is False:
+            return d, float("nan"), float("nan"), i
+        am, asd = surface.average_surface_distance(gt, labels[0])
+        return d, am, asd, i
+    return calculate_metrics(targets.cpu().numpy().astype(np.uint8)[0][0], labels[0].cpu().numpy(), surface_metrics)
+
+
+def validate_dsc_asd_mc(model, loader, n_samples, samples_per_pass=1, surface_metrics=None):
+    """`validate_dsc_asd` on the mask of the Monte-Carlo mean prediction (uncertainty.mc_predict with `n_samples` draws per
+    batch): the same four lists, then two more, per volume: the mean predictive entropy and the mean mutual information over
+    its voxels (means of the device maps; two scalars cross to the host).  Like `validate_dsc_asd`, it scores the first
+    volume of each batch."""
+    from .uncertainty import mc_predict
+    dsc, asd_mean, asd_std, iou, entropy, mutual_info = [], [], [], [], [], []
+    for batch in loader:
+        inputs, targets = prepare_batch(batch, device)
+        with warnings.catch_warnings():
+            warnings.filterwarnings("ignore", category=UserWarning)
+            res = mc_predict(model, inputs, n_samples, samples_per_pass, want=("entropy", "mutual_info", "mask"))
+        d, am, asd, i = _score_mask(res["mask"], targets, surface_metrics)
+        h, mi = torch.stack((res["entropy"][0].mean(), res["mutual_info"][0].mean())).tolist()
+        dsc.append(d), asd_mean.append(am), asd_std.append(asd), iou.append(i), entropy.append(h), mutual_info.append(mi)
+    return dsc, asd_mean, asd_std, iou, entropy, mutual_info
+
+
 def get_dice_score(output, target, SPATIAL_DIMENSIONS=(2, 3, 4), epsilon=1e-9):
     """Tensor-formula helper kept for API compatibility; the training loop uses the fused HIP loss instead."""
     p0, g0 = output, target

@@ -9,6 +9,11 @@ The package source is not part of the reference tree; the topology is pinned by 
 encoder block has no normalisation, 3-D encoder blocks go in->f->2f, decoder blocks take cat(skip, upsampled).
 
 Execution is MI355X-native: conv -> (BatchNorm+PReLU fused) per block, all through the HIP operators in ``ops``.
+
+``monte_carlo_dropout=p`` is the one option beyond the reference's configuration that is built: as in the package,
+``self.monte_carlo_layer = Dropout3d(p)`` between the decoder and the classifier, no ``state_dict`` keys, active in train mode only
+(``segmentation/uncertainty.py::mc_predict`` switches it on for sampling).  The reference never sets it and the package's source is
+not in its tree, so its parity is unpinned, like the rest of SURVEY Appendix A.2.
 """
 import torch
 import torch.nn as tnn
@@ -176,7 +181,7 @@ class UNet(tnn.Module):
         super().__init__()
         if dimensions != 3:
             raise NotImplementedError("only dimensions=3 (the reference's configuration) is implemented")
-        if preactivation or residual or dropout or monte_carlo_dropout or padding_mode != "zeros":
+        if preactivation or residual or dropout or padding_mode != "zeros":
             raise NotImplementedError("option not used by the reference and not implemented")
         if not padding:
             raise NotImplementedError("padding=False (valid convolutions + cropped skips) is not used by the reference")
@@ -191,7 +196,10 @@ class UNet(tnn.Module):
         skip_channels = out_channels_first_layer * 2 ** depth
         self.decoder = Decoder(skip_channels, dimensions, upsampling_type, depth, normalization, padding=padding,
                                activation=activation, initial_dilation=self.encoder.dilation)
-        self.monte_carlo_layer = None
+        # Monte-Carlo dropout, the package's hook for sampling the forward pass (segmentation/uncertainty.py::mc_predict): channel
+        # dropout between the decoder and the classifier; it has no parameters, so the state_dict is that of p = 0.  The reference
+        # never sets the option and the package's source is not in the reference tree: parity unpinned, like the rest of A.2.
+        self.monte_carlo_layer = mnn.Dropout3d(p=monte_carlo_dropout) if monte_carlo_dropout else None
         self.shared_concat_buffers = False   # round 1's concat-buffer scheme (A/B switch; not part of the reference's API)
         # the classifier's 1x1x1 convolution runs inside the last block's BatchNorm + activation pass (A/B switch; not part of the
         # reference's API): same logits bit for bit in fp32, without the full-resolution activation in between
@@ -218,12 +226,17 @@ class UNet(tnn.Module):
                 cat_bufs.append(ops.new_cat_buffer(n, 3 * blk.out_channels, sp, x))
                 sp = tuple(s // 2 for s in sp)
         # the classifier as a plain 1x1x1 convolution (no normalisation, no activation of its own) can ride on the last block
+        # ... unless the Monte-Carlo dropout layer is active (p > 0 and in train mode): it sits between the two
         clf = self.classifier
-        head = clf.conv_layer if (self.fused_head and x.is_cuda and clf.norm_layer is None and clf.activation_layer is None
-                                  and clf.dropout_layer is None) else None
+        mc = self.monte_carlo_layer
+        mc = mc if (mc is not None and mc.training and mc.p > 0) else None
+        head = clf.conv_layer if (self.fused_head and mc is None and x.is_cuda and clf.norm_layer is None
+                                  and clf.activation_layer is None and clf.dropout_layer is None) else None
         skips, enc = self.encoder(x, cat_bufs, self.fused_pool)
         if not skips:
-            return self.bottom_block(enc, head=head) if head is not None else self.classifier(self.bottom_block(enc))
-        enc = self.bottom_block(enc)
-        x = self.decoder(skips, enc, cat_bufs, head)
-        return x if head is not None else self.classifier(x)
+            x = self.bottom_block(enc, head=head)
+        else:
+            x = self.decoder(skips, self.bottom_block(enc), cat_bufs, head)
+        if head is not None:
+            return x
+        return self.classifier(x if mc is None else mc(x))
