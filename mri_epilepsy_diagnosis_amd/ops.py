@@ -15,6 +15,7 @@ Reference operators replaced (file:line in /root/reference):
   bayes_conv3d         BayesConv3d          3d_bayes_layers.py:195-232 (3d_bayes_unet.py::UNet3D(bayes=True))
 Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd).
 """
+import collections
 import ctypes
 import math
 
@@ -374,63 +375,125 @@ def norm_plan(g, pass_, align=16):
     return (info.vec, info.CL, info.VT, info.cy, info.nblk, info.groups, info.gvox)
 
 
+def _stuffed_wgrad_ok(g):
+    return ((g.kd, g.kh, g.kw) == (3, 3, 3) and (g.sd, g.sh, g.sw) == (2, 2, 2) and (g.pd, g.ph, g.pw) == (1, 1, 1)
+            and (g.dd, g.dh, g.dw) == (1, 1, 1) and g.ci % 8 == 0 and g.co % 4 == 0 and g.x_ld % 4 == 0)
+
+
+_ONE = (1, 1, 1)
+_ConvPasses = collections.namedtuple("_ConvPasses", "fwd dgrad wgrad stuffed layer")
+
+
+def _conv_passes(xshape, wshape, stride, padding, dilation, dtype=F32, x_ld=None, dy_ld=None, dx_ld=None):
+    """The geometries of a convolution layer's three passes: the one place they are built, read by the operators and by the route
+    queries alike.  The layer: x of logical shape xshape and voxel pitch x_ld, an incoming gradient of pitch dy_ld, a data gradient
+    written with pitch dx_ld (None: dense, as y always is).  stuffed: where `_stuffed_wgrad_ok`, the stride-1 geometry the weight
+    gradient runs on instead of wgrad (its gradient operand is then the dense tensor `_stuffed_wgrad` makes), else None."""
+    fwd = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=x_ld, dtype=dtype)
+    dgrad = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=dx_ld, y_ld=dy_ld, dtype=dtype)
+    wgrad = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=fwd.x_ld, y_ld=dy_ld, dtype=dtype)
+    stuffed = _conv_geom(xshape, wshape, _ONE, _ONE, _ONE, x_ld=fwd.x_ld, dtype=dtype) if _stuffed_wgrad_ok(fwd) else None
+    return _ConvPasses(fwd, dgrad, wgrad, stuffed, (tuple(xshape), tuple(wshape), stride, padding, dilation, dtype, x_ld, dx_ld))
+
+
+def _for_gradient_pitch(p, dy_ld):
+    """p's layer for an incoming gradient of pitch dy_ld: p itself where built for it (forward builds for a dense one, the usual)."""
+    return p if dy_ld == p.wgrad.y_ld else _conv_passes(*p.layer[:7], dy_ld=dy_ld, dx_ld=p.layer[7])
+
+
+def _cat_passes(xa, xb, wshape, a_ld, dy_ld=None):
+    """conv3d_cat's layer: 3x3x3 / stride 1 / pad 1 over the channels of xa (pitch a_ld) then xb's; two dense data gradients."""
+    ca = xa.shape[1]
+    return _conv_passes((xa.shape[0], ca + xb.shape[1]) + tuple(xa.shape[2:]), wshape, _ONE, _ONE, _ONE, _dt(xa), a_ld, dy_ld, dx_ld=ca)
+
+
+def _upconv_passes(xshape, wshape, scale, padding, dtype, x_ld, dy_ld=None):
+    """upsample_conv3d's layer: stride 1 over the nearest-upsampled grid, which x (pitch x_ld) is read through."""
+    n, c, d, h, w = xshape
+    return _conv_passes((n, c, d * scale, h * scale, w * scale), wshape, _ONE, padding, _ONE, dtype, x_ld, dy_ld)
+
+
+def _pair_passes(xshape, x_ld, dtype, w1shape, conv1, w2shape, conv2):
+    """conv3d_pair's layers: (the first, the second on the first's dense result); conv1 / conv2: modules like nn.Conv3d."""
+    g1 = _conv_passes(xshape, w1shape, _triple(conv1.stride), _triple(conv1.padding), _ONE, dtype, x_ld).fwd
+    return g1, _conv_passes((g1.n, g1.co, g1.dout, g1.ho, g1.wo), w2shape, _triple(conv2.stride), _triple(conv2.padding), _ONE, dtype)
+
+
+def _transpose_geom(xshape, wshape, stride, padding, output_padding, dilation, dtype):
+    """The mirrored convolution conv_transpose3d runs on: x is its output, the result (extents settled by output_padding) its input."""
+    out = tuple((i - 1) * s - 2 * p + d * (k - 1) + op + 1 for i, s, p, d, k, op in zip(xshape[2:], stride, padding, dilation, wshape[2:], output_padding))
+    g = _conv_geom((xshape[0], wshape[1]) + out, wshape, stride, padding, dilation, dtype=dtype)
+    if (g.dout, g.ho, g.wo) != tuple(xshape[2:]):
+        raise RuntimeError("conv_transpose3d: inconsistent output_padding")
+    return g
+
+
 def conv3d_routes(xshape, wshape, stride=1, padding=0, dilation=1, dtype=F32, x_ld=None, dy_ld=None, bias=True, bn_stats=False,
                   x_align=16, dy_align=16):
-    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv3d(x, w, b, ...)` and its backward launch, from the
-    geometries `_Conv3dFn` builds: x a slice of pitch x_ld, the incoming gradient one of pitch dy_ld, y and dx fresh dense tensors
-    (16-byte aligned), no bias in the data gradient, the stride-2 weight gradient on the stride-1 kernels where `_stuffed_wgrad_ok`.
-    *_align: `_ptr_align` of x / of the incoming gradient.  With bn_stats the forward name is that of the fused-statistics entry point
-    where it serves the geometry (as `conv3d(bn_stats=True)` asks first)."""
-    stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
-    g = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=x_ld, dtype=dtype)
-    fwd = conv_route(g, PASS_FWD, bn_stats, bias, x_align=x_align, y_align=16) if bn_stats else "none"
+    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv3d(x, w, b, ...)` and its backward launch, read from the
+    `_conv_passes` that `_Conv3dFn` launches by: x a slice of pitch x_ld, the incoming gradient one of pitch dy_ld, y and dx fresh
+    dense tensors (16-byte aligned), no bias in the data gradient, the stride-2 weight gradient on the stride-1 kernels where the
+    passes say so (for tensors of one dtype, as `_stuffed_wgrad` asks).  *_align: `_ptr_align` of x / of the incoming gradient.  With
+    bn_stats the forward name is that of the fused-statistics entry point where it serves the geometry (as `conv3d(bn_stats=True)`
+    asks first)."""
+    p = _conv_passes(xshape, wshape, _triple(stride), _triple(padding), _triple(dilation), dtype, x_ld, dy_ld)
+    fwd = conv_route(p.fwd, PASS_FWD, bn_stats, bias, x_align=x_align, y_align=16) if bn_stats else "none"
     if fwd == "none":
-        fwd = conv_route(g, PASS_FWD, False, bias, x_align=x_align, y_align=16)
-    gd = _conv_geom(xshape, wshape, stride, padding, dilation, y_ld=dy_ld, dtype=dtype)
-    gw = _conv_geom(xshape, wshape, stride, padding, dilation, x_ld=g.x_ld, y_ld=dy_ld, dtype=dtype)
-    wy_align = dy_align
-    if _stuffed_wgrad_ok(g):
-        gw, wy_align = _conv_geom(xshape, wshape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=dtype), 16
-    return {"fwd": fwd, "dgrad": conv_route(gd, PASS_DGRAD, x_align=16, y_align=dy_align),
+        fwd = conv_route(p.fwd, PASS_FWD, False, bias, x_align=x_align, y_align=16)
+    gw, wy_align = (p.wgrad, dy_align) if p.stuffed is None else (p.stuffed, 16)
+    return {"fwd": fwd, "dgrad": conv_route(p.dgrad, PASS_DGRAD, x_align=16, y_align=dy_align),
             "wgrad": conv_route(gw, PASS_WGRAD, x_align=x_align, y_align=wy_align)}
 
 
 def conv_transpose3d_routes(xshape, wshape, stride=1, padding=0, output_padding=0, dilation=1, dtype=F32, bias=True, x_align=16,
                             dy_align=16):
-    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv_transpose3d(x, w, b, ...)` and its backward launch, from
-    the mirrored geometry `_ConvTranspose3dFn` builds (dense tensors): the forward is the mirrored convolution's data gradient with
-    the bias, dx its forward without one, dw its weight gradient with the operands swapped.  *_align: `_ptr_align` of x / of the
-    incoming gradient."""
-    stride, padding, output_padding, dilation = _triple(stride), _triple(padding), _triple(output_padding), _triple(dilation)
-    n = xshape[0]
-    out = tuple((i - 1) * s - 2 * p + d * (k - 1) + op + 1 for i, s, p, d, k, op in zip(xshape[2:], stride, padding, dilation, wshape[2:], output_padding))
-    g = _conv_geom((n, wshape[1]) + out, wshape, stride, padding, dilation, dtype=dtype)
-    if (g.dout, g.ho, g.wo) != tuple(xshape[2:]):
-        raise RuntimeError("conv_transpose3d: inconsistent output_padding")
+    """{"fwd": name, "dgrad": name, "wgrad": name} of the kernels `conv_transpose3d(x, w, b, ...)` and its backward launch, read
+    from the `_transpose_geom` that `_ConvTranspose3dFn` launches by (dense tensors): the forward is the mirrored convolution's data
+    gradient with the bias, dx its forward without one, dw its weight gradient with the operands swapped.  *_align: `_ptr_align` of
+    x / of the incoming gradient."""
+    g = _transpose_geom(xshape, wshape, _triple(stride), _triple(padding), _triple(output_padding), _triple(dilation), dtype)
     return {"fwd": conv_route(g, PASS_DGRAD, False, bias, x_align=16, y_align=x_align),
             "dgrad": conv_route(g, PASS_FWD, x_align=dy_align, y_align=16),
             "wgrad": conv_route(g, PASS_WGRAD, x_align=dy_align, y_align=x_align)}
 
 
-def _conv_fwd(g, x, w, b):
-    L = _lib.lib()
+def _carg(a):   # a tensor (or None) as its address, a geometry by reference, anything else as it is
+    return _ptr(a) if a is None or torch.is_tensor(a) else ctypes.byref(a) if isinstance(a, ctypes.Structure) else a
+
+
+def _launch(fn, tag, work, ws_bytes, device, *args):
+    """The launch tail of the convolution family: the stream's workspace of ws_bytes (None: the entry point takes none), the
+    `_timed(tag, work)` bracket and the checked call fn(*args, workspace, its size, stream), fn an entry point of the library."""
+    tail = ()
+    if ws_bytes is not None:
+        ws = _workspace(ws_bytes, device)
+        tail = (_ptr(ws), ws.numel())
+    with _timed(tag, work):
+        rc = fn(*map(_carg, args), *tail, _stream())
+        if rc != 0:
+            check(rc, fn.__name__[len("mri3d_"):])
+
+
+def _conv_launch(fn, pass_, g, device, *args, suffix=""):
+    """`_launch` of a convolution entry point fn(g, *args, ...) for pass `pass_`: the pass's workspace, tag (+ suffix) and work."""
+    kind = ("fwd", "dgrad", "wgrad")[pass_]       # (PASS_FWD, PASS_DGRAD, PASS_WGRAD)
+    _launch(fn, lambda: _conv_tag(kind, g) + suffix, lambda: _conv_work(g, kind),
+            _lib.lib().mri3d_conv3d_workspace_bytes(ctypes.byref(g), pass_), device, g, *args)
+
+
+def _conv_fwd(g, x, w, b, part=None):
+    """y = conv(x, w) + b of geometry g.  part: the statistics partials of `_stats_partials`, for the epilogue to fill."""
     y = _new((g.n, g.co, g.dout, g.ho, g.wo), x)
-    nb = L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_FWD)
-    ws = _workspace(nb, x.device)
-    with _timed(lambda: _conv_tag("fwd", g), lambda: _conv_work(g, "fwd")):
-        check(L.mri3d_conv3d_fwd(ctypes.byref(g), _ptr(x), _ptr(w), _ptr(b), _ptr(y), _ptr(ws), ws.numel(), _stream()),
-              "conv3d_fwd")
+    if part is None:
+        _conv_launch(_lib.lib().mri3d_conv3d_fwd, PASS_FWD, g, x.device, x, w, b, y)
+    else:
+        _conv_launch(_lib.lib().mri3d_conv3d_fwd_stats, PASS_FWD, g, x.device, x, w, b, y, part, suffix=" +bn-stats")
     return y
 
 
 def _conv_dgrad(g, dy, w, b, like):
-    L = _lib.lib()
     dx = _new((g.n, g.ci, g.di, g.hi, g.wi), like)
-    nb = L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_DGRAD)
-    ws = _workspace(nb, dy.device)
-    with _timed(lambda: _conv_tag("dgrad", g), lambda: _conv_work(g, "dgrad")):
-        check(L.mri3d_conv3d_dgrad(ctypes.byref(g), _ptr(dy), _ptr(w), _ptr(b), _ptr(dx), _ptr(ws), ws.numel(),
-                                   _stream()), "conv3d_dgrad")
+    _conv_launch(_lib.lib().mri3d_conv3d_dgrad, PASS_DGRAD, g, dy.device, dy, w, b, dx)
     return dx
 
 
@@ -502,34 +565,87 @@ def _sink_done(param, grad, out):
     return None
 
 
-def _conv_wgrad(g, x, dy, w_like, want_bias, dw_out=None, db_out=None):
+def _grad_slots(ctx, saved, first=1, params=None, all_written=False):
+    """(sinks, grads) for the parameter gradients a backward kernel writes.  saved: what forward kept of `params` (ctx.params
+    unless given), inputs first.. of the function, None where a gradient cannot exist.  A wanted gradient goes to its fresh sink
+    view, else to a new tensor.  all_written: the kernel writes every gradient that can exist, wanted or not, so each gets a
+    tensor.  That is the rule of the convolutions' weight-gradient kernels: dw is computed even when only db is wanted, and db is
+    written whenever the layer HAS a bias (a NULL db would select another kernel instantiation); `_grad_slots_done` hands
+    autograd the wanted ones."""
+    params = ctx.params if params is None else params
+    want = [t is not None and ctx.needs_input_grad[first + i] for i, t in enumerate(saved)]
+    sinks = [_sink_take(p) if wt else None for p, wt in zip(params, want)]
+    grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format))
+             if wt or (all_written and t is not None) else None for sk, t, wt in zip(sinks, saved, want)]
+    return sinks, grads
+
+
+def _grad_slots_done(ctx, grads, sinks, first=1, params=None):
+    """What backward returns for the parameters of `_grad_slots`."""
+    params = ctx.params if params is None else params
+    return tuple(_sink_done(p, gr, sk) if ctx.needs_input_grad[first + i] else None for i, (p, gr, sk) in enumerate(zip(params, grads, sinks)))
+
+
+def _conv_param_grads(ctx, first, params, wgrad):
+    """(dw, db) as backward returns them for the convolution whose (weight, bias) `params` are inputs first, first + 1 of the
+    function: (None, None) unless one of them is wanted, else `wgrad(dw, db)` fills the tensors of `_grad_slots`."""
+    if not any(p is not None and ctx.needs_input_grad[first + i] for i, p in enumerate(params)):
+        return None, None
+    sinks, grads = _grad_slots(ctx, params, first, params, all_written=True)
+    wgrad(*grads)
+    return _grad_slots_done(ctx, grads, sinks, first, params)
+
+
+def _conv_wgrad(g, x, dy, w_like, want_bias, dw_out=None, db_out=None, split=None):
+    """split: (xb, ca, b_ld) of conv3d_cat — x holds the first ca channels of the operand, xb (pitch b_ld) the others."""
     L = _lib.lib()
     dw = dw_out if dw_out is not None else torch.empty_like(w_like, memory_format=torch.contiguous_format)
     db = (db_out if db_out is not None else torch.empty(g.co, dtype=w_like.dtype, device=w_like.device)) if want_bias else None
-    nb = L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_WGRAD)
-    ws = _workspace(nb, x.device)
-    with _timed(lambda: _conv_tag("wgrad", g), lambda: _conv_work(g, "wgrad")):
-        check(L.mri3d_conv3d_wgrad(ctypes.byref(g), _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
-                                   _stream()), "conv3d_wgrad")
+    if split is None:
+        _conv_launch(L.mri3d_conv3d_wgrad, PASS_WGRAD, g, x.device, x, dy, dw, db)
+    else:
+        _conv_launch(L.mri3d_conv3d_wgrad_cat, PASS_WGRAD, g, x.device, x, *split, dy, dw, db, suffix=" cat")
     return dw, db
 
 
-def _stuffed_wgrad_ok(g):
-    return ((g.kd, g.kh, g.kw) == (3, 3, 3) and (g.sd, g.sh, g.sw) == (2, 2, 2) and (g.pd, g.ph, g.pw) == (1, 1, 1)
-            and (g.dd, g.dh, g.dw) == (1, 1, 1) and g.ci % 8 == 0 and g.co % 4 == 0 and g.x_ld % 4 == 0)
-
-
-def _stuffed_wgrad(g, gw, x, dy, w):
-    """(geometry, incoming gradient) the weight gradient of forward geometry `g` runs on: (gw, dy) as given, except where
-    `_stuffed_wgrad_ok`."""
-    if not (_stuffed_wgrad_ok(g) and dy.dtype == x.dtype):
-        return gw, dy
+def _stuffed_wgrad(p, x, dy):
+    """(geometry, incoming gradient) the weight gradient of the passes `p` runs on: (p.wgrad, dy) as given, except where
+    `_stuffed_wgrad_ok` and the two tensors share a dtype."""
+    if p.stuffed is None or dy.dtype != x.dtype:
+        return p.wgrad, dy
     # 3x3x3 / stride 2 / pad 1 (modified_3dunet.py:23-38): dW[tap] = sum_o X[2o - 1 + tap] dY[o] is the STRIDE-1 weight
     # gradient of X against dY spread onto the even voxels of a zero volume — 8x the arithmetic, but on the MFMA
     # weight-gradient kernel (~100 TFLOP/s) instead of the generic one (4.6 TFLOP/s on the 8 -> 16 layer at 80x96x80)
+    g = p.fwd
     dyw = torch.empty((g.n, g.co, g.di, g.hi, g.wi), dtype=dy.dtype, device=dy.device, memory_format=CL3D).zero_()
     dyw[:, :, ::2, ::2, ::2].copy_(dy)
-    return _conv_geom(x.shape, w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=g.co, dtype=g.dtype), dyw
+    return p.stuffed, dyw
+
+
+def _autocast_in(x):
+    """The activation input x in the storage dtype of the active `autocast` region (x itself outside one)."""
+    return convert(x, _autocast_dtype) if _autocast_dtype is not None and x.dtype != _autocast_dtype else x
+
+
+def _stats_partials(holder, blocks, g, x, bias):
+    """BatchNorm follows in batch-statistics mode: the conv epilogue accumulates sum(a), sum(a^2) per output channel (float64
+    partials, one per workgroup) instead of a statistics pass over y afterwards.  Returns the partials for the `blocks` workgroups
+    the statistics query answered (None for 0: the kernel does not serve the geometry) and hands them to `holder`."""
+    if blocks <= 0:
+        return None
+    part = torch.empty(blocks * g.co * 2, dtype=torch.float64, device=x.device)
+    holder.append((part, blocks, bias.detach() if bias is not None else None))
+    return part
+
+
+def _apply_with_bn_stats(fn, bn_stats, *args):
+    """fn.apply(*args, holder): with bn_stats the result carries the statistics its forward handed to holder (`_stats_partials`),
+    where `norm_act` picks them up."""
+    holder = [] if bn_stats else None
+    y = fn.apply(*args, holder)
+    if holder:
+        y._mri3d_bn_stats = holder[0]
+    return y
 
 
 class _Conv3dFn(torch.autograd.Function):
@@ -539,51 +655,25 @@ class _Conv3dFn(torch.autograd.Function):
         _require_param(weight, bias)
         x, x_ld = _nd(x)
         w = weight.contiguous()
-        g = _conv_geom(x.shape, w.shape, stride, padding, dilation, x_ld=x_ld, dtype=_dt(x))
-        y = None
-        if stats_holder is not None:
-            # BatchNorm follows in batch-statistics mode: let the conv epilogue accumulate sum(a), sum(a^2) per output channel
-            # (float64 partials, one per workgroup) instead of a statistics pass over y afterwards
-            L = _lib.lib()
-            blocks = L.mri3d_conv3d_fwd_stats_blocks(ctypes.byref(g))
-            if blocks > 0:
-                y = _new((g.n, g.co, g.dout, g.ho, g.wo), x)
-                part = torch.empty(blocks * g.co * 2, dtype=torch.float64, device=x.device)
-                ws = _workspace(L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_FWD), x.device)
-                with _timed(lambda: _conv_tag("fwd", g) + " +bn-stats", lambda: _conv_work(g, "fwd")):
-                    check(L.mri3d_conv3d_fwd_stats(ctypes.byref(g), _ptr(x), _ptr(w), _ptr(bias), _ptr(y), _ptr(part), _ptr(ws),
-                                                   ws.numel(), _stream()), "conv3d_fwd_stats")
-                stats_holder.append((part, blocks, bias.detach() if bias is not None else None))
-        if y is None:
-            y = _conv_fwd(g, x, w, bias)
+        p = _conv_passes(x.shape, w.shape, stride, padding, dilation, _dt(x), x_ld)
+        g = p.fwd
+        part = _stats_partials(stats_holder, _lib.lib().mri3d_conv3d_fwd_stats_blocks(ctypes.byref(g)), g, x, bias) if stats_holder is not None else None
+        y = _conv_fwd(g, x, w, bias, part)
         ctx.save_for_backward(x, w)
-        ctx.geom = g
-        ctx.has_bias = bias is not None
-        ctx.params = (weight, bias)
+        ctx.passes, ctx.params = p, (weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        g = ctx.geom
         dy, y_ld = _nd(dy)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            gd = _conv_geom(x.shape, w.shape, (g.sd, g.sh, g.sw), (g.pd, g.ph, g.pw), (g.dd, g.dh, g.dw), y_ld=y_ld,
-                            dtype=g.dtype)
-            dx = _conv_dgrad(gd, dy, w, None, x)       # dx is a fresh dense tensor (pitch = Cin)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = _conv_geom(x.shape, w.shape, (g.sd, g.sh, g.sw), (g.pd, g.ph, g.pw), (g.dd, g.dh, g.dw), x_ld=g.x_ld,
-                            y_ld=y_ld, dtype=g.dtype)
-            wp, bp = ctx.params
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            dw_out = _sink_take(wp) if ctx.needs_input_grad[1] else None
-            db_out = _sink_take(bp) if want_b else None
-            gw, dyw = _stuffed_wgrad(g, gw, x, dy, w)
-            dw, db = _conv_wgrad(gw, x, dyw, w, ctx.has_bias, dw_out, db_out)
-            dw = _sink_done(wp, dw, dw_out) if ctx.needs_input_grad[1] else None
-            db = _sink_done(bp, db, db_out) if want_b else None
-        return dx, dw, db, None, None, None, None
+        p = _for_gradient_pitch(ctx.passes, y_ld)
+        dx = _conv_dgrad(p.dgrad, dy, w, None, x) if ctx.needs_input_grad[0] else None      # a fresh dense tensor (pitch = Cin)
+
+        def wgrad(dw, db):
+            gw, dyw = _stuffed_wgrad(p, x, dy)
+            _conv_wgrad(gw, x, dyw, w, db is not None, dw, db)
+        return (dx, *_conv_param_grads(ctx, 1, ctx.params, wgrad), None, None, None, None)
 
 
 class _Conv3dCatFn(torch.autograd.Function):
@@ -601,62 +691,40 @@ class _Conv3dCatFn(torch.autograd.Function):
         xa, a_ld = _nd(xa)
         xb, b_ld = _nd(xb)
         w = weight.contiguous()
-        ca, cb = xa.shape[1], xb.shape[1]
-        g = _conv_geom((xa.shape[0], ca + cb) + tuple(xa.shape[2:]), w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=a_ld, dtype=_dt(xa))
+        p = _cat_passes(xa, xb, w.shape, a_ld)
+        g, ca = p.fwd, xa.shape[1]
         y = _new((g.n, g.co, g.dout, g.ho, g.wo), xa)
-        ws = _workspace(L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_FWD), xa.device)
+        ws_bytes = L.mri3d_conv3d_workspace_bytes(ctypes.byref(g), PASS_FWD)
         part = None
         if stats_holder is not None:
             # the partials are sized by the query about exactly what is launched: geometry, split and second-tensor pitch (the
             # pitch takes part in the choice between the marching and the tiled kernel, whose grids differ)
-            blocks = L.mri3d_conv3d_fwd_cat_stats_blocks(ctypes.byref(g), ca, b_ld)
-            if blocks > 0:
-                part = torch.empty(blocks * g.co * 2, dtype=torch.float64, device=xa.device)
-                stats_holder.append((part, blocks, bias.detach() if bias is not None else None))
-        with _timed(lambda: _conv_tag("fwd", g) + " cat" + (" +bn-stats" if part is not None else ""), lambda: _conv_work(g, "fwd")):
-            check(L.mri3d_conv3d_fwd_cat(ctypes.byref(g), _ptr(xa), _ptr(xb), ca, b_ld, _ptr(w), _ptr(bias), _ptr(y), _ptr(part),
-                                         _ptr(ws), ws.numel(), _stream()), "conv3d_fwd_cat")
+            part = _stats_partials(stats_holder, L.mri3d_conv3d_fwd_cat_stats_blocks(ctypes.byref(g), ca, b_ld), g, xa, bias)
+        _launch(L.mri3d_conv3d_fwd_cat, lambda: _conv_tag("fwd", g) + " cat" + (" +bn-stats" if part is not None else ""),
+                lambda: _conv_work(g, "fwd"), ws_bytes, xa.device, g, xa, xb, ca, b_ld, w, bias, y, part)
         ctx.save_for_backward(xa, xb, w)
-        ctx.geom, ctx.b_ld, ctx.has_bias, ctx.params = g, b_ld, bias is not None, (weight, bias)
+        ctx.passes, ctx.b_ld, ctx.params = p, b_ld, (weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         xa, xb, w = ctx.saved_tensors
-        g, L = ctx.geom, _lib.lib()
         dy, y_ld = _nd(dy)
+        p = _for_gradient_pitch(ctx.passes, y_ld)
         ca, cb = xa.shape[1], xb.shape[1]
-        dxa = dxb = dw = db = None
+        dxa = dxb = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            gd = _conv_geom((g.n, g.ci, g.di, g.hi, g.wi), w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=ca, y_ld=y_ld, dtype=g.dtype)
             dxa, dxb = _new(xa.shape, xa), _new(xb.shape, xb)      # two dense tensors
-            ws = _workspace(L.mri3d_conv3d_workspace_bytes(ctypes.byref(gd), PASS_DGRAD), dy.device)
-            with _timed(lambda: _conv_tag("dgrad", gd) + " cat", lambda: _conv_work(gd, "dgrad")):
-                check(L.mri3d_conv3d_dgrad_cat(ctypes.byref(gd), _ptr(dy), _ptr(w), _ptr(dxa), _ptr(dxb), ca, cb, _ptr(ws),
-                                               ws.numel(), _stream()), "conv3d_dgrad_cat")
-        if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
-            gw = _conv_geom((g.n, g.ci, g.di, g.hi, g.wi), w.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=g.x_ld, y_ld=y_ld, dtype=g.dtype)
-            wp, bp = ctx.params
-            want_b = ctx.has_bias and ctx.needs_input_grad[3]
-            dw_out = _sink_take(wp) if ctx.needs_input_grad[2] else None
-            db_out = _sink_take(bp) if want_b else None
-            dw = dw_out if dw_out is not None else torch.empty_like(w, memory_format=torch.contiguous_format)
-            db = (db_out if db_out is not None else torch.empty(g.co, dtype=w.dtype, device=w.device)) if ctx.has_bias else None
-            ws = _workspace(L.mri3d_conv3d_workspace_bytes(ctypes.byref(gw), PASS_WGRAD), dy.device)
-            with _timed(lambda: _conv_tag("wgrad", gw) + " cat", lambda: _conv_work(gw, "wgrad")):
-                check(L.mri3d_conv3d_wgrad_cat(ctypes.byref(gw), _ptr(xa), _ptr(xb), ca, ctx.b_ld, _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws),
-                                               ws.numel(), _stream()), "conv3d_wgrad_cat")
-            dw = _sink_done(wp, dw, dw_out) if ctx.needs_input_grad[2] else None
-            db = _sink_done(bp, db, db_out) if want_b else None
+            _conv_launch(_lib.lib().mri3d_conv3d_dgrad_cat, PASS_DGRAD, p.dgrad, dy.device, dy, w, dxa, dxb, ca, cb, suffix=" cat")
+        dw, db = _conv_param_grads(ctx, 2, ctx.params, lambda dw, db: _conv_wgrad(p.wgrad, xa, dy, w, db is not None, dw, db,
+                                                                                 split=(xb, ca, ctx.b_ld)))
         return dxa, dxb, dw, db, None
 
 
 def conv3d_cat(xa, xb, weight, bias=None, padding=1, bn_stats=False):
     """conv3d(torch.cat((xa, xb), dim=1), weight, bias, padding=padding) — without the concatenation where the MFMA kernels serve all
     three passes of the geometry (3x3x3 / stride 1 / pad 1, channel counts in multiples of 16), with an explicit one otherwise."""
-    if _autocast_dtype is not None:
-        xa = convert(xa, _autocast_dtype) if xa.dtype != _autocast_dtype else xa
-        xb = convert(xb, _autocast_dtype) if xb.dtype != _autocast_dtype else xb
+    xa, xb = _autocast_in(xa), _autocast_in(xb)
     ok = (xa.is_cuda and xa.dim() == 5 and xb.shape[0] == xa.shape[0] and xb.shape[2:] == xa.shape[2:] and xa.dtype == xb.dtype
           and tuple(weight.shape[2:]) == (3, 3, 3) and _triple(padding) == (1, 1, 1) and weight.shape[1] == xa.shape[1] + xb.shape[1])
     if ok:
@@ -664,32 +732,20 @@ def conv3d_cat(xa, xb, weight, bias=None, padding=1, bn_stats=False):
         a_nd, a_ld = _nd(xa)
         b_nd, b_ld = _nd(xb)
         ca, cb = xa.shape[1], xb.shape[1]
-        shape = (xa.shape[0], ca + cb) + tuple(xa.shape[2:])
-        gf = _conv_geom(shape, weight.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=a_ld, dtype=_dt(a_nd))
-        gd = _conv_geom(shape, weight.shape, (1, 1, 1), (1, 1, 1), (1, 1, 1), x_ld=ca, dtype=_dt(a_nd))
+        p = _cat_passes(a_nd, b_nd, weight.shape, a_ld)
         ok = (a_nd.data_ptr() % 16 == 0 and b_nd.data_ptr() % 16 == 0
-              and L.mri3d_conv3d_cat_supported(ctypes.byref(gf), ca, b_ld, PASS_FWD)
-              and L.mri3d_conv3d_cat_supported(ctypes.byref(gf), ca, b_ld, PASS_WGRAD)
-              and L.mri3d_conv3d_cat_supported(ctypes.byref(gd), ca, cb, PASS_DGRAD))
+              and L.mri3d_conv3d_cat_supported(ctypes.byref(p.fwd), ca, b_ld, PASS_FWD)
+              and L.mri3d_conv3d_cat_supported(ctypes.byref(p.fwd), ca, b_ld, PASS_WGRAD)
+              and L.mri3d_conv3d_cat_supported(ctypes.byref(p.dgrad), ca, cb, PASS_DGRAD))
     if not ok:
         return conv3d(cat_channels([xa, xb]), weight, bias, 1, padding, 1, bn_stats=bn_stats)
-    holder = [] if bn_stats else None
-    y = _Conv3dCatFn.apply(xa, xb, weight, bias, holder)
-    if holder:
-        y._mri3d_bn_stats = holder[0]
-    return y
+    return _apply_with_bn_stats(_Conv3dCatFn, bn_stats, xa, xb, weight, bias)
 
 
 def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, bn_stats=False):
     """bn_stats=True: the caller applies a batch-statistics BatchNorm to the result next (nn.conv_norm_act); where the MFMA
     forward kernel serves the geometry its epilogue accumulates the statistics, and `norm_act` picks them up from the result."""
-    if _autocast_dtype is not None and x.dtype != _autocast_dtype:
-        x = convert(x, _autocast_dtype)
-    holder = [] if bn_stats else None
-    y = _Conv3dFn.apply(x, weight, bias, _triple(stride), _triple(padding), _triple(dilation), holder)
-    if holder:
-        y._mri3d_bn_stats = holder[0]
-    return y
+    return _apply_with_bn_stats(_Conv3dFn, bn_stats, _autocast_in(x), weight, bias, _triple(stride), _triple(padding), _triple(dilation))
 
 
 # ----------------------------------------------------------------------------------------------- BayesConv3d
@@ -734,8 +790,8 @@ def _stream_work(n_tensors, like, eps_numel=0):
 def _bayes_square(x, x_ld):
     n, c, d, h, w = x.shape
     x2 = _new(x.shape, x)
-    with _timed(lambda: "bayes_square %d @%dx%dx%d n%d" % (c, d, h, w, n), lambda: _stream_work(2, x)):
-        check(_lib.lib().mri3d_bayes_square(_ptr(x), _ptr(x2), n * d * h * w, c, x_ld, c, _dt(x), _stream()), "bayes_square")
+    _launch(_lib.lib().mri3d_bayes_square, lambda: "bayes_square %d @%dx%dx%d n%d" % (c, d, h, w, n), lambda: _stream_work(2, x), None, None,
+            x, x2, n * d * h * w, c, x_ld, c, _dt(x))
     return x2
 
 
@@ -753,50 +809,44 @@ class _BayesConv3dFn(torch.autograd.Function):
         L = _lib.lib()
         x, x_ld = _nd(x)
         w_mean, w_var = w_mean.contiguous(), w_var.contiguous()
-        g = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, x_ld=x_ld, dtype=_dt(x))
+        pm = _conv_passes(x.shape, w_mean.shape, stride, padding, dilation, _dt(x), x_ld)     # the mean reads x where it lies,
+        pv = _conv_passes(x.shape, w_var.shape, stride, padding, dilation, _dt(x))            # the variance a dense x^2 (and dvar)
+        g = pm.fwd
         y = _conv_fwd(g, x, w_mean, mu_bias)
-        g2 = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=_dt(x))
         var_bias = logsigma_bias * logsigma_bias if logsigma_bias is not None else None
-        var_out = _conv_fwd(g2, _bayes_square(x, x_ld), w_var, var_bias)
+        var_out = _conv_fwd(pv.fwd, _bayes_square(x, x_ld), w_var, var_bias)
         if tuple(eps.shape) != tuple(y.shape):
             raise RuntimeError("bayes_conv3d: eps has shape %s, the output %s" % (tuple(eps.shape), tuple(y.shape)))
         eps, eps_ld = _nd(eps)
         nvox = g.n * g.dout * g.ho * g.wo
-        with _timed(lambda: "bayes_sample_fwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n), lambda: _stream_work(3, y, eps.numel())):
-            check(L.mri3d_bayes_sample_fwd(_ptr(y), _ptr(var_out), _ptr(eps), _ptr(y), nvox, g.co, g.co, g.co, eps_ld, g.co, g.dtype,
-                                           _stream()), "bayes_sample_fwd")
+        _launch(L.mri3d_bayes_sample_fwd, lambda: "bayes_sample_fwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n),
+                lambda: _stream_work(3, y, eps.numel()), None, None, y, var_out, eps, y, nvox, g.co, g.co, g.co, eps_ld, g.co, g.dtype)
         ctx.save_for_backward(x, w_mean, w_var, var_out, eps, logsigma_bias)
-        ctx.geom, ctx.eps_ld, ctx.has_bias = g, eps_ld, mu_bias is not None
+        ctx.passes, ctx.eps_ld, ctx.has_bias = (pm, pv), eps_ld, mu_bias is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
         x, w_mean, w_var, var_out, eps, logsigma_bias = ctx.saved_tensors
-        g = ctx.geom
-        stride, padding, dilation = (g.sd, g.sh, g.sw), (g.pd, g.ph, g.pw), (g.dd, g.dh, g.dw)
         dy, y_ld = _nd(dy)
+        pm, pv = _for_gradient_pitch(ctx.passes[0], y_ld), ctx.passes[1]
+        g = pm.fwd
         nvox = g.n * g.dout * g.ho * g.wo
         dvar = _new(dy.shape, dy)
-        with _timed(lambda: "bayes_sample_bwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n), lambda: _stream_work(3, dy, eps.numel())):
-            check(L.mri3d_bayes_sample_bwd(_ptr(dy), _ptr(var_out), _ptr(eps), _ptr(dvar), nvox, g.co, y_ld, g.co, ctx.eps_ld, g.co,
-                                           g.dtype, _stream()), "bayes_sample_bwd")
+        _launch(L.mri3d_bayes_sample_bwd, lambda: "bayes_sample_bwd %d @%dx%dx%d n%d" % (g.co, g.dout, g.ho, g.wo, g.n),
+                lambda: _stream_work(3, dy, eps.numel()), None, None, dy, var_out, eps, dvar, nvox, g.co, y_ld, g.co, ctx.eps_ld, g.co, g.dtype)
         dx = dw_mean = dw_var = dmb = dlb = None
         if ctx.needs_input_grad[0]:
-            gd = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, y_ld=y_ld, dtype=g.dtype)
-            dx = _conv_dgrad(gd, dy, w_mean, None, x)
-            gdv = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=g.dtype)
-            dx_var = _conv_dgrad(gdv, dvar, w_var, None, x)
-            with _timed(lambda: "bayes_dx %d @%dx%dx%d n%d" % (g.ci, g.di, g.hi, g.wi, g.n), lambda: _stream_work(4, x)):
-                check(L.mri3d_bayes_dx(_ptr(dx), _ptr(dx_var), _ptr(x), _ptr(dx), g.n * g.di * g.hi * g.wi, g.ci, g.ci, g.ci, g.x_ld,
-                                       g.ci, g.dtype, _stream()), "bayes_dx")
+            dx = _conv_dgrad(pm.dgrad, dy, w_mean, None, x)
+            dx_var = _conv_dgrad(pv.dgrad, dvar, w_var, None, x)
+            _launch(L.mri3d_bayes_dx, lambda: "bayes_dx %d @%dx%dx%d n%d" % (g.ci, g.di, g.hi, g.wi, g.n), lambda: _stream_work(4, x), None, None,
+                    dx, dx_var, x, dx, g.n * g.di * g.hi * g.wi, g.ci, g.ci, g.ci, g.x_ld, g.ci, g.dtype)
         want_b = ctx.has_bias and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2] or want_b:
-            gw = _conv_geom(x.shape, w_mean.shape, stride, padding, dilation, x_ld=g.x_ld, y_ld=y_ld, dtype=g.dtype)
-            gw, dyw = _stuffed_wgrad(g, gw, x, dy, w_mean)
+            gw, dyw = _stuffed_wgrad(pm, x, dy)
             dw_mean, dmb = _conv_wgrad(gw, x, dyw, w_mean, ctx.has_bias)
-            g2 = _conv_geom(x.shape, w_var.shape, stride, padding, dilation, dtype=g.dtype)
-            gw2, dvw = _stuffed_wgrad(g2, g2, x, dvar, w_var)
+            gw2, dvw = _stuffed_wgrad(pv, x, dvar)
             dw_var, dvb = _conv_wgrad(gw2, _bayes_square(x, g.x_ld), dvw, w_var, ctx.has_bias)
             if ctx.has_bias:
                 dlb = 2.0 * logsigma_bias * dvb
@@ -816,8 +866,7 @@ def bayes_conv3d(x, mu_weight, logsigma_weight, mu_bias=None, logsigma_bias=None
     if (mu_bias is None) != (logsigma_bias is None):
         raise RuntimeError("bayes_conv3d: mu_bias and logsigma_bias come together")
     _require_device(x)
-    if _autocast_dtype is not None and x.dtype != _autocast_dtype:
-        x = convert(x, _autocast_dtype)
+    x = _autocast_in(x)
     stride, padding, dilation = _triple(stride), _triple(padding), _triple(dilation)
     g = _conv_geom(x.shape, mu_weight.shape, stride, padding, dilation)
     if training:
@@ -844,49 +893,30 @@ class _ConvPairFn(torch.autograd.Function):
         _require_param(w2, b2)
         x, x_ld = _nd(x)
         w1c, w2c = w1.contiguous(), w2.contiguous()
-        g1 = _conv_geom(x.shape, w1c.shape, conv1[0], conv1[1], (1, 1, 1), x_ld=x_ld, dtype=_dt(x))
+        g1, p2 = _pair_passes(x.shape, x_ld, _dt(x), w1c.shape, conv1, w2c.shape, conv2)
         a1 = _conv_fwd(g1, x, w1c, b1)
-        g2 = _conv_geom(a1.shape, w2c.shape, conv2[0], conv2[1], (1, 1, 1), dtype=_dt(x))
-        y = _conv_fwd(g2, a1, w2c, b2)
+        y = _conv_fwd(p2.fwd, a1, w2c, b2)
         ctx.save_for_backward(x, a1, w2c)
-        ctx.geoms = (g1, g2)
-        ctx.params = (w1, b1, w2, b2)
+        ctx.passes, ctx.params = (g1, p2), (w1, b1, w2, b2)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
         x, a1, w2c = ctx.saved_tensors
-        g1, g2 = ctx.geoms
         w1, b1, w2, b2 = ctx.params
         dy, y_ld = _nd(dy)
-        stride2, pad2 = (g2.sd, g2.sh, g2.sw), (g2.pd, g2.ph, g2.pw)
-        gw2 = _conv_geom(a1.shape, w2c.shape, stride2, pad2, (1, 1, 1), y_ld=y_ld, dtype=g2.dtype)
+        g1, gw2 = ctx.passes[0], _for_gradient_pitch(ctx.passes[1], y_ld).wgrad
         # second convolution: the ordinary weight gradient
-        need_w2, need_b2 = ctx.needs_input_grad[3], b2 is not None and ctx.needs_input_grad[4]
-        dw2 = db2 = None
-        if need_w2 or need_b2:
-            dw2_out = _sink_take(w2) if need_w2 else None
-            db2_out = _sink_take(b2) if need_b2 else None
-            dw2, db2 = _conv_wgrad(gw2, a1, dy, w2c, b2 is not None, dw2_out, db2_out)
-            dw2 = _sink_done(w2, dw2, dw2_out) if need_w2 else None
-            db2 = _sink_done(b2, db2, db2_out) if need_b2 else None
+        dw2, db2 = _conv_param_grads(ctx, 3, (w2, b2), lambda dw, db: _conv_wgrad(gw2, a1, dy, w2c, db is not None, dw, db))
+
         # first convolution: from dy, w2 and x, without the gradient of a1
-        need_w1, need_b1 = ctx.needs_input_grad[1], b1 is not None and ctx.needs_input_grad[2]
-        dw1 = db1 = None
-        if need_w1 or need_b1:
-            dw1_out = _sink_take(w1) if need_w1 else None
-            db1_out = _sink_take(b1) if need_b1 else None
-            dw1 = dw1_out if dw1_out is not None else torch.empty_like(w1, memory_format=torch.contiguous_format)
-            db1 = (db1_out if db1_out is not None else torch.empty(g1.co, dtype=w1.dtype, device=w1.device)) if b1 is not None else None
-            ws = _workspace(L.mri3d_convpair_workspace_bytes(ctypes.byref(g1), ctypes.byref(gw2)), x.device)
-            with _timed(lambda: _conv_tag("wgrad", g1) + " through " + _conv_tag("dgrad", gw2),
-                        lambda: {"flops": _conv_work(g1, "wgrad")["flops"] + _conv_work(gw2, "dgrad")["flops"],
-                                 "bytes": _esz(dy) * (x.numel() + dy.numel())}):
-                check(L.mri3d_convpair_wgrad_first(ctypes.byref(g1), ctypes.byref(gw2), _ptr(x), _ptr(dy), _ptr(w2c), _ptr(dw1), _ptr(db1),
-                                                   _ptr(ws), ws.numel(), _stream()), "convpair_wgrad_first")
-            dw1 = _sink_done(w1, dw1, dw1_out) if need_w1 else None
-            db1 = _sink_done(b1, db1, db1_out) if need_b1 else None
+        def wgrad_first(dw, db):
+            _launch(L.mri3d_convpair_wgrad_first, lambda: _conv_tag("wgrad", g1) + " through " + _conv_tag("dgrad", gw2),
+                    lambda: {"flops": _conv_work(g1, "wgrad")["flops"] + _conv_work(gw2, "dgrad")["flops"],
+                             "bytes": _esz(dy) * (x.numel() + dy.numel())},
+                    L.mri3d_convpair_workspace_bytes(ctypes.byref(g1), ctypes.byref(gw2)), x.device, g1, gw2, x, dy, w2c, dw, db)
+        dw1, db1 = _conv_param_grads(ctx, 1, (w1, b1), wgrad_first)
         return None, dw1, db1, dw2, db2, None, None
 
 
@@ -898,20 +928,16 @@ def conv3d_pair_supported(x, conv1, conv2):
     if _triple(conv1.dilation) != (1, 1, 1) or _triple(conv2.dilation) != (1, 1, 1) or conv1.weight.shape[1] != x.shape[1]:
         return False
     try:
-        g1 = _conv_geom(tuple(x.shape), tuple(conv1.weight.shape), _triple(conv1.stride), _triple(conv1.padding), (1, 1, 1),
-                        x_ld=_pitch_of(x) or x.shape[1], dtype=_dt(x))
-        g2 = _conv_geom((g1.n, g1.co, g1.dout, g1.ho, g1.wo), tuple(conv2.weight.shape), _triple(conv2.stride), _triple(conv2.padding),
-                        (1, 1, 1), dtype=_dt(x))
+        g1, p2 = _pair_passes(x.shape, _pitch_of(x) or x.shape[1], _dt(x), conv1.weight.shape, conv1, conv2.weight.shape, conv2)
     except RuntimeError:
         return False
-    return bool(_lib.lib().mri3d_convpair_supported(ctypes.byref(g1), ctypes.byref(g2)))
+    return bool(_lib.lib().mri3d_convpair_supported(ctypes.byref(g1), ctypes.byref(p2.fwd)))
 
 
 def conv3d_pair(x, conv1, conv2):
     """conv2(conv1(x)) for two nn.Conv3d modules; the fused backward where conv3d_pair_supported, else the two operators."""
     if conv3d_pair_supported(x, conv1, conv2):
-        return _ConvPairFn.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias,
-                                 (_triple(conv1.stride), _triple(conv1.padding)), (_triple(conv2.stride), _triple(conv2.padding)))
+        return _ConvPairFn.apply(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias, conv1, conv2)
     y = conv3d(x, conv1.weight, conv1.bias, conv1.stride, conv1.padding, conv1.dilation)
     return conv3d(y, conv2.weight, conv2.bias, conv2.stride, conv2.padding, conv2.dilation)
 
@@ -938,21 +964,12 @@ class _ConvTranspose3dFn(torch.autograd.Function):
         _require_param(weight, bias)
         x = _cl(x)
         w = weight.contiguous()  # (Cin_t, Cout_t, kd, kh, kw) == conv weight (Co=Cin_t, Ci=Cout_t)
-        n, cin_t, di, hi, wi = x.shape
-        if w.shape[0] != cin_t:
-            raise RuntimeError("conv_transpose3d: weight expects %d input channels, got %d" % (w.shape[0], cin_t))
-        cout_t, kd, kh, kw = w.shape[1], w.shape[2], w.shape[3], w.shape[4]
-        od = (di - 1) * stride[0] - 2 * padding[0] + dilation[0] * (kd - 1) + output_padding[0] + 1
-        oh = (hi - 1) * stride[1] - 2 * padding[1] + dilation[1] * (kh - 1) + output_padding[1] + 1
-        ow = (wi - 1) * stride[2] - 2 * padding[2] + dilation[2] * (kw - 1) + output_padding[2] + 1
-        # mirrored conv: input (n, cout_t, od, oh, ow) -> output (n, cin_t, di, hi, wi)
-        g = _conv_geom((n, cout_t, od, oh, ow), w.shape, stride, padding, dilation, dtype=_dt(x))
-        if (g.dout, g.ho, g.wo) != (di, hi, wi):
-            raise RuntimeError("conv_transpose3d: inconsistent output_padding")
+        if w.shape[0] != x.shape[1]:
+            raise RuntimeError("conv_transpose3d: weight expects %d input channels, got %d" % (w.shape[0], x.shape[1]))
+        g = _transpose_geom(x.shape, w.shape, stride, padding, output_padding, dilation, _dt(x))
         y = _conv_dgrad(g, x, w, bias, x)
         ctx.save_for_backward(x, w)
-        ctx.geom = g
-        ctx.has_bias = bias is not None
+        ctx.geom, ctx.has_bias = g, bias is not None
         return y
 
     @staticmethod
@@ -971,9 +988,7 @@ class _ConvTranspose3dFn(torch.autograd.Function):
 
 
 def conv_transpose3d(x, weight, bias=None, stride=1, padding=0, output_padding=0, dilation=1):
-    if _autocast_dtype is not None and x.dtype != _autocast_dtype:
-        x = convert(x, _autocast_dtype)
-    return _ConvTranspose3dFn.apply(x, weight, bias, _triple(stride), _triple(padding), _triple(output_padding),
+    return _ConvTranspose3dFn.apply(_autocast_in(x), weight, bias, _triple(stride), _triple(padding), _triple(output_padding),
                                     _triple(dilation))
 
 
@@ -1108,21 +1123,6 @@ def _backward_x(who, x, g0, *grads):
     if g0.x_ld != g0.c:  # dx shares x's pitch in the kernel: give it a dense x instead
         x = x.contiguous(memory_format=CL3D)
     return x
-
-
-def _grad_slots(ctx, saved):
-    """(sinks, grads) for the parameter gradients a backward kernel writes.  saved: what forward kept of ctx.params, inputs 1..
-    of the function, None where a gradient cannot exist.  A wanted gradient goes to its fresh sink view, else to a new tensor."""
-    params, want = ctx.params, [t is not None and ctx.needs_input_grad[1 + i] for i, t in enumerate(saved)]
-    sinks = [_sink_take(p) if wt else None for p, wt in zip(params, want)]
-    grads = [(sk if sk is not None else torch.empty_like(t, memory_format=torch.contiguous_format)) if wt else None
-             for sk, t, wt in zip(sinks, saved, want)]
-    return sinks, grads
-
-
-def _grad_slots_done(ctx, grads, sinks):
-    """What backward returns for the parameters of `_grad_slots`."""
-    return tuple(_sink_done(p, gr, sk) for p, gr, sk in zip(ctx.params, grads, sinks))
 
 
 class _NormActFn(torch.autograd.Function):
@@ -1635,51 +1635,38 @@ class _UpConv3dFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, scale, padding):
         _require_device(x)
         _require_param(weight, bias)
-        L = _lib.lib()
         x, x_ld = _nd(x)
         w = weight.contiguous()
-        n, c, d, h, wd = x.shape
-        g = _conv_geom((n, c, d * scale, h * scale, wd * scale), w.shape, (1, 1, 1), padding, (1, 1, 1), x_ld=x_ld, dtype=_dt(x))
+        p = _upconv_passes(x.shape, w.shape, scale, padding, _dt(x), x_ld)
+        g = p.fwd
         y = _new((g.n, g.co, g.dout, g.ho, g.wo), x)
-        with _timed(lambda: _conv_tag("fwd", g) + " of nearest x%d" % scale,
-                    lambda: {"flops": _conv_work(g, "fwd")["flops"], "bytes": _esz(x) * (x.numel() + y.numel())}):
-            check(L.mri3d_upconv3d_fwd(ctypes.byref(g), scale, _ptr(x), _ptr(w), _ptr(bias), _ptr(y), _stream()), "upconv3d_fwd")
+        _launch(_lib.lib().mri3d_upconv3d_fwd, lambda: _conv_tag("fwd", g) + " of nearest x%d" % scale,
+                lambda: {"flops": _conv_work(g, "fwd")["flops"], "bytes": _esz(x) * (x.numel() + y.numel())},
+                None, None, g, scale, x, w, bias, y)
         ctx.save_for_backward(x, w)
-        ctx.geom, ctx.scale, ctx.padding = g, scale, padding
-        ctx.has_bias = bias is not None
-        ctx.params = (weight, bias)
+        ctx.passes, ctx.scale, ctx.params = p, scale, (weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
         x, w = ctx.saved_tensors
-        g0, scale = ctx.geom, ctx.scale
+        scale = ctx.scale
         dy, y_ld = _nd(dy)
-        fine = (g0.n, g0.ci, g0.di, g0.hi, g0.wi)
-        dx = dw = db = None
+        p = _for_gradient_pitch(ctx.passes, y_ld)
+        gd, gw = p.dgrad, p.wgrad
+        dx = None
         if ctx.needs_input_grad[0]:
-            gd = _conv_geom(fine, w.shape, (1, 1, 1), ctx.padding, (1, 1, 1), x_ld=g0.ci, y_ld=y_ld, dtype=g0.dtype)
             dx = _new(tuple(x.shape), x)
-            with _timed(lambda: _conv_tag("dgrad", gd) + " onto nearest x%d" % scale,
-                        lambda: {"flops": _conv_work(gd, "dgrad")["flops"], "bytes": _esz(dy) * (dx.numel() + dy.numel())}):
-                check(L.mri3d_upconv3d_dgrad(ctypes.byref(gd), scale, _ptr(dy), _ptr(w), _ptr(dx), _stream()), "upconv3d_dgrad")
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            gw = _conv_geom(fine, w.shape, (1, 1, 1), ctx.padding, (1, 1, 1), x_ld=g0.x_ld, y_ld=y_ld, dtype=g0.dtype)
-            wp, bp = ctx.params
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            dw_out = _sink_take(wp) if ctx.needs_input_grad[1] else None
-            db_out = _sink_take(bp) if want_b else None
-            dw = dw_out if dw_out is not None else torch.empty_like(w, memory_format=torch.contiguous_format)
-            db = (db_out if db_out is not None else torch.empty(gw.co, dtype=w.dtype, device=w.device)) if ctx.has_bias else None
-            ws = _workspace(L.mri3d_upconv3d_workspace_bytes(ctypes.byref(gw), scale), x.device)
-            with _timed(lambda: _conv_tag("wgrad", gw) + " of nearest x%d" % scale,
-                        lambda: {"flops": _conv_work(gw, "wgrad")["flops"], "bytes": _esz(dy) * (x.numel() + dy.numel())}):
-                check(L.mri3d_upconv3d_wgrad(ctypes.byref(gw), scale, _ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), ws.numel(),
-                                             _stream()), "upconv3d_wgrad")
-            dw = _sink_done(wp, dw, dw_out) if ctx.needs_input_grad[1] else None
-            db = _sink_done(bp, db, db_out) if want_b else None
-        return dx, dw, db, None, None
+            _launch(L.mri3d_upconv3d_dgrad, lambda: _conv_tag("dgrad", gd) + " onto nearest x%d" % scale,
+                    lambda: {"flops": _conv_work(gd, "dgrad")["flops"], "bytes": _esz(dy) * (dx.numel() + dy.numel())},
+                    None, None, gd, scale, dy, w, dx)
+
+        def wgrad(dw, db):
+            _launch(L.mri3d_upconv3d_wgrad, lambda: _conv_tag("wgrad", gw) + " of nearest x%d" % scale,
+                    lambda: {"flops": _conv_work(gw, "wgrad")["flops"], "bytes": _esz(dy) * (x.numel() + dy.numel())},
+                    L.mri3d_upconv3d_workspace_bytes(ctypes.byref(gw), scale), x.device, gw, scale, x, dy, dw, db)
+        return (dx, *_conv_param_grads(ctx, 1, ctx.params, wgrad), None, None)
 
 
 def upsample_conv3d_supported(x, weight, scale, stride=1, padding=0, dilation=1):
@@ -1691,12 +1678,10 @@ def upsample_conv3d_supported(x, weight, scale, stride=1, padding=0, dilation=1)
         return False
     if x.data_ptr() % 16:      # a channel slice that does not start on four channels: the two operators take it
         return False
-    n, c, d, h, w = x.shape
-    if weight.shape[1] != c:
+    if weight.shape[1] != x.shape[1]:
         return False
     try:
-        g = _conv_geom((n, c, d * scale, h * scale, w * scale), tuple(weight.shape), (1, 1, 1), _triple(padding), (1, 1, 1),
-                       x_ld=_pitch_of(x) or c, dtype=_dt(x))
+        g = _upconv_passes(tuple(x.shape), tuple(weight.shape), scale, _triple(padding), _dt(x), _pitch_of(x) or x.shape[1]).fwd
     except RuntimeError:
         return False
     return bool(_lib.lib().mri3d_upconv3d_supported(ctypes.byref(g), scale))
