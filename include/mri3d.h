@@ -278,6 +278,18 @@ int mri3d_maxpool3d_bwd(const Mri3dPoolGeom* g, const void* dy, const uint8_t* i
  * otherwise sum in a separate full-resolution pass. */
 int mri3d_maxpool3d_bwd_add(const Mri3dPoolGeom* g, const void* dy, const uint8_t* idx, const void* addend,
                             int32_t addend_ld, void* dx, mri3d_stream_t stream);
+/* WHICH KERNEL mri3d_maxpool3d_fwd (pass = MRI3D_PASS_FWD), mri3d_maxpool3d_bwd (MRI3D_PASS_DGRAD, addend_ld = 0) or
+ * mri3d_maxpool3d_bwd_add (MRI3D_PASS_DGRAD, addend_ld = the addend's pitch) launches for this geometry.  Host only: no device is
+ * needed, nothing is launched; it runs the entry point's checks and reads the launch plan the entry point launches by.
+ * align_tensors: the largest power of two <= 16 that divides the base address of every tensor of the pass (x and y; dy, dx and the
+ * addend); align_idx: the same for the index bytes.  name (at least 40 bytes) receives the kernel template of csrc/resample.hip
+ * without its "_kernel" and its template arguments as the plan chose them, T = f32 | bf16:
+ *   "maxpool2_fwd<T,{4,8}>"       MaxPool3d(2) on even extents, lanes along input lines; VEC = 8: bf16 only, here and below
+ *   "maxpool_fwd<T,{1,4,8}>"      every other pool, and a MaxPool3d(2) whose channels, pitches or alignments allow no vector
+ *   "maxpool_bwd<T,{1,4,8}>"      followed by "+add" with an addend
+ * Grids and other run-time arguments are not part of a name.  The names are stable: the test suite pins its parity cases to them. */
+int mri3d_maxpool3d_route(const Mri3dPoolGeom* g, int32_t pass, int32_t addend_ld, int32_t align_tensors, int32_t align_idx,
+                          char* name, size_t name_bytes);
 
 /* norm_act followed by MaxPool3d(2) with the activation kept as the skip tensor, as ONE operator — the tail of an encoder level
  * of `unet.UNet` (conv -> BatchNorm3d -> PReLU -> skip, MaxPool3d(2)).  _fwd reads x once and writes skip = act(norm(x)), pooled =
@@ -321,6 +333,17 @@ size_t mri3d_upsample3d_workspace_bytes(const Mri3dUpGeom* g);
 int mri3d_upsample3d_fwd(const Mri3dUpGeom* g, const void* x, void* y, mri3d_stream_t stream);
 int mri3d_upsample3d_bwd(const Mri3dUpGeom* g, const void* dy, void* dx, void* workspace, size_t ws_bytes,
                          mri3d_stream_t stream);
+/* WHICH KERNEL mri3d_upsample3d_fwd (pass = MRI3D_PASS_FWD) or mri3d_upsample3d_bwd (MRI3D_PASS_DGRAD) launches for this geometry,
+ * as mri3d_maxpool3d_route answers for the pool.  align: the largest power of two <= 16 that divides the base address of both
+ * tensors.  name (at least 40 bytes), T = f32 | bf16:
+ *   "upsample2x_fwd_march<T,{4,8},{1,2,4,8}>"   trilinear x2 without align_corners, channels and pitches in quads: <T, VEC, NPV>
+ *   "upsample_fwd<T,{1,4}>"                     every other forward
+ *   "upsample2x_bwd_march<T>"                   trilinear x2 as above with c % 16 == 0
+ *   "upsample2x_bwd<T>"                         trilinear x2 as above, every other channel count (the LDS-tiled kernel)
+ *   "upsample_nearest_int_bwd<T,{2,4}>"         nearest with output = S x input in every axis, channels and pitches in quads
+ *   "tables+upsample_bwd<T,{1,4}>"              every other backward: upsample_tables_kernel fills the workspace, then the gather
+ * Segment lengths, tile counts and grids are not part of a name. */
+int mri3d_upsample3d_route(const Mri3dUpGeom* g, int32_t pass, int32_t align, char* name, size_t name_bytes);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused softmax(dim=C) + soft-Dice loss — F.softmax + get_dice_loss + .mean()

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <initializer_list>
 #include "../../include/mri3d.h"
 
 namespace mri3d {
@@ -127,6 +128,28 @@ inline bool pool2_ok(const Mri3dPoolGeom& g, int vec) {
     return g.kd == 2 && g.kh == 2 && g.kw == 2 && g.sd == 2 && g.sh == 2 && g.sw == 2 && g.pd == 0 && g.ph == 0 && g.pw == 0 &&
            g.di == 2 * g.dout && g.hi == 2 * g.ho && g.wi == 2 * g.wo && cv >= 1 && cv <= 32 && (cv & (cv - 1)) == 0 &&
            (int64_t)g.di * g.hi * g.wi * g.x_ld < ((int64_t)1 << 31);
+}
+
+// channels per lane of a pooling pass: 8 (bf16 only: 16-byte accesses), 4 or 1.  A vector needs the channels and every pitch in
+// whole vectors, every tensor (aligns: their ptr_align) aligned to one, and the index bytes (align_idx) to one byte per channel.
+inline int pool_vec(int dtype, int c, std::initializer_list<int> pitches, std::initializer_list<int> aligns, int align_idx) {
+    int lds = c, align = 16;
+    for (int ld : pitches) lds |= ld;   // (a | b) % 2^k == 0 exactly when both are
+    for (int a : aligns) align = std::min(align, a);
+    if (lds % 4 != 0 || !align_vec4(dtype, align) || align_idx < 4) return 1;
+    return dtype == MRI3D_BF16 && lds % 8 == 0 && align16(align) && align_idx >= 8 ? 8 : 4;
+}
+
+// forward of a pool: its vector width, whether the line-contiguous MaxPool3d(2) kernels serve it (lanes then walk input columns),
+// and the slab plan that goes with the two
+struct PoolFwdLanes { int vec; bool lines; int hch, grid; };
+inline PoolFwdLanes pool_fwd_lanes(const Mri3dPoolGeom& g, std::initializer_list<int> pitches, std::initializer_list<int> aligns,
+                                   int align_idx) {
+    PoolFwdLanes p;
+    p.vec = pool_vec(g.dtype, g.c, pitches, aligns, align_idx);
+    p.lines = p.vec >= 4 && pool2_ok(g, p.vec);
+    slab_plan(g.n * g.dout, g.ho, p.lines ? g.wi : g.wo, g.c / p.vec, p.hch, p.grid);
+    return p;
 }
 
 // ---------------------------------------------------------------- device helpers

@@ -1427,20 +1427,17 @@ extern "C" int mri3d_norm_act_pool_fwd(const Mri3dNormGeom* g, const Mri3dPoolGe
                   "norm_act_pool_fwd: x, skip, pooled and idx must be aligned to 4 elements");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const NapArgs a = nap_args(*g, mean, invstd, gamma, beta, alpha);
-    // bf16: 16-byte accesses where the layout allows them, as norm_act_fwd_kernel and maxpool2_fwd_kernel choose
-    const bool v8 = g->dtype == MRI3D_BF16 && g->c % 8 == 0 && g->x_ld % 8 == 0 && g->y_ld % 8 == 0 && pg->y_ld % 8 == 0 &&
-                    aligned16(x, skip, pooled) && (reinterpret_cast<uintptr_t>(idx) & 7) == 0;
-    int hch, grid;
-    slab_plan(pg->n * pg->dout, pg->ho, pg->wi, pg->c / (v8 ? 8 : 4), hch, grid);
+    // the lanes of the pool forward (bf16: 16-byte accesses where the layout allows them), with x as a third tensor
+    const PoolFwdLanes p = pool_fwd_lanes(*pg, {g->x_ld, g->y_ld, pg->y_ld}, {ptr_align(x, skip, pooled)}, ptr_align(idx));
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
         if constexpr (sizeof(T) == 2) {
-            if (v8)
-                hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip,
-                                   (T*)pooled, idx, hch, a);
+            if (p.vec == 8)
+                hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 8>), dim3(p.grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip,
+                                   (T*)pooled, idx, p.hch, a);
         }
-        if (!v8)
-            hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip, (T*)pooled,
-                               idx, hch, a);
+        if (p.vec != 8)
+            hipLaunchKernelGGL((norm_act_pool_fwd_kernel<T, 4>), dim3(p.grid), dim3(256), 0, s, *pg, (const T*)x, (T*)skip, (T*)pooled,
+                               idx, p.hch, a);
     });
     return check_launch("norm_act_pool_fwd");
 }

@@ -3,13 +3,16 @@
 // AE_model.py:27, cnn_model.py:115-148; MaxPool3d(4,2) cnn_model.py:221,232; nn.Upsample(trilinear) in unet.UNet
 // decoder; nearest in modified_3dunet.py:13 and AE_model.py:70-73; F.interpolate(size=) AE_model.py:119.
 //
-// All four kernels are HBM-bound streaming passes (algorithmic bytes = one read of the source + one write of the
-// destination); lanes run along channels then voxels so every wave touches contiguous NDHWC memory.  Backward passes
-// are written as gathers (each destination element is produced by exactly one thread) => deterministic, no atomics.
+// Every pass is an HBM-bound streaming pass (algorithmic bytes = one read of the source + one write of the destination);
+// lanes run along channels then voxels so every wave touches contiguous NDHWC memory.  Backward passes are written as
+// gathers (each destination element is produced by exactly one thread) => deterministic, no atomics.  The slab kernels
+// serve every geometry; MaxPool3d(2), trilinear x2 and nearest xS have kernels of their own.  Which one a pass launches,
+// and with what grid, is decided by the four plan functions at the end of the file.
 #include "common.h"
 #include <limits.h>
 #include <algorithm>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace mri3d {
 
@@ -474,18 +477,17 @@ __device__ __forceinline__ void up2_axis_weights(int i, int S, float (&w)[4]) {
     if (i == S - 1) { w[2] = 1.f; w[3] = 0.f; }
 }
 
-// CQ = channel quads per pass (2: 8 channels, 4: 16 channels).  A voxel's slice of CQ*4 channels is what one staging
-// request reads contiguously: 32 B (CQ = 2) left three quarters of every 128-byte line unused (2 TB/s of L2->LDS traffic
-// measured as the bound), so the 16-channel variant with a 2x2x16 coarse tile is used whenever C % 16 == 0.
-template <int CQ> struct Up2Tile;
-template <> struct Up2Tile<2> { static constexpr int TD = 2, TH = 4, TW = 16; };
-template <> struct Up2Tile<4> { static constexpr int TD = 2, TH = 2, TW = 16; };
+// A pass takes TCQ = 2 channel quads: a voxel's slice of 8 channels is what one staging request reads contiguously.  For
+// fp32 that is 32 B, a quarter of a 128-byte line (2 TB/s of L2->LDS traffic measured as the bound); the geometries with
+// C % 16 == 0, where whole lines could be staged, take the marching kernel below instead.
+constexpr int TCQ = 2, TTD = 2, TTH = 4, TTW = 16;   // channel quads per pass, coarse tile d x h x w
+constexpr size_t kUp2TileLds = (size_t)(2 * TTD + 2) * (2 * TTH + 2) * (2 * TTW + 2) * TCQ * sizeof(float4);
 
-template <typename T, int CQ>
+template <typename T>
 __global__ void __launch_bounds__(256, 2)
 upsample2x_bwd_kernel(Mri3dUpGeom g, const T* __restrict__ dy, T* __restrict__ dx, int tilesD, int tilesH, int tilesW,
                       int ntiles) {
-    constexpr int UTD = Up2Tile<CQ>::TD, UTH = Up2Tile<CQ>::TH, UTW = Up2Tile<CQ>::TW;
+    constexpr int CQ = TCQ, UTD = TTD, UTH = TTH, UTW = TTW;
     constexpr int UFD = 2 * UTD + 2, UFH = 2 * UTH + 2, UFW = 2 * UTW + 2, UFV = UFD * UFH * UFW;
     static_assert(UTD * UTH * UTW * CQ == 256, "one lane per (coarse voxel, channel quad)");
     extern __shared__ __attribute__((aligned(16))) float4 ubuf[];   // [fine voxel][CQ channel quads]
@@ -836,15 +838,151 @@ upsample2x_fwd_march_kernel(Mri3dUpGeom g, const T* __restrict__ x, T* __restric
     }
 }
 
-static inline bool up2x_fast_ok(const Mri3dUpGeom& g) {
-    return g.mode == MRI3D_UP_TRILINEAR && !g.align_corners && g.dout == 2 * g.di && g.ho == 2 * g.hi && g.wo == 2 * g.wi &&
-           g.rd == 0.5f && g.rh == 0.5f && g.rw == 0.5f && g.c % 4 == 0 && g.x_ld % 4 == 0 && g.y_ld % 4 == 0;
+// ------------------------------------------------------------------ launch plans
+// One host function per pass decides which kernel instantiation runs, and with what grid, tile counts and workspace, from the
+// geometry and the alignments of the tensors (ptr_align values, never the pointers).  The entry points launch what it answers;
+// mri3d_maxpool3d_route / mri3d_upsample3d_route copy out its name (vocabulary: include/mri3d.h).
+enum class ResampleKernel { maxpool_fwd, maxpool2_fwd, maxpool_bwd, up_fwd, up2x_fwd_march, up_bwd, up_nearest_int_bwd, up2x_bwd_tile, up2x_bwd_march };
+
+struct ResamplePlan {
+    ResampleKernel kern;
+    int vec = 1;           // channels per lane item
+    int npv = 0;           // up2x_fwd_march: NPV; up_nearest_int_bwd: S
+    int hch = 0;           // slab kernels: rows of H per slab
+    int grid = 0;
+    int segs = 0, segl = 0, tilesH = 0, tilesW = 0, passes = 0;   // tile and marching kernels: D segments (tile kernel: D tiles; forward:
+    int items = 0;                                                // of segl planes), tiles in H and W, channel passes; their product x N
+    size_t smem = 0;       // dynamic LDS bytes
+    bool tables = false;   // the per-axis tables are built in the workspace first
+    char name[40];
+};
+
+static const char* type_name(int dtype) { return dtype == MRI3D_BF16 ? "bf16" : "f32"; }
+
+static ResamplePlan pool_fwd_plan(const Mri3dPoolGeom& g, int align, int align_idx) {
+    const PoolFwdLanes l = pool_fwd_lanes(g, {g.x_ld, g.y_ld}, {align}, align_idx);
+    ResamplePlan p;
+    p.kern = l.lines ? ResampleKernel::maxpool2_fwd : ResampleKernel::maxpool_fwd;   // MaxPool3d(2) on even extents: whole lines per wave-load
+    p.vec = l.vec, p.hch = l.hch, p.grid = l.grid;
+    snprintf(p.name, sizeof(p.name), "%s<%s,%d>", l.lines ? "maxpool2_fwd" : "maxpool_fwd", type_name(g.dtype), p.vec);
+    return p;
 }
 
-// rows of H per slab so that one slab is ~8 passes of a 256-thread block, and the resulting grid size
-static inline bool vec_ok(int dtype, int c, int a_ld, int b_ld, const void* a, const void* b) {
-    return c % 4 == 0 && a_ld % 4 == 0 && b_ld % 4 == 0 && aligned_vec4(dtype, a, b);
+static ResamplePlan pool_bwd_plan(const Mri3dPoolGeom& g, int align, int align_idx, bool addend, int a_ld, int align_addend) {
+    ResamplePlan p;
+    p.kern = ResampleKernel::maxpool_bwd;
+    p.vec = pool_vec(g.dtype, g.c, {g.x_ld, g.y_ld, addend ? a_ld : 0}, {align, addend ? align_addend : 16}, align_idx);
+    slab_plan(g.n * g.di, g.hi, g.wi, g.c / p.vec, p.hch, p.grid);
+    snprintf(p.name, sizeof(p.name), "maxpool_bwd<%s,%d>%s", type_name(g.dtype), p.vec, addend ? "+add" : "");
+    return p;
 }
+
+static bool up_generic_only() {
+    static const int generic = tuning_knob("MRI3D_UP_GENERIC", 0);   // tuning aid (A/B, tools/upsample_probe.py): the slab kernels only
+    return generic != 0;
+}
+
+// slab kernels: 4 channels per lane where the channels, both pitches and both tensors allow it
+static int up_vec(const Mri3dUpGeom& g, int align) {
+    return g.c % 4 == 0 && g.x_ld % 4 == 0 && g.y_ld % 4 == 0 && align_vec4(g.dtype, align) ? 4 : 1;
+}
+
+// trilinear x2 without align_corners, 4 channels per access: what the tile and marching kernels compute
+static bool up2x_fast_ok(const Mri3dUpGeom& g, int align) {
+    return g.mode == MRI3D_UP_TRILINEAR && !g.align_corners && g.dout == 2 * g.di && g.ho == 2 * g.hi && g.wo == 2 * g.wi &&
+           g.rd == 0.5f && g.rh == 0.5f && g.rw == 0.5f && up_vec(g, align) == 4;
+}
+
+static ResamplePlan up_fwd_plan(const Mri3dUpGeom& g, int align) {
+    ResamplePlan p;
+    if (!up_generic_only() && up2x_fast_ok(g, align)) {
+        // marching kernel: lane items of 16 bytes where the tensors allow it (bf16: channels and pitches in whole octets)
+        const bool oct = g.dtype == MRI3D_BF16 && g.c % 8 == 0 && g.x_ld % 8 == 0 && g.y_ld % 8 == 0 && align16(align);
+        const int vec = oct ? 8 : 4, pieces = g.c / vec;
+        const int npv = pieces >= 8 ? 8 : pieces >= 4 ? 4 : pieces >= 2 ? 2 : 1;
+        const int mtilesH = cdiv(g.hi, UTH), mtilesW = cdiv(g.wi, UTW), mpasses = cdiv(pieces, npv);
+        int segl = UMD;   // every segment stages two planes more than it owns: long segments unless the grid would not fill the chip
+        while (segl > 4 && (int64_t)g.n * cdiv(g.di, segl) * mpasses * mtilesH * mtilesW < 1024) segl /= 2;
+        const int segsD = cdiv(g.di, segl);
+        const int64_t items = (int64_t)g.n * segsD * mpasses * mtilesH * mtilesW;
+        if (items <= 0x7ffffff0 && (int64_t)g.ho * g.wo * g.y_ld <= 0x7fffffff &&
+            (int64_t)g.hi * g.wi * g.x_ld <= 0x7fffffff) {
+            p.kern = ResampleKernel::up2x_fwd_march;
+            p.vec = vec, p.npv = npv, p.segs = segsD, p.segl = segl, p.tilesH = mtilesH, p.tilesW = mtilesW, p.passes = mpasses;
+            p.items = (int)items;
+            p.grid = (int)std::min<int64_t>((items + 7) / 8 * 8, 256 * 4 * 8);
+            snprintf(p.name, sizeof(p.name), "upsample2x_fwd_march<%s,%d,%d>", type_name(g.dtype), vec, npv);
+            return p;
+        }
+    }
+    p.kern = ResampleKernel::up_fwd;
+    p.vec = up_vec(g, align);
+    slab_plan(g.n * g.dout, g.ho, g.wo, g.c / p.vec, p.hch, p.grid);
+    snprintf(p.name, sizeof(p.name), "upsample_fwd<%s,%d>", type_name(g.dtype), p.vec);
+    return p;
+}
+
+static ResamplePlan up_bwd_plan(const Mri3dUpGeom& g, int align) {
+    ResamplePlan p;
+    if (!up_generic_only() && up2x_fast_ok(g, align)) {
+        if (g.c % 16 == 0) {
+            const int segsD = cdiv(g.di, MD), tilesH = cdiv(g.hi, MTH), tilesW = cdiv(g.wi, MTW), cpasses = g.c / 16;
+            const int64_t items = (int64_t)g.n * segsD * cpasses * tilesH * tilesW;
+            if (items <= 0x7ffffff0 && (int64_t)g.ho * g.wo * g.y_ld <= 0x7fffffff) {
+                p.kern = ResampleKernel::up2x_bwd_march;
+                p.vec = 4, p.segs = segsD, p.tilesH = tilesH, p.tilesW = tilesW, p.passes = cpasses, p.items = (int)items;
+                p.grid = (int)std::min<int64_t>((items + 7) / 8 * 8, 256 * 3 * 8);
+                snprintf(p.name, sizeof(p.name), "upsample2x_bwd_march<%s>", type_name(g.dtype));
+                return p;
+            }
+        }
+        // every other channel count in quads — and a geometry past the marching kernel's 32-bit limits — takes the 8-channel tile
+        const int tilesD = cdiv(g.di, TTD), tilesH = cdiv(g.hi, TTH), tilesW = cdiv(g.wi, TTW);
+        const int64_t nt = (int64_t)g.n * tilesD * tilesH * tilesW;
+        if (nt <= 0x7fffffff) {
+            p.kern = ResampleKernel::up2x_bwd_tile;
+            p.vec = 4, p.segs = tilesD, p.tilesH = tilesH, p.tilesW = tilesW, p.items = (int)nt, p.smem = kUp2TileLds;
+            p.grid = (int)std::min<int64_t>(nt, 2048);
+            snprintf(p.name, sizeof(p.name), "upsample2x_bwd<%s>", type_name(g.dtype));
+            return p;
+        }
+    }
+    p.vec = up_vec(g, align);
+    slab_plan(g.n * g.di, g.hi, g.wi, g.c / p.vec, p.hch, p.grid);
+    // nearest neighbour with output = S x input in every axis (S = 2, 4): the plain S^3 box sum
+    const int sc = g.di > 0 ? g.dout / g.di : 0;
+    if (!up_generic_only() && g.mode == MRI3D_UP_NEAREST && p.vec == 4 && (sc == 2 || sc == 4) && g.dout == sc * g.di &&
+        g.ho == sc * g.hi && g.wo == sc * g.wi) {
+        p.kern = ResampleKernel::up_nearest_int_bwd;
+        p.npv = sc;
+        snprintf(p.name, sizeof(p.name), "upsample_nearest_int_bwd<%s,%d>", type_name(g.dtype), sc);
+        return p;
+    }
+    p.kern = ResampleKernel::up_bwd;
+    p.tables = true;
+    snprintf(p.name, sizeof(p.name), "tables+upsample_bwd<%s,%d>", type_name(g.dtype), p.vec);
+    return p;
+}
+
+// Launches the kernel instantiation `kern` on the plan's grid with the plan's dynamic LDS (allowed once per instantiation: the
+// size is a constant of the kernel that asks for any).
+template <auto kern, typename... Args>
+static void launch(const ResamplePlan& p, hipStream_t s, Args... args) {
+    if (p.smem != 0) {
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.smem);
+        (void)attr;
+    }
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.smem, s, args...);
+}
+
+// Calls f with std::integral_constant<int, v> for the one of Vs that equals v.
+template <int... Vs, typename F>
+static void with_int(int v, F f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
+
+// lane items of 8 channels (16 bytes) exist for bf16 tensors only
+template <typename T, int VEC> constexpr bool has_vec = VEC < 8 || sizeof(T) == 2;
 
 }  // namespace mri3d
 
@@ -865,67 +1003,45 @@ static int pool_check(const Mri3dPoolGeom* g, const char* who) {
     return MRI3D_OK;
 }
 
+// the checks of the backward that both its entry points and the route query make: a_ld is the addend's pitch, where there is one
+static int pool_bwd_check(const Mri3dPoolGeom* g, bool addend, int32_t a_ld, const char* who) {
+    if (int rc = pool_check(g, who)) return rc;
+    MRI3D_REQUIRE(!addend || a_ld >= g->c, MRI3D_EINVAL, "%s: addend pitch %d < %d channels", who, a_ld, g->c);
+    return MRI3D_OK;
+}
+
 extern "C" int mri3d_maxpool3d_fwd(const Mri3dPoolGeom* g, const void* x, void* y, uint8_t* idx,
                                    mri3d_stream_t stream) {
-    int rc = pool_check(g, "maxpool3d_fwd");
-    if (rc) return rc;
+    if (int rc = pool_check(g, "maxpool3d_fwd")) return rc;
     MRI3D_REQUIRE(x && y && idx, MRI3D_EINVAL, "maxpool3d_fwd: null pointer");
+    const ResamplePlan p = pool_fwd_plan(*g, ptr_align(x, y), ptr_align(idx));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    bool v4 = vec_ok(g->dtype, g->c, g->x_ld, g->y_ld, x, y) && (reinterpret_cast<uintptr_t>(idx) & 3) == 0;
-    int hch, grid;
-    const bool v8 = v4 && g->dtype == MRI3D_BF16 && g->c % 8 == 0 && g->x_ld % 8 == 0 && g->y_ld % 8 == 0 && aligned16(x, y) &&
-                    (reinterpret_cast<uintptr_t>(idx) & 7) == 0;
-    slab_plan(g->n * g->dout, g->ho, g->wo, g->c / (v8 ? 8 : (v4 ? 4 : 1)), hch, grid);
-    if (v4 && pool2_ok(*g, v8 ? 8 : 4)) {   // MaxPool3d(2) on even extents: lanes walk input columns (whole lines per wave-load)
-        slab_plan(g->n * g->dout, g->ho, g->wi, g->c / (v8 ? 8 : 4), hch, grid);
-        MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-            if constexpr (sizeof(T) == 2) {
-                if (v8) hipLaunchKernelGGL((maxpool2_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, idx, hch);
-            }
-            if (!v8) hipLaunchKernelGGL((maxpool2_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, idx, hch);
-        });
-        return check_launch("maxpool3d_fwd");
-    }
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-        if constexpr (sizeof(T) == 2) {
-            if (v8) hipLaunchKernelGGL((maxpool_fwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, idx, hch);
-        }
-        if (v8) {
-        } else if (v4)
-            hipLaunchKernelGGL((maxpool_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, idx, hch);
+        if (p.kern == ResampleKernel::maxpool2_fwd)
+            with_int<4, 8>(p.vec, [&](auto V) {
+                if constexpr (has_vec<T, V.value>) launch<maxpool2_fwd_kernel<T, V.value>>(p, s, *g, (const T*)x, (T*)y, idx, p.hch);
+            });
         else
-            hipLaunchKernelGGL((maxpool_fwd_kernel<T, 1>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, idx, hch);
+            with_int<1, 4, 8>(p.vec, [&](auto V) {
+                if constexpr (has_vec<T, V.value>) launch<maxpool_fwd_kernel<T, V.value>>(p, s, *g, (const T*)x, (T*)y, idx, p.hch);
+            });
     });
-    return check_launch("maxpool3d_fwd");
+    return check_launch(p.name);
 }
 
 static int maxpool_bwd_impl(const Mri3dPoolGeom* g, const void* dy, const uint8_t* idx, const void* addend, int32_t a_ld,
                             void* dx, mri3d_stream_t stream) {
-    int rc = pool_check(g, "maxpool3d_bwd");
-    if (rc) return rc;
+    if (int rc = pool_bwd_check(g, addend != nullptr, a_ld, "maxpool3d_bwd")) return rc;
     MRI3D_REQUIRE(dy && dx && idx, MRI3D_EINVAL, "maxpool3d_bwd: null pointer");
-    MRI3D_REQUIRE(addend == nullptr || a_ld >= g->c, MRI3D_EINVAL, "maxpool3d_bwd: addend pitch %d < %d channels", a_ld, g->c);
+    const ResamplePlan p = pool_bwd_plan(*g, ptr_align(dx, dy), ptr_align(idx), addend != nullptr, a_ld, ptr_align(addend));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    bool v4 = vec_ok(g->dtype, g->c, g->x_ld, g->y_ld, dx, dy) && (reinterpret_cast<uintptr_t>(idx) & 3) == 0 &&
-              (addend == nullptr || (a_ld % 4 == 0 && aligned_vec4(g->dtype, addend)));
-    int hch, grid;
-    const bool v8 = v4 && g->dtype == MRI3D_BF16 && g->c % 8 == 0 && g->x_ld % 8 == 0 && g->y_ld % 8 == 0 && aligned16(dx, dy) &&
-                    (reinterpret_cast<uintptr_t>(idx) & 7) == 0 && (addend == nullptr || (a_ld % 8 == 0 && aligned16(addend)));
-    slab_plan(g->n * g->di, g->hi, g->wi, g->c / (v8 ? 8 : (v4 ? 4 : 1)), hch, grid);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-        if constexpr (sizeof(T) == 2) {
-            if (v8) hipLaunchKernelGGL((maxpool_bwd_kernel<T, 8>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, idx, (T*)dx, hch,
-                                       (const T*)addend, a_ld);
-        }
-        if (v8) {
-        } else if (v4)
-            hipLaunchKernelGGL((maxpool_bwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, idx, (T*)dx, hch,
-                               (const T*)addend, a_ld);
-        else
-            hipLaunchKernelGGL((maxpool_bwd_kernel<T, 1>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, idx, (T*)dx, hch,
-                               (const T*)addend, a_ld);
+        with_int<1, 4, 8>(p.vec, [&](auto V) {
+            if constexpr (has_vec<T, V.value>)
+                launch<maxpool_bwd_kernel<T, V.value>>(p, s, *g, (const T*)dy, idx, (T*)dx, p.hch, (const T*)addend, (int)a_ld);
+        });
     });
-    return check_launch("maxpool3d_bwd");
+    return check_launch(p.name);
 }
 
 extern "C" int mri3d_maxpool3d_bwd(const Mri3dPoolGeom* g, const void* dy, const uint8_t* idx, void* dx,
@@ -937,6 +1053,25 @@ extern "C" int mri3d_maxpool3d_bwd_add(const Mri3dPoolGeom* g, const void* dy, c
                                        int32_t addend_ld, void* dx, mri3d_stream_t stream) {
     MRI3D_REQUIRE(addend != nullptr, MRI3D_EINVAL, "maxpool3d_bwd_add: null addend");
     return maxpool_bwd_impl(g, dy, idx, addend, addend_ld, dx, stream);
+}
+
+static int route_args_check(int32_t pass, const char* name, size_t name_bytes, const char* who) {
+    MRI3D_REQUIRE(name != nullptr && name_bytes >= sizeof(ResamplePlan::name), MRI3D_EINVAL, "%s: name buffer of at least %zu bytes required",
+                  who, sizeof(ResamplePlan::name));
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "%s: unknown pass %d", who, pass);
+    return MRI3D_OK;
+}
+
+extern "C" int mri3d_maxpool3d_route(const Mri3dPoolGeom* g, int32_t pass, int32_t addend_ld, int32_t align_tensors,
+                                     int32_t align_idx, char* name, size_t name_bytes) {
+    if (int rc = route_args_check(pass, name, name_bytes, "maxpool3d_route")) return rc;
+    MRI3D_REQUIRE(addend_ld == 0 || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "maxpool3d_route: only the backward takes an addend");
+    if (int rc = pass == MRI3D_PASS_FWD ? pool_check(g, "maxpool3d_route") : pool_bwd_check(g, addend_ld != 0, addend_ld, "maxpool3d_route"))
+        return rc;
+    const ResamplePlan p = pass == MRI3D_PASS_FWD ? pool_fwd_plan(*g, align_tensors, align_idx)
+                                                  : pool_bwd_plan(*g, align_tensors, align_idx, addend_ld != 0, addend_ld, align_tensors);
+    snprintf(name, name_bytes, "%s", p.name);
+    return MRI3D_OK;
 }
 
 static int up_check(const Mri3dUpGeom* g, const char* who) {
@@ -957,125 +1092,58 @@ extern "C" size_t mri3d_upsample3d_workspace_bytes(const Mri3dUpGeom* g) {
 }
 
 extern "C" int mri3d_upsample3d_fwd(const Mri3dUpGeom* g, const void* x, void* y, mri3d_stream_t stream) {
-    int rc = up_check(g, "upsample3d_fwd");
-    if (rc) return rc;
+    if (int rc = up_check(g, "upsample3d_fwd")) return rc;
     MRI3D_REQUIRE(x && y, MRI3D_EINVAL, "upsample3d_fwd: null pointer");
+    const ResamplePlan p = up_fwd_plan(*g, ptr_align(x, y));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static const int no_fast_f = tuning_knob("MRI3D_UP_GENERIC", 0);   // tuning aid (A/B)
-    if (!no_fast_f && up2x_fast_ok(*g) && aligned_vec4(g->dtype, x, y)) {
-        // marching kernel: lane items of 16 bytes where the tensors allow it (bf16: channels and pitches in whole octets)
-        const bool oct = g->dtype == MRI3D_BF16 && g->c % 8 == 0 && g->x_ld % 8 == 0 && g->y_ld % 8 == 0 &&
-                         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-        const int vec = oct ? 8 : 4, pieces = g->c / vec;
-        const int npv = pieces >= 8 ? 8 : pieces >= 4 ? 4 : pieces >= 2 ? 2 : 1;
-        const int mtilesH = cdiv(g->hi, UTH), mtilesW = cdiv(g->wi, UTW), mpasses = cdiv(pieces, npv);
-        int segl = UMD;   // every segment stages two planes more than it owns: long segments unless the grid would not fill the chip
-        while (segl > 4 && (int64_t)g->n * cdiv(g->di, segl) * mpasses * mtilesH * mtilesW < 1024) segl /= 2;
-        const int segsD = cdiv(g->di, segl);
-        const int64_t items = (int64_t)g->n * segsD * mpasses * mtilesH * mtilesW;
-        if (items <= 0x7ffffff0 && (int64_t)g->ho * g->wo * g->y_ld <= 0x7fffffff &&
-            (int64_t)g->hi * g->wi * g->x_ld <= 0x7fffffff) {
-            const int grid = (int)std::min<int64_t>((items + 7) / 8 * 8, 256 * 4 * 8);
-#define MRI3D_UPF(Tv, VECv, NPVv)                                                                                      \
-    hipLaunchKernelGGL((upsample2x_fwd_march_kernel<Tv, VECv, NPVv>), dim3(grid), dim3(256), 0, s, *g, (const Tv*)x,  \
-                       (Tv*)y, segsD, segl, mtilesH, mtilesW, mpasses, (int)items)
-#define MRI3D_UPF_N(Tv, VECv)                                                                                          \
-    do {                                                                                                              \
-        if (npv == 8) MRI3D_UPF(Tv, VECv, 8);                                                                         \
-        else if (npv == 4) MRI3D_UPF(Tv, VECv, 4);                                                                    \
-        else if (npv == 2) MRI3D_UPF(Tv, VECv, 2);                                                                    \
-        else MRI3D_UPF(Tv, VECv, 1);                                                                                  \
-    } while (0)
-            if (g->dtype == MRI3D_F32) MRI3D_UPF_N(float, 4);
-            else if (oct) MRI3D_UPF_N(bf16_t, 8);
-            else MRI3D_UPF_N(bf16_t, 4);
-#undef MRI3D_UPF_N
-#undef MRI3D_UPF
-            return check_launch("upsample3d_fwd(2x march)");
-        }
-    }
-    bool v4 = vec_ok(g->dtype, g->c, g->x_ld, g->y_ld, x, y);
-    int hch, grid;
-    slab_plan(g->n * g->dout, g->ho, g->wo, g->c / (v4 ? 4 : 1), hch, grid);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-        if (v4)
-            hipLaunchKernelGGL((upsample_fwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, hch);
+        if (p.kern == ResampleKernel::up2x_fwd_march)
+            with_int<4, 8>(p.vec, [&](auto V) {
+                with_int<1, 2, 4, 8>(p.npv, [&](auto N) {
+                    constexpr int VEC = decltype(V)::value;
+                    if constexpr (has_vec<T, VEC>)
+                        launch<upsample2x_fwd_march_kernel<T, VEC, N.value>>(p, s, *g, (const T*)x, (T*)y, p.segs, p.segl, p.tilesH, p.tilesW,
+                                                                              p.passes, p.items);
+                });
+            });
         else
-            hipLaunchKernelGGL((upsample_fwd_kernel<T, 1>), dim3(grid), dim3(256), 0, s, *g, (const T*)x, (T*)y, hch);
+            with_int<1, 4>(p.vec, [&](auto V) { launch<upsample_fwd_kernel<T, V.value>>(p, s, *g, (const T*)x, (T*)y, p.hch); });
     });
-    return check_launch("upsample3d_fwd");
+    return check_launch(p.name);
 }
 
 extern "C" int mri3d_upsample3d_bwd(const Mri3dUpGeom* g, const void* dy, void* dx, void* workspace, size_t ws_bytes,
                                     mri3d_stream_t stream) {
-    int rc = up_check(g, "upsample3d_bwd");
-    if (rc) return rc;
+    if (int rc = up_check(g, "upsample3d_bwd")) return rc;
     MRI3D_REQUIRE(dy && dx, MRI3D_EINVAL, "upsample3d_bwd: null pointer");
     MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_upsample3d_workspace_bytes(g), MRI3D_EWORKSPACE,
                   "upsample3d_bwd: workspace %zu < %zu", ws_bytes, mri3d_upsample3d_workspace_bytes(g));
+    const ResamplePlan p = up_bwd_plan(*g, ptr_align(dx, dy));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    static const int no_fast = tuning_knob("MRI3D_UP_GENERIC", 0);   // tuning aid (A/B)
-    if (!no_fast && up2x_fast_ok(*g) && aligned_vec4(g->dtype, dx, dy)) {
-        static const int march = tuning_knob("MRI3D_UP_MARCH", 1);   // tuning aid (A/B)
-        if (march && g->c % 16 == 0) {
-            const int segsD = cdiv(g->di, MD), tilesH = cdiv(g->hi, MTH), tilesW = cdiv(g->wi, MTW), cpasses = g->c / 16;
-            const int64_t items = (int64_t)g->n * segsD * cpasses * tilesH * tilesW;
-            if (items <= 0x7ffffff0 && (int64_t)g->ho * g->wo * g->y_ld <= 0x7fffffff) {
-                const int grid = (int)std::min<int64_t>((items + 7) / 8 * 8, 256 * 3 * 8);
-                MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-                    hipLaunchKernelGGL(upsample2x_bwd_march_kernel<T>, dim3(grid), dim3(256), 0, s, *g, (const T*)dy, (T*)dx,
-                                       segsD, tilesH, tilesW, cpasses, (int)items);
-                });
-                return check_launch("upsample3d_bwd(2x march)");
-            }
-        }
-        // 16-channel passes pay off for fp32 (0.93 vs 1.25 ms on the c32 level); bf16 already reads 32-byte slices with 8
-        // channels... measured 0.68 ms (CQ = 2) vs 0.96 ms (CQ = 4), so it keeps the 8-channel tile
-        const bool wide = g->c % 16 == 0 && g->dtype == MRI3D_F32;
-        const int utd = wide ? Up2Tile<4>::TD : Up2Tile<2>::TD, uth = wide ? Up2Tile<4>::TH : Up2Tile<2>::TH, utw = 16;
-        const int tilesD = cdiv(g->di, utd), tilesH = cdiv(g->hi, uth), tilesW = cdiv(g->wi, utw);
-        const int64_t nt = (int64_t)g->n * tilesD * tilesH * tilesW;
-        if (nt <= 0x7fffffff) {
-            const size_t smem = (size_t)(2 * utd + 2) * (2 * uth + 2) * (2 * utw + 2) * (wide ? 4 : 2) * sizeof(float4);
-            const int grid = (int)std::min<int64_t>(nt, 2048);
-#define MRI3D_UP2B(CQv)                                                                                               \
-    {                                                                                                                 \
-        auto kern = upsample2x_bwd_kernel<T, CQv>;                                                                    \
-        static const hipError_t attr_ = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                      \
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);   \
-        (void)attr_;   /* once per kernel (smem is a constant of the instantiation), not per launch */                \
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, *g, (const T*)dy, (T*)dx, tilesD, tilesH, tilesW,    \
-                           (int)nt);                                                                                  \
-    }
-            MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-                if (wide) MRI3D_UP2B(4) else MRI3D_UP2B(2)
-            });
-#undef MRI3D_UP2B
-            return check_launch("upsample3d_bwd(2x)");
-        }
-    }
-    bool v4 = vec_ok(g->dtype, g->c, g->x_ld, g->y_ld, dx, dy);
-    int hch, grid;
-    slab_plan(g->n * g->di, g->hi, g->wi, g->c / (v4 ? 4 : 1), hch, grid);
-    // nearest neighbour with output = S x input in every axis (S = 2, 4): the plain S^3 box sum
-    const int sc = g->di > 0 ? g->dout / g->di : 0;
-    if (!no_fast && g->mode == MRI3D_UP_NEAREST && v4 && (sc == 2 || sc == 4) && g->dout == sc * g->di && g->ho == sc * g->hi &&
-        g->wo == sc * g->wi) {
-        MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-            if (sc == 4)
-                hipLaunchKernelGGL((upsample_nearest_int_bwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, (T*)dx, hch);
-            else
-                hipLaunchKernelGGL((upsample_nearest_int_bwd_kernel<T, 2>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, (T*)dx, hch);
-        });
-        return check_launch("upsample3d_bwd(nearest, integer scale)");
-    }
     int* tab = static_cast<int*>(workspace);
-    hipLaunchKernelGGL(upsample_tables_kernel, dim3(3), dim3(256), 0, s, *g, tab);
+    if (p.tables) hipLaunchKernelGGL(upsample_tables_kernel, dim3(3), dim3(256), 0, s, *g, tab);
     MRI3D_DISPATCH_DTYPE(g->dtype, T, {
-        if (v4)
-            hipLaunchKernelGGL((upsample_bwd_kernel<T, 4>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, (T*)dx, tab, hch);
-        else
-            hipLaunchKernelGGL((upsample_bwd_kernel<T, 1>), dim3(grid), dim3(256), 0, s, *g, (const T*)dy, (T*)dx, tab, hch);
+        switch (p.kern) {
+        case ResampleKernel::up2x_bwd_march:
+            launch<upsample2x_bwd_march_kernel<T>>(p, s, *g, (const T*)dy, (T*)dx, p.segs, p.tilesH, p.tilesW, p.passes, p.items);
+            break;
+        case ResampleKernel::up2x_bwd_tile:
+            launch<upsample2x_bwd_kernel<T>>(p, s, *g, (const T*)dy, (T*)dx, p.segs, p.tilesH, p.tilesW, p.items);
+            break;
+        case ResampleKernel::up_nearest_int_bwd:
+            with_int<2, 4>(p.npv, [&](auto S) { launch<upsample_nearest_int_bwd_kernel<T, S.value>>(p, s, *g, (const T*)dy, (T*)dx, p.hch); });
+            break;
+        default:
+            with_int<1, 4>(p.vec, [&](auto V) { launch<upsample_bwd_kernel<T, V.value>>(p, s, *g, (const T*)dy, (T*)dx, (const int*)tab, p.hch); });
+        }
     });
-    return check_launch("upsample3d_bwd");
+    return check_launch(p.name);
+}
+
+extern "C" int mri3d_upsample3d_route(const Mri3dUpGeom* g, int32_t pass, int32_t align, char* name, size_t name_bytes) {
+    if (int rc = route_args_check(pass, name, name_bytes, "upsample3d_route")) return rc;
+    if (int rc = up_check(g, "upsample3d_route")) return rc;
+    const ResamplePlan p = pass == MRI3D_PASS_FWD ? up_fwd_plan(*g, align) : up_bwd_plan(*g, align);
+    snprintf(name, name_bytes, "%s", p.name);
+    return MRI3D_OK;
 }

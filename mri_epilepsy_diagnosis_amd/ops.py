@@ -366,6 +366,23 @@ def conv_route(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16
     return name.value.decode()
 
 
+def pool_route(g, pass_, addend_ld=0, align=16, idx_align=16):
+    """Name of the kernel max_pool3d launches for the PoolGeom `g` in pass `pass_` (PASS_FWD, PASS_DGRAD; addend_ld: the pitch of
+    max_pool3d_skip's second gradient), host only, as `conv_route`.  align / idx_align: `_ptr_align` of the tensors / of the index
+    bytes.  The vocabulary is documented at mri3d_maxpool3d_route in include/mri3d.h."""
+    name = ctypes.create_string_buffer(64)
+    check(_lib.lib().mri3d_maxpool3d_route(ctypes.byref(g), pass_, addend_ld, align, idx_align, name, 64), "maxpool3d_route")
+    return name.value.decode()
+
+
+def upsample_route(g, pass_, align=16):
+    """Name of the kernel upsample3d launches for the UpGeom `g` in pass `pass_` (PASS_FWD, PASS_DGRAD), host only, as `conv_route`
+    (vocabulary: mri3d_upsample3d_route in include/mri3d.h)."""
+    name = ctypes.create_string_buffer(64)
+    check(_lib.lib().mri3d_upsample3d_route(ctypes.byref(g), pass_, align, name, 64), "upsample3d_route")
+    return name.value.decode()
+
+
 def norm_plan(g, pass_, align=16):
     """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
     tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is
@@ -462,8 +479,9 @@ def _carg(a):   # a tensor (or None) as its address, a geometry by reference, an
 
 
 def _launch(fn, tag, work, ws_bytes, device, *args):
-    """The launch tail of the convolution family: the stream's workspace of ws_bytes (None: the entry point takes none), the
-    `_timed(tag, work)` bracket and the checked call fn(*args, workspace, its size, stream), fn an entry point of the library."""
+    """The launch tail of the convolution, pool and upsample operators: the stream's workspace of ws_bytes (None: the entry point
+    takes none), the `_timed(tag, work)` bracket and the checked call fn(*args, workspace, its size, stream), fn an entry point of
+    the library."""
     tail = ()
     if ws_bytes is not None:
         ws = _workspace(ws_bytes, device)
@@ -1073,8 +1091,14 @@ def _norm_geom(x, x_ld, y_ld, act_code, alpha, slope, eps, instance=0, group_c=0
     return NormGeom(n, d * h * w, c, x_ld, y_ld, instance, act_code, alpha_n, float(slope), float(eps), group_c, _dt(x))
 
 
-def _repitched(g, x_ld, y_ld):
-    return NormGeom(g.n, g.vox, g.c, x_ld, y_ld, g.instance, g.act, g.alpha_n, g.slope, g.eps, g.group_c, g.dtype)
+def _repitched(g, x_ld, y_ld, dtype=None):
+    """A copy of the geometry g (NormGeom, PoolGeom or UpGeom) with other voxel pitches — what a backward pass makes of its
+    forward's geometry — and, where given, the storage type of the gradient it reads."""
+    g = type(g).from_buffer_copy(g)
+    g.x_ld, g.y_ld = x_ld, y_ld
+    if dtype is not None:
+        g.dtype = dtype
+    return g
 
 
 def _norm_statistics(who, g, x, groups, mode, running_mean, running_var, momentum, eps, fused_stats):
@@ -1300,9 +1324,9 @@ def norm_act_pointwise(x, weight, bias=None, gamma=None, beta=None, alpha=None, 
                                      act, slope, fused)
 
 
-def _pool_tail_geom(x, s_ld, p_ld, kernel, stride, padding):
-    """(PoolGeom, pooled extents) of the max pool that follows act(norm(x)): voxel pitches s_ld (its input: skip / dskip) and
-    p_ld (pooled / dpool)."""
+def _pool_geom(x, s_ld, p_ld, kernel, stride, padding):
+    """(PoolGeom, pooled extents) of a max pool over a tensor of x's shape — x itself, or the act(norm(x)) of `norm_act_pool`:
+    voxel pitches s_ld (its input / that one's gradient) and p_ld (pooled / dpool)."""
     n, c, d, h, w = x.shape
     do, ho, wo = (_pool_out(i, k, s, p, False) for i, k, s, p in zip((d, h, w), kernel, stride, padding))
     return PoolGeom(n, d, h, w, do, ho, wo, c, *kernel, *stride, *padding, s_ld, p_ld, _dt(x)), (do, ho, wo)
@@ -1318,7 +1342,7 @@ def norm_act_pool_supported(x, kernel_size=2, stride=None, padding=0, stats_mode
     s = _triple(stride) if stride is not None else k
     c = x.shape[1]
     g = _norm_geom(x, x_ld, c, _ACT_CODES[act], alpha, 0.0, 0.0)
-    pg, out = _pool_tail_geom(x, c, c, k, s, _triple(padding))
+    pg, out = _pool_geom(x, c, c, k, s, _triple(padding))
     if min(out) <= 0:
         return False
     return bool(_lib.lib().mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)))
@@ -1340,7 +1364,7 @@ class _NormActPoolFn(torch.autograd.Function):
         act_code = _ACT_CODES[act]
         two = (2, 2, 2)
         g = _norm_geom(x, x_ld, c, act_code, alpha, slope, eps)
-        pg, (do, ho, wo) = _pool_tail_geom(x, c, c, two, two, (0, 0, 0))
+        pg, (do, ho, wo) = _pool_geom(x, c, c, two, two, (0, 0, 0))
         if not L.mri3d_norm_act_pool_supported(ctypes.byref(g), ctypes.byref(pg)):
             raise RuntimeError("norm_act_pool: c=%d pitch %d extents %s is not served (ask norm_act_pool_supported first)"
                                % (c, x_ld, (d, h, w)))
@@ -1385,7 +1409,7 @@ class _NormActPoolFn(torch.autograd.Function):
         x = _backward_x("norm_act_pool", x, g0, dpool, dskip)
         two = (2, 2, 2)
         g = _repitched(g0, c, s_ld)
-        pg, _ = _pool_tail_geom(x, s_ld, p_ld, two, two, (0, 0, 0))
+        pg, _ = _pool_geom(x, s_ld, p_ld, two, two, (0, 0, 0))
         prelu = g.act == ACT_PRELU
         sinks, grads = _grad_slots(ctx, (gamma, beta, alpha if prelu else None))
         dx = _new(x.shape, x) if ctx.needs_input_grad[0] else None
@@ -1475,17 +1499,15 @@ class _MaxPool3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kernel, stride, padding):
         _require_device(x)
-        L = _lib.lib()
         x, x_ld = _nd(x)
         n, c, d, h, w = x.shape
-        do, ho, wo = (_pool_out(i, k, s, p, False) for i, k, s, p in zip((d, h, w), kernel, stride, padding))
+        g, (do, ho, wo) = _pool_geom(x, x_ld, c, kernel, stride, padding)
         if do <= 0 or ho <= 0 or wo <= 0:
             raise RuntimeError("max_pool3d: output size is too small (input %s, kernel %s)" % ((d, h, w), kernel))
-        g = PoolGeom(n, d, h, w, do, ho, wo, c, *kernel, *stride, *padding, x_ld, c, _dt(x))
         y = _new((n, c, do, ho, wo), x)
         idx = torch.empty(n * do * ho * wo * c, dtype=torch.uint8, device=x.device)
-        with _timed(lambda: "maxpool_fwd c%d" % c, lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel() + (_esz(x) + 1) * y.numel()}):
-            check(L.mri3d_maxpool3d_fwd(ctypes.byref(g), _ptr(x), _ptr(y), _ptr(idx), _stream()), "maxpool3d_fwd")
+        _launch(_lib.lib().mri3d_maxpool3d_fwd, lambda: "maxpool_fwd c%d" % c,
+                lambda: {"flops": 0.0, "bytes": _esz(x) * x.numel() + (_esz(x) + 1) * y.numel()}, None, x.device, g, x, y, idx)
         ctx.save_for_backward(idx)
         ctx.geom = g
         ctx.xshape = tuple(x.shape)
@@ -1493,16 +1515,23 @@ class _MaxPool3dFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        L = _lib.lib()
-        (idx,) = ctx.saved_tensors
-        dy, dy_ld = _nd(dy)
-        dx = _new(ctx.xshape, dy)
-        g0 = ctx.geom
-        g = PoolGeom(g0.n, g0.di, g0.hi, g0.wi, g0.dout, g0.ho, g0.wo, g0.c, g0.kd, g0.kh, g0.kw, g0.sd, g0.sh, g0.sw,
-                     g0.pd, g0.ph, g0.pw, g0.c, dy_ld, _dt(dy))
-        with _timed(lambda: "maxpool_bwd c%d" % g.c, lambda: {"flops": 0.0, "bytes": _esz(dy) * dx.numel() + (_esz(dy) + 1) * dy.numel()}):
-            check(L.mri3d_maxpool3d_bwd(ctypes.byref(g), _ptr(dy), _ptr(idx), _ptr(dx), _stream()), "maxpool3d_bwd")
-        return dx, None, None, None
+        return _pool_backward(ctx, dy)
+
+
+def _pool_backward(ctx, dy, dskip=None, ds_ld=0):
+    """dx = maxpool_bwd(dy), plus dskip (the other gradient of x, NDHWC with voxel pitch ds_ld) where `_MaxPoolSkipFn` has one."""
+    (idx,) = ctx.saved_tensors
+    dy, dy_ld = _nd(dy)
+    dx = _new(ctx.xshape, dy)
+    g = _repitched(ctx.geom, ctx.geom.c, dy_ld, _dt(dy))
+    if dskip is None:
+        _launch(_lib.lib().mri3d_maxpool3d_bwd, lambda: "maxpool_bwd c%d" % g.c,
+                lambda: {"flops": 0.0, "bytes": _esz(dy) * dx.numel() + (_esz(dy) + 1) * dy.numel()}, None, dy.device, g, dy, idx, dx)
+    else:
+        _launch(_lib.lib().mri3d_maxpool3d_bwd_add, lambda: "maxpool_bwd+skip c%d" % g.c,
+                lambda: {"flops": 0.0, "bytes": _esz(dy) * 2 * dx.numel() + (_esz(dy) + 1) * dy.numel()}, None, dy.device,
+                g, dy, idx, dskip, ds_ld, dx)
+    return dx, None, None, None
 
 
 class _MaxPoolSkipFn(torch.autograd.Function):
@@ -1521,21 +1550,11 @@ class _MaxPoolSkipFn(torch.autograd.Function):
             return _MaxPool3dFn.backward(ctx, dy)
         if dy is None:
             return dskip, None, None, None
-        L = _lib.lib()
-        (idx,) = ctx.saved_tensors
-        dy, dy_ld = _nd(dy)
         dskip, ds_ld = _nd(dskip)
         if tuple(dskip.shape) != ctx.xshape or dskip.dtype != dy.dtype:
             raise RuntimeError("max_pool3d_skip backward: skip gradient %s %s does not match the input %s %s"
                                % (tuple(dskip.shape), dskip.dtype, ctx.xshape, dy.dtype))
-        dx = _new(ctx.xshape, dy)
-        g0 = ctx.geom
-        g = PoolGeom(g0.n, g0.di, g0.hi, g0.wi, g0.dout, g0.ho, g0.wo, g0.c, g0.kd, g0.kh, g0.kw, g0.sd, g0.sh, g0.sw,
-                     g0.pd, g0.ph, g0.pw, g0.c, dy_ld, _dt(dy))
-        with _timed(lambda: "maxpool_bwd+skip c%d" % g.c, lambda: {"flops": 0.0, "bytes": _esz(dy) * 2 * dx.numel() + (_esz(dy) + 1) * dy.numel()}):
-            check(L.mri3d_maxpool3d_bwd_add(ctypes.byref(g), _ptr(dy), _ptr(idx), _ptr(dskip), ds_ld, _ptr(dx), _stream()),
-                  "maxpool3d_bwd_add")
-        return dx, None, None, None
+        return _pool_backward(ctx, dy, dskip, ds_ld)
 
 
 def max_pool3d_skip(x, kernel_size, stride=None, padding=0):
@@ -1558,7 +1577,6 @@ class _Upsample3dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, out_size, mode, align_corners, ratios, out):
         _require_device(x)
-        L = _lib.lib()
         x, x_ld = _nd(x)
         n, c, d, h, w = x.shape
         do, ho, wo = out_size
@@ -1574,8 +1592,8 @@ class _Upsample3dFn(torch.autograd.Function):
             y = _slice_view(buf, y_off, c)
         g = UpGeom(n, d, h, w, do, ho, wo, c, x_ld, y_ld, mode, 1 if align_corners else 0, ratios[0], ratios[1], ratios[2],
                    _dt(x))
-        with _timed(lambda: "upsample_fwd c%d" % c, lambda: {"flops": 0.0, "bytes": _esz(x) * (x.numel() + y.numel())}):
-            check(L.mri3d_upsample3d_fwd(ctypes.byref(g), _ptr(x), _ptr(y), _stream()), "upsample3d_fwd")
+        _launch(_lib.lib().mri3d_upsample3d_fwd, lambda: "upsample_fwd c%d" % c,
+                lambda: {"flops": 0.0, "bytes": _esz(x) * (x.numel() + y.numel())}, None, x.device, g, x, y)
         ctx.geom = g
         ctx.xshape = tuple(x.shape)
         return y
@@ -1583,15 +1601,11 @@ class _Upsample3dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
-        g0 = ctx.geom
         dy, dy_ld = _nd(dy)
         dx = _new(ctx.xshape, dy)
-        g = UpGeom(g0.n, g0.di, g0.hi, g0.wi, g0.dout, g0.ho, g0.wo, g0.c, g0.c, dy_ld, g0.mode, g0.align_corners, g0.rd,
-                   g0.rh, g0.rw, _dt(dy))
-        ws = _workspace(L.mri3d_upsample3d_workspace_bytes(ctypes.byref(g)), dy.device)
-        with _timed(lambda: "upsample_bwd c%d" % g.c, lambda: {"flops": 0.0, "bytes": _esz(dy) * (dx.numel() + dy.numel())}):
-            check(L.mri3d_upsample3d_bwd(ctypes.byref(g), _ptr(dy), _ptr(dx), _ptr(ws), ws.numel(), _stream()),
-                  "upsample3d_bwd")
+        g = _repitched(ctx.geom, ctx.geom.c, dy_ld, _dt(dy))
+        _launch(L.mri3d_upsample3d_bwd, lambda: "upsample_bwd c%d" % g.c, lambda: {"flops": 0.0, "bytes": _esz(dy) * (dx.numel() + dy.numel())},
+                L.mri3d_upsample3d_workspace_bytes(ctypes.byref(g)), dy.device, g, dy, dx)
         return dx, None, None, None, None, None
 
 

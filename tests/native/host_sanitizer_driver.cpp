@@ -242,6 +242,50 @@ int main() {
         dg.n = 2; dg.vox = (int64_t)160 * 192 * 160; dg.c = 2; dg.ct = 1; dg.x_ld = 2; dg.t_ld = 1; dg.eps = 1e-9f;
         EXPECT(mri3d_softmax_dice_workspace_bytes(&dg) > 0);
     }
+    {   // pool / upsample route queries: the four launch plans over channels, dtypes and alignments name a kernel, launch nothing
+        char rname[40];
+        long routes = 0;
+        for (int c : {1, 3, 4, 8, 12, 16, 24, 40, 64})
+            for (int dt = 0; dt < 2; ++dt)
+                for (int align : {4, 8, 16}) {
+                    Mri3dPoolGeom pg;
+                    memset(&pg, 0, sizeof(pg));
+                    pg.n = 2; pg.di = 8; pg.hi = 6; pg.wi = 10; pg.dout = 4; pg.ho = 3; pg.wo = 5; pg.c = c; pg.x_ld = c; pg.y_ld = c;
+                    pg.kd = pg.kh = pg.kw = 2; pg.sd = pg.sh = pg.sw = 2; pg.dtype = dt;
+                    for (int addend_ld : {-1, 0, c, c + 4}) {
+                        memset(rname, 0x7f, sizeof(rname));
+                        const int pass = addend_ld < 0 ? MRI3D_PASS_FWD : MRI3D_PASS_DGRAD;
+                        EXPECT(mri3d_maxpool3d_route(&pg, pass, addend_ld < 0 ? 0 : addend_ld, align, align, rname, sizeof(rname)) == MRI3D_OK);
+                        EXPECT(memchr(rname, 0, sizeof(rname)) != nullptr && rname[0] != 0);
+                        ++routes;
+                    }
+                    Mri3dUpGeom ug;
+                    memset(&ug, 0, sizeof(ug));
+                    ug.n = 2; ug.di = 4; ug.hi = 5; ug.wi = 6; ug.c = c; ug.x_ld = c; ug.y_ld = c; ug.dtype = dt;
+                    for (int kind = 0; kind < 3; ++kind) {      // trilinear x2, nearest x4, trilinear to a size
+                        const int sc = kind == 0 ? 2 : 4;
+                        ug.dout = kind == 2 ? 7 : sc * ug.di; ug.ho = kind == 2 ? 9 : sc * ug.hi; ug.wo = kind == 2 ? 11 : sc * ug.wi;
+                        ug.mode = kind == 1 ? MRI3D_UP_NEAREST : MRI3D_UP_TRILINEAR;
+                        ug.rd = (float)ug.di / ug.dout; ug.rh = (float)ug.hi / ug.ho; ug.rw = (float)ug.wi / ug.wo;
+                        for (int pass : {MRI3D_PASS_FWD, MRI3D_PASS_DGRAD}) {
+                            memset(rname, 0x7f, sizeof(rname));
+                            EXPECT(mri3d_upsample3d_route(&ug, pass, align, rname, sizeof(rname)) == MRI3D_OK);
+                            EXPECT(memchr(rname, 0, sizeof(rname)) != nullptr && rname[0] != 0);
+                            ++routes;
+                        }
+                    }
+                    if (c == 1 && dt == 0 && align == 4) {       // argument validation
+                        EXPECT(mri3d_maxpool3d_route(nullptr, MRI3D_PASS_FWD, 0, 16, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
+                        EXPECT(mri3d_maxpool3d_route(&pg, MRI3D_PASS_WGRAD, 0, 16, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
+                        EXPECT(mri3d_maxpool3d_route(&pg, MRI3D_PASS_FWD, c, 16, 16, rname, sizeof(rname)) == MRI3D_EINVAL);      // an addend in the forward
+                        EXPECT(mri3d_maxpool3d_route(&pg, MRI3D_PASS_DGRAD, 0, 16, 16, rname, 8) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_route(nullptr, MRI3D_PASS_FWD, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_route(&ug, MRI3D_PASS_WGRAD, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_route(&ug, MRI3D_PASS_FWD, 16, nullptr, sizeof(rname)) == MRI3D_EINVAL);
+                    }
+                }
+        EXPECT(routes == 9 * 2 * 3 * (4 + 6));
+    }
     EXPECT(mri3d_norm_workspace_bytes(nullptr) == 0);
     EXPECT(mri3d_mask_overlap_workspace_bytes() > 0 && mri3d_order_stats_workspace_bytes() > 0 && mri3d_znorm_workspace_bytes() > 0);
     EXPECT(mri3d_surface_distance_workspace_bytes(160, 192, 160) > 0);

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as cc
+import resample_cases as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -110,9 +111,10 @@ def test_norm_act_bf16(mode, act, c):
 def test_pool_upsample_cat_add_bf16():
     ops = _ops()
     torch.manual_seed(3)
-    x = _rb(torch.randn(2, 8, 8, 10, 12))
+    p = rc.BF16_CHAIN_POOL                                     # (rc.BF16_CHAIN_UP: the two upsamples of the pooled tensor)
+    x = _rb(torch.randn(rc.N, p.c, *p.sp))
     xr = x.clone().requires_grad_(True)
-    pr = F.max_pool3d(xr, 2)
+    pr = F.max_pool3d(xr, p.k)
     ur = F.interpolate(pr, scale_factor=2, mode="trilinear", align_corners=False)
     nr = F.interpolate(pr, scale_factor=2, mode="nearest")
     cr = torch.cat((ur, nr), dim=1)
@@ -122,7 +124,7 @@ def test_pool_upsample_cat_add_bf16():
     g_cat = xr.grad.clone()
 
     xg = _dev(x).requires_grad_(True)
-    pg = ops.max_pool3d(xg, 2)
+    pg = ops.max_pool3d(xg, p.k)
     ug = ops.upsample3d(pg, scale_factor=2, mode="trilinear", align_corners=False)
     ng = ops.upsample3d(pg, scale_factor=2, mode="nearest")
     cg = ops.cat_channels([ug, ng])
@@ -137,13 +139,13 @@ def test_pool_upsample_cat_add_bf16():
     _close(ag, _rb(ur.detach()) + x, "add")
 
 
-@pytest.mark.parametrize("c,sp", [(8, (5, 9, 19)), (16, (17, 4, 16)), (32, (3, 6, 33)), (64, (18, 5, 7)), (12, (4, 5, 18)), (40, (2, 9, 17))])
+@pytest.mark.parametrize("c,sp", [(r.c, r.sp) for r in rc.BF16_TRILINEAR])
 def test_trilinear_x2_forward_backward_bf16(c, sp):
     """nn.Upsample(scale_factor=2, mode='trilinear') of the U-Net decoder in the bf16 region: the marching kernels with 16-byte lane
     items (channels in octets) and with 8-byte ones (12 channels), ragged columns, two D segments, one and two channel passes."""
     ops = _ops()
     torch.manual_seed(c)
-    x = _rb(torch.randn(2, c, *sp))
+    x = _rb(torch.randn(rc.N, c, *sp))
     xr = x.clone().requires_grad_(True)
     ur = F.interpolate(xr, scale_factor=2, mode="trilinear", align_corners=False)
     dy = _rb(torch.randn_like(ur))
@@ -156,13 +158,14 @@ def test_trilinear_x2_forward_backward_bf16(c, sp):
     _close(xg.grad, xr.grad, "trilinear x2 backward")
 
 
-@pytest.mark.parametrize("scale", [2, 4])
+@pytest.mark.parametrize("scale", [r.scale for r in rc.BF16_NEAREST])
 def test_nearest_upsampling_backward_with_an_integer_scale_bf16(scale):
     """nn.Upsample(scale_factor=S, mode='nearest') backward on bf16 tensors (the S^3 box-sum kernel; AE_model.py:110-120 uses S = 4):
     fp32 accumulation of the S^3 fine gradients, one rounding of the result."""
     ops = _ops()
     torch.manual_seed(11)
-    x = _rb(torch.randn(2, 8, 3, 5, 7))
+    r = next(r for r in rc.BF16_NEAREST if r.scale == scale)
+    x = _rb(torch.randn(rc.N, r.c, *r.sp))
     xr = x.clone().requires_grad_(True)
     yr = F.interpolate(xr, scale_factor=scale, mode="nearest")
     dy = _rb(torch.randn_like(yr))

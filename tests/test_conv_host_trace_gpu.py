@@ -1,5 +1,6 @@
-"""Launch trace of the convolution family's host path: which C-ABI entry points `conv3d`, `conv3d_cat`, `bayes_conv3d`,
-`conv3d_pair`, `conv_transpose3d` and `upsample_conv3d` call, in which order, with which geometries, integers and tensors, under
+"""Launch trace of the convolution family's and the pool / upsample family's host path: which C-ABI entry points `conv3d`,
+`conv3d_cat`, `bayes_conv3d`, `conv3d_pair`, `conv_transpose3d`, `upsample_conv3d`, `max_pool3d`, `max_pool3d_skip` and `upsample3d`
+call, in which order, with which geometries, integers and tensors, under
 which `KernelTimer` tags, and which gradients their backward hands to autograd (a tensor, or None because a `GradSink` took it).
 
 The recorder stands in for `ops._lib.lib()` while a case runs and forwards every call to the real library.  It writes down the entry
@@ -25,6 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import resample_cases as rc  # noqa: E402
 from mri_epilepsy_diagnosis_amd import ops, parallel  # noqa: E402
 
 GOLDEN_FILE = os.path.join(ROOT, "tests", "golden", "conv_host_trace.json")
@@ -195,8 +197,45 @@ def _upconv(ci, co, sp, served=True):
     return make
 
 
+def _smallest(rows):
+    return min(rows, key=lambda r: r.c * r.sp[0] * r.sp[1] * r.sp[2])
+
+
+def _pool():
+    r = _smallest(rc.POOL)
+
+    def make():
+        x = _act(1, (rc.N, r.c) + r.sp)
+        return {"x": x}, {}, lambda: ops.max_pool3d(x, r.k, r.s)
+    return make
+
+
+def _pool_skip():
+    r = _smallest(rc.POOL_SKIP)
+
+    def make():
+        x = _act(1, (rc.N, r.c) + r.sp)
+        return {"x": x}, {}, lambda: ops.max_pool3d_skip(x, 2)
+    return make, r.pad
+
+
+def _upsample(rows, out=False):
+    r = _smallest(rows)
+
+    def make():
+        x = _act(1, (rc.N, r.c) + r.sp)
+        tensors, dest = {"x": x}, None
+        if out:     # the last r.c channels of a cat buffer twice as wide
+            tensors["buf"] = ops.new_cat_buffer(rc.N, 2 * r.c, tuple(int(i * r.scale) for i in r.sp), x)
+            dest = (tensors["buf"], r.c)
+        return tensors, {}, lambda: ops.upsample3d(x, size=r.size, scale_factor=r.scale, mode=r.mode, align_corners=r.ac, out=dest)
+    return make
+
+
+_TRILINEAR_X2 = [r for r in rc.UP if r.mode == "trilinear" and r.scale == 2 and not r.ac]
 _STATS_SERVED, _CAT_SERVED = (2, 16, 5, 9, 17), dict(n=32, sp=(5, 9, 17))      # (the smallest this library serves fused / split in fp32)
-# name -> (make, options): dy_pad pitches the incoming gradient; sinks = "fresh" | "twice" | "suspended" attaches parallel.FlatParams
+# name -> (make, options): dy_pad pitches the incoming gradient (of a node with two outputs: one pad each, None = that output is
+# not used); sinks = "fresh" | "twice" | "suspended" attaches parallel.FlatParams
 CASES = {
     "conv3d": (_conv3d(padding=1), {}),
     "conv3d_bn_stats_served": (_conv3d(_STATS_SERVED, padding=1, bn_stats=True), {}),
@@ -224,6 +263,15 @@ CASES = {
     "transpose_output_padding": (_transpose(stride=2, output_padding=1), {}),
     "upconv_served": (_upconv(8, 1, (3, 4, 5)), {}),
     "upconv_refused": (_upconv(16, 8, (2, 3, 2), served=False), {}),
+    "max_pool3d": (_pool(), {}),
+    "max_pool3d_skip_both": (_pool_skip()[0], {"dy_pad": (0, 0)}),
+    "max_pool3d_skip_pool_only": (_pool_skip()[0], {"dy_pad": (0, None)}),
+    "max_pool3d_skip_skip_only": (_pool_skip()[0], {"dy_pad": (None, 0)}),
+    "max_pool3d_skip_pitched_dskip": (_pool_skip()[0], {"dy_pad": (0, _pool_skip()[1])}),
+    "upsample3d_nearest_x2": (_upsample([r for r in rc.UP if r.mode == "nearest" and r.scale == 2]), {}),
+    "upsample3d_trilinear_x2": (_upsample(_TRILINEAR_X2), {}),
+    "upsample3d_size": (_upsample([r for r in rc.UP if r.size is not None]), {}),
+    "upsample3d_out_cat_buffer": (_upsample(_TRILINEAR_X2, out=True), {}),
 }
 for _name, _make in (("conv3d", _conv3d(padding=1)), ("cat", _cat(**_CAT_SERVED)), ("pair", _pair((1, 3, 1))), ("upconv", _upconv(8, 1, (3, 4, 5)))):
     for _mode in ("fresh", "twice", "suspended"):
@@ -246,10 +294,17 @@ def run_case(name):
         labels.update({p.grad.data_ptr(): "sink:" + k for k, p in params.items()})
     with Recorder(labels) as rec, ops.suspend_grad_sinks() if sinks == "suspended" else contextlib.nullcontext():
         ys = [fwd() for _ in range(2 if sinks == "twice" else 1)]
-        dy = _act(9, tuple(ys[0].shape), False, opt.get("dy_pad", 0), ys[0].dtype)
-        labels[dy.data_ptr()] = "dy"
-        if ys[0].requires_grad:
-            torch.autograd.backward(ys, [dy] * len(ys))
+        if isinstance(ys[0], tuple):        # one node with two outputs: their gradients are "dy" and "dy1", each with its own pad
+            ys = list(ys[0])
+            dys = [None if pad is None else _act(9 + i, tuple(y.shape), False, pad, y.dtype) for i, (y, pad) in enumerate(zip(ys, opt["dy_pad"]))]
+        else:
+            dys = [_act(9, tuple(ys[0].shape), False, opt.get("dy_pad", 0), ys[0].dtype)] * len(ys)
+        for i, dy in enumerate(dys):
+            if dy is not None:
+                labels.setdefault(dy.data_ptr(), "dy%d" % i if i else "dy")
+        used = [(y, dy) for y, dy in zip(ys, dys) if dy is not None]
+        if used[0][0].requires_grad:
+            torch.autograd.backward([y for y, _ in used], [dy for _, dy in used])
         torch.cuda.synchronize()
         trace = rec.trace()
     out = {"y": ys[0].detach()}

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import conv_cases as cc
+import resample_cases as rc
 from mri_epilepsy_diagnosis_amd import _lib, ops
 from util import assert_close, seeded_rand, seeded_randn, to_ncdhw
 
@@ -192,10 +193,9 @@ def test_dropout3d_masks_whole_channels():
 
 
 # ---------------------------------------------------------------------------------------------- pooling / upsampling
-@pytest.mark.parametrize("c,sp,k,s", [(16, (8, 12, 10), 2, 2), (8, (9, 7, 11), 2, 2), (3, (6, 6, 6), 2, 2),
-                                      (4, (13, 12, 14), 4, 2), (1, (8, 8, 8), 2, 2), (64, (4, 6, 4), 2, 2)])
+@pytest.mark.parametrize("c,sp,k,s", [(r.c, r.sp, r.k, r.s) for r in rc.POOL])
 def test_max_pool3d(c, sp, k, s):
-    x = seeded_randn(1, (2, c, *sp))
+    x = seeded_randn(1, (rc.N, c, *sp))
     xr = x.clone().requires_grad_(True)
     yr = F.max_pool3d(xr, k, s)
     gy = seeded_randn(2, tuple(yr.shape))
@@ -207,7 +207,7 @@ def test_max_pool3d(c, sp, k, s):
     assert_close(to_ncdhw(xd.grad), xr.grad, rel=1e-6, what="dx")
 
 
-@pytest.mark.parametrize("c,sp,pad", [(16, (6, 8, 10), 0), (8, (5, 7, 9), 8), (3, (4, 4, 6), 0), (32, (2, 2, 2), 16)])
+@pytest.mark.parametrize("c,sp,pad", [(r.c, r.sp, r.pad) for r in rc.POOL_SKIP])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
 def test_max_pool3d_skip_sums_both_gradients_in_the_pool_kernel(c, sp, pad, dtype):
     """(pool(x), x) as one node (unet.UNet encoder: `skip = x; x = pool(x)`): outputs equal the two-op form, and the input
@@ -252,21 +252,12 @@ def test_max_pool3d_ties_pick_first_like_torch():
     assert torch.equal(to_ncdhw(xd.grad), xr.grad)
 
 
-UP_CASES = [("nearest", None, 2, None, 16, (5, 6, 7)), ("nearest", None, 4, None, 8, (3, 4, 2)),
-            ("nearest", (9, 11, 13), None, None, 4, (4, 5, 6)), ("nearest", (7, 7, 7), None, None, 1, (7, 3, 9)),
-            ("trilinear", None, 2, False, 32, (5, 6, 4)), ("trilinear", None, 2, True, 8, (5, 6, 4)),
-            ("trilinear", (7, 9, 11), None, False, 4, (4, 5, 6)), ("trilinear", None, 2, False, 3, (1, 4, 5)),
-            # x2 trilinear marching along D (4 x 16 coarse columns, 16-plane segments): ragged columns in h and w, two segments,
-            # 8 / 4 / 2 / 1 pieces per voxel, a half-empty second channel pass (24 channels), two full passes (64)
-            ("trilinear", None, 2, False, 64, (18, 9, 19)), ("trilinear", None, 2, False, 24, (3, 5, 33)),
-            ("trilinear", None, 2, False, 16, (17, 4, 16)), ("trilinear", None, 2, False, 8, (2, 7, 5)),
-            ("trilinear", None, 2, False, 4, (33, 3, 18)), ("trilinear", None, 2, False, 4, (1, 3, 5)), ("trilinear", None, 2, False, 8, (2, 1, 1)),
-            ("trilinear", None, 2, False, 12, (5, 1, 21))]
+UP_CASES = [(r.mode, r.size, r.scale, r.ac, r.c, r.sp) for r in rc.UP]        # (their kernels: tests/test_resample_routes.py)
 
 
 @pytest.mark.parametrize("mode,size,scale,ac,c,sp", UP_CASES)
 def test_upsample3d(mode, size, scale, ac, c, sp):
-    x = seeded_randn(1, (2, c, *sp))
+    x = seeded_randn(1, (rc.N, c, *sp))
     xr = x.clone().requires_grad_(True)
     yr = F.interpolate(xr, size=size, scale_factor=scale, mode=mode, align_corners=ac)
     gy = seeded_randn(2, tuple(yr.shape))
