@@ -470,12 +470,31 @@ int mri3d_aggregate_patches_argmax(const void* logits, int32_t c, int32_t ld, in
  *            N == 1); P = sum c_ijk xh^i yh^j zh^k over i in 0..order, j in 0..order-i, k in 0..order-i-j, coefficients in
  *            that nesting order: coef_host is a HOST array of s x (order+1)(order+2)(order+3)/6 floats handed to the kernel by
  *            value.  order <= 3 (MRI3D_ENOTSUP above).  y == x (in place) is allowed, a partial overlap is not.
+ *   kspace_mix: the k-space half of TorchIO's RandomMotion (the `RescaleIntensity((0, 1)), RandomMotion()` pair that opens the
+ *            reference's transform lists, commented out).  The artefact Fourier-transforms n = K + 1 volumes (the unmoved one
+ *            and K rigidly moved copies, made by warp3d), fills slabs of the shifted spectrum ALONG THE LAST AXIS ONLY, each slab
+ *            from one spectrum, transforms back and keeps the real part.  The slab masks depend on the w frequency alone, so
+ *            the transforms along d and h cancel against their inverses; along w, a mask times a spectrum is a circular
+ *            convolution with the mask's inverse transform, whose imaginary part meets a real image and is dropped:
+ *              out[i,d,h,z] = sum_{m<n} sum_{z'<w} coef[i,m,(z - z') mod w] * images[i,m,d,h,z']
+ *              coef[i,m,r]  = (1/w) sum_{k in S_m} cos(2 pi k r / w)
+ *            S_m = the unshifted frequencies whose shifted position falls in the slab(s) filled from image m (drawn and summed
+ *            by the caller in float64: transforms.motion_coefficients).  images: DEVICE (s,n,d,h,w) fp32 contiguous; coef:
+ *            DEVICE (s,n,w) fp32; out: DEVICE (s,d,h,w), must not overlap images or coef.  fp32 accumulation in one fixed order
+ *            (m ascending, then z' ascending): bit-identical run to run, no atomics, no workspace.  MRI3D_EINVAL before any
+ *            launch for a null pointer, a non-positive extent, n outside 1..8 or w > 256 (a lane keeps w / 64 outputs in
+ *            registers and a block the input rows of its 4 waves in LDS; the reference's volumes are 160-200 wide).
  * ---------------------------------------------------------------------------------------------- */
 int mri3d_warp3d(const float* image, float* image_out, const void* label, void* label_out, int32_t label_bytes, int32_t s,
                  int32_t d, int32_t h, int32_t w, const float* affine, const float* grid, int32_t gd, int32_t gh, int32_t gw,
                  float pad_value, const float* pad_values, mri3d_stream_t stream);
 int mri3d_bias_field_f32(const float* x, float* y, int32_t s, int32_t d, int32_t h, int32_t w, const float* coef_host,
                          int32_t order, mri3d_stream_t stream);
+int mri3d_kspace_mix_f32(const float* images, /* DEVICE (s, n, d, h, w) contiguous */
+                         float* out,          /* DEVICE (s, d, h, w); must not overlap images */
+                         int32_t s, int32_t n, int32_t d, int32_t h, int32_t w,
+                         const float* coef,   /* DEVICE (s, n, w) */
+                         mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Channel-slice plumbing: torch.cat along channels (unet.UNet decoder, modified_3dunet.py:158-178) and

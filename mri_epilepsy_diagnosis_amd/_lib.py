@@ -130,6 +130,7 @@ SIGNATURES = {
     "mri3d_warp3d": (c_int32, [_FP, _FP, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _FP, _FP, c_int32, c_int32,
                                c_int32, c_float, _FP, _P]),
     "mri3d_bias_field_f32": (c_int32, [_FP, _FP, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),
+    "mri3d_kspace_mix_f32": (c_int32, [_FP, _FP, c_int32, c_int32, c_int32, c_int32, c_int32, _FP, _P]),
     "mri3d_copy_channels": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_add_channels": (c_int32, [_P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_convert_channels": (c_int32, [_P, c_int32, _P, c_int32, c_int64, c_int32, c_int32, c_int32, _P]),

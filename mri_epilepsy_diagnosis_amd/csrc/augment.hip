@@ -200,12 +200,6 @@ bias_field_kernel(const float* __restrict__ x, float* __restrict__ y, int D, int
     }
 }
 
-static bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    if (!a || !b) return false;
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb + bbytes && pb < pa + abytes;
-}
-
 }  // namespace mri3d
 
 using namespace mri3d;

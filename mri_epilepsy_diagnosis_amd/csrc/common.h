@@ -90,6 +90,13 @@ inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nu
     return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
 }
 
+// the byte ranges [a, a + abytes) and [b, b + bbytes) share a byte (a null pointer overlaps nothing)
+inline bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    if (!a || !b) return false;
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return pa < pb + bbytes && pb < pa + abytes;
+}
+
 // largest power of two <= 16 that divides every given address (a null pointer divides by everything): what the route query is
 // told about a tensor instead of its pointer
 inline int ptr_align(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {

@@ -12,6 +12,13 @@ The classes below carry TorchIO's names and arguments so that list can be writte
 tree: the arithmetic is this project's definition (include/mri3d.h, "Augmentation"; float64 restatement in
 tests/augment_ref.py) — "parity unpinned", like the patch pipeline.
 
+The reference's lists open with two more lines, commented out: `RescaleIntensity((0, 1)),  # so that there are no negative values
+for RandomMotion` and `RandomMotion()`; segmentation/routine.py imports both names.  Both are here, under the same terms (TorchIO
+absent, "parity unpinned"; float64 restatement in tests/motion_ref.py).  RandomMotion needs no Fourier transform: TorchIO fills
+slabs of the shifted spectrum along the LAST axis only, so the transforms along the other two axes cancel and the artefact is a
+sum of 1-D circular filters along w over the unmoved volume and its K moved copies (`motion_coefficients`, `kspace_mix`;
+derivation in include/mri3d.h).
+
 Every random number is drawn on the HOST with numpy's `default_rng` (as `patches.Queue` does): which parameters are drawn is a
 property of the seed, not of TorchIO.  A transform first PLANS — draws its parameters for a volume shape and records them in
 `last_params` — and then the plan runs: flips, affines and an elastic deformation that are adjacent in a `Compose` fold into ONE
@@ -124,6 +131,63 @@ def n_coefficients(order):
     return (order + 1) * (order + 2) * (order + 3) // 6
 
 
+def kspace_mix(images, coef, out=None):
+    """One `mri3d_kspace_mix_f32` launch: out[i,d,h,z] = sum_m sum_z' coef[i,m,(z - z') mod W] images[i,m,d,h,z'].
+    images: (S,n,D,H,W) float32 device tensor; coef: (S,n,W) host array (rounded to fp32 here, once) or float32 device tensor;
+    out: (S,D,H,W) float32 device tensor that overlaps neither.  Returns out."""
+    _require_cuda(images, "kspace_mix")
+    if out is not None:
+        _require_cuda(out, "kspace_mix")
+    if images.dtype != torch.float32 or images.dim() != 5:
+        raise RuntimeError("kspace_mix: needs a float32 (S, n, D, H, W) tensor, got %s %s" % (images.dtype, tuple(images.shape)))
+    images = images.contiguous()
+    s, n, d, h, w = (int(v) for v in images.shape)
+    if isinstance(coef, torch.Tensor):
+        _require_cuda(coef, "kspace_mix")
+        c_dev = coef.to(torch.float32).contiguous()
+    else:
+        c_dev = torch.from_numpy(np.ascontiguousarray(coef, dtype=np.float32)).to(images.device)
+    if tuple(c_dev.shape) != (s, n, w):
+        raise ValueError("kspace_mix: coefficients %s for images %s, expected (S, n, W)" % (tuple(c_dev.shape), tuple(images.shape)))
+    if out is None:
+        out = torch.empty((s, d, h, w), dtype=torch.float32, device=images.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (s, d, h, w) or not out.is_contiguous():
+        raise ValueError("kspace_mix: out must be a contiguous float32 %s tensor" % ((s, d, h, w),))
+    L = _lib.lib()
+    _lib.check(L.mri3d_kspace_mix_f32(_ptr(images), _ptr(out), s, n, d, h, w, _ptr(c_dev), _stream()), "kspace_mix")
+    return out
+
+
+def motion_coefficients(times, w, n):
+    """The 1-D filters of a motion artefact, float64: (coef (n, w), slabs).  TorchIO's rule, restated: with K = n - 1 ascending
+    `times`, the slab ends are e_k = floor(w times[k]), then w; slab j covers the shifted-spectrum positions [e_{j-1}, e_j)
+    along the last axis (empty slabs are allowed) and is filled from list entry j, the list being the images (0 = unmoved,
+    k = moved by transform k) with entries 0 and idx swapped first, idx = the smallest index with times[idx] > 0.5, or K if
+    there is none.  Shifted position p holds frequency fftshift(arange(w))[p].  coef[m, r] = (1/w) sum_{k in S_m} cos(2 pi k r / w)
+    over the frequencies S_m filled from image m; slabs = [(image, ini, fin), ...]."""
+    times = np.asarray(times, dtype=np.float64).reshape(-1)
+    w, n = int(w), int(n)
+    K = n - 1
+    if w < 1 or n < 1 or len(times) != K or np.any(np.diff(times) < 0):
+        raise ValueError("motion_coefficients: %d images take %d ascending times (got %r), w >= 1" % (n, K, times))
+    order = list(range(n))
+    above = np.nonzero(times > 0.5)[0]
+    idx = int(above.min()) if len(above) else K
+    order[0], order[idx] = order[idx], order[0]
+    ends = [min(max(int(np.floor(w * t)), 0), w) for t in times] + [w]
+    freq = np.fft.fftshift(np.arange(w))
+    r = np.arange(w)
+    coef = np.zeros((n, w), dtype=np.float64)
+    slabs, ini = [], 0
+    for j, fin in enumerate(ends):
+        slabs.append((order[j], ini, fin))
+        k = freq[ini:fin]
+        # the angle's integer part is taken off exactly: cos(2 pi ((k r) mod w) / w)
+        coef[order[j]] += np.cos(2.0 * np.pi * ((k[:, None] * r[None, :]) % w) / w).sum(axis=0) / w
+        ini = max(ini, fin)
+    return coef, slabs
+
+
 # ------------------------------------------------------------------ plan steps (host descriptors)
 class Warp:
     """s = M o + u(o): M a 4x4 homogeneous float64 matrix (output voxel -> source voxel), grid (3,gd,gh,gw) float64 or None,
@@ -142,6 +206,17 @@ class Bias:
 
     def __init__(self, coefficients, order):
         self.coefficients, self.order = coefficients, order
+
+
+class Motion:
+    """A motion artefact: K 4x4 float64 matrices (output voxel -> source voxel of moved copy k), the pad rule of the copies
+    and the (K + 1, W) float64 filters of `motion_coefficients`.  K = 0 (a skipped transform) runs nothing.  `fold` never merges
+    it with a neighbour: a warp before it and a warp after it stay two launches."""
+    kind = "motion"
+
+    def __init__(self, matrices=(), coef=None, pad="minimum"):
+        self.matrices = np.asarray(matrices, dtype=np.float64).reshape(-1, 4, 4)
+        self.coef, self.pad = coef, pad
 
 
 class Call:
@@ -214,11 +289,33 @@ def _run_warp(images, labels, steps):
     return images, labels
 
 
+def _run_motion(images, steps):
+    """The K moved copies of every subject by the existing `warp3d` (image only, the step's pad rule) into an (S, K + 1, D, H, W)
+    buffer whose slot 0 is the input, then ONE `kspace_mix` launch for the batch.  Label maps are not touched."""
+    K = len(steps[0].matrices)
+    if K == 0:
+        return images
+    coef = np.stack([st.coef for st in steps])
+    out = {}
+    for name, img in images.items():
+        s = int(img.shape[0])
+        buf = torch.empty((s, K + 1) + tuple(img.shape[1:]), dtype=torch.float32, device=img.device)
+        buf[:, 0].copy_(img)
+        minimum = _minimum(img) if any(st.pad == "minimum" for st in steps) else None
+        # a launch writes contiguous volumes, and slot k of subject i is one: a launch per (subject, copy)
+        for i, st in enumerate(steps):
+            pad = minimum[i:i + 1] if st.pad == "minimum" else float(st.pad or 0.0)
+            for k in range(K):
+                warp3d(img[i:i + 1], None, st.matrices[k, :3][None], None, pad, image_out=buf[i, k + 1][None])
+        out[name] = kspace_mix(buf, coef)
+    return out
+
+
 def execute(images, labels, plans):
     """Run per-subject plans on a batch: images / labels are dicts name -> (S,D,H,W) device tensors, plans S folded step lists.
     When all plans have the same step kinds, every warp and bias step is ONE launch for the batch; otherwise each subject runs
-    on its own."""
-    kinds = [tuple(st.kind for st in p) for p in plans]
+    on its own.  Motion steps count as the same kind only with the same number of moved copies."""
+    kinds = [tuple(st.kind if st.kind != "motion" else ("motion", len(st.matrices)) for st in p) for p in plans]
     if len(set(kinds)) > 1:
         parts = [execute({k: v[i:i + 1] for k, v in images.items()}, {k: v[i:i + 1] for k, v in labels.items()}, [plans[i]])
                  for i in range(len(plans))]
@@ -234,11 +331,13 @@ def execute(images, labels, plans):
                 raise ValueError("one bias-field order per launch")
             coef = np.stack([st.coefficients for st in steps])
             images = {k: bias_field(v, coef, steps[0].order) for k, v in images.items()}
-        else:
+        elif kind == "call":
             outs = [st.fn({k: v[i:i + 1] for k, v in images.items()}, {k: v[i:i + 1] for k, v in labels.items()})
                     for i, st in enumerate(steps)]
             images = {k: torch.cat([o[0][k] for o in outs]) for k in images}
             labels = {k: torch.cat([o[1][k] for o in outs]) for k in labels}
+        else:
+            images = _run_motion(images, steps)
     return images, labels
 
 
@@ -446,6 +545,40 @@ class RandomBiasField(Transform):
         return [Bias(coef, self.order)], shape
 
 
+class RandomMotion(Transform):
+    """torchio.RandomMotion(degrees=10, translation=10, num_transforms=2): the volume is moved rigidly `num_transforms` = K
+    times — three angles uniform in +-degrees, three translations uniform in +-translation voxels (the project's unit-spacing
+    convention; (min, max) pairs are accepted), about the volume centre, trilinear, padded with the image minimum — and the
+    K + 1 spectra are spliced along the last axis at the times t_k = k/(K+1) + U(-0.3/(K+1), +0.3/(K+1)), k = 1..K
+    (`motion_coefficients`).  Image only: label maps pass through with the same bits, no launch and no copy.  TorchIO is
+    absent from the reference tree: this is the project's restatement, "parity unpinned".
+    `last_params`: times, degrees (K,3), translation (K,3), matrices (K,3,4) float64 before the fp32 rounding, slabs, coefficients."""
+
+    def __init__(self, degrees=10, translation=10, num_transforms=2, p=1, seed=None):
+        super().__init__(p, seed)
+        self.degrees, self.translation = _pair(degrees, "degrees"), _pair(translation, "translation")
+        self.num_transforms = int(num_transforms)
+        if not 1 <= self.num_transforms <= 7:
+            raise ValueError("RandomMotion: num_transforms 1..7 (the kernel mixes at most 8 volumes), got %d" % self.num_transforms)
+
+    def _skeleton(self, shape):
+        return [Motion()]
+
+    def _plan(self, shape, rng):
+        K = self.num_transforms
+        degrees, translation = np.empty((K, 3)), np.empty((K, 3))
+        for k in range(K):
+            degrees[k] = rng.uniform(*self.degrees, size=3)
+            translation[k] = rng.uniform(*self.translation, size=3)
+        step = 1.0 / (K + 1)
+        times = step * np.arange(1, K + 1) + rng.uniform(-0.3 * step, 0.3 * step, size=K)
+        matrices = np.stack([affine_matrix((1.0, 1.0, 1.0), degrees[k], translation[k], shape) for k in range(K)])
+        coef, slabs = motion_coefficients(times, shape[2], K + 1)
+        self.last_params = {"applied": True, "times": times, "degrees": degrees, "translation": translation,
+                            "matrices": matrices[:, :3].copy(), "slabs": slabs, "coefficients": coef.copy()}
+        return [Motion(matrices, coef, "minimum")], shape
+
+
 class Compose(Transform):
     """torchio.Compose([...]): the stages in order, adjacent spatial stages folded into one resampling (see `fold`).
     `last_params` = {'stages': each stage's own record, 'warps': the folded maps as launched (float64, before the fp32 rounding)}."""
@@ -505,6 +638,55 @@ class HistogramStandardization(Transform):
 
     def _plan(self, shape, rng):
         self.last_params = {"applied": True}
+        return [Call(self._fn)], shape
+
+
+class RescaleIntensity(Transform):
+    """torchio.RescaleIntensity(out_min_max, percentiles=(0, 100)) over `preprocessing.percentile` and
+    `mri3d_piecewise_linear_f32`: the cut-offs are the two percentiles of the whole image; values are clipped to them and
+    mapped linearly onto out_min_max.  An image without range (equal cut-offs) maps to out_min.  Labels are untouched.
+    TorchIO is absent from the reference tree: "parity unpinned".  The cut-offs are known when the stage RUNS: this
+    instance's `last_params['cutoffs']` = {image name: (low, high)} float64 is filled in then (a `Compose` copies its stages'
+    records at planning time, before that)."""
+
+    def __init__(self, out_min_max, percentiles=(0, 100), p=1, seed=None):
+        super().__init__(p, seed)
+        self.out_min_max = _pair(out_min_max, "out_min_max", symmetric=False)
+        self.percentiles = _pair(percentiles, "percentiles", symmetric=False)
+        if not 0 <= self.percentiles[0] <= self.percentiles[1] <= 100:
+            raise ValueError("RescaleIntensity: percentiles must lie in 0..100, got %r" % (percentiles,))
+
+    def _rescale(self, v):
+        low, high = (float(c) for c in preprocessing.percentile(v, self.percentiles))
+        out_min, out_max = self.out_min_max
+        if high > low:
+            slope = (out_max - out_min) / (high - low)
+            edges = np.asarray([low, high], dtype=np.float64)
+            slopes = np.asarray([0.0, slope, 0.0], dtype=np.float64)
+            intercepts = np.asarray([out_min, out_min - slope * low, out_max], dtype=np.float64)
+        else:
+            edges, slopes, intercepts = np.zeros(0), np.zeros(1), np.asarray([out_min], dtype=np.float64)
+        x = v.contiguous()
+        y = torch.empty_like(x)
+        as_p = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a.size else None  # noqa: E731
+        _lib.check(_lib.lib().mri3d_piecewise_linear_f32(_ptr(x), _ptr(y), x.numel(), as_p(edges), as_p(slopes), as_p(intercepts),
+                                                         len(slopes), _stream()), "piecewise_linear")
+        return y, (low, high)
+
+    def _fn(self, images, labels):
+        out, cutoffs = {}, {}
+        for k, v in images.items():
+            if v.dtype != torch.float32:
+                raise RuntimeError("RescaleIntensity: images must be float32, got %s for %r" % (v.dtype, k))
+            out[k], cutoffs[k] = self._rescale(v)
+        self.last_params = {"applied": True, "cutoffs": cutoffs}
+        return out, labels
+
+    def _skeleton(self, shape):
+        return [Call(lambda images, labels: (images, labels))]
+
+    def _plan(self, shape, rng):
+        self.last_params = {"applied": True, "cutoffs": {}}
         return [Call(self._fn)], shape
 
 
