@@ -345,6 +345,28 @@ int mri3d_upsample3d_bwd(const Mri3dUpGeom* g, const void* dy, void* dx, void* w
  * Segment lengths, tile counts and grids are not part of a name. */
 int mri3d_upsample3d_route(const Mri3dUpGeom* g, int32_t pass, int32_t align, char* name, size_t name_bytes);
 
+/* THE NUMBERS OF THE LAUNCH PLAN whose kernel mri3d_maxpool3d_route / mri3d_upsample3d_route name: same arguments, same checks,
+ * same plan function, host only.  Fields a kernel does not use are 0.
+ *   vec       channels per lane item (1, 4, 8)
+ *   npv       upsample2x_fwd_march: lane items per voxel and channel pass (NPV); upsample_nearest_int_bwd: the scale S
+ *   hch       slab kernels: rows of H per slab (hch < the pass's H extent: a slab is a part of a plane, the last part may be ragged)
+ *   grid      workgroups launched; the kernels loop where the plan has more slabs / items than that
+ *   segs      marching kernels: segments along D per column (forward: of segl coarse planes, backward: of 8); tile kernel: D tiles
+ *   segl      upsample2x_fwd_march: coarse planes per segment (16, 8 or 4)
+ *   tiles_h, tiles_w   tile and marching kernels: coarse tiles in H and W
+ *   passes    marching kernels: channel passes per tile
+ *   items     tile and marching kernels: n x segs x tiles_h x tiles_w x passes work items
+ *   tables    1: upsample_tables_kernel fills the workspace before the gather
+ *   lds_bytes dynamic LDS of the launch
+ * Both return MRI3D_OK or the error the route query gives for the arguments; out must not be NULL. */
+typedef struct Mri3dResamplePlanInfo {
+    int32_t vec, npv, hch, grid, segs, segl, tiles_h, tiles_w, passes, items, tables;
+    int64_t lds_bytes;
+} Mri3dResamplePlanInfo;
+int32_t mri3d_maxpool3d_plan_query(const Mri3dPoolGeom* g, int32_t pass, int32_t addend_ld, int32_t align_tensors,
+                                   int32_t align_idx, Mri3dResamplePlanInfo* out);
+int32_t mri3d_upsample3d_plan_query(const Mri3dUpGeom* g, int32_t pass, int32_t align, Mri3dResamplePlanInfo* out);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused softmax(dim=C) + soft-Dice loss — F.softmax + get_dice_loss + .mean()
  * (segmentation/routine.py:239-253,272-274).  target has ct = 1 (broadcast over classes, the

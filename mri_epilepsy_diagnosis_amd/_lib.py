@@ -33,6 +33,11 @@ class NormPlanInfo(Structure):
     _fields_ = [(n, c_int32) for n in ("vec", "CL", "VT", "cy", "nblk", "groups")] + [("gvox", c_int64)]
 
 
+class ResamplePlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("vec", "npv", "hch", "grid", "segs", "segl", "tiles_h", "tiles_w", "passes", "items",
+                                       "tables")] + [("lds_bytes", c_int64)]
+
+
 class PoolGeom(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "di", "hi", "wi", "dout", "ho", "wo", "c", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph", "pw",
@@ -97,6 +102,7 @@ SIGNATURES = {
     "mri3d_maxpool3d_bwd": (c_int32, [POINTER(PoolGeom), _P, _P, _P, _P]),
     "mri3d_maxpool3d_bwd_add": (c_int32, [POINTER(PoolGeom), _P, _P, _P, c_int32, _P, _P]),
     "mri3d_maxpool3d_route": (c_int32, [POINTER(PoolGeom), c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "mri3d_maxpool3d_plan_query": (c_int32, [POINTER(PoolGeom), c_int32, c_int32, c_int32, c_int32, POINTER(ResamplePlanInfo)]),
     "mri3d_norm_act_pool_supported": (c_int32, [POINTER(NormGeom), POINTER(PoolGeom)]),
     "mri3d_norm_act_pool_workspace_bytes": (c_size_t, [POINTER(NormGeom), POINTER(PoolGeom)]),
     "mri3d_norm_act_pool_fwd": (c_int32, [POINTER(NormGeom), POINTER(PoolGeom), _P, _FP, _FP, _FP, _FP, _FP, _P, _P, _P, _P]),
@@ -106,6 +112,7 @@ SIGNATURES = {
     "mri3d_upsample3d_fwd": (c_int32, [POINTER(UpGeom), _P, _P, _P]),
     "mri3d_upsample3d_bwd": (c_int32, [POINTER(UpGeom), _P, _P, _P, c_size_t, _P]),
     "mri3d_upsample3d_route": (c_int32, [POINTER(UpGeom), c_int32, c_int32, c_char_p, c_size_t]),
+    "mri3d_upsample3d_plan_query": (c_int32, [POINTER(UpGeom), c_int32, c_int32, POINTER(ResamplePlanInfo)]),
     "mri3d_softmax_dice_workspace_bytes": (c_size_t, [POINTER(DiceGeom)]),
     "mri3d_softmax_dice_fwd": (c_int32, [POINTER(DiceGeom), _P, _P, _FP, _FP, _P, c_size_t, _P]),
     "mri3d_softmax_dice_bwd": (c_int32, [POINTER(DiceGeom), _P, _P, _FP, _FP, _P, _P]),

@@ -1074,6 +1074,26 @@ extern "C" int mri3d_maxpool3d_route(const Mri3dPoolGeom* g, int32_t pass, int32
     return MRI3D_OK;
 }
 
+// the numbers of a plan as the query structs carry them
+static void plan_info(const ResamplePlan& p, Mri3dResamplePlanInfo* out) {
+    out->vec = p.vec, out->npv = p.npv, out->hch = p.hch, out->grid = p.grid;
+    out->segs = p.segs, out->segl = p.segl, out->tiles_h = p.tilesH, out->tiles_w = p.tilesW, out->passes = p.passes;
+    out->items = p.items, out->tables = p.tables ? 1 : 0;
+    out->lds_bytes = (int64_t)p.smem;
+}
+
+extern "C" int32_t mri3d_maxpool3d_plan_query(const Mri3dPoolGeom* g, int32_t pass, int32_t addend_ld, int32_t align_tensors,
+                                              int32_t align_idx, Mri3dResamplePlanInfo* out) {
+    MRI3D_REQUIRE(out != nullptr, MRI3D_EINVAL, "maxpool3d_plan_query: null result");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "maxpool3d_plan_query: unknown pass %d", pass);
+    MRI3D_REQUIRE(addend_ld == 0 || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "maxpool3d_plan_query: only the backward takes an addend");
+    if (int rc = pass == MRI3D_PASS_FWD ? pool_check(g, "maxpool3d_plan_query") : pool_bwd_check(g, addend_ld != 0, addend_ld, "maxpool3d_plan_query"))
+        return rc;
+    plan_info(pass == MRI3D_PASS_FWD ? pool_fwd_plan(*g, align_tensors, align_idx)
+                                     : pool_bwd_plan(*g, align_tensors, align_idx, addend_ld != 0, addend_ld, align_tensors), out);
+    return MRI3D_OK;
+}
+
 static int up_check(const Mri3dUpGeom* g, const char* who) {
     MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
     MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
@@ -1145,5 +1165,13 @@ extern "C" int mri3d_upsample3d_route(const Mri3dUpGeom* g, int32_t pass, int32_
     if (int rc = up_check(g, "upsample3d_route")) return rc;
     const ResamplePlan p = pass == MRI3D_PASS_FWD ? up_fwd_plan(*g, align) : up_bwd_plan(*g, align);
     snprintf(name, name_bytes, "%s", p.name);
+    return MRI3D_OK;
+}
+
+extern "C" int32_t mri3d_upsample3d_plan_query(const Mri3dUpGeom* g, int32_t pass, int32_t align, Mri3dResamplePlanInfo* out) {
+    MRI3D_REQUIRE(out != nullptr, MRI3D_EINVAL, "upsample3d_plan_query: null result");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "upsample3d_plan_query: unknown pass %d", pass);
+    if (int rc = up_check(g, "upsample3d_plan_query")) return rc;
+    plan_info(pass == MRI3D_PASS_FWD ? up_fwd_plan(*g, align) : up_bwd_plan(*g, align), out);
     return MRI3D_OK;
 }

@@ -383,6 +383,30 @@ def upsample_route(g, pass_, align=16):
     return name.value.decode()
 
 
+RESAMPLE_PLAN_FIELDS = ("vec", "npv", "hch", "grid", "segs", "segl", "tiles_h", "tiles_w", "passes", "items", "tables", "lds_bytes")
+
+
+def _resample_plan_dict(info):
+    return {f: int(getattr(info, f)) for f in RESAMPLE_PLAN_FIELDS}
+
+
+def pool_plan(g, pass_, addend_ld=0, align=16, idx_align=16):
+    """Numbers of the launch plan whose kernel `pool_route` names (same arguments, host only): a dict of the fields of
+    Mri3dResamplePlanInfo (include/mri3d.h)."""
+    info = _lib.ResamplePlanInfo()
+    check(_lib.lib().mri3d_maxpool3d_plan_query(ctypes.byref(g), pass_, addend_ld, align, idx_align, ctypes.byref(info)),
+          "maxpool3d_plan_query")
+    return _resample_plan_dict(info)
+
+
+def upsample_plan(g, pass_, align=16):
+    """Numbers of the launch plan whose kernel `upsample_route` names (same arguments, host only): a dict of the fields of
+    Mri3dResamplePlanInfo (include/mri3d.h)."""
+    info = _lib.ResamplePlanInfo()
+    check(_lib.lib().mri3d_upsample3d_plan_query(ctypes.byref(g), pass_, align, ctypes.byref(info)), "upsample3d_plan_query")
+    return _resample_plan_dict(info)
+
+
 def norm_plan(g, pass_, align=16):
     """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
     tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is

@@ -242,9 +242,10 @@ int main() {
         dg.n = 2; dg.vox = (int64_t)160 * 192 * 160; dg.c = 2; dg.ct = 1; dg.x_ld = 2; dg.t_ld = 1; dg.eps = 1e-9f;
         EXPECT(mri3d_softmax_dice_workspace_bytes(&dg) > 0);
     }
-    {   // pool / upsample route queries: the four launch plans over channels, dtypes and alignments name a kernel, launch nothing
+    {   // pool / upsample route and plan queries: the four launch plans over channels, dtypes and alignments name a kernel and
+        // give its numbers, launch nothing
         char rname[40];
-        long routes = 0;
+        long routes = 0, plans = 0;
         for (int c : {1, 3, 4, 8, 12, 16, 24, 40, 64})
             for (int dt = 0; dt < 2; ++dt)
                 for (int align : {4, 8, 16}) {
@@ -258,6 +259,12 @@ int main() {
                         EXPECT(mri3d_maxpool3d_route(&pg, pass, addend_ld < 0 ? 0 : addend_ld, align, align, rname, sizeof(rname)) == MRI3D_OK);
                         EXPECT(memchr(rname, 0, sizeof(rname)) != nullptr && rname[0] != 0);
                         ++routes;
+                        Mri3dResamplePlanInfo info;
+                        memset(&info, 0x7f, sizeof(info));
+                        EXPECT(mri3d_maxpool3d_plan_query(&pg, pass, addend_ld < 0 ? 0 : addend_ld, align, align, &info) == MRI3D_OK);
+                        EXPECT((info.vec == 1 || info.vec == 4 || info.vec == 8) && c % info.vec == 0 && info.hch >= 1 && info.grid >= 1 &&
+                               info.items == 0 && info.tables == 0 && info.lds_bytes == 0);
+                        ++plans;
                     }
                     Mri3dUpGeom ug;
                     memset(&ug, 0, sizeof(ug));
@@ -272,6 +279,17 @@ int main() {
                             EXPECT(mri3d_upsample3d_route(&ug, pass, align, rname, sizeof(rname)) == MRI3D_OK);
                             EXPECT(memchr(rname, 0, sizeof(rname)) != nullptr && rname[0] != 0);
                             ++routes;
+                            Mri3dResamplePlanInfo info;
+                            memset(&info, 0x7f, sizeof(info));
+                            EXPECT(mri3d_upsample3d_plan_query(&ug, pass, align, &info) == MRI3D_OK);
+                            EXPECT((info.vec == 1 || info.vec == 4 || info.vec == 8) && c % info.vec == 0 && info.grid >= 1 &&
+                                   (info.tables == 0 || info.tables == 1) && info.lds_bytes >= 0);
+                            if (info.items != 0)      // the tile and marching kernels: their items are the product of their counts
+                                EXPECT((int64_t)info.items == (int64_t)ug.n * info.segs * info.tiles_h * info.tiles_w * (info.passes ? info.passes : 1) &&
+                                       info.grid <= (info.items + 7) / 8 * 8);
+                            else
+                                EXPECT(info.hch >= 1 && info.segl == 0);
+                            ++plans;
                         }
                     }
                     if (c == 1 && dt == 0 && align == 4) {       // argument validation
@@ -282,9 +300,17 @@ int main() {
                         EXPECT(mri3d_upsample3d_route(nullptr, MRI3D_PASS_FWD, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
                         EXPECT(mri3d_upsample3d_route(&ug, MRI3D_PASS_WGRAD, 16, rname, sizeof(rname)) == MRI3D_EINVAL);
                         EXPECT(mri3d_upsample3d_route(&ug, MRI3D_PASS_FWD, 16, nullptr, sizeof(rname)) == MRI3D_EINVAL);
+                        Mri3dResamplePlanInfo info;
+                        EXPECT(mri3d_maxpool3d_plan_query(nullptr, MRI3D_PASS_FWD, 0, 16, 16, &info) == MRI3D_EINVAL);
+                        EXPECT(mri3d_maxpool3d_plan_query(&pg, MRI3D_PASS_FWD, 0, 16, 16, nullptr) == MRI3D_EINVAL);
+                        EXPECT(mri3d_maxpool3d_plan_query(&pg, MRI3D_PASS_WGRAD, 0, 16, 16, &info) == MRI3D_EINVAL);
+                        EXPECT(mri3d_maxpool3d_plan_query(&pg, MRI3D_PASS_FWD, c, 16, 16, &info) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_plan_query(nullptr, MRI3D_PASS_FWD, 16, &info) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_plan_query(&ug, MRI3D_PASS_FWD, 16, nullptr) == MRI3D_EINVAL);
+                        EXPECT(mri3d_upsample3d_plan_query(&ug, MRI3D_PASS_WGRAD, 16, &info) == MRI3D_EINVAL);
                     }
                 }
-        EXPECT(routes == 9 * 2 * 3 * (4 + 6));
+        EXPECT(routes == 9 * 2 * 3 * (4 + 6) && plans == routes);
     }
     EXPECT(mri3d_norm_workspace_bytes(nullptr) == 0);
     EXPECT(mri3d_mask_overlap_workspace_bytes() > 0 && mri3d_order_stats_workspace_bytes() > 0 && mri3d_znorm_workspace_bytes() > 0);

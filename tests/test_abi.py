@@ -48,7 +48,8 @@ def test_version_and_error_string_without_gpu():
 def test_struct_layouts_match_header(tmp_path):
     """Compile the public header with gcc and compare sizeof/offsetof with the ctypes mirrors."""
     structs = {"Mri3dConvGeom": _lib.ConvGeom, "Mri3dNormGeom": _lib.NormGeom, "Mri3dPoolGeom": _lib.PoolGeom,
-               "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom, "Mri3dNormPlanInfo": _lib.NormPlanInfo}
+               "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom, "Mri3dNormPlanInfo": _lib.NormPlanInfo,
+               "Mri3dResamplePlanInfo": _lib.ResamplePlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mri3d.h"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -101,6 +102,32 @@ def test_norm_plan_query_is_declared_bound_and_host_only():
     assert L.mri3d_norm_plan_query(ctypes.byref(g), 7, 16, ctypes.byref(info)) == -1
     assert L.mri3d_norm_plan_query(None, _lib.NORM_PASS_FWD, 16, ctypes.byref(info)) == -1
     assert L.mri3d_norm_plan_query(ctypes.byref(g), _lib.NORM_PASS_FWD, 16, None) == -1
+
+
+def test_resample_plan_queries_are_declared_bound_and_host_only():
+    for name in ("mri3d_maxpool3d_plan_query", "mri3d_upsample3d_plan_query"):
+        assert name in _declared() and name in _lib.SIGNATURES
+    assert [f for f, _ in _lib.ResamplePlanInfo._fields_] == ["vec", "npv", "hch", "grid", "segs", "segl", "tiles_h", "tiles_w", "passes",
+                                                              "items", "tables", "lds_bytes"]
+    L = _lib.lib()
+    info = _lib.ResamplePlanInfo()
+    # the 16-channel decoder level of a full-size volume: 2 x 80x96x80 coarse, 1200 items of 16 planes; 2400 items in the backward
+    ug = _lib.UpGeom(2, 80, 96, 80, 160, 192, 160, 16, 16, 16, _lib.UP_TRILINEAR, 0, 0.5, 0.5, 0.5, _lib.F32)
+    assert L.mri3d_upsample3d_plan_query(ctypes.byref(ug), _lib.PASS_FWD, 16, ctypes.byref(info)) == 0
+    assert (info.vec, info.npv, info.segs, info.segl, info.tiles_h, info.tiles_w, info.passes, info.items, info.grid) == \
+        (4, 4, 5, 16, 24, 5, 1, 1200, 1200)
+    assert L.mri3d_upsample3d_plan_query(ctypes.byref(ug), _lib.PASS_DGRAD, 16, ctypes.byref(info)) == 0
+    assert (info.vec, info.segs, info.tiles_h, info.tiles_w, info.passes, info.items, info.grid, info.tables) == (4, 10, 24, 5, 1, 2400, 2400, 0)
+    assert L.mri3d_upsample3d_plan_query(ctypes.byref(ug), _lib.PASS_WGRAD, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_upsample3d_plan_query(None, _lib.PASS_FWD, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_upsample3d_plan_query(ctypes.byref(ug), _lib.PASS_FWD, 16, None) == -1
+    pg = _lib.PoolGeom(2, 2, 26, 80, 1, 13, 40, 16, 2, 2, 2, 2, 2, 2, 0, 0, 0, 16, 16, _lib.F32)
+    assert L.mri3d_maxpool3d_plan_query(ctypes.byref(pg), _lib.PASS_FWD, 0, 16, 16, ctypes.byref(info)) == 0
+    assert (info.vec, info.hch, info.grid, info.items, info.lds_bytes) == (4, 6, 6, 0, 0)       # 2 planes x chunks of 6, 6 and 1 rows
+    assert L.mri3d_maxpool3d_plan_query(ctypes.byref(pg), _lib.PASS_DGRAD, 16, 16, 16, ctypes.byref(info)) == 0 and info.hch == 6
+    assert L.mri3d_maxpool3d_plan_query(ctypes.byref(pg), _lib.PASS_FWD, 16, 16, 16, ctypes.byref(info)) == -1    # an addend in the forward
+    assert L.mri3d_maxpool3d_plan_query(None, _lib.PASS_FWD, 0, 16, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_maxpool3d_plan_query(ctypes.byref(pg), _lib.PASS_FWD, 0, 16, 16, None) == -1
 
 
 def test_host_code_is_clean_under_address_and_ub_sanitizers():

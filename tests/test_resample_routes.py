@@ -4,16 +4,23 @@ mri3d_maxpool3d_route / mri3d_upsample3d_route answer, without a device, from th
 function per pass in csrc/resample.hip).  So the coverage of the GPU parity cases of tests/resample_cases.py is checked here:
 
   a. every row reaches the kernel it declares, queried with the alignments its tensors have on the device;
-  b. every instantiation name (VOCABULARY, hand-written) is reached by a row or listed in UNREACHED, which is exactly the rest;
+  b. every instantiation name (VOCABULARY, hand-written) is reached by a row: UNREACHED, exactly the rest, is empty;
   c. a sweep over dtypes, channels, extents, pitches, alignments and modes finds no name outside VOCABULARY, no 16-byte bf16 kernel
      on a tensor that is not 16-byte aligned and pitched in octets, and no vector kernel on channels that are not whole quads;
   d. the geometries at which the x2 forward halves its segment length keep their kernel (the length itself is a run-time argument,
-     not part of a name)."""
+     not part of a name);
+  e. every parity row (PARITY_POOL, PARITY_UP) reaches the names AND the plan numbers it declares (ops.pool_plan / ops.upsample_plan),
+     and is there for what its section says: more items than workgroups, slabs that are parts of a plane, its segment length;
+  f. a sweep of both plan queries finds no plan corner — kernel x vec x segment-length class x (items > grid) x chunked — that no
+     parity row reaches;
+  g. geometries past the 32-bit limits of the x2 kernels and of the line-contiguous pool decline to the kernels without them
+     (host only: nothing is allocated)."""
 import itertools
 
 import pytest
 
 import resample_cases as rc
+import resample_run as run
 from mri_epilepsy_diagnosis_amd import ops
 from mri_epilepsy_diagnosis_amd._lib import BF16, F32, PASS_DGRAD, PASS_FWD, UP_NEAREST, UP_TRILINEAR, PoolGeom, UpGeom
 
@@ -31,13 +38,8 @@ VOCABULARY = {
                         ["upsample_nearest_int_bwd<%s,%d>" % (t, s) for t in TYPES for s in (2, 4)] +
                         ["tables+upsample_bwd<%s,%d>" % (t, v) for t in TYPES for v in (1, 4)],
 }
-# what no row of tests/resample_cases.py reaches: bf16 tensors whose channels come in quads but not octets (or unaligned ones), a
-# bf16 pool backward without an addend on odd channels, and bf16 tensors on the slab upsample kernels
-UNREACHED = (
-    "maxpool2_fwd<bf16,4>", "maxpool_fwd<bf16,4>", "maxpool_bwd<bf16,1>", "maxpool_bwd<bf16,4>", "maxpool_bwd<bf16,4>+add",
-    "upsample2x_fwd_march<bf16,4,1>", "upsample2x_fwd_march<bf16,4,4>", "upsample2x_fwd_march<bf16,4,8>",
-    "upsample_fwd<bf16,1>", "tables+upsample_bwd<bf16,1>", "tables+upsample_bwd<bf16,4>",
-)
+# what no row of tests/resample_cases.py reaches: nothing (PARITY_POOL_UNREACHED / PARITY_UP_UNREACHED took the last eleven)
+UNREACHED = ()
 
 
 def pool_geom(dtype, c, sp, k, s, x_ld=None, y_ld=None, n=rc.N):
@@ -77,6 +79,10 @@ def row_routes():
         g = up_geom(r.dtype, r.c, r.sp, r.mode, r.size, r.scale, r.ac)
         yield "up/" + r.id, "up", PASS_FWD, r.fwd, ops.upsample_route(g, PASS_FWD)
         yield "up/" + r.id, "up", PASS_DGRAD, r.bwd, ops.upsample_route(g, PASS_DGRAD)
+    for r, dtype in rc.PARITY_PAIRS:
+        got, family = run.plans(r, dtype), "pool" if run.is_pool(r) else "up"
+        yield "parity/%s/%s" % (r.id, dtype), family, PASS_FWD, r.fwd[dtype], got["fwd"][0]
+        yield "parity/%s/%s" % (r.id, dtype), family, PASS_DGRAD, r.bwd[dtype], got["bwd"][0]
 
 
 # ---- a.
@@ -92,6 +98,7 @@ def test_every_instantiation_has_a_row_or_is_listed_as_unreached():
     reached = {got for _, _, _, _, got in row_routes()}
     assert reached <= set(names)
     assert sorted(set(names) - reached) == sorted(UNREACHED)
+    assert UNREACHED == ()
 
 
 # ---- c.
@@ -169,3 +176,111 @@ def test_the_segment_length_steps_of_the_x2_forward_keep_their_kernel():
         for dtype, fwd in (("f32", "upsample2x_fwd_march<f32,4,%d>" % min(8, c // 4)), ("bf16", "upsample2x_fwd_march<bf16,8,%d>" % (c // 8))):
             assert ops.upsample_route(up_geom(dtype, c, sp, "trilinear", scale=2, ac=False), PASS_FWD) == fwd
             assert ops.upsample_route(up_geom(dtype, c, sp, "trilinear", scale=2, ac=False), PASS_DGRAD) == "upsample2x_bwd_march<%s>" % dtype
+
+
+# ---- e.
+def test_every_parity_row_reaches_the_names_and_numbers_it_declares():
+    wrong = [w for r, dtype in rc.PARITY_PAIRS for w in run.declared_mismatches(r, dtype, run.plans(r, dtype))]
+    assert not wrong, "%d declaration(s) missed:\n  %s" % (len(wrong), "\n  ".join(wrong))
+
+
+def _slab_extent(row, pass_, name):
+    """(slabs, H extent) of a slab kernel's pass: the forward walks output planes (the line-contiguous pool: output rows of input
+    columns), the backward input planes"""
+    out = run.out_size(row)
+    d, h = (out[0], out[1]) if pass_ == "fwd" else (row.sp[0], row.sp[1])
+    return rc.N * d, h
+
+
+def corner(row, dtype, pass_, name, plan):
+    """the plan corner a pass sits in: (kernel, channels per lane item, segment-length class, more work than workgroups, slabs that
+    are parts of a plane).  The storage type, the pieces per voxel and the addend select an instantiation or an argument, not another
+    plan: b. holds every instantiation to a row."""
+    kernel = name[:name.index("<")]
+    if name.startswith("upsample2x"):
+        return (kernel, plan["vec"], plan["segl"], plan["items"] > plan["grid"], False)
+    nd, h = _slab_extent(row, pass_, name)
+    hchunks = -(-h // plan["hch"])
+    return (kernel, plan["vec"], 0, nd * hchunks > plan["grid"], plan["hch"] < h)
+
+
+def _corners_of_rows():
+    return {corner(r, t, p, *run.plans(r, t)[p]) for r, t in rc.PARITY_PAIRS for p in ("fwd", "bwd")}
+
+
+def test_the_sections_of_the_parity_table_are_what_they_say():
+    def all_(rows, pass_, pred, dtypes=None):
+        for r in rows:
+            for t in r.dtypes:
+                name, plan = run.plans(r, t)[pass_]
+                assert pred(corner(r, t, pass_, name, plan)), (r.id, t, pass_, name, plan)
+    all_(rc.PARITY_UP_SEGMENTS[:1], "fwd", lambda c: c[2] == 16)
+    all_(rc.PARITY_UP_SEGMENTS[1:], "fwd", lambda c: c[2] == 8)
+    all_(rc.PARITY_UP_SEGMENTS, "bwd", lambda c: c[3])
+    all_([r for r in rc.PARITY_UP_LOOPS if "bwd" not in r.id], "fwd", lambda c: c[3])
+    all_([r for r in rc.PARITY_UP_LOOPS if r.id.startswith("slab") or "bwd" in r.id], "bwd", lambda c: c[3])
+    all_(rc.PARITY_POOL_LOOPS, "fwd", lambda c: c[3])
+    all_(rc.PARITY_POOL_LOOPS, "bwd", lambda c: c[3])
+    all_(rc.PARITY_POOL_CHUNKS[:1] + rc.PARITY_POOL_CHUNKS[2:] + rc.PARITY_UP_CHUNKS, "fwd", lambda c: c[4])
+    all_(rc.PARITY_POOL_CHUNKS + [r for r in rc.PARITY_UP_CHUNKS if "loop" not in r.id], "bwd", lambda c: c[4])
+    all_([r for r in rc.PARITY_UP_CHUNKS if "loop" in r.id], "fwd", lambda c: c[3] and c[4])
+    # the ragged last part: chunks of 6, 6 and 1 rows in the line-contiguous pool, 12 and 1 in the slab pool
+    r = rc.PARITY_POOL_CHUNKS[0]
+    assert run.out_size(r)[1] == 13 and run.plans(r, "f32")["fwd"][1]["hch"] == 6
+    # the second channel pass of x2_c36 holds one live piece of eight, that of x2_c20 one of four
+    for rid, npv in (("x2_c36_one_live_piece", 8), ("x2_c20_two_passes", 4)):
+        r = next(r for r in rc.PARITY_UP if r.id == rid)
+        for t in r.dtypes:
+            plan = run.plans(r, t)["fwd"][1]
+            assert (plan["vec"], plan["npv"], plan["passes"]) == (4, npv, 2) and r.c // 4 - npv == 1
+
+
+# ---- f.
+SWEEP_UP = [((3, 5, 7), None), ((4, 6, 8), None), ((1, 1, 1), None), ((2045, 5, 3), None), ((1030, 5, 3), None), ((4200, 1, 2), None),
+            ((2, 9, 70), None), ((2, 9, 300), None), ((1025, 1, 513), None), ((12296, 1, 17), None), ((65552, 1, 1), None), ((1026, 5, 1), None)]
+SWEEP_MAX_ELEMENTS = 1 << 24      # a corner that only larger volumes reach has no row: its test would not run in seconds
+SWEEP_POOL = [(5, 7, 9), (4, 6, 8), (8, 8, 4), (8200, 2, 2), (8200, 2, 3), (2, 26, 80), (2, 26, 81), (2, 14, 300)]
+
+
+def test_no_plan_corner_of_a_sweep_is_without_a_parity_row():
+    have, missing = _corners_of_rows(), set()
+    for dtype, c, align in itertools.product(TYPES, CHANNELS, ALIGNS):
+        esz = run.ESZ[dtype]
+        lay = None if align == 16 else (c + 16 // esz, align // esz)      # a slice at `align` bytes of a wider buffer
+        if lay is not None and (lay[1] * esz) % 16 == 0:
+            continue
+        layout = {} if lay is None else {"x": lay, "dy": lay, "out": lay, "dskip": lay}
+        for sp in SWEEP_POOL:
+            for (k, s), addend in itertools.product(((2, 2), (4, 2)), (False, True)):
+                row = rc._pool("sweep", c, sp, k=k, s=s, addend=addend, layout=layout, fwd=("", 0, 0), bwd=(0, 0))
+                if min(run.out_size(row)) <= 0:
+                    continue
+                got = run.plans(row, dtype)
+                missing |= {corner(row, dtype, p, *got[p]) for p in ("fwd", "bwd")} - have
+        for (sp, _), (mode, size, scale, ac) in itertools.product(SWEEP_UP, UP_KINDS):
+            if size is not None:
+                size = tuple(i + i // 2 + 1 for i in sp)
+            row = rc._up("sweep", mode, c, sp, size=size, scale=scale, ac=ac, layout=layout, fwd="%s", bwd="%s")
+            if rc.N * c * run.out_size(row)[0] * run.out_size(row)[1] * run.out_size(row)[2] > SWEEP_MAX_ELEMENTS:
+                continue
+            got = run.plans(row, dtype)
+            missing |= {corner(row, dtype, p, *got[p]) for p in ("fwd", "bwd")} - have
+    assert not missing, "%d plan corner(s) without a parity row:\n  %s" % (len(missing), "\n  ".join(map(str, sorted(missing))))
+
+
+# ---- g.
+def test_geometries_past_the_32_bit_limits_decline():
+    # a fine plane above 2^31 - 1 elements
+    sp = (2, 16400, 16400)
+    assert 4 * sp[1] * sp[2] * 16 > 2 ** 31 - 1
+    g = up_geom("f32", 16, sp, "trilinear", scale=2, ac=False, n=1)
+    assert ops.upsample_route(g, PASS_FWD) == "upsample_fwd<f32,4>" and ops.upsample_route(g, PASS_DGRAD) == "upsample2x_bwd<f32>"
+    assert ops.upsample_plan(g, PASS_FWD)["items"] == 0 and ops.upsample_plan(g, PASS_DGRAD)["lds_bytes"] > 0
+    # more than 0x7ffffff0 items (the plane limits hold: 4 x 2 voxels of 16 channels)
+    g = up_geom("f32", 128, (2 ** 27, 8, 1), "trilinear", scale=2, ac=False, n=8)      # 2^31 marching items, 2^30 tiles
+    assert ops.upsample_route(g, PASS_DGRAD) == "upsample2x_bwd<f32>" and ops.upsample_plan(g, PASS_DGRAD)["items"] == 2 ** 30
+    g = up_geom("f32", 4, (2 ** 29, 1, 1), "trilinear", scale=2, ac=False, n=128)
+    assert 128 * 2 ** 29 // 16 > 0x7ffffff0 and ops.upsample_route(g, PASS_FWD) == "upsample_fwd<f32,4>"
+    # one sample of 2^31 elements leaves the line-contiguous pool; one element less keeps it
+    assert ops.pool_route(pool_geom("f32", 16, (2 ** 9, 2 ** 9, 2 ** 9), 2, 2), PASS_FWD) == "maxpool_fwd<f32,4>"
+    assert ops.pool_route(pool_geom("f32", 16, (2 ** 9, 2 ** 9, 2 ** 9 - 2), 2, 2), PASS_FWD) == "maxpool2_fwd<f32,4>"
