@@ -400,6 +400,52 @@ int mri3d_mask_overlap(const uint8_t* pred, const uint8_t* gt, int64_t nvox, int
                        size_t ws_bytes, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Label maps on the device (labels.hip): the raw label volume becomes a uint8 class map, the loss and the validation
+ * scores read that class map.  Storage types of a label volume (int32 and float32 share a size, hence codes of their own):
+ * ---------------------------------------------------------------------------------------------- */
+enum { MRI3D_LABEL_U8 = 0, MRI3D_LABEL_I16 = 1, MRI3D_LABEL_I32 = 2, MRI3D_LABEL_F32 = 3 };
+
+/* Id remap — prepare_batch's binarisation (segmentation/routine.py:185-196: np.isin(first, LIST_FCD) -> 1,
+ * targets >= 1000 -> 1, targets != 1 -> 0) and, with another table, the class map of a FreeSurfer parcellation (the seg_parc
+ * checkpoints).  in: n labels of in_dtype (any MRI3D_LABEL_*); out: MRI3D_LABEL_U8 or MRI3D_LABEL_F32.  Per element v, with
+ * lut[0..lut_len) uint8 on the device (1 <= lut_len <= 65536) and above, other in 0..255:
+ *     v >= lut_len (compared as a value: 1000.5 and +inf count)   -> above
+ *     v an integer in [0, lut_len)                                -> lut[v]
+ *     anything else (negative, fractional, NaN, -inf)             -> other
+ * lut_len = 1000, lut[i] = 1 for i in LIST_FCD or i == 1, above = 1, other = 0 is prepare_batch's rule for its first sample.
+ * out == in is allowed when the two have the same type (in place); any other overlap is MRI3D_EINVAL, as is a pointer that
+ * is not aligned to its own element.  16 bytes per load where the addresses allow it, single elements in front and behind. */
+int mri3d_label_remap(const void* in, int32_t in_dtype, void* out, int32_t out_dtype, int64_t n, const uint8_t* lut,
+                      int32_t lut_len, int32_t above, int32_t other, mri3d_stream_t stream);
+
+/* Softmax-Dice against a class map — F.softmax + get_dice_loss + .mean() (segmentation/routine.py:239-253,272-274) with the
+ * target given as class indices instead of float one-hot channels: g_c(v) = [labels(v) == c].  logits (n, vox, x_ld >= c)
+ * fp32 or bf16, labels dense uint8 (n, vox), 2 <= c <= 32 (else MRI3D_ENOTSUP).  A label >= c belongs to no class: the voxel
+ * adds to sum_p only (the way to ignore voxels).  loss, stats ([n*c*3] floats (tp, sum_p, sum_g)) and the backward
+ * expression are those of mri3d_softmax_dice_*; sums are taken in double in a fixed order: same inputs, same bits. */
+typedef struct Mri3dDiceIndexGeom {
+    int32_t n;
+    int64_t vox;
+    int32_t c;
+    int32_t x_ld;
+    float eps;
+    int32_t dtype;
+} Mri3dDiceIndexGeom;
+size_t mri3d_softmax_dice_index_workspace_bytes(const Mri3dDiceIndexGeom* g);
+int mri3d_softmax_dice_index_fwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels, float* loss,
+                                 float* stats, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_softmax_dice_index_bwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels,
+                                 const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream);
+
+/* Confusion counts of two class maps — the per-class form of validate_dsc_asd's Dice / IoU (segmentation/routine.py:198-235,
+ * metrics.py:312-329), exact integers.  pred, gt: nvox uint8 each, 2 <= c <= 32 (else MRI3D_ENOTSUP).
+ *   counts[g*c + p] = #(gt == g and pred == p)      counts[c*c] = #(gt >= c or pred >= c)        (int64[c*c + 1])
+ * workspace: mri3d_confusion_workspace_bytes(c) bytes (0 for c outside 2..32), 8-byte aligned. */
+size_t mri3d_confusion_workspace_bytes(int32_t c);
+int mri3d_confusion_counts(const uint8_t* pred, const uint8_t* gt, int64_t nvox, int32_t c, int64_t* counts,
+                           void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Intensity standardisation ahead of the path: the reference's collate function runs `normalize`
  * (classification/train_ENC_CLF.ipynb cell 9) on every volume — np.percentile at 13 percentiles over all voxels, then a
  * piecewise-linear map between landmarks evaluated in float64.

@@ -15,6 +15,7 @@ ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_PRELU = 0, 1, 2, 3
 UP_NEAREST, UP_TRILINEAR = 0, 1
 PASS_FWD, PASS_DGRAD, PASS_WGRAD = 0, 1, 2
 NORM_PASS_STATS, NORM_PASS_FWD, NORM_PASS_BWD = 0, 1, 2
+LABEL_U8, LABEL_I16, LABEL_I32, LABEL_F32 = 0, 1, 2, 3
 
 
 class ConvGeom(Structure):
@@ -53,6 +54,10 @@ class UpGeom(Structure):
 class DiceGeom(Structure):
     _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("ct", c_int32), ("x_ld", c_int32),
                 ("t_ld", c_int32), ("eps", c_float), ("dtype", c_int32)]
+
+
+class DiceIndexGeom(Structure):
+    _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("x_ld", c_int32), ("eps", c_float), ("dtype", c_int32)]
 
 
 _P = c_void_p
@@ -119,6 +124,12 @@ SIGNATURES = {
     "mri3d_argmax_u8": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P]),
     "mri3d_mask_overlap_workspace_bytes": (c_size_t, []),
     "mri3d_mask_overlap": (c_int32, [_P, _P, c_int64, _P, _P, c_size_t, _P]),
+    "mri3d_label_remap": (c_int32, [_P, c_int32, _P, c_int32, c_int64, _P, c_int32, c_int32, c_int32, _P]),
+    "mri3d_softmax_dice_index_workspace_bytes": (c_size_t, [POINTER(DiceIndexGeom)]),
+    "mri3d_softmax_dice_index_fwd": (c_int32, [POINTER(DiceIndexGeom), _P, _P, _FP, _FP, _P, c_size_t, _P]),
+    "mri3d_softmax_dice_index_bwd": (c_int32, [POINTER(DiceIndexGeom), _P, _P, _FP, _FP, _P, _P]),
+    "mri3d_confusion_workspace_bytes": (c_size_t, [c_int32]),
+    "mri3d_confusion_counts": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
     "mri3d_order_stats_workspace_bytes": (c_size_t, []),
     "mri3d_order_stats_f32": (c_int32, [_P, c_int64, _P, c_int32, _P, _P, c_size_t, _P]),
     "mri3d_piecewise_linear_f32": (c_int32, [_P, _P, c_int64, _P, _P, _P, c_int32, _P]),

@@ -159,6 +159,11 @@ inline PoolFwdLanes pool_fwd_lanes(const Mri3dPoolGeom& g, std::initializer_list
     return p;
 }
 
+// ---------------------------------------------------------------- softmax-Dice finalize shared by loss.hip and labels.hip
+// part[n][blk][c][3] = (tp, sum_p, sum_g) partial double sums of nblk blocks per sample -> stats[n][c][3] and the mean loss, on one
+// block in a fixed order (defined in loss.hip): the float-target and the class-index loss are one expression of the three sums.
+void dice_finalize(const double* part, float* stats, float* loss, int n, int c, int nblk, float eps, hipStream_t stream);
+
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

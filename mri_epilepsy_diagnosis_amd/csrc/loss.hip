@@ -109,6 +109,10 @@ dice_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats,
     if (threadIdx.x == 0) loss[0] = (float)(acc_loss / (double)(N * C));
 }
 
+void dice_finalize(const double* part, float* stats, float* loss, int n, int c, int nblk, float eps, hipStream_t stream) {
+    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, stream, part, stats, loss, n, c, nblk, eps);
+}
+
 template <typename T, int C>
 __global__ void __launch_bounds__(256)
 dice_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, const float* __restrict__ stats,
@@ -274,7 +278,7 @@ extern "C" int mri3d_softmax_dice_fwd(const Mri3dDiceGeom* g, const void* logits
                        (const float*)target, part, g->vox, g->ct, g->x_ld, g->t_ld)
     MRI3D_DISPATCH_DTYPE(g->dtype, T, { DICE_DISPATCH(CALL) });
 #undef CALL
-    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, part, stats, loss, g->n, g->c, nblk, g->eps);
+    dice_finalize(part, stats, loss, g->n, g->c, nblk, g->eps, s);
     return check_launch("softmax_dice_fwd");
 }
 

@@ -13,7 +13,10 @@ Reference operators replaced (file:line in /root/reference):
   softmax_dice_loss    F.softmax + get_dice_loss + mean   segmentation/routine.py:239-253,272-274
   cat_channels / add   torch.cat(dim=1) / residual adds   modified_3dunet.py:108,158
   bayes_conv3d         BayesConv3d          3d_bayes_layers.py:195-232 (3d_bayes_unet.py::UNet3D(bayes=True))
-Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd).
+  remap_labels         np.isin + boolean-mask writes of prepare_batch   segmentation/routine.py:185-196
+  softmax_dice_index_loss   the same loss against a uint8 class map (2..32 classes)   segmentation/routine.py:272-274
+Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd);
+confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask.
 """
 import collections
 import ctypes
@@ -1884,6 +1887,120 @@ def dice_iou_from_counts(counts):
     # the same expression on the (exactly representable up to 2^24 voxels) counts
     intersection, union = np.float32(n_and), np.float32(n_or)
     return dsc, float(intersection) / union
+
+
+# ----------------------------------------------------------------------------------------------- label maps (csrc/labels.hip)
+_LABEL_DTYPES = {torch.uint8: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.int32: _lib.LABEL_I32,
+                 torch.float32: _lib.LABEL_F32}
+
+
+def _require_labels(who, *ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("%s runs only on ROCm device tensors (got %s); there is no CPU fallback" % (who, t.device))
+
+
+def remap_labels(labels, lut, above=0, other=0, out_dtype=torch.uint8, out=None):
+    """Raw label ids -> classes through a uint8 device table: v >= len(lut) -> `above`, v an integer in [0, len(lut)) -> lut[v],
+    anything else (negative, fractional, NaN) -> `other`.  `labels` is uint8 / int16 / int32 / float32 of any shape, the result
+    uint8 or float32 of that shape; out=labels (same dtype) remaps in place.  prepare_batch's binarisation
+    (segmentation/routine.py:185-196) is one table of this kind, a parcellation's class map another (segmentation/labels.py)."""
+    _require_labels("remap_labels", labels, lut)
+    if labels.dtype not in _LABEL_DTYPES:
+        raise RuntimeError("remap_labels: labels must be uint8, int16, int32 or float32, got %s" % labels.dtype)
+    if lut.dtype != torch.uint8 or lut.dim() != 1 or not lut.is_contiguous():
+        raise RuntimeError("remap_labels: the table must be a contiguous 1-D uint8 tensor")
+    if out is None:
+        if out_dtype not in (torch.uint8, torch.float32):
+            raise RuntimeError("remap_labels: out_dtype must be uint8 or float32, got %s" % out_dtype)
+        out = torch.empty(labels.shape, dtype=out_dtype, device=labels.device)
+        labels = labels.contiguous()
+    elif out.shape != labels.shape or not out.is_contiguous() or not labels.is_contiguous() or out.device != labels.device \
+            or out.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError("remap_labels: out must be a contiguous uint8 / float32 tensor of the (contiguous) labels' shape and device")
+    if labels.numel():
+        check(_lib.lib().mri3d_label_remap(_ptr(labels), _LABEL_DTYPES[labels.dtype], _ptr(out), _LABEL_DTYPES[out.dtype],
+                                           labels.numel(), _ptr(lut), lut.numel(), int(above), int(other), _stream()), "label_remap")
+    return out
+
+
+class _SoftmaxDiceIndexFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        _require_device(logits)
+        _require_labels("softmax_dice_index_loss", labels)
+        if labels.dtype != torch.uint8:
+            raise RuntimeError("softmax_dice_index_loss: labels must be a uint8 class map, got %s" % labels.dtype)
+        L = _lib.lib()
+        logits = _cl(logits)
+        n, c, d, h, w = logits.shape
+        if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
+            raise RuntimeError("softmax_dice_index_loss: labels shape %s incompatible with logits %s"
+                               % (tuple(labels.shape), tuple(logits.shape)))
+        labels = labels.contiguous()
+        g = _lib.DiceIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits))
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        stats = torch.empty(n * c * 3, dtype=torch.float32, device=logits.device)
+        ws = _workspace(L.mri3d_softmax_dice_index_workspace_bytes(ctypes.byref(g)), logits.device)
+        check(L.mri3d_softmax_dice_index_fwd(ctypes.byref(g), _ptr(logits), _ptr(labels), _ptr(loss), _ptr(stats), _ptr(ws),
+                                             ws.numel(), _stream()), "softmax_dice_index_fwd")
+        ctx.save_for_backward(logits, labels, stats)
+        ctx.geom = g
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        L = _lib.lib()
+        logits, labels, stats = ctx.saved_tensors
+        dloss = dloss.to(torch.float32).contiguous()
+        dlogits = _new(logits.shape, logits)
+        check(L.mri3d_softmax_dice_index_bwd(ctypes.byref(ctx.geom), _ptr(logits), _ptr(labels), _ptr(stats), _ptr(dloss),
+                                             _ptr(dlogits), _stream()), "softmax_dice_index_bwd")
+        return dlogits, None, None
+
+
+def softmax_dice_index_loss(logits, labels, eps=1e-9):
+    """`softmax_dice_loss` with the target as a uint8 class map (N, 1, D, H, W) or (N, D, H, W) instead of float one-hot channels:
+    mean over (n, c) of 1 - dice(softmax(logits)[:, c], labels == c), for 2..32 classes.  A label >= C belongs to no class (the
+    voxel is ignored by every class's numerator and target sum).  One byte of target per voxel instead of 4*C."""
+    return _SoftmaxDiceIndexFn.apply(logits, labels, eps)
+
+
+def confusion_counts(pred, gt, classes):
+    """Exact confusion counts of two uint8 class maps on the device: (conf, outside) with conf[g, p] = #(gt == g and pred == p), an
+    int64 (C, C) device tensor, and outside = #(gt >= C or pred >= C), an int64 device scalar.  2 <= classes <= 32."""
+    _require_labels("confusion_counts", pred, gt)
+    for t in (pred, gt):
+        if t.dtype != torch.uint8:
+            raise RuntimeError("confusion_counts: class maps must be uint8, got %s" % t.dtype)
+    if pred.shape != gt.shape:
+        raise RuntimeError("confusion_counts: shapes differ %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+    L = _lib.lib()
+    c = int(classes)
+    pred, gt = pred.contiguous(), gt.contiguous()
+    out = torch.empty(max(c, 0) * max(c, 0) + 1, dtype=torch.int64, device=pred.device)
+    ws = _workspace(L.mri3d_confusion_workspace_bytes(c), pred.device)
+    check(L.mri3d_confusion_counts(_ptr(pred), _ptr(gt), pred.numel(), c, _ptr(out), _ptr(ws), ws.numel(), _stream()),
+          "confusion_counts")
+    return out[:c * c].view(c, c), out[c * c]
+
+
+def class_scores_from_confusion(conf):
+    """Per-class (Dice, IoU) float64 arrays of a (C, C) confusion matrix conf[gt, pred], each class scored as the binary mask
+    `== c` with `dice_iou_from_counts`' arithmetic: 2*tp / (|gt| + |pred|) and float32(tp) / float32(|gt or pred|); NaN where the
+    denominator is 0."""
+    import numpy as np
+    m = conf.cpu().numpy() if torch.is_tensor(conf) else np.asarray(conf)
+    m = m.astype(np.int64)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise RuntimeError("class_scores_from_confusion: expected a square matrix, got shape %s" % (m.shape,))
+    dice, iou = np.full(m.shape[0], np.nan), np.full(m.shape[0], np.nan)
+    for k in range(m.shape[0]):
+        tp, sg, sp = int(m[k, k]), int(m[k, :].sum()), int(m[:, k].sum())
+        if sg + sp:
+            dice[k] = 2 * tp / (sg + sp)
+            iou[k] = float(np.float32(tp)) / np.float32(sg + sp - tp)
+    return dice, iou
 
 
 # ----------------------------------------------------------------------------------------------- cat / add

@@ -9,6 +9,7 @@ with the same public names, argument order and call sequence, driving the HIP op
                                                          scheduler.step(mean val loss); save every `save_epoch`
   validate_dsc_asd :217                                  argmax -> uint8 mask on device (one fused kernel), Dice/IoU
   get_model_and_optimizer :338                           seeds, UNet(...), AdamW defaults, ReduceLROnPlateau
+  (none)                                                 validate_classes: per-class Dice / IoU of a multi-class model (labels.py)
 
 Differences, all deliberate: (1) F.softmax + get_dice_loss + .mean() (three full-resolution passes) is ONE fused HIP
 kernel (`ops.softmax_dice_loss`); (2) the TorchIO/NIfTI loader builders (`get_loaders`, :97-183) are out of scope
@@ -24,7 +25,7 @@ import numpy as np
 import torch
 
 from .. import ops, parallel
-from . import surface
+from . import labels as label_maps, surface
 from ..unet import UNet
 
 device = torch.device("cuda") if torch.cuda.is_available() else "cpu"
@@ -51,14 +52,34 @@ def get_loaders(*args, **kwargs):
 
 def prepare_batch(batch, device):
     """Move the volume to the device and binarise the label map as the reference does (routine.py:185-196):
-    FreeSurfer ids in LIST_FCD -> 1 (first sample only, as in the reference), ids >= 1000 -> 1, everything else -> 0."""
+    FreeSurfer ids in LIST_FCD -> 1 (first sample only, as in the reference), ids >= 1000 -> 1, everything else -> 0.
+    A float32 / int16 / int32 label map that is already on the device is rewritten there in one pass (LabelMap.binary_fcd: same
+    values, same dtype, in place); anything else takes the reference's host statements below."""
     inputs = batch[MRI][DATA].to(device)
     targets = batch[LABEL][DATA]
+    if targets.is_cuda and targets.dtype in _DEVICE_LABEL_DTYPES and targets.dim() == 5 and targets.shape[1] == 1 \
+            and targets.is_contiguous() and targets.numel():
+        if targets.dtype == torch.float32:
+            _binary_fcd()(targets, out=targets)
+        else:
+            targets.copy_(_binary_fcd()(targets))
+        return inputs, targets.to(device)
     first = targets[0][0]
     first[torch.from_numpy(np.isin(first.cpu().numpy(), LIST_FCD))] = 1
     targets[targets >= 1000] = 1
     targets[targets != 1] = 0
     return inputs, targets.to(device)
+
+
+_DEVICE_LABEL_DTYPES = (torch.float32, torch.int16, torch.int32)     # uint8: torch evaluates `>= 1000` in uint8, the host path keeps that
+_fcd_map = None
+
+
+def _binary_fcd():
+    global _fcd_map
+    if _fcd_map is None:
+        _fcd_map = label_maps.LabelMap.binary_fcd()
+    return _fcd_map
 
 
 def get_iou_score(prediction, ground_truth):
@@ -84,13 +105,15 @@ def calculate_metrics(surface, prediction, surface_metrics=None):
     return dsc, asd_mean, asd_std, get_iou_score(prediction, surface)
 
 
-def validate_dsc_asd(model, loader, surface_metrics=None):
+def validate_dsc_asd(model, loader, surface_metrics=None, prepare=None):
     """Reference validate_dsc_asd (routine.py:217-237): per sample (dsc, asd gt->pred, asd pred->gt, iou).
-    surface_metrics: None = on the device (default); False = skip (NaN); a callable(surface, prediction) -> (a, b) = host."""
+    surface_metrics: None = on the device (default); False = skip (NaN); a callable(surface, prediction) -> (a, b) = host.
+    prepare(batch, device) -> (inputs, targets) defaults to `prepare_batch`."""
     dsc, asd_mean, asd_std, iou = [], [], [], []
+    prepare = prepare_batch if prepare is None else prepare
     model.eval()
     for batch in loader:
-        inputs, targets = prepare_batch(batch, device)
+        inputs, targets = prepare(batch, device)
         with torch.no_grad():
             logits = forward(model, inputs)
         labels = ops.argmax_mask(logits)  # (N, D, H, W) uint8 on device: no logits D2H
@@ -123,15 +146,16 @@ def _score_mask(labels, targets, surface_metrics):
     return calculate_metrics(targets.cpu().numpy().astype(np.uint8)[0][0], labels[0].cpu().numpy(), surface_metrics)
 
 
-def validate_dsc_asd_mc(model, loader, n_samples, samples_per_pass=1, surface_metrics=None):
+def validate_dsc_asd_mc(model, loader, n_samples, samples_per_pass=1, surface_metrics=None, prepare=None):
     """`validate_dsc_asd` on the mask of the Monte-Carlo mean prediction (uncertainty.mc_predict with `n_samples` draws per
     batch): the same four lists, then two more, per volume: the mean predictive entropy and the mean mutual information over
     its voxels (means of the device maps; two scalars cross to the host).  Like `validate_dsc_asd`, it scores the first
     volume of each batch."""
     from .uncertainty import mc_predict
     dsc, asd_mean, asd_std, iou, entropy, mutual_info = [], [], [], [], [], []
+    prepare = prepare_batch if prepare is None else prepare
     for batch in loader:
-        inputs, targets = prepare_batch(batch, device)
+        inputs, targets = prepare(batch, device)
         with warnings.catch_warnings():
             warnings.filterwarnings("ignore", category=UserWarning)
             res = mc_predict(model, inputs, n_samples, samples_per_pass, want=("entropy", "mutual_info", "mask"))
@@ -139,6 +163,29 @@ def validate_dsc_asd_mc(model, loader, n_samples, samples_per_pass=1, surface_me
         h, mi = torch.stack((res["entropy"][0].mean(), res["mutual_info"][0].mean())).tolist()
         dsc.append(d), asd_mean.append(am), asd_std.append(asd), iou.append(i), entropy.append(h), mutual_info.append(mi)
     return dsc, asd_mean, asd_std, iou, entropy, mutual_info
+
+
+def validate_classes(model, loader, label_map, prepare=None):
+    """Per-class scores of a multi-class model: for every volume of every batch, (Dice, IoU) float64 arrays of `label_map.classes`
+    entries (NaN for a class that neither map contains), from the arg-max mask and the class map's exact confusion counts on the
+    device (ops.argmax_mask + ops.confusion_counts: one small matrix per volume crosses to the host).  Returns the two lists.
+    prepare(batch, device) -> (inputs, uint8 class map) defaults to `prepare_batch_index` with `label_map`."""
+    if prepare is None:
+        def prepare(batch, dev):
+            return label_maps.prepare_batch_index(batch, dev, label_map)
+    dice, iou = [], []
+    model.eval()
+    for batch in loader:
+        inputs, classes = prepare(batch, device)
+        with torch.no_grad():
+            logits = forward(model, inputs)
+        masks = ops.argmax_mask(logits)
+        gt = classes.reshape(masks.shape)
+        for k in range(masks.shape[0]):
+            conf, _ = ops.confusion_counts(masks[k], gt[k], label_map.classes)
+            d, i = ops.class_scores_from_confusion(conf)
+            dice.append(d), iou.append(i)
+    return dice, iou
 
 
 def get_dice_score(output, target, SPATIAL_DIMENSIONS=(2, 3, 4), epsilon=1e-9):
@@ -161,19 +208,21 @@ def forward(model, inputs):
     return logits
 
 
-def run_epoch(epoch_idx, action, loader, model, optimizer, scheduler=False, experiment=False, loss_fn=None):
+def run_epoch(epoch_idx, action, loader, model, optimizer, scheduler=False, experiment=False, loss_fn=None, prepare=None):
     """One pass over `loader` (segmentation/routine.py:261-294: zero_grad -> forward -> softmax-Dice -> backward -> step ->
-    .item()).  `loss_fn(logits, targets)` defaults to the fused softmax+Dice HIP kernel.  On the device the sequence
-    zero_grad -> forward -> loss (-> backward) is captured once per batch shape into a hipGraph and replayed
+    .item()).  `loss_fn(logits, targets)` defaults to the fused softmax+Dice HIP kernel, `prepare(batch, device)` ->
+    (inputs, targets) to `prepare_batch` (class-index training: ops.softmax_dice_index_loss with labels.prepare_batch_index).
+    On the device the sequence zero_grad -> forward -> loss (-> backward) is captured once per batch shape into a hipGraph and replayed
     (parallel.StepCache: same kernels, same results, one launch instead of ~300); CPU modules / tensors (the oracle-driven host
     tests) and anything that cannot be captured run eagerly."""
     is_training = action == Action.TRAIN
     loss_fn = ops.softmax_dice_loss if loss_fn is None else loss_fn
+    prepare = prepare_batch if prepare is None else prepare
     epoch_losses = []
     model.train(is_training)
     cache = parallel.StepCache.of(model)
     for batch in loader:
-        inputs, targets = prepare_batch(batch, device)
+        inputs, targets = prepare(batch, device)
         optimizer.zero_grad()
         with torch.set_grad_enabled(is_training), warnings.catch_warnings():
             warnings.filterwarnings("ignore", category=UserWarning)
@@ -189,15 +238,15 @@ def run_epoch(epoch_idx, action, loader, model, optimizer, scheduler=False, expe
 
 
 def train(num_epochs, training_loader, validation_loader, model, optimizer, scheduler, weights_stem, save_epoch=1,
-          experiment=False, verbose=True, loss_fn=None, weights_dir="weights"):
+          experiment=False, verbose=True, loss_fn=None, weights_dir="weights", prepare=None):
     start_time = time.time()
     epoch_train_loss, epoch_val_loss = [], []
-    run_epoch(0, Action.VALIDATE, validation_loader, model, optimizer, scheduler, experiment, loss_fn)
+    run_epoch(0, Action.VALIDATE, validation_loader, model, optimizer, scheduler, experiment, loss_fn, prepare)
     for epoch_idx in range(1, num_epochs + 1):
         epoch_train_losses = run_epoch(epoch_idx, Action.TRAIN, training_loader, model, optimizer, scheduler,
-                                       experiment, loss_fn)
+                                       experiment, loss_fn, prepare)
         epoch_val_losses = run_epoch(epoch_idx, Action.VALIDATE, validation_loader, model, optimizer, scheduler,
-                                     experiment, loss_fn)
+                                     experiment, loss_fn, prepare)
         if verbose:
             print("Epoch {} of {} took {:.3f}s".format(epoch_idx, num_epochs, time.time() - start_time))
             print("  training loss (in-iteration): \t{:.6f}".format(epoch_train_losses[-1]))

@@ -1,0 +1,470 @@
+"""GPU suite of the label path (csrc/labels.hip): id remap, softmax-Dice against a class map, confusion counts, and their wiring
+through ops, segmentation/labels.py and segmentation/routine.py.
+
+Remap and confusion counts are integer rules: exact equality with tests/labels_ref.py.
+
+Index Dice is compared with labels_ref.dice_index_ref in float64, fed the same logits after rounding to the storage type.
+  loss      relative error <= 1e-5 (the bar of test_softmax_dice_loss)
+  gradient  absolute error <= 8 x max(e32, 2^-23 max|grad64|), e32 the distance of torch's CPU float32 autograd from float64 on that
+            case (tests/test_mc_gpu.py's convention: the factor covers the device's expf and another summation order); bf16
+            storage adds 2^-8 |grad64| per element for the rounding of the stored gradient.
+
+Launch plan of the Dice kernels, as the cases below use it (labels.hip: idx_blocks_fwd, kIdxVox4): a block is 256 lanes, a sample
+gets min(ceil(items / 1024), 2048 / N) blocks in the forward, items = voxels, or 4-voxel groups plus single voxels for two dense
+classes.  5x7x9 = 315 voxels: one block, a partial first trip, and for C = 2 a head / tail of single voxels beside the groups
+(sample 1 starts 315 = 3 mod 4 voxels into the batch).  7x11x37 = 2849 voxels: 3 blocks = 768 lanes, three whole trips and 545
+voxels more (C > 2); C = 2: 713 / 716 items on one block, two whole trips and 201 / 204 more.
+The backward has another plan (labels.hip: mri3d_softmax_dice_index_bwd): min(ceil(items / 256), 2048, 4096 / N) blocks per sample,
+one item per lane until the cap of 2048 blocks = 524 288 lanes, so only a sample of more than 524 288 items makes its loop go
+round, as every full-size volume does (160x192x160: 9.4 trips).  81x81x81 = 531 441 voxels: 2048 blocks, one whole trip and 7153
+voxels more (C > 2).  C = 2, 129x129x129 = 2 146 689 voxels: sample 0 has 536 672 groups + 1 single voxel = 536 673 items, one whole
+trip and 12 385 more; sample 1 starts 1 mod 4 voxels into the batch: 3 + 536 671 + 2 = 536 676 items, 12 388 more."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import labels_ref
+from guard import SentinelSlice, guarded, kernels_launched
+from mri_epilepsy_diagnosis_amd import _lib, ops, parallel
+from mri_epilepsy_diagnosis_amd.segmentation import labels as label_maps, routine
+from mri_epilepsy_diagnosis_amd.unet import UNet
+from oracle import losses, unet_recon
+from util import REL_TOL, seeded_randn
+
+pytestmark = pytest.mark.gpu
+
+BF, F32 = torch.bfloat16, torch.float32
+CL = torch.channels_last_3d
+SMALL, TRIPS = (5, 7, 9), (7, 11, 37)
+BWD_TRIPS = {2: (129, 129, 129), 3: (81, 81, 81), 8: (81, 81, 81), 9: (81, 81, 81), 17: (81, 81, 81)}
+NP_OF = {torch.uint8: np.uint8, torch.int16: np.int16, torch.int32: np.int32, torch.float32: np.float32}
+
+
+# ------------------------------------------------------------------------------------------------ remap
+def _raw_labels(n, dtype, seed):
+    """n labels of `dtype` on the CPU: ids across every table length of the suite, the edge values the dtype holds in front."""
+    g = torch.Generator().manual_seed(seed)
+    hi = {torch.uint8: 256, torch.int16: 32768}.get(dtype, 70000)
+    x = torch.randint(0, hi, (n,), generator=g).double()
+    if dtype != torch.uint8:
+        x[torch.rand(n, generator=g) < 0.05] *= -1.0
+    if dtype == F32:
+        x[torch.rand(n, generator=g) < 0.1] += 0.5
+    info = None if dtype == F32 else torch.iinfo(dtype)
+    edge = [v for v in labels_ref.EDGE_VALUES if info is None or (v == v and abs(v) != float("inf") and v == int(v) and info.min <= v <= info.max)]
+    k = min(n, len(edge))
+    x[:k] = torch.tensor(edge[:k], dtype=torch.float64)
+    return x.to(dtype)
+
+
+@pytest.fixture(scope="module")
+def luts():
+    g = torch.Generator().manual_seed(5)
+    return {n: torch.randint(0, 256, (n,), generator=g).to(torch.uint8) for n in (1, 256, 1000, 65536)}
+
+
+@pytest.mark.parametrize("out_dtype", [torch.uint8, F32], ids=["to_u8", "to_f32"])
+@pytest.mark.parametrize("in_dtype", [torch.uint8, torch.int16, torch.int32, F32], ids=["u8", "i16", "i32", "f32"])
+def test_remap_is_the_reference_rule(in_dtype, out_dtype, luts):
+    sizes = [(1, 0), (15, 0), (16, 0), (17, 0), (315, 0), (100003, 0), (100003, 3)]       # (n, elements the view starts into its buffer)
+    for lut_len in (1, 256, 1000, 65536):
+        lut = luts[lut_len].cuda()
+        for n, off in sizes if lut_len == 1000 else [(315, 0), (100003, 3)]:
+            raw = _raw_labels(n + off, in_dtype, 17 + n)[off:]
+            want = labels_ref.remap_ref(raw.numpy(), luts[lut_len].numpy(), 7, 9, NP_OF[out_dtype])
+            x = _raw_labels(n + off, in_dtype, 17 + n).cuda()[off:]
+            keep = x.clone()
+            g = guarded(n + off, out_dtype)
+            out = g.region[off:]
+            assert ops.remap_labels(x, lut, 7, 9, out=out) is out
+            g.assert_guards_intact("remap %s -> %s n = %d" % (in_dtype, out_dtype, n))
+            assert bool(g.untouched()[:off].all())
+            assert np.array_equal(out.cpu().numpy(), want), (lut_len, n, off)
+            assert torch.equal(x.view(torch.uint8), keep.view(torch.uint8))           # the input is read only (bits: NaN included)
+            fresh = ops.remap_labels(x, lut, 7, 9, out_dtype)
+            assert fresh.dtype == out_dtype and fresh.shape == x.shape and np.array_equal(fresh.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("n,off", [(1, 0), (17, 0), (315, 0), (100003, 0), (100003, 3)])
+def test_remap_float32_in_place(n, off, luts):
+    raw = _raw_labels(n + off, F32, 23)
+    want = labels_ref.remap_ref(raw.numpy()[off:], luts[1000].numpy(), 1, 0, np.float32)
+    g = guarded(n + off, F32)
+    g.region.copy_(raw)
+    x = g.region[off:]
+    assert ops.remap_labels(x, luts[1000].cuda(), 1, 0, out=x) is x
+    g.assert_guards_intact("in-place remap")
+    assert np.array_equal(x.cpu().numpy(), want)
+    assert torch.equal(g.region[:off].cpu().view(torch.int32), raw[:off].view(torch.int32))
+
+
+def test_remap_beyond_the_first_trip(luts):
+    """The vector loop goes round: 2048 blocks x 256 lanes x 4 loads = 2 097 152 vectors of 4 floats per trip; 8 888 611 floats from
+    element 3 of their buffer are 1 single element, 2 222 152 vectors (one whole trip and 125 000 more) and 2 single elements."""
+    n, off = 8888611, 3
+    raw = _raw_labels(n + off, F32, 37)
+    want = labels_ref.remap_ref(raw.numpy()[off:], luts[1000].numpy(), 7, 9)
+    x = raw.cuda()[off:]
+    g = guarded(n + off, torch.uint8)
+    ops.remap_labels(x, luts[1000].cuda(), 7, 9, out=g.region[off:])
+    g.assert_guards_intact("remap beyond the first trip")
+    assert np.array_equal(g.region[off:].cpu().numpy(), want)
+    ops.remap_labels(x, luts[1000].cuda(), 7, 9, out=x)                       # and in place
+    assert np.array_equal(x.cpu().numpy(), want.astype(np.float32))
+
+
+def test_remap_uint8_in_place_and_misaligned_pairs(luts):
+    raw = _raw_labels(5000, torch.uint8, 29)
+    want = labels_ref.remap_ref(raw.numpy(), luts[256].numpy(), 3, 4)
+    x = raw.cuda()
+    ops.remap_labels(x, luts[256].cuda(), 3, 4, out=x)
+    assert np.array_equal(x.cpu().numpy(), want)
+    # input and output misaligned differently: no vector span, every element singly
+    src, dst = _raw_labels(4099, torch.int16, 31), guarded(4100, torch.uint8)
+    x = src.cuda()[1:]
+    ops.remap_labels(x, luts[1000].cuda(), 1, 0, out=dst.region[2:])
+    dst.assert_guards_intact("misaligned remap")
+    assert np.array_equal(dst.region[2:].cpu().numpy(), labels_ref.remap_ref(src.numpy()[1:], luts[1000].numpy(), 1, 0))
+
+
+# ------------------------------------------------------------------------------------------------ prepare_batch
+def _fcd_batch(dtype, device):
+    g = torch.Generator().manual_seed(41)
+    lab = torch.randint(0, 2100, (2, 1, 6, 10, 9), generator=g).double()
+    ids = torch.tensor(labels_ref.LIST_FCD + [1, 1000, 999, 2035], dtype=torch.float64)
+    lab[0, 0, 0, :3].reshape(-1)[:len(ids)] = ids
+    lab[1, 0, 0, :3].reshape(-1)[:len(ids)] = ids
+    if dtype == F32:
+        lab[:, 0, 1, 0, :6] = torch.tensor([float("nan"), float("inf"), -1.0, 0.5, 999.5, 1000.5], dtype=torch.float64)
+    return {routine.MRI: {routine.DATA: seeded_randn(1, (2, 1, 6, 10, 9)).to(device)}, routine.LABEL: {routine.DATA: lab.to(dtype).to(device)}}
+
+
+@pytest.mark.parametrize("dtype", [F32, torch.int16], ids=["float32", "int16"])
+def test_prepare_batch_device_path_is_the_host_path(dtype):
+    host = _fcd_batch(dtype, "cpu")
+    _, want = routine.prepare_batch(host, "cpu")
+    dev = _fcd_batch(dtype, "cuda")
+    held = dev[routine.LABEL][routine.DATA]
+    (inputs, got), names = kernels_launched(lambda: routine.prepare_batch(dev, "cuda"))
+    assert any("label_remap_kernel" in k for k in names), names
+    assert got.dtype == dtype and got.is_cuda and inputs.is_cuda
+    assert torch.equal(got.cpu().view(torch.uint8), want.view(torch.uint8))                  # bit for bit
+    assert got.data_ptr() == held.data_ptr() and dev[routine.LABEL][routine.DATA] is held      # rewritten in place, as the host path does
+    assert torch.equal(held.cpu().view(torch.uint8), want.view(torch.uint8))
+    assert float(want[0, 0, 0, 0, 0]) == 1 and float(want[1, 0, 0, 0, 0]) == 0                # id 8: LIST_FCD counts for the first sample only
+
+
+def test_prepare_batch_uint8_keeps_the_host_path():
+    lab = torch.randint(0, 256, (2, 1, 4, 6, 8), generator=torch.Generator().manual_seed(43)).to(torch.uint8)
+    dev = {routine.MRI: {routine.DATA: torch.zeros(2, 1, 4, 6, 8).cuda()}, routine.LABEL: {routine.DATA: lab.cuda()}}
+    _, want = routine.prepare_batch({routine.MRI: {routine.DATA: torch.zeros(2, 1, 4, 6, 8)}, routine.LABEL: {routine.DATA: lab.clone()}}, "cpu")
+    (_, got), names = kernels_launched(lambda: routine.prepare_batch(dev, "cuda"))
+    assert not any("label_remap_kernel" in k for k in names), names
+    assert torch.equal(got.cpu(), want)
+
+
+def test_label_map_on_the_device():
+    raw = torch.randint(0, 2100, (3, 1, 4, 6, 9), generator=torch.Generator().manual_seed(47)).to(torch.int32)
+    raw[:, 0, 0, 0, :3] = torch.tensor([8, 1, 2035], dtype=torch.int32)
+    fcd = label_maps.LabelMap.binary_fcd()
+    got = fcd(raw.cuda())
+    assert got.dtype == torch.uint8 and got.shape == raw.shape
+    assert np.array_equal(got.cpu().numpy(), labels_ref.binarise_ref(raw.numpy()).astype(np.uint8))
+    assert got[:, 0, 0, 0, :3].cpu().tolist() == [[1, 1, 1], [0, 1, 1], [0, 1, 1]]
+    assert np.array_equal(fcd(raw.cuda(), F32).cpu().numpy(), labels_ref.binarise_ref(raw.numpy()).astype(np.float32))
+    tables = fcd.tables("cuda")
+    assert all(a is b for a, b in zip(tables, fcd.tables(raw.cuda().device)))          # one copy per device, made once
+    groups = label_maps.LabelMap.from_groups({1: [17, 53], 3: [1006], 2: [2035, 8]})
+    want = labels_ref.remap_ref(raw.numpy(), groups.lut, 0, 0)
+    assert np.array_equal(groups(raw.cuda()).cpu().numpy(), want) and set(np.unique(want)) <= {0, 1, 2, 3}
+    batch = {routine.MRI: {routine.DATA: torch.zeros(3, 1, 4, 6, 9)}, routine.LABEL: {routine.DATA: raw[:, 0]}}      # (N, D, H, W) labels
+    inputs, classes = label_maps.prepare_batch_index(batch, "cuda", groups)
+    assert inputs.is_cuda and classes.shape == (3, 1, 4, 6, 9) and np.array_equal(classes.cpu().numpy(), want)
+
+
+# ------------------------------------------------------------------------------------------------ index Dice
+def _labels(kind, C, spatial, seed):
+    g = torch.Generator().manual_seed(seed)
+    lab = torch.randint(0, C, (2,) + spatial, generator=g)
+    if kind == "ignored":                      # values that are no class, 255 among them
+        lab[torch.rand(lab.shape, generator=g) < 0.2] = C
+        lab[torch.rand(lab.shape, generator=g) < 0.1] = 255
+        lab[1, 0, 0, :2] = torch.tensor([C + 1 if C < 254 else 254, 255])
+    elif kind == "absent":                     # class C - 1 never occurs in sample 0, class 0 never in sample 1
+        lab[0][lab[0] == C - 1] = 0
+        lab[1][lab[1] == 0] = C - 1
+    elif kind == "single":                     # every voxel of sample 0 is class 1; sample 1 stays mixed
+        lab[0] = 1
+    return lab.to(torch.uint8)
+
+
+def _logits(C, spatial, dtype, seed):
+    return (3.0 * torch.randn(2, C, *spatial, generator=torch.Generator().manual_seed(seed))).to(dtype)
+
+
+def _ref_parts(z, lab):
+    """float64 loss and gradient of the stored logits, and e32: how far torch's CPU float32 autograd is from that gradient."""
+    l64, g64 = labels_ref.dice_index_ref(z, lab)
+    _, g32 = labels_ref.dice_index_ref(z, lab, dtype=F32)
+    return l64.item(), g64, (g32.double() - g64).abs().max().item()
+
+
+def _bound(g64, e32, dtype):
+    bound = torch.full_like(g64, 8.0 * max(e32, 2.0 ** -23 * g64.abs().max().item()))
+    return bound + 2.0 ** -8 * g64.abs() if dtype == BF else bound
+
+
+def _reference(z, lab):
+    """float64 loss and gradient of the stored logits, and the gradient's bound."""
+    l64, g64, e32 = _ref_parts(z, lab)
+    return l64, g64, _bound(g64, e32, z.dtype), e32
+
+
+def _device_run(z, lab, label_shape=None):
+    x = z.cuda().contiguous(memory_format=CL).requires_grad_(True)
+    t = lab.cuda() if label_shape is None else lab.cuda().reshape(label_shape)
+    loss = ops.softmax_dice_index_loss(x, t)
+    loss.backward()
+    return loss.detach(), x.grad
+
+
+def _check(what, z, lab, label_shape=None, ref=None):
+    l64, g64, bound, e32 = _reference(z, lab) if ref is None else ref
+    loss, grad = _device_run(z, lab, label_shape)
+    assert loss.dtype == F32 and loss.shape == () and grad.dtype == z.dtype and grad.shape == z.shape
+    rel = abs(loss.item() - l64) / abs(l64)
+    err = (grad.cpu().double() - g64).abs()
+    worst = (err / bound).max().item()
+    print("%s: loss %.7f rel err %.2e; grad max err %.3e (max|grad| %.3e, e32 %.2e), worst err / bound %.3f"
+          % (what, loss.item(), rel, err.max().item(), g64.abs().max().item(), e32, worst))
+    assert bool(torch.isfinite(grad.float()).all()), what
+    assert rel <= 1e-5, "%s: loss %.8f vs %.8f" % (what, loss.item(), l64)
+    assert worst <= 1.0, "%s: gradient error is %.2f x its bound" % (what, worst)
+    return loss, grad
+
+
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 3, 8, 9, 12, 17, 20, 32])       # 12 and 20: rows in 4-element vectors that end inside the bucket
+def test_index_dice_against_float64(C, dtype):
+    _check("C=%d %s" % (C, dtype), _logits(C, SMALL, dtype, 100 + C), _labels("mixed", C, SMALL, 200 + C))
+
+
+# one case per forward instantiation (class bucket 2, 4, 8, 16, 32 x storage type) whose loop goes round: 2849 voxels per sample,
+# see the plan numbers in the module docstring; C = 8 and 32 read their rows in 4-element vectors, 3, 9 and 17 element by element.
+# (The backward takes one trip here: 12 blocks, 3 for C = 2; its cases follow.)
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 3, 8, 9, 17, 32])
+def test_index_dice_beyond_the_first_trip(C, dtype):
+    _check("trips C=%d %s" % (C, dtype), _logits(C, TRIPS, dtype, 300 + C), _labels("mixed", C, TRIPS, 400 + C), (2, 1) + TRIPS)
+
+
+@pytest.fixture(scope="module")
+def big_case():
+    """The latest (C, logits, labels, float64 parts) of the backward's trip cases: the logits hold bfloat16 values, so the float32
+    and the bfloat16 case of one C (run one after the other) share one float64 reference."""
+    return {}
+
+
+# one case per backward instantiation whose loop goes round (the plan numbers are in the module docstring): gradient and loss parity
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 3, 8, 9, 17])
+def test_index_dice_backward_beyond_the_first_trip(C, dtype, big_case):
+    if big_case.get("C") != C:
+        big_case.clear()
+        z, lab = _logits(C, BWD_TRIPS[C], BF, 1200 + C), _labels("ignored", C, BWD_TRIPS[C], 1300 + C)
+        big_case.update(C=C, z=z, lab=lab, parts=_ref_parts(z, lab))
+    z, lab, (l64, g64, e32) = big_case["z"], big_case["lab"], big_case["parts"]
+    vox = lab[0].numel()
+    assert vox % 2 == 1 and (vox // 4 if C == 2 else vox) > 2048 * 256
+    _check("backward trips C=%d %s" % (C, dtype), z.to(dtype), lab, ref=(l64, g64, _bound(g64, e32, dtype), e32))
+
+
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 5, 32])
+@pytest.mark.parametrize("kind", ["ignored", "absent", "single"])
+def test_index_dice_label_patterns(kind, C, dtype):
+    lab = _labels(kind, C, SMALL, 500 + C)
+    if kind == "ignored":
+        assert int((lab >= C).sum()) > 50 and int((lab == 255).sum()) > 10
+    _check("%s C=%d %s" % (kind, C, dtype), _logits(C, SMALL, dtype, 600 + C), lab)
+
+
+def _abi_fwd_bwd(logits_buf, dlogits_buf, lab, C, ld, dtype, stats, loss):
+    """The two entry points on raw NDHWC buffers of pitch ld (logits_buf, dlogits_buf: (N, D, H, W, ld) memory)."""
+    L = _lib.lib()
+    n, vox = lab.shape[0], lab[0].numel()
+    g = _lib.DiceIndexGeom(n, vox, C, ld, 1e-9, _lib.BF16 if dtype == BF else _lib.F32)
+    ws = torch.empty(L.mri3d_softmax_dice_index_workspace_bytes(ctypes.byref(g)), dtype=torch.uint8, device="cuda")
+    dloss = torch.ones(1, device="cuda")
+    st = ops._stream()
+    rc = L.mri3d_softmax_dice_index_fwd(ctypes.byref(g), ops._ptr(logits_buf), ops._ptr(lab), ops._ptr(loss), ops._ptr(stats), ops._ptr(ws),
+                                        ws.numel(), st)
+    assert rc == 0, L.mri3d_last_error()
+    rc = L.mri3d_softmax_dice_index_bwd(ctypes.byref(g), ops._ptr(logits_buf), ops._ptr(lab), ops._ptr(stats), ops._ptr(dloss),
+                                        ops._ptr(dlogits_buf), st)
+    assert rc == 0, L.mri3d_last_error()
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C,ld", [(2, 5), (2, 4), (5, 8), (8, 12), (8, 11), (12, 12), (20, 24), (32, 40)])
+def test_index_dice_pitched_logits_and_guard_bands(C, ld, dtype):
+    """Logits and their gradient as channel slices [0, C) of ld-channel buffers: the other channels hold huge logits that must not be
+    read, and sentinels that must not be written; dlogits and stats sit between guard bands."""
+    z, lab = _logits(C, SMALL, dtype, 700 + C), _labels("ignored", C, SMALL, 800 + C)
+    l64, g64, bound, _ = _reference(z, lab)
+    wide = torch.full((2,) + SMALL + (ld,), 3.0e4, dtype=dtype, device="cuda")           # NDHWC memory; exp(3e4) would be inf
+    wide[..., :C] = z.permute(0, 2, 3, 4, 1).cuda()
+    dz = SentinelSlice(2, ld, SMALL, dtype, 0, C)
+    stats, loss = guarded(2 * C * 3, F32), guarded(1, F32)
+    _abi_fwd_bwd(wide, dz.slice, lab.cuda(), C, ld, dtype, stats.region, loss.region)
+    dz.assert_outside_intact("pitched dlogits")
+    stats.assert_guards_intact("stats"), loss.assert_guards_intact("loss")
+    assert not bool(dz.slice_untouched().any()) and not bool(stats.untouched().any())
+    assert abs(loss.region.item() - l64) / abs(l64) <= 1e-5
+    err = (dz.slice.cpu().double() - g64).abs()
+    assert (err / bound).max().item() <= 1.0, (err / bound).max().item()
+    # stats are (tp, sum_p, sum_g) per (n, c): sum_g is the exact count of the class
+    st = stats.region.cpu().reshape(2, C, 3)
+    want_g = torch.stack([(lab.reshape(2, -1) == c).sum(1) for c in range(C)], 1).float()
+    assert torch.equal(st[..., 2], want_g)
+    assert torch.allclose(st[..., 1].sum(1), torch.full((2,), float(lab[0].numel())), rtol=1e-5)     # probabilities sum to one per voxel
+
+
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 9, 32])
+def test_index_dice_same_bits_run_to_run(C, dtype):
+    z, lab = _logits(C, TRIPS, dtype, 900 + C), _labels("ignored", C, TRIPS, 950 + C)
+    l1, g1 = _device_run(z, lab)
+    l2, g2 = _device_run(z, lab)
+    assert torch.equal(l1.view(torch.int32), l2.view(torch.int32))
+    assert torch.equal(g1.view(torch.int16 if dtype == BF else torch.int32), g2.view(torch.int16 if dtype == BF else torch.int32))
+
+
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [2, 3, 8])
+def test_index_dice_agrees_with_the_float_target_loss(C, dtype):
+    z, lab = _logits(C, SMALL, dtype, 1000 + C), _labels("ignored", C, SMALL, 1100 + C)
+    x = z.cuda().contiguous(memory_format=CL)
+    onehot = labels_ref.one_hot(lab, C, F32).cuda().contiguous(memory_format=CL)
+    a, b = ops.softmax_dice_index_loss(x, lab.cuda()).item(), ops.softmax_dice_loss(x, onehot).item()
+    assert abs(a - b) / abs(b) <= 1e-5, (a, b)
+
+
+@pytest.mark.parametrize("C", [1, 33])
+def test_index_dice_refuses_unsupported_class_counts(C):
+    z = torch.zeros(1, C, 4, 4, 4, device="cuda").contiguous(memory_format=CL)
+    with pytest.raises(_lib.Mri3dError, match="classes must be in"):
+        ops.softmax_dice_index_loss(z, torch.zeros(1, 4, 4, 4, dtype=torch.uint8, device="cuda"))
+
+
+# ------------------------------------------------------------------------------------------------ confusion
+def _class_maps(n, C, seed, outside=True):
+    g = torch.Generator().manual_seed(seed)
+    gt = torch.randint(0, C, (n,), generator=g)
+    pred = torch.where(torch.rand(n, generator=g) < 0.7, gt, torch.randint(0, C, (n,), generator=g))
+    if outside:
+        gt[torch.rand(n, generator=g) < 0.03] = C
+        pred[torch.rand(n, generator=g) < 0.02] = 255
+    return pred.to(torch.uint8), gt.to(torch.uint8)
+
+
+@pytest.mark.parametrize("C", [2, 5, 32])
+def test_confusion_counts_are_exact(C):
+    for n, po, go in ((1, 0, 0), (15, 0, 0), (16, 0, 0), (4097, 0, 0), (100003, 0, 0), (100003, 3, 3), (100003, 1, 2), (700001, 5, 5)):
+        pred, gt = _class_maps(n + max(po, go), C, 7 * n + C)
+        p, t = pred[po:po + n], gt[go:go + n]
+        want, want_out = labels_ref.confusion_ref(p.numpy(), t.numpy(), C)
+        conf, outside = ops.confusion_counts(pred.cuda()[po:po + n], gt.cuda()[go:go + n], C)
+        assert conf.dtype == torch.int64 and conf.shape == (C, C) and outside.dtype == torch.int64
+        assert np.array_equal(conf.cpu().numpy(), want) and int(outside) == want_out, (n, po, go)
+        assert int(conf.sum()) + int(outside) == n
+
+
+@pytest.mark.parametrize("C", [2, 32])
+def test_confusion_counts_of_a_full_volume(C):
+    shape = (160, 192, 160)
+    pred, gt = _class_maps(shape[0] * shape[1] * shape[2], C, 77 + C)
+    # a label map is piecewise constant: long runs of one class along w
+    gt = gt.reshape(-1, 16)[:, :1].expand(-1, 16).reshape(shape).contiguous()
+    pred = pred.reshape(shape)
+    want, want_out = labels_ref.confusion_ref(pred.numpy(), gt.numpy(), C)
+    conf, outside = ops.confusion_counts(pred.cuda(), gt.cuda(), C)
+    assert np.array_equal(conf.cpu().numpy(), want) and int(outside) == want_out
+
+
+def test_confusion_at_two_classes_gives_the_mask_overlap_scores():
+    pred, gt = _class_maps(6 * 10 * 9 * 37, 2, 91, outside=False)
+    pred, gt = pred.cuda(), gt.cuda()
+    conf, outside = ops.confusion_counts(pred, gt, 2)
+    assert int(outside) == 0
+    dice, iou = ops.class_scores_from_confusion(conf)
+    d, i = ops.dice_iou_from_counts(ops.mask_overlap_counts(pred, gt))
+    assert dice.dtype == np.float64 and iou.dtype == np.float64
+    assert dice[1] == d and iou[1] == float(i)
+    want_d, want_i = labels_ref.class_scores_ref(conf.cpu().numpy())
+    assert np.allclose(dice, want_d, rtol=1e-15) and np.allclose(iou, want_i, rtol=2.0 ** -23)
+    empty = torch.zeros(1000, dtype=torch.uint8, device="cuda")
+    dice, iou = ops.class_scores_from_confusion(ops.confusion_counts(empty, empty, 2)[0])
+    assert dice[0] == 1.0 and iou[0] == 1.0 and np.isnan(dice[1]) and np.isnan(iou[1])
+
+
+# ------------------------------------------------------------------------------------------------ model level
+IDS = [17, 53, 1006, 2035]       # -> classes 1..4, background 0
+
+
+def _parcellation_batches(count):
+    out = []
+    for i in range(count):
+        g = torch.Generator().manual_seed(60 + i)
+        pick = torch.randint(0, 6, (1, 1, 16, 16, 16), generator=g)            # 4 ids of the map, 2 ids outside it
+        raw = torch.tensor(IDS + [4, 3000])[pick].to(torch.int16)
+        out.append({routine.MRI: {routine.DATA: seeded_randn(50 + i, (1, 1, 16, 16, 16))}, routine.LABEL: {routine.DATA: raw}})
+    return out
+
+
+def test_class_index_training_and_per_class_validation():
+    lm = label_maps.LabelMap.from_ids(IDS)
+    assert lm.classes == 5
+    batches = _parcellation_batches(2)
+    torch.manual_seed(0)
+    orc = unet_recon.UNetRecon(out_classes=5, out_channels_first_layer=8)
+    model = UNet(in_channels=1, out_classes=5, dimensions=3, num_encoding_blocks=3, out_channels_first_layer=8, normalization="batch",
+                 upsampling_type="linear", padding=True, activation="PReLU")
+    model.load_state_dict(orc.state_dict())
+    model.cuda()
+
+    def prepare(batch, dev):
+        return label_maps.prepare_batch_index(batch, dev, lm)
+    opt = torch.optim.AdamW(model.parameters())
+    got = routine.run_epoch(1, routine.Action.TRAIN, batches, model, opt, loss_fn=ops.softmax_dice_index_loss, prepare=prepare)
+    cache = parallel.StepCache.of(model)
+    assert (cache.captures, cache.eager_runs, cache.replays) == (1, 0, 2)
+    # the oracle on the CPU, float one-hot target of the same class map
+    oopt = torch.optim.AdamW(orc.parameters())
+    orc.train()
+    want = []
+    for b in batches:
+        classes = labels_ref.remap_ref(b[routine.LABEL][routine.DATA].numpy(), lm.lut, 0, 0)
+        oopt.zero_grad()
+        loss = losses.softmax_dice_loss(orc(b[routine.MRI][routine.DATA]), labels_ref.one_hot(torch.from_numpy(classes), 5, F32))
+        loss.backward()
+        oopt.step()
+        want.append(loss.item())
+    print("index-Dice trajectory", got.tolist(), "oracle", want)
+    np.testing.assert_allclose(got, want, rtol=REL_TOL)
+    assert batches[0][routine.LABEL][routine.DATA].dtype == torch.int16 and not batches[0][routine.LABEL][routine.DATA].is_cuda
+
+    dice, iou = routine.validate_classes(model, batches, lm)
+    assert len(dice) == len(iou) == 2
+    model.eval()
+    for k, b in enumerate(batches):
+        with torch.no_grad():
+            mask = ops.argmax_mask(model(b[routine.MRI][routine.DATA].cuda())).cpu().numpy()
+        classes = labels_ref.remap_ref(b[routine.LABEL][routine.DATA].numpy(), lm.lut, 0, 0)
+        conf, _ = labels_ref.confusion_ref(mask, classes, 5)
+        want_d, want_i = labels_ref.class_scores_ref(conf)
+        assert dice[k].shape == (5,) and np.allclose(dice[k], want_d, rtol=1e-15, equal_nan=True)
+        assert np.allclose(iou[k], want_i, rtol=2.0 ** -23, equal_nan=True)
