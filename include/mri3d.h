@@ -517,6 +517,39 @@ int mri3d_aggregate_patches_argmax(const void* logits, int32_t c, int32_t ld, in
                                    uint8_t* out, int32_t nvol, int32_t d, int32_t h, int32_t w, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Detection (reference detection/patch_utils.py, detection/model_utils.py): mirrored left/right patch pairs cut along the
+ * grey-matter template, and the patch map painted back into a voxel mask.  Volume, template and masks are dense (nx, ny, nz)
+ * arrays in the reference's axis order, A[x, y, z] at (x*ny + y)*nz + z.  Slice z is B = np.rot90(A[:, :, z]), B[r, c] =
+ * A[c, ny-1-r, z]; a strip is the h rows r = row0 .. row0+h-1; a patch is (z, row0, col0) with
+ *   channel 0  B[row0+i, col0+t],   channel 1  B[row0+i, nx-1-col0-t],   i < h, t < w.
+ *   strip_starts:        starts[z][row0], z < nz, row0 <= ny-h: the first column of the strip holding a template value > 0, -1
+ *                        for an empty strip.
+ *   mirror_patches:      out[p] = the (2, h, w) patch of table[p] = (z, row0, col0), a DEVICE table of npatch x 3 int32; dense
+ *                        NCHW (channels_last = 0) or [p][i][t][channel] (channels_last = 1).  Bit-exact copy.  `order`: NULL, or
+ *                        a device permutation of 0..npatch-1 giving the order in which the patches are worked on (it changes no
+ *                        result).  The host cannot read the table: an entry that leaves the volume (or an order entry outside
+ *                        0..npatch-1) is never dereferenced, that patch is written as zeros (resp. not written).
+ *   mirror_patch_labels: out[p] = 1 where any mask byte under channel 0 of patch p is non-zero, else 0.
+ *   patch_vote:          map, out: [4][strips][slices] uint8.  count = non-zero 4-neighbours in the (strip, slice) plane of the
+ *                        same patch kind, zero outside the array; out = 1 where count == 4, 0 where count == 0, else map.  Every
+ *                        cell is decided from `map`: out must not overlap it (MRI3D_EINVAL).
+ *   paint_patches:       map [4][ny/h][nz] (kind 0 side, 1 middle, 2 middle mirrored, 3 side mirrored), starts [nz][ny/h] (of the
+ *                        strips row0 = j*h) -> out (nx, ny, nz): a voxel takes the map value of the patch whose channel-0 footprint
+ *                        covers it, the middle patch where a side and a middle patch overlap; 0 in empty strips, in rows past the
+ *                        last whole strip and outside every patch.  Side patches exist where start < nx/2 - w.
+ * All: MRI3D_EINVAL for a null pointer, h <= 0, h > ny, w <= 0, nx/2 - w < 1 (no room for a middle patch), npatch <= 0;
+ * MRI3D_ENOTSUP for sizes that leave int32 indexing.  No allocation, no synchronisation, no workspace.
+ * ---------------------------------------------------------------------------------------------- */
+int mri3d_strip_starts_f32(const float* gm, int32_t nx, int32_t ny, int32_t nz, int32_t h, int32_t* starts, mri3d_stream_t stream);
+int mri3d_mirror_patches_f32(const float* volume, int32_t nx, int32_t ny, int32_t nz, const int32_t* table, const int32_t* order,
+                             int64_t npatch, int32_t h, int32_t w, int32_t channels_last, float* out, mri3d_stream_t stream);
+int mri3d_mirror_patch_labels_u8(const uint8_t* mask, int32_t nx, int32_t ny, int32_t nz, const int32_t* table, int64_t npatch,
+                                 int32_t h, int32_t w, uint8_t* out, mri3d_stream_t stream);
+int mri3d_patch_vote_u8(const uint8_t* map, int32_t strips, int32_t slices, uint8_t* out, mri3d_stream_t stream);
+int mri3d_paint_patches_u8(const uint8_t* map, const int32_t* starts, int32_t nx, int32_t ny, int32_t nz, int32_t h, int32_t w,
+                           uint8_t* out, mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Augmentation: the random stages of the reference's TorchIO `training_transform`
  * (segmentation/results_validation.ipynb, the `training_transform = Compose([...])` cell; pretraining_3d_unet.ipynb cell 24:
  * RandomBiasField, RandomFlip(axes=(0,)), OneOf({RandomAffine(): 0.8, RandomElasticDeformation(): 0.2}); applied through

@@ -145,6 +145,11 @@ SIGNATURES = {
                                              c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_aggregate_patches_argmax": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, c_int32,
                                                  c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P]),
+    "mri3d_strip_starts_f32": (c_int32, [_FP, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "mri3d_mirror_patches_f32": (c_int32, [_FP, c_int32, c_int32, c_int32, _P, _P, c_int64, c_int32, c_int32, c_int32, _FP, _P]),
+    "mri3d_mirror_patch_labels_u8": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int64, c_int32, c_int32, _P, _P]),
+    "mri3d_patch_vote_u8": (c_int32, [_P, c_int32, c_int32, _P, _P]),
+    "mri3d_paint_patches_u8": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "mri3d_warp3d": (c_int32, [_FP, _FP, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _FP, _FP, c_int32, c_int32,
                                c_int32, c_float, _FP, _P]),
     "mri3d_bias_field_f32": (c_int32, [_FP, _FP, c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P]),

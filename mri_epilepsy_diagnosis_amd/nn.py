@@ -282,6 +282,51 @@ class MaxPool3d(tnn.MaxPool3d):
         return ops.max_pool3d_skip(x, self.kernel_size, self.stride, self.padding)
 
 
+# 2-D layers (detection/model_utils.py:19-52): a (N, C, H, W) image is the (N, C, 1, H, W) volume of one slice, so the 3-D operators
+# serve it as they are.  Each layer takes the 4-D tensor of its torch namesake and returns one, or takes the 5-D form with D = 1 and
+# returns that: a model that stays in the 5-D form between its layers (detection.model.PatchModel) moves no data between layouts.
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _as_slice(x, who):
+    """(x as (N, C, 1, H, W), whether it came as (N, C, H, W))."""
+    if x.dim() == 4:
+        return x.unsqueeze(2), True
+    if x.dim() == 5 and x.shape[2] == 1:
+        return x, False
+    raise RuntimeError("mri3d %s expects (N, C, H, W) or (N, C, 1, H, W), got shape %s" % (who, tuple(x.shape)))
+
+
+class Conv2d(tnn.Conv2d):
+    def forward(self, x):
+        if self.padding_mode != "zeros" or self.groups != 1 or isinstance(self.padding, str):
+            raise NotImplementedError("mri3d Conv2d supports padding_mode='zeros', groups=1, numeric padding")
+        x, four = _as_slice(x, "Conv2d")
+        # the 4-D parameter stays the leaf (and the state_dict entry); its 5-D view is no GradSink owner, so the weight gradient goes
+        # back through autograd into the parameter
+        y = ops.conv3d(x, self.weight.unsqueeze(2), self.bias, (1,) + _pair(self.stride), (0,) + _pair(self.padding),
+                       (1,) + _pair(self.dilation))
+        return y.squeeze(2) if four else y
+
+
+class BatchNorm2d(tnn.BatchNorm2d):
+    def forward(self, x):
+        x, four = _as_slice(x, "BatchNorm2d")
+        y = fused_norm_act(self, None, x)
+        return y.squeeze(2) if four else y
+
+
+class MaxPool2d(tnn.MaxPool2d):
+    def forward(self, x):
+        if self.ceil_mode or self.return_indices or self.dilation not in (1, (1, 1)):
+            raise NotImplementedError("mri3d MaxPool2d supports floor mode, dilation 1, no indices")
+        x, four = _as_slice(x, "MaxPool2d")
+        stride = self.kernel_size if self.stride is None else self.stride
+        y = ops.max_pool3d(x, (1,) + _pair(self.kernel_size), (1,) + _pair(stride), (0,) + _pair(self.padding))
+        return y.squeeze(2) if four else y
+
+
 class Upsample(tnn.Upsample):
     def forward(self, x):
         return ops.upsample3d(x, self.size, self.scale_factor, self.mode, self.align_corners)
