@@ -474,6 +474,38 @@ int mri3d_znorm_mean_mask_f32(const float* x, float* y, int64_t n, double* stats
 int mri3d_crop_or_pad_f32(const float* x, float* y, int32_t outer, int32_t di, int32_t hi, int32_t wi, int32_t dout,
                           int32_t ho, int32_t wo, float fill, mri3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Intensity statistics of a stack of volumes (intensity.hip): what the reference looks at before and after harmonisation.
+ * plot_histogram (classification/transfer/full_sample_classification.ipynb cell 9) evaluates scipy.stats.gaussian_kde over all
+ * voxels of a volume at np.linspace(min, max, 100), for 140 volumes (classification/weights/data_140.csv); the landmark training
+ * of HistogramStandardization.train (segmentation/.ipynb_checkpoints/baseline_3d_unet-checkpoint.ipynb, `_get_average_mapping`
+ * restated in classification/train_ENC_CLF.ipynb cell 9) needs the same per-volume range and masks.
+ * x: `batch` rows of n fp32 values; mask (may be NULL): `batch` rows of n bytes, a voxel counts where its byte is non-zero.
+ *   moments[row][8] (float64) = {count, non-finite count, min, max, mean, unbiased variance, 0, 0}.  count is the number of counted
+ *     voxels; the non-finite ones among them (NaN, +-inf) are counted apart and min, max, mean and variance describe the finite
+ *     rest: +inf, -inf, NaN, NaN when there is none, variance NaN below two finite voxels and exactly 0 when min == max.  Sums of x
+ *     and x^2 are taken in float64 in a fixed order (block partials in the workspace, then one block per row): same input, same
+ *     bits, whatever the alignment of a row and the contents of the workspace.
+ *   kde: density[row][j] = sum_i exp(-(p_j - x_i)^2 / 2h^2) / (count sqrt(2 pi h^2)) over the counted voxels of the row,
+ *     h^2 = variance * factor^2, gaussian_kde's covariance.  bw_rule 0: Scott, factor = count^(-1/5) (scipy's default, the
+ *     reference's); 1: Silverman, (count 3/4)^(-1/5); 2: factor = bw_scalar > 0.  `moments` is the device array the moments entry
+ *     wrote; no host round trip lies between the two.  positions: m float64 on the device shared by all rows, or NULL for
+ *     np.linspace(min, max, num=m) of each row, bit for bit (j * step and + min rounded separately, the last position max itself,
+ *     m == 1: [min]).  positions_out[row][m] receives the positions used, density[row][m] the estimate, both float64.  The
+ *     exponent is evaluated in fp32 on centred, scaled values, sums run in fp32 over 256 voxels and in float64 beyond, in a fixed
+ *     order.  A row with count < 2, variance 0 or a non-finite voxel gets NaN densities.  1 <= m <= 1024, else MRI3D_EINVAL.
+ *   workspace: mri3d_intensity_workspace_bytes(n, batch, m) bytes, 8-byte aligned, serves both entries (m = 0: moments alone);
+ *     0 for invalid arguments.  mri3d_kde_plan: out = {blocks per row, voxels per tile, position slots per lane, trips of a
+ *     block's tile loop}.  Both queries are host only.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mri3d_intensity_workspace_bytes(int64_t n, int32_t batch, int32_t m);
+int mri3d_kde_plan(int64_t n, int32_t batch, int32_t m, int32_t out[4]);
+int mri3d_intensity_moments_f32(const float* x, const uint8_t* mask, int64_t n, int32_t batch, double* moments,
+                                void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_kde_f32(const float* x, const uint8_t* mask, int64_t n, int32_t batch, const double* moments, const double* positions,
+                  int32_t m, int32_t bw_rule, double bw_scalar, double* positions_out, double* density, void* workspace,
+                  size_t ws_bytes, mri3d_stream_t stream);
+
 /* Average surface distance inputs of validate_dsc_asd (segmentation/routine.py:205-214): for two (d,h,w) uint8 masks
  * (non-zero = inside) and the 256-entry surface-element area table of metrics.py:57-71 (HOST array, for the spacing in use)
  *   sums[0] = sum(dist_to_pred_surface * area), sums[1] = sum(area) over the surface elements of gt,

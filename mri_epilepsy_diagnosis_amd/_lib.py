@@ -5,7 +5,7 @@ shared object is missing instead of silently degrading.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint8, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint8, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmri3d_hip.so")
@@ -16,6 +16,7 @@ UP_NEAREST, UP_TRILINEAR = 0, 1
 PASS_FWD, PASS_DGRAD, PASS_WGRAD = 0, 1, 2
 NORM_PASS_STATS, NORM_PASS_FWD, NORM_PASS_BWD = 0, 1, 2
 LABEL_U8, LABEL_I16, LABEL_I32, LABEL_F32 = 0, 1, 2, 3
+BW_SCOTT, BW_SILVERMAN, BW_FACTOR = 0, 1, 2
 
 
 class ConvGeom(Structure):
@@ -136,6 +137,10 @@ SIGNATURES = {
     "mri3d_znorm_workspace_bytes": (c_size_t, []),
     "mri3d_znorm_mean_mask_f32": (c_int32, [_P, _P, c_int64, _P, _P, c_size_t, _P]),
     "mri3d_crop_or_pad_f32": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, _P]),
+    "mri3d_intensity_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "mri3d_kde_plan": (c_int32, [c_int64, c_int32, c_int32, _P]),
+    "mri3d_intensity_moments_f32": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "mri3d_kde_f32": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, c_double, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_distance_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mri3d_surface_distance": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_elements": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P]),

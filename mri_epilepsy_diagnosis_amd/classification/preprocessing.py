@@ -109,6 +109,57 @@ def normalize(tensor, landmarks, mask=None, cutoff=None, epsilon=1e-5):
     return out.reshape(shape)
 
 
+def _get_average_mapping(percentiles_database):
+    """The reference's `_get_average_mapping` (classification/train_ENC_CLF.ipynb cell 9, TorchIO's): every image's first and last
+    percentile are sent to STANDARD_RANGE by a line of its own, and the landmarks are the mean over images of the lines applied to
+    their percentiles.  percentiles_database: (images, percentiles) float64.  The reference's arithmetic, operation by operation."""
+    db = np.asarray(percentiles_database)
+    low, high = STANDARD_RANGE
+    first, last = db[:, 0], db[:, -1]
+    slopes = np.nan_to_num((high - low) / (last - first))      # an image without range: 0/0 -> 0, c/0 -> the largest float
+    intercept = np.mean(low - slopes * first)
+    return slopes.dot(db) / len(db) + intercept
+
+
+def train_landmarks(images, cutoff=None, mask=None, masking_function=None, output_path=None):
+    """TorchIO's `HistogramStandardization.train` (the call of segmentation/.ipynb_checkpoints/baseline_3d_unet-checkpoint.ipynb
+    that made fcd_train_data_landmarks.npy) with device tensors where it has image paths: per image the 13 percentiles of
+    `normalize` over the voxels its mask selects, then the average mapping over images.  Returns the float64 landmark vector
+    `normalize` takes; `output_path` also saves it with np.save.
+    mask: None, one mask for every image, or a sequence of one per image, applied as `normalize` applies its mask.
+    masking_function: tensor -> mask (e.g. transforms.ZNormalization.mean), evaluated on the device; it and `mask` exclude each
+    other, as in TorchIO."""
+    images = list(images)
+    if not images:
+        raise ValueError("train_landmarks: no images")
+    if mask is not None and masking_function is not None:
+        raise ValueError("train_landmarks: give a mask or a masking_function, not both")
+    if isinstance(mask, (list, tuple)):
+        if len(mask) != len(images):
+            raise ValueError("train_landmarks: %d masks for %d images" % (len(mask), len(images)))
+        masks = list(mask)
+    else:
+        masks = [mask] * len(images)
+    quantiles_cutoff = _standardize_cutoff(DEFAULT_CUTOFF if cutoff is None else cutoff)
+    percentiles = _get_percentiles(100 * np.array(quantiles_cutoff))
+    database = []
+    for tensor, m in zip(images, masks):
+        if not torch.is_tensor(tensor) or not tensor.is_cuda:
+            raise RuntimeError("train_landmarks runs only on ROCm device tensors (got %s); there is no CPU fallback"
+                               % (tensor.device if torch.is_tensor(tensor) else type(tensor).__name__))
+        if masking_function is not None:
+            m = masking_function(tensor)
+        data = tensor.reshape(-1).to(torch.float32).contiguous()
+        sel = data if m is None else data[torch.as_tensor(m, device=data.device).reshape(-1).bool()]
+        if sel.numel() == 0:
+            raise ValueError("train_landmarks: the mask of image %d selects no voxel" % len(database))
+        database.append(percentile(sel, percentiles))
+    mapping = _get_average_mapping(np.vstack(database))
+    if output_path is not None:
+        np.save(output_path, mapping)
+    return mapping
+
+
 def default_collate(batch, landmarks, device="cuda"):
     """collate_fn of the reference (cell 9) with the volumes standardised on the device: batch = [(X, y, domain), ...]."""
     X = torch.stack([normalize(item[0].to(device), landmarks) for item in batch])

@@ -15,6 +15,7 @@ Reference operators replaced (file:line in /root/reference):
   bayes_conv3d         BayesConv3d          3d_bayes_layers.py:195-232 (3d_bayes_unet.py::UNet3D(bayes=True))
   remap_labels         np.isin + boolean-mask writes of prepare_batch   segmentation/routine.py:185-196
   softmax_dice_index_loss   the same loss against a uint8 class map (2..32 classes)   segmentation/routine.py:272-274
+  gaussian_kde / intensity_moments   scipy.stats.gaussian_kde over a volume's voxels   full_sample_classification.ipynb cell 9
 Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd);
 confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask.
 """
@@ -2001,6 +2002,78 @@ def class_scores_from_confusion(conf):
             dice[k] = 2 * tp / (sg + sp)
             iou[k] = float(np.float32(tp)) / np.float32(sg + sp - tp)
     return dice, iou
+
+
+# ----------------------------------------------------------------------------------------------- intensity statistics (csrc/intensity.hip)
+def _intensity_rows(who, x, mask):
+    """x as (B, n) float32 rows (a 1-D tensor is one row, anything else a batch along its first axis) and the matching mask rows."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError("%s: needs a float32 ROCm device tensor (got %s on %s); there is no CPU fallback" % (who, x.dtype, x.device))
+    rows = x.contiguous().reshape(1, -1) if x.dim() <= 1 else x.contiguous().reshape(x.shape[0], -1)
+    if rows.shape[0] == 0 or rows.shape[1] == 0:
+        raise RuntimeError("%s: empty tensor of shape %s" % (who, tuple(x.shape)))
+    if mask is not None:
+        if not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8):
+            raise RuntimeError("%s: the mask must be a bool / uint8 ROCm device tensor (got %s on %s); there is no CPU fallback"
+                               % (who, mask.dtype, mask.device))
+        if mask.numel() != rows.numel():
+            raise RuntimeError("%s: mask of shape %s does not match the tensor's %s" % (who, tuple(mask.shape), tuple(x.shape)))
+        mask = mask.contiguous().view(torch.uint8).reshape(rows.shape)
+    return rows, mask
+
+
+def intensity_moments(x, mask=None):
+    """Per-volume moments on the device: a (B, 8) float64 tensor [count, non-finite count, min, max, mean, unbiased variance, 0, 0]
+    over the voxels of each row of `x` (float32; a 1-D tensor is one volume, anything else a batch along its first axis) that `mask`
+    (bool / uint8, same shape) counts.  min, max, mean and variance describe the finite counted voxels."""
+    rows, mask = _intensity_rows("intensity_moments", x, mask)
+    L = _lib.lib()
+    b, n = rows.shape
+    out = torch.empty((b, 8), dtype=torch.float64, device=rows.device)
+    ws = _workspace(L.mri3d_intensity_workspace_bytes(n, b, 0), rows.device)
+    check(L.mri3d_intensity_moments_f32(_ptr(rows), _ptr(mask), n, b, _ptr(out), _ptr(ws), ws.numel(), _stream()), "intensity_moments")
+    return out
+
+
+def _bandwidth_rule(bw_method):
+    if bw_method is None or bw_method == "scott":
+        return _lib.BW_SCOTT, 0.0
+    if bw_method == "silverman":
+        return _lib.BW_SILVERMAN, 0.0
+    if isinstance(bw_method, str) or callable(bw_method):
+        raise ValueError("gaussian_kde: bw_method must be None, 'scott', 'silverman' or a positive number, got %r" % (bw_method,))
+    factor = float(bw_method)
+    if not (factor > 0.0 and factor < float("inf")):
+        raise ValueError("gaussian_kde: the bandwidth factor must be positive and finite, got %r" % (bw_method,))
+    return _lib.BW_FACTOR, factor
+
+
+def gaussian_kde(x, num_positions=100, positions=None, bw_method=None, mask=None, moments=None):
+    """scipy.stats.gaussian_kde(values, bw_method)(positions) for every volume of a batch, on the device: (positions, density), two
+    (B, m) float64 tensors.  `positions` None is np.linspace(min, max, num_positions) of each volume's counted voxels, bit for bit;
+    else a 1-D float64 device tensor shared by all volumes.  `bw_method` None / 'scott' / 'silverman' / a number (the factor), as
+    in scipy.  Where scipy has no answer (fewer than 2 counted voxels, no variance, a non-finite voxel) the densities are NaN.
+    `moments` takes the result of `intensity_moments(x, mask)` when the caller already has it."""
+    rows, mask = _intensity_rows("gaussian_kde", x, mask)
+    rule, factor = _bandwidth_rule(bw_method)
+    L = _lib.lib()
+    b, n = rows.shape
+    if positions is not None:
+        if not positions.is_cuda or positions.dtype != torch.float64 or positions.dim() != 1:
+            raise RuntimeError("gaussian_kde: positions must be a 1-D float64 ROCm device tensor (got %s %s on %s); there is no CPU "
+                               "fallback" % (tuple(positions.shape), positions.dtype, positions.device))
+        positions = positions.contiguous()
+    m = int(num_positions) if positions is None else positions.numel()
+    if moments is None:
+        moments = intensity_moments(rows, mask)
+    elif tuple(moments.shape) != (b, 8) or moments.dtype != torch.float64 or not moments.is_cuda or not moments.is_contiguous():
+        raise RuntimeError("gaussian_kde: moments must be the contiguous (%d, 8) float64 device tensor of intensity_moments" % b)
+    pos_out = torch.empty((b, max(m, 0)), dtype=torch.float64, device=rows.device)
+    density = torch.empty((b, max(m, 0)), dtype=torch.float64, device=rows.device)
+    ws = _workspace(L.mri3d_intensity_workspace_bytes(n, b, m), rows.device)
+    check(L.mri3d_kde_f32(_ptr(rows), _ptr(mask), n, b, _ptr(moments), _ptr(positions), m, rule, factor, _ptr(pos_out), _ptr(density),
+                          _ptr(ws), ws.numel(), _stream()), "kde")
+    return pos_out, density
 
 
 # ----------------------------------------------------------------------------------------------- cat / add

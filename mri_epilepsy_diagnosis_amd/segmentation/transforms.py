@@ -629,6 +629,20 @@ class HistogramStandardization(Transform):
         super().__init__(p, seed)
         self.landmarks_dict = {k: np.asarray(v) for k, v in landmarks_dict.items()}
 
+    @classmethod
+    def train(cls, images, image_key=None, cutoff=None, mask=None, masking_function=None, output_path=None):
+        """torchio.HistogramStandardization.train over `preprocessing.train_landmarks`, with volumes that are already on the device
+        where TorchIO takes paths: `images` is a sequence of device tensors, or of subject dicts whose `image_key` entry is one.
+        Returns the landmark vector, so that HistogramStandardization(landmarks_dict={MRI: HistogramStandardization.train(...)})
+        reads like the reference's notebook."""
+        images = list(images)
+        if any(isinstance(s, dict) for s in images):
+            if image_key is None:
+                raise ValueError("HistogramStandardization.train: subject dicts need image_key")
+            images = [s[image_key] for s in images]
+        return preprocessing.train_landmarks(images, cutoff=cutoff, mask=mask, masking_function=masking_function,
+                                             output_path=output_path)
+
     def _fn(self, images, labels):
         return {k: (preprocessing.normalize(v, self.landmarks_dict[k]) if k in self.landmarks_dict else v)
                 for k, v in images.items()}, labels
