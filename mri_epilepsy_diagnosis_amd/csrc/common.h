@@ -159,10 +159,12 @@ inline PoolFwdLanes pool_fwd_lanes(const Mri3dPoolGeom& g, std::initializer_list
     return p;
 }
 
-// ---------------------------------------------------------------- softmax-Dice finalize shared by loss.hip and labels.hip
-// part[n][blk][c][3] = (tp, sum_p, sum_g) partial double sums of nblk blocks per sample -> stats[n][c][3] and the mean loss, on one
-// block in a fixed order (defined in loss.hip): the float-target and the class-index loss are one expression of the three sums.
-void dice_finalize(const double* part, float* stats, float* loss, int n, int c, int nblk, float eps, hipStream_t stream);
+// a workspace of 8-byte elements (double or 64-bit integer partials): present, large enough and 8-byte aligned
+inline int ws_check8(const char* who, const void* workspace, size_t ws_bytes, size_t need) {
+    MRI3D_REQUIRE(workspace && ws_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, MRI3D_EWORKSPACE,
+                  "%s: workspace %zu < %zu, or not 8-byte aligned", who, ws_bytes, need);
+    return MRI3D_OK;
+}
 
 // ---------------------------------------------------------------- device helpers
 __device__ __forceinline__ float wave_sum(float v) {

@@ -1,74 +1,77 @@
-// loss.hip — fused softmax(dim=C) + soft-Dice loss and its gradient, plus the argmax->uint8 mask used by validation.
+// loss.hip — fused softmax(dim=C) + soft-Dice loss and its gradient for both target forms (float channels, 2..8 classes; a uint8
+// class map, 2..32 classes), plus the argmax->uint8 mask used by validation.
 // Reference: F.softmax(logits, dim=1) -> get_dice_loss(probabilities, targets) -> .mean()
 // (segmentation/routine.py:239-253, 272-274); labels = logits.argmax(dim=1) (routine.py:226-227).
 //
 //   p = softmax(z);  tp_c = sum p_c g_c,  fp_c = sum p_c (1-g_c),  fn_c = sum (1-p_c) g_c
 //   dice_c = 2 tp_c / (2 tp_c + fp_c + fn_c + eps) = 2 tp_c / (sum p_c + sum g_c + eps)
 //   loss = mean_{n,c} (1 - dice_{n,c})
-// The reference feeds a (N,1,...) target against (N,2,...) probabilities, i.e. g_c = g for every class (SURVEY
-// Appendix C.1); ct == 1 reproduces that broadcast, ct == c is the per-class form.
+// Float target: the reference feeds a (N,1,...) target against (N,2,...) probabilities, i.e. g_c = g for every class (SURVEY
+// Appendix C.1); ct == 1 reproduces that broadcast, ct == c is the per-class form.  Class map: g_c = [label == c], a label >= C
+// belongs to no class.
 //
-// HBM-bound: forward = one read of logits+target; backward = one read of both + one write of dlogits.
+// The two forms have their own forward and backward loops (the class map's 4-voxel path, class buckets and integer sum_g have no
+// float-target counterpart) and share what stands around them: the softmax, the block's row of partial sums, the finalize kernel,
+// the gradient's coefficients, the grid rules and the host checks.
+//
+// HBM-bound.  Bytes per voxel: forward C * esz + target, backward 2 * C * esz + target; target = 4 * ct (float) or 1 (class map).
 #include "common.h"
+#include <math.h>
 #include <algorithm>
 
 namespace mri3d {
 
 constexpr int kDiceMaxC = 8;
-constexpr int kDiceMaxBlocks = 1024;
+constexpr int kIdxMinC = 2, kIdxMaxC = 32;
+// blocks of one forward launch over all samples: the cap fixes the summation order, so each form keeps its own
+constexpr int kDiceMaxBlocks = 1024, kIdxMaxBlocks = 2048;
 
-template <int C>
-__device__ __forceinline__ void softmax_c(const float* z, float (&p)[C]) {
+// ------------------------------------------------------------------ shared by both target forms
+// z -> softmax(z) in place
+template <int K> __device__ __forceinline__ void softmax_inplace(float (&z)[K]) {
     float m = z[0];
 #pragma unroll
-    for (int j = 1; j < C; ++j) m = fmaxf(m, z[j]);
+    for (int j = 1; j < K; ++j) m = fmaxf(m, z[j]);
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < C; ++j) { p[j] = expf(z[j] - m); s += p[j]; }
-    float inv = 1.f / s;
+    for (int j = 0; j < K; ++j) { z[j] = expf(z[j] - m); s += z[j]; }
+    const float inv = 1.f / s;
 #pragma unroll
-    for (int j = 0; j < C; ++j) p[j] *= inv;
+    for (int j = 0; j < K; ++j) z[j] *= inv;
 }
 
-// part[n][blk][c][3] = (tp, sum_p, sum_g)
-template <typename T, int C>
-__global__ void __launch_bounds__(256)
-dice_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, double* __restrict__ part,
-                int64_t vox, int ct, int x_ld, int t_ld) {
-    __shared__ double red[4][C * 3];
-    const int n = blockIdx.y;
-    const T* zn = logits + (int64_t)n * vox * x_ld;
-    const float* tn = target + (int64_t)n * vox * t_ld;
-    double tp[C], sp[C], sg[C];  // torch's CPU reductions (the oracle's arithmetic) accumulate float sums in double
-#pragma unroll
-    for (int j = 0; j < C; ++j) { tp[j] = 0.0; sp[j] = 0.0; sg[j] = 0.0; }
-    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < vox; v += (int64_t)gridDim.x * blockDim.x) {
-        float z[C], p[C];
-#pragma unroll
-        for (int j = 0; j < C; ++j) z[j] = ldf(zn + v * x_ld + j);
-        softmax_c<C>(z, p);
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            float g = tn[v * t_ld + (ct == 1 ? 0 : j)];
-            tp[j] += (double)(p[j] * g);
-            sp[j] += (double)p[j];
-            sg[j] += (double)g;
-        }
-    }
+// A lane's sums of classes [0, C) -> the block's row part[n][blk = blockIdx.x][c][3] = (tp, sum_p, sum_g): wave shuffles, then the
+// four waves through LDS (red, the kernel's) in a fixed order.  sum_g is a double sum (float target) or a count added as integers
+// (class map).  The kernels' code is sensitive to how this tail is written (the 32-class forward's register allocation follows
+// it): n, red and the two spellings of the sum_g reduction keep every forward kernel's loop as it was compiled before the two
+// forms shared this function.
+template <int K, typename G>
+__device__ __forceinline__ void dice_block_row(const double (&tp)[K], const double (&sp)[K], const G (&sg)[K], int C, int n,
+                                               double (&red)[4][K * 3], double* __restrict__ part) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
-    for (int j = 0; j < C; ++j) {
-        double a = wave_sum_d(tp[j]), b = wave_sum_d(sp[j]), c = wave_sum_d(sg[j]);
-        if (lane == 0) { red[wave][j * 3] = a; red[wave][j * 3 + 1] = b; red[wave][j * 3 + 2] = c; }
+    for (int j = 0; j < K; ++j) {
+        if (j < C) {
+            const double a = wave_sum_d(tp[j]), b = wave_sum_d(sp[j]);
+            G c = sg[j];
+            if constexpr (sizeof(G) == sizeof(double)) {
+                c = wave_sum_d(c);
+            } else {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+            }
+            if (lane == 0) { red[wave][j * 3] = a; red[wave][j * 3 + 1] = b; red[wave][j * 3 + 2] = (double)c; }
+        }
     }
     __syncthreads();
-    if (threadIdx.x < C * 3) {
-        double s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if ((int)threadIdx.x < C * 3) {
+        const double s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
         part[((size_t)n * gridDim.x + blockIdx.x) * C * 3 + threadIdx.x] = s;
     }
 }
 
-// one block of 256 threads: (n, c) pairs are handled 8 at a time by 32 partial lanes each (fixed-order double sums)
+// part -> stats[n][c][3] and the mean loss: the float-target and the class-index loss are one expression of the three sums.
+// One block of 256 threads: (n, c) pairs are handled 8 at a time by 32 partial lanes each (fixed-order double sums)
 __global__ void __launch_bounds__(256)
 dice_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats, float* __restrict__ loss, int N, int C,
                      int nblk, float eps) {
@@ -109,8 +112,40 @@ dice_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats,
     if (threadIdx.x == 0) loss[0] = (float)(acc_loss / (double)(N * C));
 }
 
-void dice_finalize(const double* part, float* stats, float* loss, int n, int c, int nblk, float eps, hipStream_t stream) {
-    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, stream, part, stats, loss, n, c, nblk, eps);
+// d(1 - dice_c)/dp_c(v) = -(2 g den - 2 tp)/den^2 scaled by dloss/(N*C) = ka * g + kb, from the (tp, sum_p, sum_g) of one (n, c)
+__device__ __forceinline__ void dice_coeffs(const float* __restrict__ st, float scale, float eps, float& ka, float& kb) {
+    const float tp = st[0], sp = st[1], sg = st[2];
+    const float den = sp + sg + eps;
+    ka = -2.f * scale / den;              // multiplies g
+    kb = 2.f * scale * tp / (den * den);  // constant term
+}
+
+// ------------------------------------------------------------------ float target
+template <typename T, int C>
+__global__ void __launch_bounds__(256)
+dice_fwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, double* __restrict__ part,
+                int64_t vox, int ct, int x_ld, int t_ld) {
+    __shared__ double red[4][C * 3];
+    const int n = blockIdx.y;
+    const T* zn = logits + (int64_t)n * vox * x_ld;
+    const float* tn = target + (int64_t)n * vox * t_ld;
+    double tp[C], sp[C], sg[C];  // torch's CPU reductions (the oracle's arithmetic) accumulate float sums in double
+#pragma unroll
+    for (int j = 0; j < C; ++j) { tp[j] = 0.0; sp[j] = 0.0; sg[j] = 0.0; }
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < vox; v += (int64_t)gridDim.x * blockDim.x) {
+        float p[C];
+#pragma unroll
+        for (int j = 0; j < C; ++j) p[j] = ldf(zn + v * x_ld + j);
+        softmax_inplace<C>(p);
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            float g = tn[v * t_ld + (ct == 1 ? 0 : j)];
+            tp[j] += (double)(p[j] * g);
+            sp[j] += (double)p[j];
+            sg[j] += (double)g;
+        }
+    }
+    dice_block_row<C>(tp, sp, sg, C, n, red, part);
 }
 
 template <typename T, int C>
@@ -122,21 +157,15 @@ dice_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, 
     const T* zn = logits + (int64_t)n * vox * x_ld;
     const float* tn = target + (int64_t)n * vox * t_ld;
     T* dn = dlogits + (int64_t)n * vox * x_ld;
-    // d(1 - dice)/dp_c(v) = -(2 g den - 2 tp)/den^2, scaled by dloss/(N*C)
     float ka[C], kb[C];
     const float scale = dloss[0] / (float)(N * C);
 #pragma unroll
-    for (int j = 0; j < C; ++j) {
-        float tp = stats[(n * C + j) * 3], sp = stats[(n * C + j) * 3 + 1], sg = stats[(n * C + j) * 3 + 2];
-        float den = sp + sg + eps;
-        ka[j] = -2.f * scale / den;          // multiplies g
-        kb[j] = 2.f * scale * tp / (den * den);  // constant term
-    }
+    for (int j = 0; j < C; ++j) dice_coeffs(stats + (n * C + j) * 3, scale, eps, ka[j], kb[j]);
     for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < vox; v += (int64_t)gridDim.x * blockDim.x) {
-        float z[C], p[C], dp[C];
+        float p[C], dp[C];
 #pragma unroll
-        for (int j = 0; j < C; ++j) z[j] = ldf(zn + v * x_ld + j);
-        softmax_c<C>(z, p);
+        for (int j = 0; j < C; ++j) p[j] = ldf(zn + v * x_ld + j);
+        softmax_inplace<C>(p);
         float dot = 0.f;
 #pragma unroll
         for (int j = 0; j < C; ++j) {
@@ -149,6 +178,220 @@ dice_bwd_kernel(const T* __restrict__ logits, const float* __restrict__ target, 
     }
 }
 
+// ------------------------------------------------------------------ class-map target
+// how a lane reads its logits: one element at a time; a voxel's classes in 4-element vectors (c, x_ld multiples of 4, aligned
+// base); or, for two dense classes, 4 voxels = 8 logits per lane (16-byte aligned logits, 4-byte aligned labels)
+enum { kIdxScalar = 0, kIdxRows4 = 1, kIdxVox4 = 2 };
+
+// One instantiation per class bucket CB in {2, 4, 8, 16, 32}, serving CB/2 < C <= CB (C == 2: CB = 2).  Classes C..CB-1 read as
+// -inf: their probability is exactly 0, and adding 0 leaves every float sum as the C-class computation has it.
+template <typename T, int CB>
+__device__ __forceinline__ void idx_load_row(const T* p, int C, int mode, float (&z)[CB]) {
+    if constexpr (CB >= 4) {
+        if (mode == kIdxRows4) {
+#pragma unroll
+            for (int j = 0; j < CB; j += 4) {
+                float4 t = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+                if (j < C) t = ldf4(p + j);
+                z[j] = t.x, z[j + 1] = t.y, z[j + 2] = t.z, z[j + 3] = t.w;
+            }
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CB; ++j) z[j] = j < C ? ldf(p + j) : -INFINITY;
+}
+
+// 8 consecutive elements (4 voxels of 2 classes), p 16-byte (bf16) / 32-byte (fp32) aligned
+__device__ __forceinline__ void idx_ld8(const float* p, float (&r)[8]) {
+    const float4 a = ldf4(p), b = ldf4(p + 4);
+    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w, r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+}
+__device__ __forceinline__ void idx_ld8(const bf16_t* p, float (&r)[8]) {
+    const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(p);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) r[k] = (float)v[k];
+}
+__device__ __forceinline__ void idx_st8(float* p, const float (&r)[8]) {
+    stf4(p, make_float4(r[0], r[1], r[2], r[3]));
+    stf4(p + 4, make_float4(r[4], r[5], r[6], r[7]));
+}
+__device__ __forceinline__ void idx_st8(bf16_t* p, const float (&r)[8]) {
+    bf16x8_t o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = (bf16_t)r[k];
+    *reinterpret_cast<bf16x8_t*>(p) = o;
+}
+
+// The voxels of sample n as work items of the 4-voxel path: `head` single voxels up to the first one whose index in the whole
+// batch is a multiple of 4 (there logits and labels are aligned), `groups` groups of 4, then the rest as single voxels.
+struct IdxVox4Plan {
+    int64_t head, groups, items;
+    __device__ __forceinline__ IdxVox4Plan(int64_t n, int64_t vox) {
+        head = (4 - ((n * vox) & 3)) & 3;
+        if (head > vox) head = vox;
+        groups = (vox - head) >> 2;
+        items = groups + (vox - groups * 4);
+    }
+    // item i >= groups is a single voxel: which one
+    __device__ __forceinline__ int64_t single(int64_t i) const {
+        const int64_t s = i - groups;
+        return s < head ? s : groups * 4 + s;
+    }
+};
+
+// tp and sum_p of a lane in double (torch's CPU reductions, the oracle's arithmetic, accumulate float sums in double); sum_g is a
+// count.  tp only receives p[label]: a select per class, no indexed registers.
+template <int CB> struct IdxAcc {
+    double tp[CB], sp[CB];
+    unsigned sg[CB];
+    __device__ __forceinline__ void add(const float (&p)[CB], unsigned lab) {
+#pragma unroll
+        for (int j = 0; j < CB; ++j) {
+            const bool hit = lab == (unsigned)j;
+            tp[j] += (double)(hit ? p[j] : 0.f);
+            sp[j] += (double)p[j];
+            sg[j] += hit ? 1u : 0u;
+        }
+    }
+};
+
+template <typename T, int CB>
+__global__ void __launch_bounds__(256)
+dice_index_fwd_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ labels, double* __restrict__ part, int64_t vox,
+                      int C, int x_ld, int mode) {
+    __shared__ double red[4][CB * 3];
+    const int n = blockIdx.y;
+    const T* zn = logits + (int64_t)n * vox * x_ld;
+    const uint8_t* ln = labels + (int64_t)n * vox;
+    IdxAcc<CB> a;
+#pragma unroll
+    for (int j = 0; j < CB; ++j) { a.tp[j] = 0.0; a.sp[j] = 0.0; a.sg[j] = 0u; }
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    if (CB == 2 && mode == kIdxVox4) {
+        if constexpr (CB == 2) {
+            const IdxVox4Plan plan(n, vox);
+            for (int64_t i = tid; i < plan.items; i += nth) {
+                if (i < plan.groups) {
+                    const int64_t v0 = plan.head + i * 4;
+                    float z[8];
+                    idx_ld8(zn + v0 * 2, z);
+                    const uint32_t lw = *reinterpret_cast<const uint32_t*>(ln + v0);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float p[2] = {z[2 * k], z[2 * k + 1]};
+                        softmax_inplace<2>(p);
+                        a.add(p, (lw >> (8 * k)) & 0xffu);
+                    }
+                } else {
+                    const int64_t v = plan.single(i);
+                    float p[2] = {ldf(zn + v * 2), ldf(zn + v * 2 + 1)};
+                    softmax_inplace<2>(p);
+                    a.add(p, ln[v]);
+                }
+            }
+        }
+    } else {
+#pragma unroll 1
+        for (int64_t v = tid; v < vox; v += nth) {
+            float p[CB];
+            idx_load_row<T, CB>(zn + v * x_ld, C, mode, p);
+            softmax_inplace<CB>(p);
+            a.add(p, ln[v]);
+        }
+    }
+    dice_block_row<CB>(a.tp, a.sp, a.sg, C, n, red, part);
+}
+
+// ka * [label == c] + kb (dice_bwd_kernel's fmaf(ka, g, kb) at g = 1 and g = 0), then the softmax Jacobian
+template <int CB>
+__device__ __forceinline__ void idx_grad(float (&p)[CB], unsigned lab, const float (&ka)[CB], const float (&kb)[CB]) {
+    float dp[CB], dot = 0.f;
+#pragma unroll
+    for (int j = 0; j < CB; ++j) {
+        dp[j] = lab == (unsigned)j ? ka[j] + kb[j] : kb[j];
+        dot = fmaf(p[j], dp[j], dot);
+    }
+#pragma unroll
+    for (int j = 0; j < CB; ++j) p[j] *= dp[j] - dot;
+}
+
+template <typename T, int CB>
+__global__ void __launch_bounds__(256)
+dice_index_bwd_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ labels, const float* __restrict__ stats,
+                      const float* __restrict__ dloss, T* __restrict__ dlogits, int64_t vox, int N, int C, int x_ld, int mode,
+                      float eps) {
+    const int n = blockIdx.y;
+    const T* zn = logits + (int64_t)n * vox * x_ld;
+    const uint8_t* ln = labels + (int64_t)n * vox;
+    T* dn = dlogits + (int64_t)n * vox * x_ld;
+    // the two coefficients of every class, one class per lane, then to every lane's registers through LDS
+    __shared__ float ska[CB], skb[CB];
+    if (threadIdx.x < CB) {
+        const int j = threadIdx.x;
+        float a = 0.f, b = 0.f;        // a class >= C has p = 0 and takes no part
+        if (j < C) dice_coeffs(stats + (n * C + j) * 3, dloss[0] / (float)(N * C), eps, a, b);
+        ska[j] = a, skb[j] = b;
+    }
+    __syncthreads();
+    float ka[CB], kb[CB];
+#pragma unroll
+    for (int j = 0; j < CB; ++j) ka[j] = ska[j], kb[j] = skb[j];
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    if (CB == 2 && mode == kIdxVox4) {
+        if constexpr (CB == 2) {
+            const IdxVox4Plan plan(n, vox);
+            for (int64_t i = tid; i < plan.items; i += nth) {
+                if (i < plan.groups) {
+                    const int64_t v0 = plan.head + i * 4;
+                    float z[8];
+                    idx_ld8(zn + v0 * 2, z);
+                    const uint32_t lw = *reinterpret_cast<const uint32_t*>(ln + v0);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float p[2] = {z[2 * k], z[2 * k + 1]};
+                        softmax_inplace<2>(p);
+                        idx_grad<2>(p, (lw >> (8 * k)) & 0xffu, ka, kb);
+                        z[2 * k] = p[0], z[2 * k + 1] = p[1];
+                    }
+                    idx_st8(dn + v0 * 2, z);
+                } else {
+                    const int64_t v = plan.single(i);
+                    float p[2] = {ldf(zn + v * 2), ldf(zn + v * 2 + 1)};
+                    softmax_inplace<2>(p);
+                    idx_grad<2>(p, ln[v], ka, kb);
+                    stf(dn + v * 2, p[0]);
+                    stf(dn + v * 2 + 1, p[1]);
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll 1      // one voxel's CB registers at a time: unrolled, the 32-class body does not fit the register file
+    for (int64_t v = tid; v < vox; v += nth) {
+        float p[CB];
+        idx_load_row<T, CB>(zn + v * x_ld, C, mode, p);
+        softmax_inplace<CB>(p);
+        idx_grad<CB>(p, ln[v], ka, kb);
+        T* d = dn + v * x_ld;
+        bool stored = false;
+        if constexpr (CB >= 4) {
+            if (mode == kIdxRows4) {
+#pragma unroll
+                for (int j = 0; j < CB; j += 4)
+                    if (j < C) stf4(d + j, make_float4(p[j], p[j + 1], p[j + 2], p[j + 3]));
+                stored = true;
+            }
+        }
+        if (!stored) {
+#pragma unroll
+            for (int j = 0; j < CB; ++j)
+                if (j < C) stf(d + j, p[j]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ arg-max
 template <typename T>
 __global__ void __launch_bounds__(256)
 argmax_u8_kernel(const T* __restrict__ logits, uint8_t* __restrict__ out, int64_t nvox, int C, int ld) {
@@ -165,92 +408,57 @@ argmax_u8_kernel(const T* __restrict__ logits, uint8_t* __restrict__ out, int64_
     }
 }
 
-// ------------------------------------------------------------------ mask overlap counts (validation metrics)
-// validate_dsc_asd scores the arg-max mask against the label map on the host (segmentation/routine.py:198-235,
-// metrics.py:312-329): Dice = 2*sum(gt & pred) / (sum(gt) + sum(pred)), IoU = #(pred>0 and gt>0) / #(pred>0 or gt>0).
-// All five sums are integers, so they are taken on the device in one pass over the two uint8 masks (16 voxels per lane
-// per load) and only 40 bytes leave the GPU instead of two volumes; integer addition is order-independent => exact.
-//   out[0] = sum(gt)  out[1] = sum(pred)  out[2] = sum(gt & pred)  out[3] = #(gt>0 & pred>0)  out[4] = #(gt>0 | pred>0)
-constexpr int kOvlBlocks = 512;
-
-__device__ __forceinline__ void ovl_acc(unsigned g, unsigned p, unsigned long long (&c)[5]) {
-    c[0] += g;
-    c[1] += p;
-    c[2] += g & p;
-    c[3] += (g != 0u && p != 0u) ? 1u : 0u;
-    c[4] += (g != 0u || p != 0u) ? 1u : 0u;
+// ------------------------------------------------------------------ host side of both Dice forms
+// forward: a lane takes about 4 items, and all samples together at most `cap` blocks
+static int dice_fwd_blocks(int64_t items, int n, int cap) {
+    const int64_t want = cdiv64(items, 256 * 4);
+    return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap / n));
 }
 
-__global__ void __launch_bounds__(256)
-mask_overlap_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ gt, int64_t n, int vec,
-                    unsigned long long* __restrict__ part) {
-    __shared__ unsigned long long red[4][5];
-    unsigned long long c[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    int64_t done = 0;
-    if (vec) {
-        const int64_t n16 = n >> 4;
-        const uint4* p4 = reinterpret_cast<const uint4*>(pred);
-        const uint4* g4 = reinterpret_cast<const uint4*>(gt);
-        for (int64_t i = tid; i < n16; i += nth) {
-            const uint4 pv = p4[i], gv = g4[i];
-            const unsigned pw[4] = {pv.x, pv.y, pv.z, pv.w}, gw[4] = {gv.x, gv.y, gv.z, gv.w};
-#pragma unroll
-            for (int w = 0; w < 4; ++w)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) ovl_acc((gw[w] >> (8 * b)) & 0xffu, (pw[w] >> (8 * b)) & 0xffu, c);
-        }
-        done = n16 << 4;
-    }
-    for (int64_t i = done + tid; i < n; i += nth) ovl_acc(gt[i], pred[i], c);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        unsigned long long v = c[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5)
-        part[(size_t)blockIdx.x * 5 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+// backward: one item per lane up to the stream cap, and at most 4096 blocks over all samples
+static int dice_bwd_blocks(int64_t items, int n) {
+    int64_t b = stream_grid(items, 256);
+    if (b * n > 4096) b = std::max(4096 / n, 1);
+    return (int)b;
 }
 
-__global__ void mask_overlap_finalize_kernel(const unsigned long long* __restrict__ part, int nblk, int64_t* __restrict__ out) {
-    const int k = threadIdx.x;
-    if (k >= 5) return;
-    unsigned long long s = 0ull;
-    for (int b = 0; b < nblk; ++b) s += part[(size_t)b * 5 + k];
-    out[k] = (int64_t)s;
+static size_t dice_ws_bytes(int cap, int n, int c) { return ((size_t)cap + (size_t)n) * c * 3 * sizeof(double); }
+
+// what the two geometries have in common: Geom is Mri3dDiceGeom or Mri3dDiceIndexGeom
+template <typename Geom> static int dice_check(const Geom* g, const char* who, int cmax) {
+    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
+    MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
+    MRI3D_REQUIRE(g->n > 0 && g->vox > 0, MRI3D_EINVAL, "%s: empty tensor", who);
+    MRI3D_REQUIRE(g->c >= kIdxMinC && g->c <= cmax, MRI3D_ENOTSUP, "%s: classes must be in [%d,%d], got %d", who, kIdxMinC, cmax, g->c);
+    MRI3D_REQUIRE(g->x_ld >= g->c, MRI3D_EINVAL, "%s: pitch %d < classes %d", who, g->x_ld, g->c);
+    return MRI3D_OK;
 }
 
-static int dice_blocks(const Mri3dDiceGeom& g) {
-    int64_t want = cdiv64(g.vox, 256 * 4);
-    int cap = kDiceMaxBlocks / g.n;
-    if (cap < 1) cap = 1;
-    int b = (int)(want < cap ? want : cap);
-    return b < 1 ? 1 : b;
+static int dice_float_check(const Mri3dDiceGeom* g, const char* who) {
+    int rc = dice_check(g, who, kDiceMaxC);
+    if (rc) return rc;
+    MRI3D_REQUIRE(g->ct == 1 || g->ct == g->c, MRI3D_EINVAL, "%s: target channels %d must be 1 or %d", who, g->ct, g->c);
+    MRI3D_REQUIRE(g->t_ld >= g->ct, MRI3D_EINVAL, "%s: target pitch %d < target channels %d", who, g->t_ld, g->ct);
+    return MRI3D_OK;
 }
+
+static int dice_finalize(const char* who, const double* part, float* stats, float* loss, int n, int c, int nblk, float eps,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, part, stats, loss, n, c, nblk, eps);
+    return check_launch(who);
+}
+
+static int idx_mode(const Mri3dDiceIndexGeom& g, const void* logits, const void* labels, const void* dlogits = nullptr) {
+    if (g.c == 2 && g.x_ld == 2 && aligned16(logits, dlogits) && (reinterpret_cast<uintptr_t>(labels) & 3) == 0) return kIdxVox4;
+    if (g.c % 4 == 0 && g.x_ld % 4 == 0 && aligned_vec4(g.dtype, logits, dlogits)) return kIdxRows4;
+    return kIdxScalar;
+}
+// work items of one sample: voxels, or the 4-voxel path's groups and (at most 6) single voxels
+static int64_t idx_items(const Mri3dDiceIndexGeom& g, int mode) { return mode == kIdxVox4 ? g.vox / 4 + 6 : g.vox; }
 
 }  // namespace mri3d
 
 using namespace mri3d;
-
-static int dice_check(const Mri3dDiceGeom* g, const char* who) {
-    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
-    MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
-    MRI3D_REQUIRE(g->n > 0 && g->vox > 0, MRI3D_EINVAL, "%s: empty tensor", who);
-    MRI3D_REQUIRE(g->c >= 2 && g->c <= kDiceMaxC, MRI3D_ENOTSUP, "%s: classes must be in [2,%d], got %d", who, kDiceMaxC,
-                  g->c);
-    MRI3D_REQUIRE(g->ct == 1 || g->ct == g->c, MRI3D_EINVAL, "%s: target channels %d must be 1 or %d", who, g->ct, g->c);
-    MRI3D_REQUIRE(g->x_ld >= g->c && g->t_ld >= g->ct, MRI3D_EINVAL, "%s: bad pitch", who);
-    return MRI3D_OK;
-}
-
-extern "C" size_t mri3d_softmax_dice_workspace_bytes(const Mri3dDiceGeom* g) {
-    if (!g) return 0;
-    return (size_t)(kDiceMaxBlocks + g->n) * g->c * 3 * sizeof(double);
-}
 
 #define DICE_DISPATCH(CALL)                 \
     switch (g->c) {                         \
@@ -263,33 +471,44 @@ extern "C" size_t mri3d_softmax_dice_workspace_bytes(const Mri3dDiceGeom* g) {
         default: CALL(8); break;            \
     }
 
+#define IDX_DISPATCH(CALL)           \
+    do {                             \
+        if (g->c <= 2) CALL(2);      \
+        else if (g->c <= 4) CALL(4); \
+        else if (g->c <= 8) CALL(8); \
+        else if (g->c <= 16) CALL(16); \
+        else CALL(32);               \
+    } while (0)
+
+extern "C" size_t mri3d_softmax_dice_workspace_bytes(const Mri3dDiceGeom* g) {
+    return g ? dice_ws_bytes(kDiceMaxBlocks, g->n, g->c) : 0;
+}
+
 extern "C" int mri3d_softmax_dice_fwd(const Mri3dDiceGeom* g, const void* logits, const void* target, float* loss,
                                       float* stats, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
-    int rc = dice_check(g, "softmax_dice_fwd");
+    int rc = dice_float_check(g, "softmax_dice_fwd");
     if (rc) return rc;
     MRI3D_REQUIRE(logits && target && loss && stats, MRI3D_EINVAL, "softmax_dice_fwd: null pointer");
-    MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_softmax_dice_workspace_bytes(g), MRI3D_EWORKSPACE,
-                  "softmax_dice_fwd: workspace %zu < %zu", ws_bytes, mri3d_softmax_dice_workspace_bytes(g));
+    rc = ws_check8("softmax_dice_fwd", workspace, ws_bytes, mri3d_softmax_dice_workspace_bytes(g));
+    if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int nblk = dice_blocks(*g);
+    const int nblk = dice_fwd_blocks(g->vox, g->n, kDiceMaxBlocks);
     double* part = static_cast<double*>(workspace);
 #define CALL(CC)                                                                                              \
     hipLaunchKernelGGL((dice_fwd_kernel<T, CC>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits,         \
                        (const float*)target, part, g->vox, g->ct, g->x_ld, g->t_ld)
     MRI3D_DISPATCH_DTYPE(g->dtype, T, { DICE_DISPATCH(CALL) });
 #undef CALL
-    dice_finalize(part, stats, loss, g->n, g->c, nblk, g->eps, s);
-    return check_launch("softmax_dice_fwd");
+    return dice_finalize("softmax_dice_fwd", part, stats, loss, g->n, g->c, nblk, g->eps, s);
 }
 
 extern "C" int mri3d_softmax_dice_bwd(const Mri3dDiceGeom* g, const void* logits, const void* target,
                                       const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream) {
-    int rc = dice_check(g, "softmax_dice_bwd");
+    int rc = dice_float_check(g, "softmax_dice_bwd");
     if (rc) return rc;
     MRI3D_REQUIRE(logits && target && stats && dloss && dlogits, MRI3D_EINVAL, "softmax_dice_bwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int nblk = stream_grid(g->vox, 256);
-    if (nblk * g->n > 4096) nblk = 4096 / g->n > 0 ? 4096 / g->n : 1;
+    const int nblk = dice_bwd_blocks(g->vox, g->n);
 #define CALL(CC)                                                                                              \
     hipLaunchKernelGGL((dice_bwd_kernel<T, CC>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits,         \
                        (const float*)target, stats, dloss, (T*)dlogits, g->vox, g->n, g->ct, g->x_ld,        \
@@ -297,6 +516,46 @@ extern "C" int mri3d_softmax_dice_bwd(const Mri3dDiceGeom* g, const void* logits
     MRI3D_DISPATCH_DTYPE(g->dtype, T, { DICE_DISPATCH(CALL) });
 #undef CALL
     return check_launch("softmax_dice_bwd");
+}
+
+extern "C" size_t mri3d_softmax_dice_index_workspace_bytes(const Mri3dDiceIndexGeom* g) {
+    if (!g || g->n <= 0 || g->c < kIdxMinC || g->c > kIdxMaxC) return 0;
+    return dice_ws_bytes(kIdxMaxBlocks, g->n, g->c);
+}
+
+extern "C" int mri3d_softmax_dice_index_fwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels, float* loss,
+                                            float* stats, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
+    int rc = dice_check(g, "softmax_dice_index_fwd", kIdxMaxC);
+    if (rc) return rc;
+    MRI3D_REQUIRE(logits && labels && loss && stats, MRI3D_EINVAL, "softmax_dice_index_fwd: null pointer");
+    rc = ws_check8("softmax_dice_index_fwd", workspace, ws_bytes, mri3d_softmax_dice_index_workspace_bytes(g));
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int mode = idx_mode(*g, logits, labels);
+    const int nblk = dice_fwd_blocks(idx_items(*g, mode), g->n, kIdxMaxBlocks);
+    double* part = static_cast<double*>(workspace);
+#define CALL(CB)                                                                                                    \
+    hipLaunchKernelGGL((dice_index_fwd_kernel<T, CB>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits, labels, \
+                       part, g->vox, g->c, g->x_ld, mode)
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(CALL); });
+#undef CALL
+    return dice_finalize("softmax_dice_index_fwd", part, stats, loss, g->n, g->c, nblk, g->eps, s);
+}
+
+extern "C" int mri3d_softmax_dice_index_bwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels,
+                                            const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream) {
+    int rc = dice_check(g, "softmax_dice_index_bwd", kIdxMaxC);
+    if (rc) return rc;
+    MRI3D_REQUIRE(logits && labels && stats && dloss && dlogits, MRI3D_EINVAL, "softmax_dice_index_bwd: null pointer");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int mode = idx_mode(*g, logits, labels, dlogits);
+    const int nblk = dice_bwd_blocks(idx_items(*g, mode), g->n);
+#define CALL(CB)                                                                                                    \
+    hipLaunchKernelGGL((dice_index_bwd_kernel<T, CB>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits, labels, \
+                       stats, dloss, (T*)dlogits, g->vox, g->n, g->c, g->x_ld, mode, g->eps)
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(CALL); });
+#undef CALL
+    return check_launch("softmax_dice_index_bwd");
 }
 
 extern "C" int mri3d_argmax_u8(const void* logits, uint8_t* out, int64_t nvox, int32_t c, int32_t ld, int32_t dtype,
@@ -309,22 +568,4 @@ extern "C" int mri3d_argmax_u8(const void* logits, uint8_t* out, int64_t nvox, i
                            ld);
     });
     return check_launch("argmax_u8");
-}
-
-extern "C" size_t mri3d_mask_overlap_workspace_bytes(void) { return (size_t)kOvlBlocks * 5 * sizeof(unsigned long long); }
-
-extern "C" int mri3d_mask_overlap(const uint8_t* pred, const uint8_t* gt, int64_t nvox, int64_t* counts, void* workspace,
-                                  size_t ws_bytes, mri3d_stream_t stream) {
-    MRI3D_REQUIRE(pred && gt && counts && nvox > 0, MRI3D_EINVAL, "mask_overlap: bad arguments");
-    MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_mask_overlap_workspace_bytes() &&
-                      (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-                  MRI3D_EWORKSPACE, "mask_overlap: workspace %zu < %zu", ws_bytes, mri3d_mask_overlap_workspace_bytes());
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int vec = ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(gt)) & 15) == 0 ? 1 : 0;
-    int nblk = (int)std::min<int64_t>(kOvlBlocks, cdiv64(nvox, 256 * 16));
-    if (nblk < 1) nblk = 1;
-    unsigned long long* part = static_cast<unsigned long long*>(workspace);
-    hipLaunchKernelGGL(mask_overlap_kernel, dim3(nblk), dim3(256), 0, s, pred, gt, nvox, vec, part);
-    hipLaunchKernelGGL(mask_overlap_finalize_kernel, dim3(1), dim3(64), 0, s, part, nblk, counts);
-    return check_launch("mask_overlap");
 }

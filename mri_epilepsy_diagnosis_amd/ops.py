@@ -1741,42 +1741,50 @@ def upsample_conv3d(x, scale, weight, bias=None, padding=0):
 
 
 class _SoftmaxDiceFn(torch.autograd.Function):
+    """Both softmax-Dice forms.  `form` = (geometry, query, fwd, bwd): geometry(logits, target, eps) checks the pair and returns it
+    as the kernels read it, with the C geometry; the other three name the workspace query and the two passes."""
+
     @staticmethod
-    def forward(ctx, logits, target, eps):
-        _require_device(logits)
-        _require_param(target)
+    def forward(ctx, logits, target, eps, form):
+        geometry, query, fwd, bwd = form
+        logits, target, g = geometry(logits, target, eps)
         L = _lib.lib()
-        logits = _cl(logits)
-        target = _cl(target)
-        n, c, d, h, w = logits.shape
-        ct = target.shape[1]
-        if tuple(target.shape) != (n, ct, d, h, w) or ct not in (1, c):
-            raise RuntimeError("softmax_dice_loss: target shape %s incompatible with logits %s"
-                               % (tuple(target.shape), tuple(logits.shape)))
-        g = DiceGeom(n, d * h * w, c, ct, c, ct, float(eps), _dt(logits))
+        n, c = logits.shape[:2]
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         stats = torch.empty(n * c * 3, dtype=torch.float32, device=logits.device)
-        ws = _workspace(L.mri3d_softmax_dice_workspace_bytes(ctypes.byref(g)), logits.device)
-        check(L.mri3d_softmax_dice_fwd(ctypes.byref(g), _ptr(logits), _ptr(target), _ptr(loss), _ptr(stats), _ptr(ws),
-                                       ws.numel(), _stream()), "softmax_dice_fwd")
+        ws = _workspace(getattr(L, query)(ctypes.byref(g)), logits.device)
+        check(getattr(L, fwd)(ctypes.byref(g), _ptr(logits), _ptr(target), _ptr(loss), _ptr(stats), _ptr(ws), ws.numel(), _stream()),
+              fwd[len("mri3d_"):])
         ctx.save_for_backward(logits, target, stats)
-        ctx.geom = g
+        ctx.geom, ctx.bwd = g, bwd
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        L = _lib.lib()
         logits, target, stats = ctx.saved_tensors
         dloss = dloss.to(torch.float32).contiguous()
         dlogits = _new(logits.shape, logits)
-        check(L.mri3d_softmax_dice_bwd(ctypes.byref(ctx.geom), _ptr(logits), _ptr(target), _ptr(stats), _ptr(dloss),
-                                       _ptr(dlogits), _stream()), "softmax_dice_bwd")
-        return dlogits, None, None
+        check(getattr(_lib.lib(), ctx.bwd)(ctypes.byref(ctx.geom), _ptr(logits), _ptr(target), _ptr(stats), _ptr(dloss), _ptr(dlogits),
+                                           _stream()), ctx.bwd[len("mri3d_"):])
+        return dlogits, None, None, None
+
+
+def _dice_float_geometry(logits, target, eps):
+    _require_device(logits)
+    _require_param(target)
+    logits, target = _cl(logits), _cl(target)
+    n, c, d, h, w = logits.shape
+    ct = target.shape[1]
+    if tuple(target.shape) != (n, ct, d, h, w) or ct not in (1, c):
+        raise RuntimeError("softmax_dice_loss: target shape %s incompatible with logits %s"
+                           % (tuple(target.shape), tuple(logits.shape)))
+    return logits, target, DiceGeom(n, d * h * w, c, ct, c, ct, float(eps), _dt(logits))
 
 
 def softmax_dice_loss(logits, target, eps=1e-9):
     """mean over (n, c) of 1 - dice(softmax(logits)[:, c], target) — segmentation/routine.py:272-274 in one kernel."""
-    return _SoftmaxDiceFn.apply(logits, target.to(torch.float32), eps)
+    return _SoftmaxDiceFn.apply(logits, target.to(torch.float32), eps, (_dice_float_geometry, "mri3d_softmax_dice_workspace_bytes",
+                                                                        "mri3d_softmax_dice_fwd", "mri3d_softmax_dice_bwd"))
 
 
 def argmax_mask(logits):
@@ -1858,19 +1866,29 @@ def mc_finalize(state, shape, samples, want=MC_OUTPUTS):
     return {k: out[k] for k in want}
 
 
+def _require_labels(who, *ts):
+    for t in ts:
+        if not t.is_cuda:
+            raise RuntimeError("%s runs only on ROCm device tensors (got %s); there is no CPU fallback" % (who, t.device))
+
+
+def _u8_pair(who, what, pred, gt):
+    """Two uint8 device maps of one shape, contiguous."""
+    for t in (pred, gt):
+        _require_labels(who, t)
+        if t.dtype != torch.uint8:
+            raise RuntimeError("%s: %s must be uint8, got %s" % (who, what, t.dtype))
+    if pred.shape != gt.shape:
+        raise RuntimeError("%s: shapes differ %s vs %s" % (who, tuple(pred.shape), tuple(gt.shape)))
+    return pred.contiguous(), gt.contiguous()
+
+
 def mask_overlap_counts(pred, gt):
     """Exact overlap counts of two uint8 masks on the device -> int64 tensor
     [sum(gt), sum(pred), sum(gt & pred), #(gt>0 & pred>0), #(gt>0 | pred>0)]  (validate_dsc_asd's Dice / IoU inputs,
     segmentation/routine.py:198-235, metrics.py:312-329)."""
-    for t in (pred, gt):
-        if not t.is_cuda:
-            raise RuntimeError("mask_overlap_counts runs only on ROCm device tensors (got %s); there is no CPU fallback" % t.device)
-        if t.dtype != torch.uint8:
-            raise RuntimeError("mask_overlap_counts: masks must be uint8, got %s" % t.dtype)
-    if pred.shape != gt.shape:
-        raise RuntimeError("mask_overlap_counts: shapes differ %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+    pred, gt = _u8_pair("mask_overlap_counts", "masks", pred, gt)
     L = _lib.lib()
-    pred, gt = pred.contiguous(), gt.contiguous()
     out = torch.empty(5, dtype=torch.int64, device=pred.device)
     ws = _workspace(L.mri3d_mask_overlap_workspace_bytes(), pred.device)
     check(L.mri3d_mask_overlap(_ptr(pred), _ptr(gt), pred.numel(), _ptr(out), _ptr(ws), ws.numel(), _stream()),
@@ -1893,12 +1911,6 @@ def dice_iou_from_counts(counts):
 # ----------------------------------------------------------------------------------------------- label maps (csrc/labels.hip)
 _LABEL_DTYPES = {torch.uint8: _lib.LABEL_U8, torch.int16: _lib.LABEL_I16, torch.int32: _lib.LABEL_I32,
                  torch.float32: _lib.LABEL_F32}
-
-
-def _require_labels(who, *ts):
-    for t in ts:
-        if not t.is_cuda:
-            raise RuntimeError("%s runs only on ROCm device tensors (got %s); there is no CPU fallback" % (who, t.device))
 
 
 def remap_labels(labels, lut, above=0, other=0, out_dtype=torch.uint8, out=None):
@@ -1925,60 +1937,33 @@ def remap_labels(labels, lut, above=0, other=0, out_dtype=torch.uint8, out=None)
     return out
 
 
-class _SoftmaxDiceIndexFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, labels, eps):
-        _require_device(logits)
-        _require_labels("softmax_dice_index_loss", labels)
-        if labels.dtype != torch.uint8:
-            raise RuntimeError("softmax_dice_index_loss: labels must be a uint8 class map, got %s" % labels.dtype)
-        L = _lib.lib()
-        logits = _cl(logits)
-        n, c, d, h, w = logits.shape
-        if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
-            raise RuntimeError("softmax_dice_index_loss: labels shape %s incompatible with logits %s"
-                               % (tuple(labels.shape), tuple(logits.shape)))
-        labels = labels.contiguous()
-        g = _lib.DiceIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits))
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        stats = torch.empty(n * c * 3, dtype=torch.float32, device=logits.device)
-        ws = _workspace(L.mri3d_softmax_dice_index_workspace_bytes(ctypes.byref(g)), logits.device)
-        check(L.mri3d_softmax_dice_index_fwd(ctypes.byref(g), _ptr(logits), _ptr(labels), _ptr(loss), _ptr(stats), _ptr(ws),
-                                             ws.numel(), _stream()), "softmax_dice_index_fwd")
-        ctx.save_for_backward(logits, labels, stats)
-        ctx.geom = g
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        L = _lib.lib()
-        logits, labels, stats = ctx.saved_tensors
-        dloss = dloss.to(torch.float32).contiguous()
-        dlogits = _new(logits.shape, logits)
-        check(L.mri3d_softmax_dice_index_bwd(ctypes.byref(ctx.geom), _ptr(logits), _ptr(labels), _ptr(stats), _ptr(dloss),
-                                             _ptr(dlogits), _stream()), "softmax_dice_index_bwd")
-        return dlogits, None, None
+def _dice_index_geometry(logits, labels, eps):
+    _require_device(logits)
+    _require_labels("softmax_dice_index_loss", labels)
+    if labels.dtype != torch.uint8:
+        raise RuntimeError("softmax_dice_index_loss: labels must be a uint8 class map, got %s" % labels.dtype)
+    logits = _cl(logits)
+    n, c, d, h, w = logits.shape
+    if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
+        raise RuntimeError("softmax_dice_index_loss: labels shape %s incompatible with logits %s"
+                           % (tuple(labels.shape), tuple(logits.shape)))
+    return logits, labels.contiguous(), _lib.DiceIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits))
 
 
 def softmax_dice_index_loss(logits, labels, eps=1e-9):
     """`softmax_dice_loss` with the target as a uint8 class map (N, 1, D, H, W) or (N, D, H, W) instead of float one-hot channels:
     mean over (n, c) of 1 - dice(softmax(logits)[:, c], labels == c), for 2..32 classes.  A label >= C belongs to no class (the
     voxel is ignored by every class's numerator and target sum).  One byte of target per voxel instead of 4*C."""
-    return _SoftmaxDiceIndexFn.apply(logits, labels, eps)
+    return _SoftmaxDiceFn.apply(logits, labels, eps, (_dice_index_geometry, "mri3d_softmax_dice_index_workspace_bytes",
+                                                      "mri3d_softmax_dice_index_fwd", "mri3d_softmax_dice_index_bwd"))
 
 
 def confusion_counts(pred, gt, classes):
     """Exact confusion counts of two uint8 class maps on the device: (conf, outside) with conf[g, p] = #(gt == g and pred == p), an
     int64 (C, C) device tensor, and outside = #(gt >= C or pred >= C), an int64 device scalar.  2 <= classes <= 32."""
-    _require_labels("confusion_counts", pred, gt)
-    for t in (pred, gt):
-        if t.dtype != torch.uint8:
-            raise RuntimeError("confusion_counts: class maps must be uint8, got %s" % t.dtype)
-    if pred.shape != gt.shape:
-        raise RuntimeError("confusion_counts: shapes differ %s vs %s" % (tuple(pred.shape), tuple(gt.shape)))
+    pred, gt = _u8_pair("confusion_counts", "class maps", pred, gt)
     L = _lib.lib()
     c = int(classes)
-    pred, gt = pred.contiguous(), gt.contiguous()
     out = torch.empty(max(c, 0) * max(c, 0) + 1, dtype=torch.int64, device=pred.device)
     ws = _workspace(L.mri3d_confusion_workspace_bytes(c), pred.device)
     check(L.mri3d_confusion_counts(_ptr(pred), _ptr(gt), pred.numel(), c, _ptr(out), _ptr(ws), ws.numel(), _stream()),

@@ -209,6 +209,16 @@ def test_dice_index_fwd_validation(what, kw, code):
     assert msg and b"softmax_dice_index_fwd" in msg, msg
 
 
+def test_dice_float_fwd_refuses_a_workspace_off_8_bytes():
+    """The float-target forward goes through the same workspace check: its partial sums are doubles too."""
+    L = _lib.lib()
+    g = _lib.DiceGeom(2, 315, 2, 1, 2, 1, 1e-9, _lib.F32)
+    need = L.mri3d_softmax_dice_workspace_bytes(ctypes.byref(g))
+    assert L.mri3d_softmax_dice_fwd(ctypes.byref(g), P(A), P(B), P(C_), P(C_ + 64), P(D + 4), need + 8, None) == EWORKSPACE
+    msg = L.mri3d_last_error()
+    assert msg and b"softmax_dice_fwd" in msg and b"8-byte aligned" in msg, msg
+
+
 @pytest.mark.parametrize("what,kw,code", BWD_BRANCHES, ids=[b[0] for b in BWD_BRANCHES])
 def test_dice_index_bwd_validation(what, kw, code):
     assert _bwd(**kw) == code, what

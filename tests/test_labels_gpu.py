@@ -1,5 +1,6 @@
-"""GPU suite of the label path (csrc/labels.hip): id remap, softmax-Dice against a class map, confusion counts, and their wiring
-through ops, segmentation/labels.py and segmentation/routine.py.
+"""GPU suite of the label path: id remap and confusion counts (csrc/labels.hip), softmax-Dice against a class map (csrc/loss.hip,
+beside the float-target form that tests/test_dice_gpu.py covers), and their wiring through ops, segmentation/labels.py and
+segmentation/routine.py.
 
 Remap and confusion counts are integer rules: exact equality with tests/labels_ref.py.
 
@@ -9,12 +10,12 @@ Index Dice is compared with labels_ref.dice_index_ref in float64, fed the same l
             case (tests/test_mc_gpu.py's convention: the factor covers the device's expf and another summation order); bf16
             storage adds 2^-8 |grad64| per element for the rounding of the stored gradient.
 
-Launch plan of the Dice kernels, as the cases below use it (labels.hip: idx_blocks_fwd, kIdxVox4): a block is 256 lanes, a sample
-gets min(ceil(items / 1024), 2048 / N) blocks in the forward, items = voxels, or 4-voxel groups plus single voxels for two dense
-classes.  5x7x9 = 315 voxels: one block, a partial first trip, and for C = 2 a head / tail of single voxels beside the groups
+Launch plan of the Dice kernels, as the cases below use it (loss.hip: dice_fwd_blocks with the class-map form's cap kIdxMaxBlocks,
+idx_items, kIdxVox4): a block is 256 lanes, a sample gets min(ceil(items / 1024), 2048 / N) blocks in the forward, items = voxels,
+or 4-voxel groups plus single voxels for two dense classes.  5x7x9 = 315 voxels: one block, a partial first trip, and for C = 2 a head / tail of single voxels beside the groups
 (sample 1 starts 315 = 3 mod 4 voxels into the batch).  7x11x37 = 2849 voxels: 3 blocks = 768 lanes, three whole trips and 545
 voxels more (C > 2); C = 2: 713 / 716 items on one block, two whole trips and 201 / 204 more.
-The backward has another plan (labels.hip: mri3d_softmax_dice_index_bwd): min(ceil(items / 256), 2048, 4096 / N) blocks per sample,
+The backward has another plan (loss.hip: dice_bwd_blocks): min(ceil(items / 256), 2048, 4096 / N) blocks per sample,
 one item per lane until the cap of 2048 blocks = 524 288 lanes, so only a sample of more than 524 288 items makes its loop go
 round, as every full-size volume does (160x192x160: 9.4 trips).  81x81x81 = 531 441 voxels: 2048 blocks, one whole trip and 7153
 voxels more (C > 2).  C = 2, 129x129x129 = 2 146 689 voxels: sample 0 has 536 672 groups + 1 single voxel = 536 673 items, one whole
@@ -27,6 +28,7 @@ import torch
 
 import labels_ref
 from guard import SentinelSlice, guarded, kernels_launched
+from loss_cases import labels_of as _labels, logits_of as _logits
 from mri_epilepsy_diagnosis_amd import _lib, ops, parallel
 from mri_epilepsy_diagnosis_amd.segmentation import labels as label_maps, routine
 from mri_epilepsy_diagnosis_amd.unet import UNet
@@ -185,25 +187,6 @@ def test_label_map_on_the_device():
 
 
 # ------------------------------------------------------------------------------------------------ index Dice
-def _labels(kind, C, spatial, seed):
-    g = torch.Generator().manual_seed(seed)
-    lab = torch.randint(0, C, (2,) + spatial, generator=g)
-    if kind == "ignored":                      # values that are no class, 255 among them
-        lab[torch.rand(lab.shape, generator=g) < 0.2] = C
-        lab[torch.rand(lab.shape, generator=g) < 0.1] = 255
-        lab[1, 0, 0, :2] = torch.tensor([C + 1 if C < 254 else 254, 255])
-    elif kind == "absent":                     # class C - 1 never occurs in sample 0, class 0 never in sample 1
-        lab[0][lab[0] == C - 1] = 0
-        lab[1][lab[1] == 0] = C - 1
-    elif kind == "single":                     # every voxel of sample 0 is class 1; sample 1 stays mixed
-        lab[0] = 1
-    return lab.to(torch.uint8)
-
-
-def _logits(C, spatial, dtype, seed):
-    return (3.0 * torch.randn(2, C, *spatial, generator=torch.Generator().manual_seed(seed))).to(dtype)
-
-
 def _ref_parts(z, lab):
     """float64 loss and gradient of the stored logits, and e32: how far torch's CPU float32 autograd is from that gradient."""
     l64, g64 = labels_ref.dice_index_ref(z, lab)
@@ -351,6 +334,18 @@ def test_index_dice_agrees_with_the_float_target_loss(C, dtype):
     onehot = labels_ref.one_hot(lab, C, F32).cuda().contiguous(memory_format=CL)
     a, b = ops.softmax_dice_index_loss(x, lab.cuda()).item(), ops.softmax_dice_loss(x, onehot).item()
     assert abs(a - b) / abs(b) <= 1e-5, (a, b)
+    if C == 2:
+        return
+    # Labels all in range, one block, no 4-voxel path: both forms run the shared softmax, block row, finalize and coefficients on
+    # the same numbers in the same order (a bucket's classes >= C add exact zeros), so loss and gradient agree bit for bit.
+    lab = _labels("mixed", C, SMALL, 1100 + C)
+    onehot = labels_ref.one_hot(lab, C, F32).cuda().contiguous(memory_format=CL)
+    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    la, lb = ops.softmax_dice_index_loss(xa, lab.cuda()), ops.softmax_dice_loss(xb, onehot)
+    la.backward(), lb.backward()
+    bits = torch.int16 if dtype == BF else torch.int32
+    assert torch.equal(la.detach().view(torch.int32), lb.detach().view(torch.int32)), (la.item(), lb.item())
+    assert torch.equal(xa.grad.view(bits), xb.grad.view(bits))
 
 
 @pytest.mark.parametrize("C", [1, 33])

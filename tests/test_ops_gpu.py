@@ -457,6 +457,15 @@ def test_mask_overlap_counts_dice_iou_exact():
     gt, pred = gt[3:], pred[3:]
     assert c.tolist() == [int(gt.sum(dtype=np.int64)), int(pred.sum(dtype=np.int64)), int((gt & pred).sum(dtype=np.int64)),
                           int(np.logical_and(gt > 0, pred > 0).sum()), int(np.logical_or(gt > 0, pred > 0).sum())]
+    # sizes around one 16-byte load and one block, views aligned, misaligned alike and misaligned differently
+    for n, po, go in ((1, 0, 0), (15, 0, 0), (16, 0, 0), (4097, 0, 0), (100003, 0, 0), (100003, 3, 3), (100003, 1, 2)):
+        rng = np.random.Generator(np.random.PCG64(11 * n + po))
+        gt = rng.integers(0, 256, size=n + go, dtype=np.uint8)
+        pred = rng.integers(0, 256, size=n + po, dtype=np.uint8)
+        c = ops.mask_overlap_counts(torch.from_numpy(pred).cuda()[po:], torch.from_numpy(gt).cuda()[go:])
+        gt, pred = gt[go:], pred[po:]
+        assert c.tolist() == [int(gt.sum(dtype=np.int64)), int(pred.sum(dtype=np.int64)), int((gt & pred).sum(dtype=np.int64)),
+                              int(np.logical_and(gt > 0, pred > 0).sum()), int(np.logical_or(gt > 0, pred > 0).sum())], (n, po, go)
     # full-size volume (BASELINE shape) against numpy
     gt, pred = O_MET.seeded_masks(77, (160, 192, 160), 0.1, 0.1, 0.9)
     dsc, iou = ops.dice_iou_from_counts(ops.mask_overlap_counts(torch.from_numpy(pred).cuda(), torch.from_numpy(gt).cuda()))
