@@ -177,6 +177,30 @@ size_t mri3d_convpair_workspace_bytes(const Mri3dConvGeom* first, const Mri3dCon
 int mri3d_convpair_wgrad_first(const Mri3dConvGeom* first, const Mri3dConvGeom* second, const void* x, const void* dy2, const float* w2,
                                float* dw1, float* dbias1, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
+/* THE NUMBERS OF THE LAUNCH PLAN of the two fused operators above: same geometry arguments and checks as the entry points, the
+ * same plan function the entry points launch by, host only (no device is needed, nothing is launched).  Fields a pass does not
+ * use are 0.
+ *   hch       upconv forward / weight gradient: rows of H per slab = min(ho, 1024 / wo), at least 1 (hch < ho: a slab is a part
+ *             of an (n, od) plane, the last part may be ragged)
+ *   grid      workgroups launched: min(slabs, 4096) forward, min(slabs, 1024) weight gradient, min(rows, 8192) data gradient,
+ *             min(ceil(rows / 4), 1024) pair; the kernels loop where there are more slabs / rows than that
+ *   gtrips    trips of that loop a workgroup makes at most: ceil(slabs / grid), ceil(rows / grid), pair: ceil(rows / (4 grid))
+ *   trips     upconv forward / weight gradient: trips of the 256-lane loop over the hch x wo voxels of a full slab
+ *   per       upconv data gradient: coarse voxels of a row per pass = 256 / scale^3
+ *   passes    upconv data gradient: passes per coarse row = ceil(wc / per); lanes past wc in the last pass are masked
+ *   chunks    pair: 64-voxel chunks of W a wave walks per row
+ *   slabs     upconv forward / weight gradient: n x dout x ceil(ho / hch)
+ *   rows      upconv data gradient: coarse rows n x dc x hc; pair: rows (n, d1, h) of the first convolution's output
+ * pass: MRI3D_PASS_FWD / _DGRAD / _WGRAD (anything else: MRI3D_EINVAL).  Both return MRI3D_OK or the error the entry point gives
+ * for the geometry (MRI3D_ENOTSUP where mri3d_upconv3d_supported / mri3d_convpair_supported is 0); g / first / second and out
+ * must not be NULL. */
+typedef struct Mri3dFusedConvPlanInfo {
+    int32_t hch, grid, gtrips, trips, per, passes, chunks;
+    int64_t slabs, rows;
+} Mri3dFusedConvPlanInfo;
+int32_t mri3d_upconv3d_plan_query(const Mri3dConvGeom* g, int32_t scale, int32_t pass, Mri3dFusedConvPlanInfo* out);
+int32_t mri3d_convpair_plan_query(const Mri3dConvGeom* first, const Mri3dConvGeom* second, Mri3dFusedConvPlanInfo* out);
+
 /* ------------------------------------------------------------------------------------------------
  * BatchNorm3d / InstanceNorm3d fused with the following activation — replaces
  * nn.BatchNorm3d + nn.PReLU (unet.UNet ConvolutionalBlock), nn.BatchNorm3d + LeakyReLU/ReLU

@@ -40,6 +40,11 @@ class ResamplePlanInfo(Structure):
                                        "tables")] + [("lds_bytes", c_int64)]
 
 
+class FusedConvPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("hch", "grid", "gtrips", "trips", "per", "passes", "chunks")] + \
+               [("slabs", c_int64), ("rows", c_int64)]
+
+
 class PoolGeom(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "di", "hi", "wi", "dout", "ho", "wo", "c", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph", "pw",
@@ -92,6 +97,8 @@ SIGNATURES = {
     "mri3d_convpair_supported": (c_int32, [POINTER(ConvGeom), POINTER(ConvGeom)]),
     "mri3d_convpair_workspace_bytes": (c_size_t, [POINTER(ConvGeom), POINTER(ConvGeom)]),
     "mri3d_convpair_wgrad_first": (c_int32, [POINTER(ConvGeom), POINTER(ConvGeom), _P, _P, _FP, _FP, _FP, _P, c_size_t, _P]),
+    "mri3d_upconv3d_plan_query": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, POINTER(FusedConvPlanInfo)]),
+    "mri3d_convpair_plan_query": (c_int32, [POINTER(ConvGeom), POINTER(ConvGeom), POINTER(FusedConvPlanInfo)]),
     "mri3d_norm_workspace_bytes": (c_size_t, [POINTER(NormGeom)]),
     "mri3d_norm_plan_query": (c_int32, [POINTER(NormGeom), c_int32, c_int32, POINTER(NormPlanInfo)]),
     "mri3d_norm_stats": (c_int32, [POINTER(NormGeom), _P, _FP, _FP, _FP, _FP, c_float, _P, c_size_t, _P]),

@@ -149,9 +149,34 @@ static bool convpair_ok(const Mri3dConvGeom& a, const Mri3dConvGeom& b) {
            (a.dtype == MRI3D_F32 || a.dtype == MRI3D_BF16) && a.n > 0;
 }
 
+// The numbers the launch goes by: the one place they are formed, read by the entry point and by mri3d_convpair_plan_query alike.
+// A wave takes one (n, d1, h) row at a time (four per workgroup trip) and walks it in chunks of 64 voxels of W.
+struct ConvPairPlan {
+    int64_t rows;
+    int grid, gtrips, chunks;
+};
+
+static ConvPairPlan convpair_plan(const Mri3dConvGeom& a) {
+    ConvPairPlan p;
+    p.rows = (int64_t)a.n * a.dout * a.ho;   // (n, d1, h)
+    p.grid = (int)std::min<int64_t>(cdiv64(p.rows, 4), kCpBlocks);
+    p.gtrips = p.grid > 0 ? (int)cdiv64(p.rows, 4 * (int64_t)p.grid) : 0;
+    p.chunks = (a.wi + 63) >> 6;
+    return p;
+}
+
 }  // namespace mri3d
 
 using namespace mri3d;
+
+extern "C" int32_t mri3d_convpair_plan_query(const Mri3dConvGeom* first, const Mri3dConvGeom* second, Mri3dFusedConvPlanInfo* out) {
+    MRI3D_REQUIRE(first && second && out, MRI3D_EINVAL, "convpair_plan_query: null pointer");
+    MRI3D_REQUIRE(convpair_ok(*first, *second), MRI3D_ENOTSUP, "convpair_plan_query: geometry not served (see mri3d_convpair_supported)");
+    const ConvPairPlan p = convpair_plan(*first);
+    MRI3D_REQUIRE(p.rows < 0x7ffffff0, MRI3D_ENOTSUP, "convpair_plan_query: too many rows");
+    *out = Mri3dFusedConvPlanInfo{0, p.grid, p.gtrips, 0, 0, 0, p.chunks, 0, p.rows};
+    return MRI3D_OK;
+}
 
 extern "C" int32_t mri3d_convpair_supported(const Mri3dConvGeom* first, const Mri3dConvGeom* second) {
     return first && second && convpair_ok(*first, *second) ? 1 : 0;
@@ -172,9 +197,9 @@ extern "C" int mri3d_convpair_wgrad_first(const Mri3dConvGeom* first, const Mri3
     MRI3D_REQUIRE(aligned_vec4(first->dtype, dy2), MRI3D_EINVAL, "convpair_wgrad_first: dy2 must be aligned to four channels");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const Mri3dConvGeom &a = *first, &b = *second;
-    const int64_t rows = (int64_t)a.n * a.dout * a.ho;   // (n, d1, h)
-    MRI3D_REQUIRE(rows < 0x7ffffff0, MRI3D_ENOTSUP, "convpair_wgrad_first: too many rows");
-    const int nb = (int)std::min<int64_t>(cdiv64(rows, 4), kCpBlocks);
+    const ConvPairPlan plan = convpair_plan(a);
+    MRI3D_REQUIRE(plan.rows < 0x7ffffff0, MRI3D_ENOTSUP, "convpair_wgrad_first: too many rows");
+    const int nb = plan.grid;
     float* part = static_cast<float*>(workspace);
     MRI3D_DISPATCH_DTYPE(a.dtype, T, {
         hipLaunchKernelGGL((convpair_wgrad_first_kernel<T, 8, 8, 6, 3>), dim3(nb), dim3(256), 0, s, (const T*)x, (const T*)dy2, w2, part, a.n,

@@ -291,9 +291,45 @@ static bool upconv_ok(const Mri3dConvGeom& g, int S) {
 
 static int upconv_hch(const Mri3dConvGeom& g) { return std::max(1, std::min(g.ho, 1024 / std::max(g.wo, 1))); }
 
+// The numbers a pass launches by: the one place they are formed, read by the entry points and by mri3d_upconv3d_plan_query alike.
+// Forward and weight gradient walk slabs (hch rows of H of one (n, od) plane, the last of a plane may be ragged), the data gradient
+// walks coarse rows (n, cd, ch) and takes `per` coarse voxels of a row per pass.
+struct UpConvPlan {
+    int hch = 0, grid = 0, gtrips = 0, trips = 0, per = 0, passes = 0;
+    int64_t slabs = 0, rows = 0;
+};
+
+static UpConvPlan upconv_plan(const Mri3dConvGeom& g, int S, int pass) {
+    UpConvPlan p;
+    if (pass == MRI3D_PASS_DGRAD) {
+        p.rows = (int64_t)g.n * (g.di / S) * (g.hi / S);
+        p.grid = (int)std::min<int64_t>(p.rows, 256 * 32);
+        p.per = 256 / (S * S * S);
+        p.passes = cdiv(g.wi / S, p.per);
+    } else {
+        p.hch = upconv_hch(g);
+        p.slabs = (int64_t)g.n * g.dout * cdiv(g.ho, p.hch);
+        p.grid = (int)std::min<int64_t>(p.slabs, pass == MRI3D_PASS_FWD ? 256 * 16 : kUcBlocks);
+        p.trips = (int)cdiv64((int64_t)std::min(p.hch, g.ho) * g.wo, 256);
+    }
+    p.gtrips = p.grid > 0 ? (int)cdiv64(std::max(p.slabs, p.rows), p.grid) : 0;
+    return p;
+}
+
 }  // namespace mri3d
 
 using namespace mri3d;
+
+extern "C" int32_t mri3d_upconv3d_plan_query(const Mri3dConvGeom* g, int32_t scale, int32_t pass, Mri3dFusedConvPlanInfo* out) {
+    MRI3D_REQUIRE(g && out, MRI3D_EINVAL, "upconv3d_plan_query: null pointer");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD || pass == MRI3D_PASS_WGRAD, MRI3D_EINVAL,
+                  "upconv3d_plan_query: pass %d", pass);
+    MRI3D_REQUIRE(upconv_ok(*g, scale), MRI3D_ENOTSUP, "upconv3d_plan_query: geometry not served (see mri3d_upconv3d_supported)");
+    const UpConvPlan p = upconv_plan(*g, scale, pass);
+    MRI3D_REQUIRE(p.rows <= 0x7fffffff, MRI3D_ENOTSUP, "upconv3d_plan_query: too many coarse rows");
+    *out = Mri3dFusedConvPlanInfo{p.hch, p.grid, p.gtrips, p.trips, p.per, p.passes, 0, p.slabs, p.rows};
+    return MRI3D_OK;
+}
 
 extern "C" int32_t mri3d_upconv3d_supported(const Mri3dConvGeom* g, int32_t scale) { return g != nullptr && upconv_ok(*g, scale) ? 1 : 0; }
 
@@ -308,9 +344,8 @@ extern "C" int mri3d_upconv3d_fwd(const Mri3dConvGeom* g, int32_t scale, const v
     MRI3D_REQUIRE(upconv_ok(*g, scale), MRI3D_ENOTSUP, "upconv3d_fwd: geometry not served (see mri3d_upconv3d_supported)");
     MRI3D_REQUIRE(aligned_vec4(g->dtype, x), MRI3D_EINVAL, "upconv3d_fwd: x must be aligned to four channels");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int hch = upconv_hch(*g);
-    const int64_t slabs = (int64_t)g->n * g->dout * cdiv(g->ho, hch);
-    const int grid = (int)std::min<int64_t>(slabs, 256 * 16);
+    const UpConvPlan plan = upconv_plan(*g, scale, MRI3D_PASS_FWD);
+    const int hch = plan.hch, grid = plan.grid;
     const int taps = g->kd * g->kh * g->kw;
     bool launched = false;
 #define MRI3D_UCF(Tv, CIv, COv, NTv)                                                                                    \
@@ -335,9 +370,10 @@ extern "C" int mri3d_upconv3d_dgrad(const Mri3dConvGeom* g, int32_t scale, const
     MRI3D_REQUIRE(upconv_ok(*g, scale), MRI3D_ENOTSUP, "upconv3d_dgrad: geometry not served (see mri3d_upconv3d_supported)");
     MRI3D_REQUIRE(aligned_vec4(g->dtype, dx), MRI3D_EINVAL, "upconv3d_dgrad: dx must be aligned to four channels");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t rows = (int64_t)g->n * (g->di / scale) * (g->hi / scale);
+    const UpConvPlan plan = upconv_plan(*g, scale, MRI3D_PASS_DGRAD);
+    const int64_t rows = plan.rows;
     MRI3D_REQUIRE(rows <= 0x7fffffff, MRI3D_ENOTSUP, "upconv3d_dgrad: too many coarse rows");
-    const int grid = (int)std::min<int64_t>(rows, 256 * 32);
+    const int grid = plan.grid;
     const int taps = g->kd * g->kh * g->kw;
     bool launched = false;
 #define MRI3D_UCD(Tv, CIv, COv, NTv)                                                                                    \
@@ -364,9 +400,8 @@ extern "C" int mri3d_upconv3d_wgrad(const Mri3dConvGeom* g, int32_t scale, const
     MRI3D_REQUIRE(workspace && ws_bytes >= mri3d_upconv3d_workspace_bytes(g, scale), MRI3D_EINVAL, "upconv3d_wgrad: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int taps = g->kd * g->kh * g->kw;
-    const int hch = upconv_hch(*g);
-    const int64_t slabs = (int64_t)g->n * g->dout * cdiv(g->ho, hch);
-    const int nb = (int)std::min<int64_t>(slabs, kUcBlocks);
+    const UpConvPlan plan = upconv_plan(*g, scale, MRI3D_PASS_WGRAD);
+    const int hch = plan.hch, nb = plan.grid;
     float* part = static_cast<float*>(workspace);
     bool launched = false;
 #define MRI3D_UCW(Tv, CIv, COv, NTv)                                                                                  \

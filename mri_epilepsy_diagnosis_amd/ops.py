@@ -411,6 +411,25 @@ def upsample_plan(g, pass_, align=16):
     return _resample_plan_dict(info)
 
 
+FUSEDCONV_PLAN_FIELDS = ("hch", "grid", "gtrips", "trips", "per", "passes", "chunks", "slabs", "rows")
+
+
+def upconv_plan(g, scale, pass_):
+    """Numbers of the launch plan of mri3d_upconv3d_fwd / _dgrad / _wgrad (PASS_FWD / PASS_DGRAD / PASS_WGRAD) for the ConvGeom `g`
+    on the virtual fine input and the scale, host only: a dict of the fields of Mri3dFusedConvPlanInfo (include/mri3d.h)."""
+    info = _lib.FusedConvPlanInfo()
+    check(_lib.lib().mri3d_upconv3d_plan_query(ctypes.byref(g), scale, pass_, ctypes.byref(info)), "upconv3d_plan_query")
+    return {f: int(getattr(info, f)) for f in FUSEDCONV_PLAN_FIELDS}
+
+
+def conv_pair_plan(first, second):
+    """Numbers of the launch plan of mri3d_convpair_wgrad_first for the two ConvGeoms, host only: a dict of the fields of
+    Mri3dFusedConvPlanInfo (include/mri3d.h)."""
+    info = _lib.FusedConvPlanInfo()
+    check(_lib.lib().mri3d_convpair_plan_query(ctypes.byref(first), ctypes.byref(second), ctypes.byref(info)), "convpair_plan_query")
+    return {f: int(getattr(info, f)) for f in FUSEDCONV_PLAN_FIELDS}
+
+
 def norm_plan(g, pass_, align=16):
     """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
     tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is

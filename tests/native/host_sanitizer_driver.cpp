@@ -361,6 +361,21 @@ int main() {
         Mri3dConvGeom s3 = second;
         s3.sh = 1; s3.ho = 191;   // six taps at stride 1 reach a row through six taps: more than the kernel's three slots
         EXPECT(mri3d_convpair_supported(&first, &s3) == 0);
+        // the plan queries: the entry points' checks, then the plan functions they launch by
+        Mri3dFusedConvPlanInfo fi;
+        for (int pass = 0; pass < 3; ++pass)
+            for (int scale : {2, 4}) {
+                EXPECT(mri3d_upconv3d_plan_query(&up, scale, pass, &fi) == MRI3D_OK && fi.grid > 0 && fi.gtrips > 0);
+                Mri3dConvGeom thin = up;
+                thin.hi = thin.ho = 4; thin.wi = thin.wo = 1028;
+                EXPECT(mri3d_upconv3d_plan_query(&thin, scale, pass, &fi) == MRI3D_OK && (pass == MRI3D_PASS_DGRAD || (fi.hch == 1 && fi.trips == 5)));
+            }
+        EXPECT(mri3d_upconv3d_plan_query(&up, 3, 0, &fi) == MRI3D_ENOTSUP && mri3d_upconv3d_plan_query(&bad2, 4, 0, &fi) == MRI3D_ENOTSUP);
+        EXPECT(mri3d_upconv3d_plan_query(&up, 4, 3, &fi) == MRI3D_EINVAL && mri3d_upconv3d_plan_query(nullptr, 4, 0, &fi) == MRI3D_EINVAL);
+        EXPECT(mri3d_upconv3d_plan_query(&up, 4, 0, nullptr) == MRI3D_EINVAL);
+        EXPECT(mri3d_convpair_plan_query(&first, &second, &fi) == MRI3D_OK && fi.rows == 4 * 80 * 192 && fi.grid == 1024 && fi.chunks == 3);
+        EXPECT(mri3d_convpair_plan_query(&first, &s3, &fi) == MRI3D_ENOTSUP && mri3d_convpair_plan_query(nullptr, &second, &fi) == MRI3D_EINVAL);
+        EXPECT(mri3d_convpair_plan_query(&first, &second, nullptr) == MRI3D_EINVAL);
     }
     {   // norm + activation and its two folds (pointwise head, max pool): every refusal below comes before a launch
         Mri3dNormGeom ng;

@@ -130,6 +130,54 @@ def test_resample_plan_queries_are_declared_bound_and_host_only():
     assert L.mri3d_maxpool3d_plan_query(ctypes.byref(pg), _lib.PASS_FWD, 0, 16, 16, None) == -1
 
 
+def test_fusedconv_plan_queries_are_declared_bound_and_host_only(tmp_path):
+    for name in ("mri3d_upconv3d_plan_query", "mri3d_convpair_plan_query"):
+        assert name in _declared() and name in _lib.SIGNATURES
+    fields = ["hch", "grid", "gtrips", "trips", "per", "passes", "chunks", "slabs", "rows"]
+    assert [f for f, _ in _lib.FusedConvPlanInfo._fields_] == fields
+    # the layout of the struct against the header, as test_struct_layouts_match_header does for the others
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mri3d.h"', 'int main(void){',
+             'printf("size %zu\\n", sizeof(Mri3dFusedConvPlanInfo));']
+    lines += ['printf("%s %%zu\\n", offsetof(Mri3dFusedConvPlanInfo, %s));' % (f, f) for f in fields] + ["return 0;}"]
+    (tmp_path / "layout.c").write_text("\n".join(lines))
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")], check=True)
+    out = dict(l.split() for l in subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout.splitlines())
+    assert int(out["size"]) == ctypes.sizeof(_lib.FusedConvPlanInfo)
+    for f in fields:
+        assert int(out[f]) == getattr(_lib.FusedConvPlanInfo, f).offset, f
+    L = _lib.lib()
+    info = _lib.FusedConvPlanInfo()
+
+    def nums(*names):
+        return tuple(getattr(info, f) for f in names)
+    # the shipped last UpBlock: Conv3d(8, 1, (3,1,1), padding (1,0,0)) over a 4x nearest upsampling of 4 x 40x48x40
+    up = _lib.ConvGeom(4, 160, 192, 160, 8, 160, 192, 160, 1, 3, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 8, 1, 0)
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 4, _lib.PASS_FWD, ctypes.byref(info)) == 0
+    assert nums(*fields) == (6, 4096, 5, 4, 0, 0, 0, 4 * 160 * 32, 0)           # slabs of 6 rows x 160: 960 voxels, 4 lane trips
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 4, _lib.PASS_WGRAD, ctypes.byref(info)) == 0
+    assert nums(*fields) == (6, 1024, 20, 4, 0, 0, 0, 4 * 160 * 32, 0)
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 4, _lib.PASS_DGRAD, ctypes.byref(info)) == 0
+    assert nums(*fields) == (0, 4 * 40 * 48, 1, 0, 4, 10, 0, 0, 4 * 40 * 48)
+    up2 = _lib.ConvGeom(4, 80, 96, 80, 8, 80, 96, 80, 1, 3, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 8, 1, 0)       # scale 2: 32 coarse voxels a pass
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up2), 2, _lib.PASS_DGRAD, ctypes.byref(info)) == 0
+    assert nums("grid", "gtrips", "per", "passes", "rows") == (7680, 1, 32, 2, 7680)
+    long_w = _lib.ConvGeom(1, 4, 4, 1028, 4, 4, 4, 1028, 1, 3, 1, 1, 1, 1, 1, 1, 0, 0, 1, 1, 1, 4, 1, 0)     # wo > 1024: one row, 5 trips
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(long_w), 4, _lib.PASS_FWD, ctypes.byref(info)) == 0
+    assert nums("hch", "trips", "slabs", "grid") == (1, 5, 16, 16)
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 3, _lib.PASS_FWD, ctypes.byref(info)) == -2        # as the entry points
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 4, 3, ctypes.byref(info)) == -1
+    assert L.mri3d_upconv3d_plan_query(None, 4, _lib.PASS_FWD, ctypes.byref(info)) == -1
+    assert L.mri3d_upconv3d_plan_query(ctypes.byref(up), 4, _lib.PASS_FWD, None) == -1
+    # the shipped first DownBlock on 4 x 160x192x160: 4 * 80 * 192 rows, four per workgroup trip, 3 chunks of W
+    first = _lib.ConvGeom(4, 160, 192, 160, 1, 80, 192, 160, 8, 6, 1, 1, 2, 1, 1, 2, 0, 0, 1, 1, 1, 1, 8, 0)
+    second = _lib.ConvGeom(4, 80, 192, 160, 8, 80, 96, 160, 8, 1, 6, 1, 1, 2, 1, 0, 2, 0, 1, 1, 1, 8, 8, 0)
+    assert L.mri3d_convpair_plan_query(ctypes.byref(first), ctypes.byref(second), ctypes.byref(info)) == 0
+    assert nums(*fields) == (0, 1024, 15, 0, 0, 0, 3, 0, 4 * 80 * 192)
+    assert L.mri3d_convpair_plan_query(ctypes.byref(second), ctypes.byref(first), ctypes.byref(info)) == -2
+    assert L.mri3d_convpair_plan_query(None, ctypes.byref(second), ctypes.byref(info)) == -1
+    assert L.mri3d_convpair_plan_query(ctypes.byref(first), ctypes.byref(second), None) == -1
+
+
 def test_host_code_is_clean_under_address_and_ub_sanitizers():
     """the library's HOST side (argument validation, plan / dispatch selection, workspace sizing, error strings)
     built with -fsanitize=address,undefined and driven without a GPU by tests/native/host_sanitizer_driver.cpp: > 100 000
