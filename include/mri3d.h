@@ -147,6 +147,28 @@ int mri3d_conv3d_fwd_march(const Mri3dConvGeom* g, const void* x, const void* x2
 int mri3d_conv3d_dgrad_march(const Mri3dConvGeom* g, const void* dy, const void* w, void* dx, void* dx2, int32_t split,
                              int32_t dx2_ld, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
+/* THE NUMBERS OF THE LAUNCH PLAN of the two entry points above: the same plan function they launch by, host only (no device is
+ * needed, nothing is launched).  Kc = input channels of the pass (forward ci, data gradient co), Nc = its output channels; the
+ * pitches of g are those the entry point gets (a split operand is queried as ONE tensor, x_ld >= ci, as the two queries above).
+ *   chunks        32-byte input-channel chunks = ceil(Kc / 8) fp32, ceil(Kc / 16) bf16 (at most 4)
+ *   blocks        16-channel output blocks = ceil(Nc / 16); one workgroup computes one block of one column segment
+ *   wgh, wgw      the 8 waves of a workgroup own wgh x wgw columns of 8 rows x 16 voxels (h x w)
+ *   gch, gcw      workgroup-columns along h and w
+ *   nseg, seglen  d segments and their length in planes (the last one may be shorter)
+ *   nbuf          LDS plane buffers per wave: 3 with one chunk (the DMA runs two items ahead), else 2 (one item ahead)
+ *   grid          workgroups = blocks x gcw x gch x nseg x n = the statistics blocks (mri3d_conv3d_march_stats_blocks)
+ *   whole_chunks  1 where Kc fills its last chunk (a single tensor of whole chunks takes the constant-offset DMA path)
+ *   dispatcher    1 where mri3d_conv3d_fwd / _dgrad / _fwd_stats would choose this kernel for the layer themselves
+ *   smem_bytes    dynamic LDS of the launch;  wp_bytes  packed-weight image in the workspace
+ * pass: MRI3D_PASS_FWD / _DGRAD; stats != 0: the forward with fused statistics (with the data gradient: MRI3D_EINVAL).  Returns
+ * MRI3D_ENOTSUP exactly where mri3d_conv3d_march_supported(g, pass) = 0 for a valid geometry, and with stats for more than 8 output
+ * blocks (mri3d_conv3d_march_stats_blocks = 0); MRI3D_EINVAL for NULL, an unknown pass or an inconsistent geometry. */
+typedef struct Mri3dMarchPlanInfo {
+    int32_t chunks, blocks, wgh, wgw, gch, gcw, nseg, seglen, nbuf, grid, whole_chunks, dispatcher;
+    int64_t smem_bytes, wp_bytes;
+} Mri3dMarchPlanInfo;
+int32_t mri3d_conv3d_march_plan_query(const Mri3dConvGeom* g, int32_t pass, int32_t stats, Mri3dMarchPlanInfo* out);
+
 /* Conv3d over a nearest-neighbour upsampled input that is never formed (csrc/upconv.hip):
  *     y = conv3d(upsample_nearest(x, scale_factor = scale), w, bias, stride 1, padding g->p*)
  * replaces nn.Upsample(scale_factor=4, mode='nearest') followed by the block's first nn.Conv3d in UpBlock

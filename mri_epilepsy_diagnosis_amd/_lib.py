@@ -45,6 +45,11 @@ class FusedConvPlanInfo(Structure):
                [("slabs", c_int64), ("rows", c_int64)]
 
 
+class MarchPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("chunks", "blocks", "wgh", "wgw", "gch", "gcw", "nseg", "seglen", "nbuf", "grid",
+                                       "whole_chunks", "dispatcher")] + [("smem_bytes", c_int64), ("wp_bytes", c_int64)]
+
+
 class PoolGeom(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "di", "hi", "wi", "dout", "ho", "wo", "c", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph", "pw",
@@ -87,6 +92,7 @@ SIGNATURES = {
     "mri3d_conv3d_wgrad_cat": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_march_supported": (c_int32, [POINTER(ConvGeom), c_int32]),
     "mri3d_conv3d_march_stats_blocks": (c_int32, [POINTER(ConvGeom)]),
+    "mri3d_conv3d_march_plan_query": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, POINTER(MarchPlanInfo)]),
     "mri3d_conv3d_fwd_march": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_dgrad_march": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, c_int32, c_int32, _P, c_size_t, _P]),
     "mri3d_upconv3d_supported": (c_int32, [POINTER(ConvGeom), c_int32]),

@@ -184,6 +184,20 @@ extern "C" int32_t mri3d_conv3d_march_stats_blocks(const Mri3dConvGeom* g) {
     return conv_march_needs(*g, false, true, true).grid;
 }
 
+// the numbers those entry points launch by: the same conv_march_plan(.., force = true, ..), host only
+extern "C" int32_t mri3d_conv3d_march_plan_query(const Mri3dConvGeom* g, int32_t pass, int32_t stats, Mri3dMarchPlanInfo* out) {
+    MRI3D_REQUIRE(g && out, MRI3D_EINVAL, "conv3d_march_plan_query: null pointer");
+    int rc = conv_check(g, "conv3d_march_plan_query");
+    if (rc) return rc;
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD, MRI3D_EINVAL, "conv3d_march_plan_query: pass %d", pass);
+    MRI3D_REQUIRE(!stats || pass == MRI3D_PASS_FWD, MRI3D_EINVAL, "conv3d_march_plan_query: statistics outside the forward");
+    Mri3dMarchPlanInfo info;
+    MRI3D_REQUIRE(conv_march_plan_info(*g, pass == MRI3D_PASS_DGRAD, stats != 0, info), MRI3D_ENOTSUP,
+                  "conv3d_march_plan_query: geometry not served (see mri3d_conv3d_march_supported; statistics: at most 8 output blocks)");
+    *out = info;
+    return MRI3D_OK;
+}
+
 extern "C" int mri3d_conv3d_fwd_march(const Mri3dConvGeom* g, const void* x, const void* x2, int32_t split, int32_t x2_ld,
                                       const void* w, const void* bias, void* y, double* stat_partials, void* workspace,
                                       size_t ws_bytes, mri3d_stream_t stream) {

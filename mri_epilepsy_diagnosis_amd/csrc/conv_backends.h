@@ -58,6 +58,8 @@ int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, i
 // compute); otherwise the dispatcher's own choice of the layers where it is the faster kernel.
 struct MarchNeeds { int grid; size_t wp_bytes; };   // workgroups (= statistics partials) and packed-weight image; grid 0: not taken
 MarchNeeds conv_march_needs(const Mri3dConvGeom& g, bool dgrad, bool stats, bool force);
+// the numbers the explicit entry points launch by (force = true), for mri3d_conv3d_march_plan_query; false: the plan refuses
+bool conv_march_plan_info(const Mri3dConvGeom& g, bool dgrad, bool stats, Mri3dMarchPlanInfo& out);
 int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
                    void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const ConvSplit& sp);
 

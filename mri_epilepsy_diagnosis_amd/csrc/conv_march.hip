@@ -678,6 +678,20 @@ MarchNeeds conv_march_needs(const Mri3dConvGeom& g, bool dgrad, bool stats, bool
     return conv_march_plan(g, dgrad, stats, force, p) ? MarchNeeds{p.grid, p.wp_bytes} : MarchNeeds{0, 0};
 }
 
+bool conv_march_plan_info(const Mri3dConvGeom& g, bool dgrad, bool stats, Mri3dMarchPlanInfo& out) {
+    MarchPlan p, d;
+    if (!conv_march_plan(g, dgrad, stats, true, p)) return false;
+    const MarchGeom& q = p.q;
+    out.chunks = q.nchunks, out.blocks = q.NTT;
+    out.wgh = q.wgh, out.wgw = q.wgw, out.gch = q.gch, out.gcw = q.gcw;
+    out.nseg = q.nseg, out.seglen = q.seglen, out.nbuf = q.nbuf;
+    out.grid = p.grid;
+    out.whole_chunks = q.Kc % (g.dtype == MRI3D_BF16 ? 16 : 8) == 0 ? 1 : 0;
+    out.dispatcher = conv_march_plan(g, dgrad, stats, false, d) ? 1 : 0;
+    out.smem_bytes = (int64_t)p.smem, out.wp_bytes = (int64_t)p.wp_bytes;
+    return true;
+}
+
 // second tensor of a split operand: forward, input channels >= split live in `second`; data gradient, output channels >= split
 int conv_march_run(const Mri3dConvGeom& g, bool dgrad, bool force, const void* in_v, const float* w, const float* bias, void* out_v,
                    void* ws, size_t ws_bytes, hipStream_t s, double* stat_part, const ConvSplit& sp) {

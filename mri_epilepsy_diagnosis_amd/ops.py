@@ -430,6 +430,19 @@ def conv_pair_plan(first, second):
     return {f: int(getattr(info, f)) for f in FUSEDCONV_PLAN_FIELDS}
 
 
+MARCH_PLAN_FIELDS = ("chunks", "blocks", "wgh", "wgw", "gch", "gcw", "nseg", "seglen", "nbuf", "grid", "whole_chunks", "dispatcher",
+                     "smem_bytes", "wp_bytes")
+
+
+def conv_march_plan(g, pass_, stats=False):
+    """Numbers of the launch plan of mri3d_conv3d_fwd_march / _dgrad_march (PASS_FWD / PASS_DGRAD; stats: the forward with fused
+    statistics) for the ConvGeom `g`, host only: a dict of the fields of Mri3dMarchPlanInfo (include/mri3d.h)."""
+    info = _lib.MarchPlanInfo()
+    check(_lib.lib().mri3d_conv3d_march_plan_query(ctypes.byref(g), pass_, 1 if stats else 0, ctypes.byref(info)),
+          "conv3d_march_plan_query")
+    return {f: int(getattr(info, f)) for f in MARCH_PLAN_FIELDS}
+
+
 def norm_plan(g, pass_, align=16):
     """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
     tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is

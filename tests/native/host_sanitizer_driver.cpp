@@ -216,6 +216,56 @@ int main() {
         EXPECT(mri3d_conv3d_fwd_cat(&c, buf2, buf2, 16, 32, buf2, buf2, buf2, nullptr, buf2, 0, nullptr) == MRI3D_EINVAL);
     }
 
+    // ---- the marching kernel's plan query over the sweep: it answers exactly where the support query says 1, its grid is the
+    // statistics block count, its weight image fits the workspace; refusals and bad arguments without a launch
+    {
+        Mri3dMarchPlanInfo mi;
+        size_t served = 0, refused = 0, dispatched = 0;
+        for (int dtype = 0; dtype < 2; ++dtype)
+            for (int ci : chans)
+                for (int co : chans)
+                    for (auto& sz : sizes)
+                        for (int pad : {0, 4, 8})
+                            for (int pass = 0; pass < 2; ++pass) {
+                                Mri3dConvGeom c = conv(2, sz[0], sz[1], sz[2], ci, co, 3, 1, 1, 1, dtype, pad, pad);
+                                const int rc = mri3d_conv3d_march_plan_query(&c, pass, 0, &mi);
+                                EXPECT(rc == (mri3d_conv3d_march_supported(&c, pass) == 1 ? MRI3D_OK : MRI3D_ENOTSUP));
+                                if (rc == MRI3D_OK) {
+                                    ++served;
+                                    dispatched += mi.dispatcher;
+                                    EXPECT(mi.chunks >= 1 && mi.chunks <= 4 && mi.blocks >= 1 && mi.wgh * mi.wgw == 8);
+                                    EXPECT(mi.nbuf == (mi.chunks == 1 ? 3 : 2) && mi.smem_bytes > 0 && mi.smem_bytes <= 160 * 1024);
+                                    EXPECT((int64_t)mi.grid == (int64_t)mi.blocks * mi.gch * mi.gcw * mi.nseg * c.n);
+                                    EXPECT((mi.nseg - 1) * mi.seglen < sz[0] && sz[0] <= mi.nseg * mi.seglen);
+                                    EXPECT(mi.wp_bytes > 0 && (size_t)mi.wp_bytes <= mri3d_conv3d_workspace_bytes(&c, pass));
+                                } else {
+                                    ++refused;
+                                }
+                                if (pass == 0) {
+                                    const int rs = mri3d_conv3d_march_plan_query(&c, 0, 1, &mi);
+                                    const int blocks = mri3d_conv3d_march_stats_blocks(&c);
+                                    EXPECT(rs == MRI3D_OK ? (blocks > 0 && blocks == mi.grid && mi.blocks <= 8) : (rs == MRI3D_ENOTSUP && blocks == 0));
+                                } else {
+                                    EXPECT(mri3d_conv3d_march_plan_query(&c, 1, 1, &mi) == MRI3D_EINVAL);   // no statistics in the data gradient
+                                }
+                            }
+        EXPECT(served > 1000 && refused > 1000 && dispatched > 0);
+        Mri3dConvGeom c = conv(1, 160, 192, 160, 16, 16, 3, 1, 1, 1, MRI3D_BF16, 0, 0);
+        EXPECT(mri3d_conv3d_march_plan_query(&c, 0, 1, &mi) == MRI3D_OK && mi.dispatcher == 1 && mi.chunks == 1 && mi.nbuf == 3);
+        EXPECT(mri3d_conv3d_march_plan_query(&c, 2, 0, &mi) == MRI3D_EINVAL);                              // no weight gradient here
+        EXPECT(mri3d_conv3d_march_plan_query(nullptr, 0, 0, &mi) == MRI3D_EINVAL && mri3d_conv3d_march_plan_query(&c, 0, 0, nullptr) == MRI3D_EINVAL);
+        for (int k : {1, 5}) {
+            Mri3dConvGeom o = conv(1, 16, 16, 16, 16, 16, k, 1, k / 2, 1, MRI3D_F32, 0, 0);
+            EXPECT(mri3d_conv3d_march_plan_query(&o, 0, 0, &mi) == MRI3D_ENOTSUP);
+        }
+        Mri3dConvGeom st = conv(1, 16, 16, 16, 16, 16, 3, 2, 1, 1, MRI3D_F32, 0, 0), di = conv(1, 16, 16, 16, 16, 16, 3, 1, 2, 2, MRI3D_F32, 0, 0);
+        EXPECT(mri3d_conv3d_march_plan_query(&st, 0, 0, &mi) == MRI3D_ENOTSUP && mri3d_conv3d_march_plan_query(&di, 1, 0, &mi) == MRI3D_ENOTSUP);
+        Mri3dConvGeom wide = conv(1, 2, 8, 16, 8, 136, 3, 1, 1, 1, MRI3D_F32, 0, 0);                       // nine output blocks
+        EXPECT(mri3d_conv3d_march_plan_query(&wide, 0, 0, &mi) == MRI3D_OK && mi.blocks == 9 && mri3d_conv3d_march_plan_query(&wide, 0, 1, &mi) == MRI3D_ENOTSUP);
+        wide.dout += 1;
+        EXPECT(mri3d_conv3d_march_plan_query(&wide, 0, 0, &mi) == MRI3D_EINVAL);
+    }
+
     // ---- other families: null geometry / null pointers / zero sizes must be refused, workspace queries must not crash
     EXPECT(mri3d_norm_stats(nullptr, P, nullptr, nullptr, nullptr, nullptr, 0.1f, P, 0, nullptr) != MRI3D_OK);
     EXPECT(mri3d_norm_act_fwd(nullptr, P, nullptr, nullptr, nullptr, nullptr, nullptr, P, nullptr) != MRI3D_OK);

@@ -49,7 +49,7 @@ def test_struct_layouts_match_header(tmp_path):
     """Compile the public header with gcc and compare sizeof/offsetof with the ctypes mirrors."""
     structs = {"Mri3dConvGeom": _lib.ConvGeom, "Mri3dNormGeom": _lib.NormGeom, "Mri3dPoolGeom": _lib.PoolGeom,
                "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom, "Mri3dNormPlanInfo": _lib.NormPlanInfo,
-               "Mri3dResamplePlanInfo": _lib.ResamplePlanInfo}
+               "Mri3dResamplePlanInfo": _lib.ResamplePlanInfo, "Mri3dMarchPlanInfo": _lib.MarchPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mri3d.h"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -176,6 +176,33 @@ def test_fusedconv_plan_queries_are_declared_bound_and_host_only(tmp_path):
     assert L.mri3d_convpair_plan_query(ctypes.byref(second), ctypes.byref(first), ctypes.byref(info)) == -2
     assert L.mri3d_convpair_plan_query(None, ctypes.byref(second), ctypes.byref(info)) == -1
     assert L.mri3d_convpair_plan_query(ctypes.byref(first), ctypes.byref(second), None) == -1
+
+
+def test_march_plan_query_is_declared_bound_and_host_only():
+    from mri_epilepsy_diagnosis_amd import ops
+    assert "mri3d_conv3d_march_plan_query" in _declared() and "mri3d_conv3d_march_plan_query" in _lib.SIGNATURES
+    fields = ["chunks", "blocks", "wgh", "wgw", "gch", "gcw", "nseg", "seglen", "nbuf", "grid", "whole_chunks", "dispatcher", "smem_bytes",
+              "wp_bytes"]
+    assert [f for f, _ in _lib.MarchPlanInfo._fields_] == fields == list(ops.MARCH_PLAN_FIELDS)      # (layout: test_struct_layouts_match_header)
+    L = _lib.lib()
+    info = _lib.MarchPlanInfo()
+    # the U-Net's full-resolution 16 -> 16 layer in bf16: 24 x 10 columns in 6 x 5 workgroups of 4 x 2, 8 segments of 20 planes
+    g = _lib.ConvGeom(1, 160, 192, 160, 16, 160, 192, 160, 16, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 16, 16, _lib.BF16)
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_FWD, 1, ctypes.byref(info)) == 0
+    got = {f: getattr(info, f) for f in fields}
+    assert got == dict(chunks=1, blocks=1, wgh=4, wgw=2, gch=6, gcw=5, nseg=8, seglen=20, nbuf=3, grid=240, whole_chunks=1, dispatcher=1,
+                       smem_bytes=14336 + 8 * 3 * 5760 + 8 * 32 * 8 + 64, wp_bytes=3 * 4608), got
+    assert got["grid"] == L.mri3d_conv3d_march_stats_blocks(ctypes.byref(g))
+    assert ops.conv_march_plan(g, _lib.PASS_DGRAD) == dict(got, dispatcher=1)
+    g.dtype = _lib.F32
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_DGRAD, 0, ctypes.byref(info)) == 0
+    assert (info.chunks, info.nbuf, info.wp_bytes, info.dispatcher) == (2, 2, 2 * 3 * 4608, 1)
+    g.ci = g.x_ld = 40                                                                     # five fp32 chunks: as the entry points
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, ctypes.byref(info)) == -2
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_DGRAD, 1, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_WGRAD, 0, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_march_plan_query(None, _lib.PASS_FWD, 0, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, None) == -1
 
 
 def test_host_code_is_clean_under_address_and_ub_sanitizers():

@@ -92,24 +92,40 @@ def _supported(ci, co, size, n, dtype, which):
 
 
 CASES = [
-    # (n, ci, co, (d, h, w))
-    (1, 16, 16, (5, 8, 16)),       # exactly one column, one segment
-    (2, 16, 16, (9, 11, 21)),      # ragged rows and voxels, two samples
-    (1, 8, 16, (6, 9, 17)),        # bf16: half-filled chunk
-    (1, 32, 16, (7, 16, 32)),      # bf16 two chunks / fp32 four; 2 x 2 columns
-    (1, 16, 48, (6, 10, 20)),      # three output blocks
-    (1, 16, 16, (26, 8, 16)),      # several d segments
-    (1, 24, 8, (10, 24, 16)),      # 8 output channels; bf16 second chunk half filled; 3 x 1 columns
-    (1, 16, 32, (4, 70, 8)),       # tall and narrow: an 8 x 1 workgroup shape, w < 16
-    (3, 16, 16, (3, 5, 130)),      # wide: a 1 x 8 workgroup shape with a ragged ninth column; depth 3
-    (1, 16, 16, (1, 8, 16)),       # a single plane
+    # (n, ci, co, (d, h, w), the forward plan numbers (ops.conv_march_plan) the comment speaks of; "bf16" / "f32": in that type only)
+    (1, 16, 16, (5, 8, 16), dict(gch=1, gcw=1, nseg=1, grid=1)),       # exactly one column, one segment
+    (2, 16, 16, (9, 11, 21), dict(gch=1, gcw=1, grid=2)),      # ragged rows and voxels, two samples
+    (1, 8, 16, (6, 9, 17), dict(bf16=dict(chunks=1, whole_chunks=0))),        # bf16: half-filled chunk
+    (1, 32, 16, (7, 16, 32), dict(bf16=dict(chunks=2), f32=dict(chunks=4), wgh=4, wgw=2, gch=1, gcw=1)),      # bf16 two chunks / fp32 four; 2 x 2 columns
+    (1, 16, 48, (6, 10, 20), dict(blocks=3, grid=3)),      # three output blocks
+    (1, 16, 16, (26, 8, 16), dict(nseg=3, seglen=9, grid=3)),      # several d segments
+    (1, 24, 8, (10, 24, 16), dict(blocks=1, bf16=dict(chunks=2, whole_chunks=0), wgh=4, wgw=2, gch=1, gcw=1)),      # 8 output channels; bf16 second chunk half filled; 3 x 1 columns
+    (1, 16, 32, (4, 70, 8), dict(wgh=8, wgw=1, gch=2, gcw=1)),       # tall and narrow: an 8 x 1 workgroup shape, w < 16
+    (3, 16, 16, (3, 5, 130), dict(wgh=1, wgw=8, gch=1, gcw=2, seglen=3)),      # wide: a 1 x 8 workgroup shape with a ragged ninth column; depth 3
+    (1, 16, 16, (1, 8, 16), dict(nseg=1, seglen=1, grid=1)),       # a single plane
 ]
+
+
+def _assert_plan(case, dtype):
+    """the plan numbers the case's comment names, through the plan query: a change of conv_march_plan that moves the case off the
+    corner it exists for fails here"""
+    _lib, ops = _env()
+    n, ci, co, size, nums = case
+    name = "bf16" if dtype == BF else "f32"
+    if -(-ci // (16 if dtype == BF else 8)) > 4:
+        return
+    g = ops._conv_geom((n, ci) + tuple(size), (co, ci, 3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), dtype=_lib.BF16 if dtype == BF else _lib.F32)
+    plan = ops.conv_march_plan(g, _lib.PASS_FWD)
+    want = {k: v for k, v in nums.items() if k not in ("bf16", "f32")}
+    want.update(nums.get(name, {}))
+    assert {k: plan[k] for k in want} == want, (case[:4], name, plan)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, BF], ids=["f32", "bf16"])
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "n%d_%d-%d_%s" % (c[0], c[1], c[2], "x".join(map(str, c[3]))))
 def test_march_forward_and_data_gradient_vs_torch_cpu(case, dtype):
-    n, ci, co, size = case
+    n, ci, co, size = case[:4]
+    _assert_plan(case, dtype)
     torch.manual_seed(sum(size) + ci + co)
     rnd = _rb if dtype == BF else (lambda t: t)
     x = rnd(torch.randn(n, ci, *size))
