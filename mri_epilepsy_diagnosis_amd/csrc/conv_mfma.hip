@@ -39,16 +39,25 @@ __host__ __device__ constexpr int tap_groups(int CK) { return CK == 16 ? 27 : 14
 //   group 12:  (2, 0, 2) | (2, 1, 2)                                  group 13:     (2, 2, 2) | padding
 // A-fragment (voxel rows) of group (class, kh), output row m == fragment of group (class, 0), row m + kh, so a wave needs 10
 // LDS fragments per class instead of 3 x 8 (conv_mfma_fwd2_kernel, one N-tile): 56 instead of 112 ds_read_b128 per chunk.
+// Group 13 is paired like this in the bf16 image only (one K = 32 step either way).  In the fp32 images it is a SINGLE group, as
+// in conv_march.hip: the eight channels of tap (2, 2, 2) spread over all four k-groups, so the group is two K = 4 steps instead
+// of four that are half zeros — 54 instead of 56 k-steps per row and chunk.  The MFMA adds its four products to the accumulator
+// one after the other in k order, so WHICH channel sits in which k-group decides the bits of the sum: single_chan() keeps the
+// order in which the paired form added the eight channels (0, 4, 1, 5, 2, 6, 3, 7; its zero products changed nothing), and the
+// results stay what they were, bit for bit.
 __host__ __device__ constexpr int pair_tap(int tg, int half) {
     return tg < 9 ? ((tg / 3) * 3 + tg % 3) * 3 + half
                   : (tg < 12 ? (half * 3 + (tg - 9)) * 3 + 2 : (tg == 12 ? (6 + half) * 3 + 2 : (half == 0 ? 26 : 27)));
 }
+// channel (within the 8-channel chunk) of k-group g in k-step s (0, 1) of the fp32 single group
+__host__ __device__ constexpr int single_chan(int g, int s) { return 2 * s + (g >> 1) + 4 * (g & 1); }
 
 // ------------------------------------------------------------------ weight packing
 // Wp[chunk][tg][nt][lane][s]:  value = W'(tap, kc, nc) with
 //   nc = nt*16 + (lane & 15)
 //   CK == 16: tap = tg,                 kc = chunk*16 + 4*(lane>>4) + s
 //   CK ==  8: tap = pair_tap(tg, lane>>5), kc = chunk*8  + 4*((lane>>4)&1) + s   (tap 27 -> 0)
+//             tg == 13 (the single group): tap = 26, kc = chunk*8 + single_chan(lane>>4, s) for s < 2; s = 2, 3 are zero, never read
 //   forward: W'(tap,kc,nc) = W[nc][kc][tap];  dgrad: W'(tap,kc,nc) = W[kc][nc][26 - tap]
 __global__ void pack_w_mfma_kernel(const float* __restrict__ w, float* __restrict__ wp, int Co, int Ci, int dgrad,
                                    int CK, int NTT, int nchunks) {
@@ -67,6 +76,9 @@ __global__ void pack_w_mfma_kernel(const float* __restrict__ w, float* __restric
         if (CK == 16) {
             tap = tg;
             kc = chunk * 16 + 4 * (lane >> 4) + s;
+        } else if (tg == 13) {
+            tap = s < 2 ? 26 : 27;
+            kc = chunk * 8 + single_chan(lane >> 4, s & 1);
         } else {
             tap = pair_tap(tg, lane >> 5);
             kc = chunk * 8 + 4 * ((lane >> 4) & 1) + s;
@@ -107,7 +119,9 @@ __global__ void pack_w_mfma_bf16_kernel(const float* __restrict__ w, bf16_t* __r
 // operand = channel li & 7 of row half hs = li >> 3; k-slot ks = lane >> 5 as in the images above.
 //   groups 2u, 2u+1 (class u = 0..3: k-slot taps (kd, kw) = (u, ks) for u < 3, (ks, 2) for u = 3):
 //       2u   (PAIR)   kh = hs         2u+1 (SINGLE) kh = 2, row half 0 only
-//   group 8: taps (kd 2, kh ks, kw 2), group 9: tap 26 in k-slot 0 — row half 0 only (the old groups 12 and 13)
+//   group 8: taps (kd 2, kh ks, kw 2), group 9: tap 26 — row half 0 only (the old groups 12 and 13).  Group 9 holds tap 26 in
+//   k-slot 0 in the bf16 image; in the fp32 image it is the single group of pack_w_mfma_kernel: elements s < 2 are channels
+//   chunk*8 + single_chan(lane>>4, s), elements 2, 3 are zero
 template <typename WT>
 __global__ void pack_w_mfma_n8_kernel(const float* __restrict__ w, WT* __restrict__ wp, int Co, int Ci, int dgrad, int nchunks) {
     constexpr int PE = 16 / sizeof(WT);   // elements per lane fragment (4 fp32 / 8 bf16)
@@ -118,7 +132,7 @@ __global__ void pack_w_mfma_n8_kernel(const float* __restrict__ w, WT* __restric
         int t = i / (PE * 64);
         const int grp = t % 10, chunk = t / 10;
         const int li = lane & 15, nc = li & 7, hs = li >> 3, ks = lane >> 5;
-        const int kc = chunk * 2 * PE + PE * ((lane >> 4) & 1) + sidx;
+        int kc = chunk * 2 * PE + PE * ((lane >> 4) & 1) + sidx;
         int tap = -1;
         if (grp < 8) {
             const int u = grp >> 1, single = grp & 1;
@@ -127,6 +141,9 @@ __global__ void pack_w_mfma_n8_kernel(const float* __restrict__ w, WT* __restric
             if (!(single && hs)) tap = (kd * 3 + kh) * 3 + kw;
         } else if (grp == 8) {
             if (!hs) tap = (2 * 3 + ks) * 3 + 2;
+        } else if constexpr (std::is_same<WT, float>::value) {
+            if (!hs && sidx < 2) tap = 26;
+            kc = chunk * 8 + single_chan(lane >> 4, sidx & 1);
         } else {
             if (!hs && ks == 0) tap = 26;
         }
@@ -403,12 +420,26 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
         }
     }
     // A-fragment LDS offsets of a tap group (k-groups 0,1 = pair_tap(tg, 0); k-groups 2,3 = pair_tap(tg, 1), tap 27 = zero weights)
+    // fp32, group 13 (the single group, tap 26): k-group kq owns channels single_chan(kq, 0) and single_chan(kq, 1), two floats
+    // apart (a_frag)
     auto a_off = [&](int tg) -> int {
+        if (!kBf16 && tg == 13) return ((wv * HH) * HW + li + (2 * HH + 2) * HW + 2) * CP + single_chan(kq, 0);
         const int ta = pair_tap(tg, 0), tb = pair_tap(tg, 1) < 27 ? pair_tap(tg, 1) : 26;
         const int oa = ((ta / 9) * HH + (ta / 3) % 3) * HW + ta % 3;
         const int ob = ((tb / 9) * HH + (tb / 3) % 3) * HW + tb % 3;
         return ((wv * HH) * HW + li + ((kq >> 1) ? ob : oa)) * CP + 4 * (kq & 1);
     };
+    // the voxel fragment of tap group tg at float offset `off` (a_off(tg) + rows) of a chunk's buffer: one ds_read_b128, or the
+    // single group's two floats, one per k-step (elements 2, 3 of the result are never used): a ds_read2_b32, eight per wave and
+    // chunk — the price of keeping the paired form's summation order (single_chan), against 8 x 16 MFMAs saved.
+    auto a_frag = [&](const float* buf, int tg, int off) -> f32x4 {
+        if (!kBf16 && tg == 13) {
+            static_assert(single_chan(0, 1) - single_chan(0, 0) == 2 && single_chan(3, 1) - single_chan(3, 0) == 2, "k-step stride");
+            return f32x4{buf[off], buf[off + 2], 0.f, 0.f};
+        }
+        return *reinterpret_cast<const f32x4*>(buf + off);
+    };
+    constexpr int kSingleSteps = kBf16 ? 4 : 2;   // fp32 k-steps of the single group (the bf16 paths do not use it)
 
     for (int it = 0; it < nitems; ++it) {
         MRI3D_STAMP(t_item);
@@ -441,8 +472,7 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
                     const int on = a_off(nfirst);
 #pragma unroll
                     for (int i = 0; i < TH + 2; ++i)
-                        if (i >= gi * nf / ng && i < (gi + 1) * nf / ng)
-                            fr[nu & 1][i] = *reinterpret_cast<const f32x4*>(bufc + on + i * HW * CP);
+                        if (i >= gi * nf / ng && i < (gi + 1) * nf / ng) fr[nu & 1][i] = a_frag(bufc, nfirst, on + i * HW * CP);
                 }
                 __builtin_amdgcn_sched_barrier(0);  // keep the prefetches above this group's MFMAs
                 // PAIR group: halo rows 0..8 -> accumulators 0..8; SINGLE group (kh = 2): halo rows 2..9 -> accumulators 0..7;
@@ -459,7 +489,7 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
 #pragma unroll
                     for (int m = 0; m < TH; m += 2)
 #pragma unroll
-                        for (int s4 = 0; s4 < 4; ++s4) {
+                        for (int s4 = 0; s4 < (g == 9 ? kSingleSteps : 4); ++s4) {   // group 9: the single group
                             acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bqa[g][s4], fr[u & 1][m + r0][s4], acc[m][0], 0, 0, 0);
                             acc[m + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bqa[g][s4], fr[u & 1][m + 1 + r0][s4], acc[m + 1][0], 0, 0, 0);
                         }
@@ -503,8 +533,7 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
                     const int on = a_off(nfirst);
 #pragma unroll
                     for (int i = 0; i < TH + 2; ++i)
-                        if (i >= kh * nf / ng && i < (kh + 1) * nf / ng)
-                            fr[nu & 1][i] = *reinterpret_cast<const f32x4*>(bufc + on + i * HW * CP);
+                        if (i >= kh * nf / ng && i < (kh + 1) * nf / ng) fr[nu & 1][i] = a_frag(bufc, nfirst, on + i * HW * CP);
                 }
                 __builtin_amdgcn_sched_barrier(0);  // keep the prefetches above this tap group's MFMAs
                 if constexpr (kBf16) {
@@ -515,11 +544,12 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
                                                                             acc[m][0], 0, 0, 0);
                 } else {
                     // accumulator reuse distance 2 (two rows alternate over the four k-steps): the fp32 MFMA sustains its peak
-                    // when an accumulator comes back after <= 3 or >= 16 instructions, not after 4..8 (tools/microbench)
+                    // when an accumulator comes back after <= 3 or >= 16 instructions, not after 4..8 (tools/microbench); the
+                    // single group's two k-steps keep that distance
 #pragma unroll
                     for (int m = 0; m < TH; m += 2)
 #pragma unroll
-                        for (int s = 0; s < 4; ++s) {
+                        for (int s = 0; s < (tg == 13 ? kSingleSteps : 4); ++s) {
                             acc[m][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bqa[tg][s], fr[u & 1][m + kh][s], acc[m][0], 0, 0, 0);
                             acc[m + 1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(bqa[tg][s], fr[u & 1][m + 1 + kh][s], acc[m + 1][0], 0, 0, 0);
                         }
@@ -556,7 +586,7 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
             if (tg + 1 < TG) {
                 const int o1 = a_off(tg + 1);
 #pragma unroll
-                for (int m = 0; m < TH; ++m) aq[an][m] = *reinterpret_cast<const f32x4*>(bufc + o1 + m * HW * CP);
+                for (int m = 0; m < TH; ++m) aq[an][m] = a_frag(bufc, tg + 1, o1 + m * HW * CP);
             }
             __builtin_amdgcn_sched_barrier(0);  // keep the prefetches above this tap group's MFMAs
             if constexpr (kBf16) {
@@ -569,7 +599,7 @@ conv_mfma_fwd2_kernel(const T* __restrict__ x, const float* __restrict__ wp, con
                                                                              acc[m][nt], 0, 0, 0);
             } else {
 #pragma unroll
-                for (int s = 0; s < 4; ++s)
+                for (int s = 0; s < (tg == 13 ? kSingleSteps : 4); ++s)   // group 13: the single group
 #pragma unroll
                     for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
