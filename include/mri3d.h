@@ -111,6 +111,34 @@ int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const void* dy, vo
 int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
                        int32_t align_x, int32_t align_y, char* name, size_t name_bytes);
 
+/* The first layer with its activation folded in — `unet.UNet`'s encoder.encoding_blocks[0].conv1: Conv3d(1, 8, 3, padding=1) +
+ * PReLU with no normalisation in between.  Two kernels instead of conv, activation, activation backward and weight gradient:
+ *   forward:  z = conv(x, w) + bias and a = act(z), both stored (the backward needs z's sign and, for dalpha, its value);
+ *   backward: dW, db and dalpha from (x, z, da); the gradient of z is formed in registers and never stored.  There is no dx.
+ * z, a, dW and db have the bits of mri3d_conv3d_fwd + mri3d_norm_act_fwd (identity norm) + mri3d_norm_act_bwd (training = 0) +
+ * mri3d_conv3d_wgrad: same FMA chains, same summation orders.  dalpha is the same float64 sum of exact products over another
+ * partition of the voxels, rounded to fp32 per channel as there.
+ * g: the convolution, g->y_ld = the pitch of z; a_ld: the pitch of a (forward) / of da (backward); act: MRI3D_ACT_RELU, _LEAKY
+ * (slope) or _PRELU (alpha: alpha_n = 1 or g->co slopes); pass: MRI3D_PASS_FWD, or MRI3D_PASS_WGRAD for the backward; align: the
+ * largest power of two <= 16 dividing the addresses of z and a / da (x is read one element at a time).
+ * mri3d_conv_cin1_act_supported = 1 (host only) for one input channel, 8 or 16 output channels, 3x3x3, stride 1, padding 1,
+ * dilation 1, fp32, pitches of z and a / da multiples of 4, align = 16, and in the backward eight output channels (with sixteen
+ * the layer's plain weight gradient is an MFMA kernel with another summation order: keep mri3d_norm_act_bwd + mri3d_conv3d_wgrad).
+ * bf16 is declined.  The entry points return MRI3D_ENOTSUP exactly where it answers 0.
+ * mri3d_conv_cin1_act_route: "cin1 act fwd co{8,16}" conv_cin1_act_fwd_kernel<CO>, "cin1 act bwd co8" conv_cin1_act_bwd_kernel<8>
+ * (+ wgrad_reduce_kernel, and cin1_act_dalpha_kernel where dalpha is wanted), "none" where the predicate declines.
+ * dbias, dalpha may be NULL (dalpha is written for PReLU only).  No allocation, no synchronisation. */
+int32_t mri3d_conv_cin1_act_supported(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, int32_t pass, int32_t align);
+size_t mri3d_conv_cin1_act_workspace_bytes(const Mri3dConvGeom* g, int32_t pass);
+int mri3d_conv_cin1_act_route(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, int32_t pass, int32_t align,
+                              char* name, size_t name_bytes);
+int mri3d_conv_cin1_act_fwd(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, float slope, const void* x,
+                            const void* w, const void* bias, const void* alpha, void* z, void* a, void* workspace, size_t ws_bytes,
+                            mri3d_stream_t stream);
+int mri3d_conv_cin1_act_bwd(const Mri3dConvGeom* g, int32_t da_ld, int32_t act, int32_t alpha_n, float slope, const void* x,
+                            const void* z, const void* da, const void* alpha, void* dw, void* dbias, void* dalpha, void* workspace,
+                            size_t ws_bytes, mri3d_stream_t stream);
+
 /* Convolution over torch.cat((x, x2), dim=1) WITHOUT the concatenation — `unet.UNet`'s decoder, x = cat((skip, upsampled))
  * in front of its first ConvolutionalBlock (segmentation/routine.py:346-356 -> unet DecodingBlock.forward).  g describes the
  * concatenated convolution (g->ci = all input channels, g->x_ld = voxel pitch of x); channels [0, split) are read from x,

@@ -86,6 +86,11 @@ SIGNATURES = {
     "mri3d_conv3d_wgrad": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_route": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "mri3d_conv3d_cat_supported": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32]),
+    "mri3d_conv_cin1_act_supported": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "mri3d_conv_cin1_act_workspace_bytes": (c_size_t, [POINTER(ConvGeom), c_int32]),
+    "mri3d_conv_cin1_act_route": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "mri3d_conv_cin1_act_fwd": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "mri3d_conv_cin1_act_bwd": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_float, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_fwd_cat_stats_blocks": (c_int32, [POINTER(ConvGeom), c_int32, c_int32]),
     "mri3d_conv3d_fwd_cat": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_dgrad_cat": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, c_int32, c_int32, _P, c_size_t, _P]),

@@ -232,6 +232,65 @@ extern "C" int mri3d_conv3d_wgrad(const Mri3dConvGeom* g, const void* x, const v
     }
 }
 
+// ---- the first layer with its activation folded in: Conv3d(1, 8|16, 3, padding=1) + PReLU / LeakyReLU / ReLU (conv_generic.hip)
+static bool cin1_act_ok(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, int32_t pass, int32_t align, const char* who) {
+    if (!g || conv_check(g, who) != MRI3D_OK) return false;
+    if (!conv_cin1_act_supported(*g, a_ld, act, alpha_n, pass, align)) return false;
+    // the backward keeps the bits of the layer's plain weight gradient only where that runs conv_generic.hip's kernel
+    return pass == MRI3D_PASS_FWD || conv_backend(*g, MRI3D_PASS_WGRAD, false, 0, 0, align, align) == ConvBackend::generic;
+}
+
+extern "C" int32_t mri3d_conv_cin1_act_supported(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, int32_t pass,
+                                                 int32_t align) {
+    return cin1_act_ok(g, a_ld, act, alpha_n, pass, align, "conv_cin1_act_supported") ? 1 : 0;
+}
+
+extern "C" size_t mri3d_conv_cin1_act_workspace_bytes(const Mri3dConvGeom* g, int32_t pass) {
+    if (!g || (pass != MRI3D_PASS_FWD && pass != MRI3D_PASS_WGRAD)) return 0;
+    return conv_cin1_act_workspace_bytes(*g, pass);   // exactly what the pass asks for
+}
+
+extern "C" int mri3d_conv_cin1_act_route(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, int32_t pass,
+                                         int32_t align, char* name, size_t name_bytes) {
+    int rc = conv_check(g, "conv_cin1_act_route");
+    if (rc) return rc;
+    MRI3D_REQUIRE(name != nullptr && name_bytes >= 32, MRI3D_EINVAL, "conv_cin1_act_route: name buffer of at least 32 bytes required");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_WGRAD, MRI3D_EINVAL, "conv_cin1_act_route: pass %d", pass);
+    if (!cin1_act_ok(g, a_ld, act, alpha_n, pass, align, "conv_cin1_act_route")) {
+        snprintf(name, name_bytes, "none");
+        return MRI3D_OK;
+    }
+    MRI3D_REQUIRE(conv_cin1_act_route_name(*g, a_ld, act, alpha_n, pass, align, name, name_bytes), MRI3D_EINVAL,
+                  "conv_cin1_act_route: name buffer too small");
+    return MRI3D_OK;
+}
+
+extern "C" int mri3d_conv_cin1_act_fwd(const Mri3dConvGeom* g, int32_t a_ld, int32_t act, int32_t alpha_n, float slope, const void* x,
+                                       const void* w, const void* bias, const void* alpha, void* z, void* a, void* workspace,
+                                       size_t ws_bytes, mri3d_stream_t stream) {
+    int rc = conv_check(g, "conv_cin1_act_fwd");
+    if (rc) return rc;
+    MRI3D_REQUIRE(x && w && z && a, MRI3D_EINVAL, "conv_cin1_act_fwd: null pointer");
+    MRI3D_REQUIRE(act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "conv_cin1_act_fwd: PReLU needs alpha");
+    MRI3D_REQUIRE(cin1_act_ok(g, a_ld, act, alpha_n, MRI3D_PASS_FWD, ptr_align(z, a, workspace), "conv_cin1_act_fwd"), MRI3D_ENOTSUP,
+                  "conv_cin1_act_fwd: geometry / activation / alignment not served (query mri3d_conv_cin1_act_supported)");
+    return conv_cin1_act_fwd(*g, a_ld, act, alpha_n, slope, (const float*)x, (const float*)w, (const float*)bias, (const float*)alpha,
+                             (float*)z, (float*)a, workspace, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mri3d_conv_cin1_act_bwd(const Mri3dConvGeom* g, int32_t da_ld, int32_t act, int32_t alpha_n, float slope, const void* x,
+                                       const void* z, const void* da, const void* alpha, void* dw, void* dbias, void* dalpha,
+                                       void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
+    int rc = conv_check(g, "conv_cin1_act_bwd");
+    if (rc) return rc;
+    MRI3D_REQUIRE(x && z && da && dw, MRI3D_EINVAL, "conv_cin1_act_bwd: null pointer");
+    MRI3D_REQUIRE(act != MRI3D_ACT_PRELU || alpha, MRI3D_EINVAL, "conv_cin1_act_bwd: PReLU needs alpha");
+    MRI3D_REQUIRE(cin1_act_ok(g, da_ld, act, alpha_n, MRI3D_PASS_WGRAD, ptr_align(z, da, workspace), "conv_cin1_act_bwd"), MRI3D_ENOTSUP,
+                  "conv_cin1_act_bwd: geometry / activation / alignment not served (query mri3d_conv_cin1_act_supported)");
+    return conv_cin1_act_bwd(*g, da_ld, act, alpha_n, slope, (const float*)x, (const float*)z, (const float*)da, (const float*)alpha,
+                             (float*)dw, (float*)dbias, (float*)dalpha, workspace, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
 // ---- which kernel would run (host only): the backend decision above, then the chosen file's own plan by name
 extern "C" int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
                                   int32_t align_x, int32_t align_y, char* name, size_t name_bytes) {

@@ -24,6 +24,16 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
 // name of the kernel instantiation the pass launches (mri3d_conv3d_route; the vocabulary is in include/mri3d.h), written from the
 // plan the launch reads.  ax / ay: ptr_align of the x-side tensor (x, dx) / of the y-side tensor (y, dy).  false: name too long.
 bool conv_generic_route_name(const Mri3dConvGeom& g, int pass, bool bias, int ax, int ay, char* name, size_t name_bytes);
+// the first layer with its activation folded in (mri3d_conv_cin1_act_*): one predicate, read by the queries and by the launches.
+// pass: MRI3D_PASS_FWD, or MRI3D_PASS_WGRAD for the backward; a_ld: pitch of a / of da; align: ptr_align of z, a / da and workspace
+bool conv_cin1_act_supported(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, int pass, int align);
+size_t conv_cin1_act_workspace_bytes(const Mri3dConvGeom& g, int pass);
+bool conv_cin1_act_route_name(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, int pass, int align, char* name, size_t name_bytes);
+int conv_cin1_act_fwd(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, float slope, const float* x, const float* w,
+                      const float* bias, const float* alpha, float* z, float* a, void* ws, size_t ws_bytes, hipStream_t s);
+int conv_cin1_act_bwd(const Mri3dConvGeom& g, int da_ld, int act, int alpha_n, float slope, const float* x, const float* z,
+                      const float* da, const float* alpha, float* dw, float* dbias, float* dalpha, void* ws, size_t ws_bytes,
+                      hipStream_t s);
 
 // conv_mfma.hip
 bool conv_mfma_supported(const Mri3dConvGeom& g, int pass);

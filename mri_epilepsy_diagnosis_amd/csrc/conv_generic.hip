@@ -1203,6 +1203,302 @@ conv_cin1_wgrad_kernel(Mri3dConvGeom g, const T* __restrict__ x, const T* __rest
     }
 }
 
+// ------------------------------------------------------------------ first layer + its activation (no normalisation in between)
+// unet.UNet's first ConvolutionalBlock is Conv3d(1, 8, 3, padding=1) + PReLU: as four launches z and its gradient cross HBM five
+// times (conv -> z; z -> a; (z, da) -> dz; (x, dz) -> dW).  The two kernels below are conv_cin1_fwd_kernel and
+// conv_cin1_wgrad_kernel with the activation folded in: every FMA chain and every summation order is theirs, so z, a, dW and db
+// keep their bits, and the gradient of z exists in registers only.
+//   a  = apply_act(fmaf(z, 1, 0), act, alpha)                  norm_act_fwd_kernel for mode none (scale 1, shift 0: -0 -> +0)
+//   dz = z > 0 ? da : da * alpha                               norm_act_bwd_reduce_body's du; its (gm * is) * du is du for scale 1
+//   dalpha = sum over z <= 0 of (double)da * (double)z         float64 per lane -> wave -> workgroup -> one pass, fixed order
+struct Cin1Act {
+    const float* alpha;   // PReLU's slopes (alpha_n of them: 1 or Co); not read for the other kinds
+    int alpha_n, act;     // MRI3D_ACT_RELU | _LEAKY | _PRELU
+    float slope;          // LeakyReLU
+};
+
+template <int CO>
+__global__ void __launch_bounds__(256)
+conv_cin1_act_fwd_kernel(Mri3dConvGeom g, const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ bias,
+                         Cin1Act pa, float* __restrict__ z, float* __restrict__ a, int a_ld, int tilesD, int tilesH, int tilesW,
+                         int ntiles) {
+    // tile, lane mapping and FMA chain of conv_cin1_fwd_kernel (see there for the two pins on the compiler).  The stores differ:
+    // a lane's 4 x 8 (2 x 16) results are 128 contiguous bytes, and stored from the lane that computed them one instruction
+    // writes 16 bytes per lane at a 128-byte stride (2.4 TB/s).  Each wave turns its 8 rows of 1 KB through LDS, four rows at a
+    // time, so that one store instruction writes one whole row: lane l holds the l-th 16 bytes of it.
+    constexpr int VPT = Cin1<CO>::VPT, TW = C1WQ * VPT, PW = TW + 4;
+    constexpr int Q = CO / 4;             // 16-byte pieces per voxel
+    constexpr int LS = VPT * CO + 4;      // floats between two lanes' results in the turn buffer (+16 B: the b128 writes hit distinct banks)
+    constexpr int RS = C1WQ * LS;         // ... and between two rows
+    __shared__ __attribute__((aligned(16))) float xs[(C1D + 2) * (C1H + 2) * PW];
+    __shared__ __attribute__((aligned(16))) float wsh[27 * CO];
+    __shared__ __attribute__((aligned(16))) float turn[C1D][4 * RS];
+    const int tid = threadIdx.x;
+    for (int e = tid; e < 27 * CO; e += 256) wsh[e] = wp[e];
+    const int wq = tid % C1WQ, hl = (tid / C1WQ) % C1H, dl = tid / (C1WQ * C1H);   // dl = the wave
+    float bv[CO];
+#pragma unroll
+    for (int c = 0; c < CO; ++c) bv[c] = bias ? bias[c] : 0.f;
+    // after the turn: this lane's channel quad and its voxel along W in every row
+    const int lane = tid & 63, tq = lane % Q, tv = lane / Q;
+    const int toff = (tv / VPT) * LS + (tv % VPT) * CO + tq * 4;
+    float al[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) al[j] = (pa.act == MRI3D_ACT_PRELU) ? pa.alpha[pa.alpha_n == 1 ? 0 : tq * 4 + j] : pa.slope;
+    float sc = 1.f, sh = 0.f;             // norm_act_fwd_kernel's scale and shift without statistics, as run-time values: a real fma
+    asm volatile("" : "+v"(sc), "+v"(sh));
+    float* tw = turn[dl];
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
+        __syncthreads();
+        cin1_stage<float, TW, C1D + 2>(xs, x + (int64_t)n * g.di * g.hi * g.wi * g.x_ld, g, d0 - 1, h0, w0, tid);
+        __syncthreads();
+        f32x2 acc[VPT][CO / 2];   // channel pairs: v_pk_fma_f32
+#pragma unroll
+        for (int v = 0; v < VPT; ++v)
+#pragma unroll
+            for (int c = 0; c < CO / 2; ++c) acc[v][c] = f32x2{bv[2 * c], bv[2 * c + 1]};
+#pragma unroll
+        for (int kd = 0; kd < 3; ++kd)
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh) {
+                const float* row = xs + ((dl + kd) * (C1H + 2) + hl + kh) * PW + wq * VPT;
+                float r[VPT + 2];
+#pragma unroll
+                for (int i = 0; i < VPT + 2; ++i) r[i] = row[i];
+                int woff = (kd * 3 + kh) * 3 * CO;
+                asm volatile("" : "+v"(woff));
+                __builtin_amdgcn_sched_barrier(0);
+                const float* wrow = wsh + woff;
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) {
+                    const float* wt = wrow + kw * CO;
+#pragma unroll
+                    for (int c = 0; c < CO / 2; ++c) {
+                        const f32x2 wv = f32x2{wt[2 * c], wt[2 * c + 1]};
+#pragma unroll
+                        for (int v = 0; v < VPT; ++v)
+                            acc[v][c] = __builtin_elementwise_fma(f32x2{r[v + kw], r[v + kw]}, wv, acc[v][c]);
+                    }
+                }
+            }
+#pragma unroll
+        for (int v = 0; v < VPT; ++v)
+#pragma unroll
+            for (int c = 0; c < CO / 2; ++c) asm volatile("" : "+v"(acc[v][c]));
+        const int od = d0 + dl;
+        // the turn buffer is the wave's own and a wave's LDS accesses complete in order: no workgroup barrier
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            if ((hl >> 2) == half) {
+                float* dst = tw + (hl & 3) * RS + wq * LS;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v)
+#pragma unroll
+                    for (int c = 0; c < CO; c += 4)
+                        *reinterpret_cast<float4*>(dst + v * CO + c) =
+                            make_float4(acc[v][c / 2].x, acc[v][c / 2].y, acc[v][c / 2 + 1].x, acc[v][c / 2 + 1].y);
+            }
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 zq = *reinterpret_cast<const float4*>(tw + j * RS + toff);
+                const int oh = h0 + half * 4 + j, ow = w0 + tv;
+                if (od < g.dout && oh < g.ho && ow < g.wo) {
+                    const int64_t vox = (((int64_t)n * g.dout + od) * g.ho + oh) * g.wo + ow;
+                    stf4(z + vox * g.y_ld + tq * 4, zq);
+                    stf4(a + vox * a_ld + tq * 4,
+                         make_float4(apply_act(fmaf(zq.x, sc, sh), pa.act, al[0]), apply_act(fmaf(zq.y, sc, sh), pa.act, al[1]),
+                                     apply_act(fmaf(zq.z, sc, sh), pa.act, al[2]), apply_act(fmaf(zq.w, sc, sh), pa.act, al[3])));
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+template <int CO>
+__global__ void __launch_bounds__(768)
+conv_cin1_act_bwd_kernel(Mri3dConvGeom g, const float* __restrict__ x, const float* __restrict__ z, const float* __restrict__ da,
+                         int da_ld, Cin1Act pa, float* __restrict__ part, float* __restrict__ bias_part,
+                         double* __restrict__ alpha_part, int tilesD, int tilesH, int tilesW, int ntiles, int nshares) {
+    // conv_cin1_wgrad_kernel (see there) with dz = act'(z) * da where it read dy: same lanes, same accumulators, same order.
+    // What differs is how the gradient reaches the lanes.  There every lane loads its own 128 bytes, 16 at a time, and the three
+    // kd groups each load all of them: 64 cache lines per load instruction, 6144 line requests per tile, which is what the kernel
+    // waits for (6 us per tile).  Here the twelve waves load z and da once, one whole 1 KB row per instruction, form dz and the
+    // products for dalpha once per element, and hand dz to the compute lanes through LDS (conv_cin1_act_fwd_kernel's turn, the
+    // other way round).  alpha_part[share][co] (may be NULL): this workgroup's float64 sum for dalpha.
+    constexpr int VPT = Cin1<CO>::VPT, TW = C1WQ * VPT, PW = TW + 4, NA = 9 * CO + CO;
+    constexpr int Q = CO / 4, LS = VPT * CO + 4, RS = C1WQ * LS, NROW = C1D * C1H, RPW = (NROW + 11) / 12;   // rows per wave
+    __shared__ __attribute__((aligned(16))) float xs[(C1D + 2) * (C1H + 2) * PW];
+    __shared__ __attribute__((aligned(16))) float dzs[NROW * RS];
+    __shared__ float red[12][NA];
+    __shared__ double ared[12][CO];
+    const int kd = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+    const int tid = threadIdx.x & 255;
+    const int per_xcd = gridDim.x / 8;
+    const int share = (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
+    const int wq = tid % C1WQ, hl = (tid / C1WQ) % C1H, dl = tid / (C1WQ * C1H);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // 0 .. 11
+    // as a loader: this lane's channel quad and its voxel along W in every row it loads
+    const int tq = lane % Q, tv = lane / Q;
+    const int toff = (tv / VPT) * LS + (tv % VPT) * CO + tq * 4;
+    float al[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        al[j] = (pa.act == MRI3D_ACT_PRELU) ? pa.alpha[pa.alpha_n == 1 ? 0 : tq * 4 + j] : (pa.act == MRI3D_ACT_LEAKY ? pa.slope : 0.f);
+    f32x2 acc[3][3][CO / 2];   // channel pairs: v_pk_fma_f32
+    float bsum[CO];
+    double asum[4];            // channels 4 tq .. 4 tq + 3
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+#pragma unroll
+            for (int c = 0; c < CO / 2; ++c) acc[a][b][c] = f32x2{0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < CO; ++c) bsum[c] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asum[j] = 0.0;
+    const bool want_alpha = alpha_part != nullptr;
+    for (int tile = share; tile < ntiles; tile += nshares) {
+        int n, d0, h0, w0;
+        decode_tile(tile, tilesD, tilesH, tilesW, TW, n, d0, h0, w0);
+        // rows wave, wave + 12, wave + 24 of the tile's 32 (d, h) rows: in flight while x is staged
+        float4 zq[RPW], dq[RPW];
+        bool ok[RPW];
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            const int row = wave + 12 * i, od = d0 + row / C1H, oh = h0 + row % C1H, ow = w0 + tv;
+            ok[i] = row < NROW && od < g.dout && oh < g.ho && ow < g.wo;
+            zq[i] = dq[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok[i]) {
+                const int64_t vox = (((int64_t)n * g.dout + od) * g.ho + oh) * g.wo + ow;
+                zq[i] = ldf4(z + vox * g.y_ld + tq * 4);
+                dq[i] = ldf4(da + vox * da_ld + tq * 4);
+            }
+        }
+        __syncthreads();   // the last tile's readers of xs and dzs are through
+        cin1_stage<float, TW, C1D + 2, 768>(xs, x + (int64_t)n * g.di * g.hi * g.wi * g.x_ld, g, d0 - 1, h0, w0, (int)threadIdx.x);
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            const int row = wave + 12 * i;
+            if (row < NROW) {   // (uniform in the wave)
+                const float zv[4] = {zq[i].x, zq[i].y, zq[i].z, zq[i].w}, dv[4] = {dq[i].x, dq[i].y, dq[i].z, dq[i].w};
+                float du[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool pos = zv[j] > 0.f;
+                    du[j] = ok[i] ? (pos ? dv[j] : dv[j] * al[j]) : 0.f;   // zero outside the volume
+                    if (want_alpha) asum[j] += (pos || !ok[i]) ? 0.0 : (double)dv[j] * (double)zv[j];
+                }
+                *reinterpret_cast<float4*>(dzs + row * RS + toff) = make_float4(du[0], du[1], du[2], du[3]);
+            }
+        }
+        __syncthreads();
+        // this lane's VPT output voxels of dz
+        f32x2 gy[VPT][CO / 2];
+        {
+            const float* gp = dzs + (dl * C1H + hl) * RS + wq * LS;
+#pragma unroll
+            for (int v = 0; v < VPT; ++v)
+#pragma unroll
+                for (int c = 0; c < CO; c += 4) {
+                    const float4 q = *reinterpret_cast<const float4*>(gp + v * CO + c);
+                    gy[v][c / 2] = f32x2{q.x, q.y};
+                    gy[v][c / 2 + 1] = f32x2{q.z, q.w};
+                }
+        }
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+            const float* row = xs + ((dl + kd) * (C1H + 2) + hl + kh) * PW + wq * VPT;
+            float r[VPT + 2];
+#pragma unroll
+            for (int i = 0; i < VPT + 2; ++i) r[i] = row[i];
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+                for (int v = 0; v < VPT; ++v)
+#pragma unroll
+                    for (int c = 0; c < CO / 2; ++c)
+                        acc[kh][kw][c] = __builtin_elementwise_fma(f32x2{r[v + kw], r[v + kw]}, gy[v][c], acc[kh][kw][c]);
+        }
+        if (kd == 1) {
+#pragma unroll
+            for (int v = 0; v < VPT; ++v)
+#pragma unroll
+                for (int c = 0; c < CO / 2; ++c) { bsum[2 * c] += gy[v][c].x; bsum[2 * c + 1] += gy[v][c].y; }
+        }
+    }
+    // waves 4 kd .. 4 kd + 3 hold plane kd's taps
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+#pragma unroll
+            for (int c = 0; c < CO; ++c) {
+                const float vsum = wave_sum_dpp((c & 1) ? acc[a][b][c / 2].y : acc[a][b][c / 2].x);
+                if (lane == 0) red[wave][(a * 3 + b) * CO + c] = vsum;
+            }
+#pragma unroll
+    for (int c = 0; c < CO; ++c) {
+        const float vsum = wave_sum_dpp(bsum[c]);
+        if (lane == 0) red[wave][9 * CO + c] = vsum;
+    }
+    if (want_alpha) {
+        // lanes of one channel quad (lane % Q) -> wave: a butterfly over the other lane bits, the same order in every run
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double v = asum[j];
+#pragma unroll
+            for (int m = 32; m >= Q; m >>= 1) v += __shfl_xor(v, m, 64);
+            if (lane < Q) ared[wave][lane * 4 + j] = v;
+        }
+    }
+    __syncthreads();
+    const int w0_ = 4 * kd;
+    if (tid < 9 * CO) {
+        const float t4 = (red[w0_][tid] + red[w0_ + 1][tid]) + (red[w0_ + 2][tid] + red[w0_ + 3][tid]);
+        part[((size_t)share * 27 + kd * 9 + tid / CO) * CO + tid % CO] = t4;   // part[share][tap][ci = 0][co]
+    } else if (tid < NA && kd == 1 && bias_part) {
+        const int c = tid - 9 * CO;
+        bias_part[(size_t)share * CO + c] = (red[w0_][tid] + red[w0_ + 1][tid]) + (red[w0_ + 2][tid] + red[w0_ + 3][tid]);
+    }
+    if (want_alpha && (int)threadIdx.x < CO) {   // the twelve waves in order
+        double t = 0.0;
+#pragma unroll
+        for (int wv = 0; wv < 12; ++wv) t += ared[wv][tid];
+        alpha_part[(size_t)share * CO + tid] = t;
+    }
+}
+
+// dalpha from the per-share float64 sums, rounded as norm_act_bwd_sums_kernel + norm_act_bwd_params_block round theirs: one fp32
+// value per channel first, then (one alpha for all channels) the float64 sum of those in channel order.  One workgroup.
+__global__ void __launch_bounds__(256)
+cin1_act_dalpha_kernel(const double* __restrict__ alpha_part, int nshares, int CO, int alpha_n, float* __restrict__ dalpha) {
+    __shared__ double r[256];
+    __shared__ float sums[16];
+    const int L = 256 / CO, c = threadIdx.x / L, ql = threadIdx.x % L;   // CO = 8 | 16
+    double t = 0.0;
+    for (int q = ql; q < nshares; q += L) t += alpha_part[(size_t)q * CO + c];
+    r[threadIdx.x] = t;
+    __syncthreads();
+    if (ql == 0) {
+        t = 0.0;
+        for (int q = 0; q < L; ++q) t += r[c * L + q];
+        sums[c] = (float)t;
+    }
+    __syncthreads();
+    if (alpha_n > 1) {
+        if ((int)threadIdx.x < CO) dalpha[threadIdx.x] = (float)(double)sums[threadIdx.x];
+    } else if (threadIdx.x == 0) {
+        t = 0.0;
+        for (int q = 0; q < CO; ++q) t += (double)sums[q];
+        dalpha[0] = (float)t;
+    }
+}
+
 // ------------------------------------------------------------------ 3x3x3 stencil: ONE input and ONE output channel
 // The autoencoder's last layer `vox = Conv3d(1, 1, 3, padding=1)` (AE_model.py:160) on the whole reconstructed volume: 8 bytes of
 // traffic and 27 FMAs per voxel.  The generic kernels spend 0.55 / 0.82 / 0.72 ms (fwd / dgrad / wgrad, 4 x 160x192x160) on it,
@@ -1952,6 +2248,88 @@ int conv_generic_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, fl
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(g.co * g.ci * taps + g.co, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, nb,
                        taps, g.ci, g.co, p.CiP, p.CoP);
     return check_launch(what);
+}
+
+// ------------------------------------------------------------------ first layer + its activation: host side
+// THE decision of mri3d_conv_cin1_act_supported / _workspace_bytes / _route / _fwd / _bwd.  g: the convolution (y_ld = z's pitch);
+// a_ld: the pitch of a (forward) or of da (backward); align: ptr_align of every tensor the pass touches.  fp32 only (bf16 streaming
+// passes are instruction-bound and keep the separate launches).  The backward is conv_cin1_wgrad_kernel's sum order, so it is
+// offered only where the plain weight gradient of the layer is that kernel: eight output channels (sixteen go to the MFMA file).
+bool conv_cin1_act_supported(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, int pass, int align) {
+    if (pass != MRI3D_PASS_FWD && pass != MRI3D_PASS_WGRAD) return false;
+    if (g.dtype != MRI3D_F32 || !cin1_ok(g)) return false;   // (cin1_ok: y_ld % 4 == 0, tile count below 2^31)
+    if (act != MRI3D_ACT_RELU && act != MRI3D_ACT_LEAKY && act != MRI3D_ACT_PRELU) return false;
+    if (act == MRI3D_ACT_PRELU && alpha_n != 1 && alpha_n != g.co) return false;
+    if (a_ld < g.co || a_ld % 4 != 0 || align < 16) return false;
+    return pass == MRI3D_PASS_FWD || g.co == 8;
+}
+
+struct Cin1ActPlan {
+    size_t part_floats, bias_floats, alpha_doubles;   // backward: the partials of dW, db and dalpha, in this order in the workspace
+    size_t ws_bytes;
+};
+
+static Cin1ActPlan cin1_act_plan(const Mri3dConvGeom& g, int pass) {
+    Cin1ActPlan p{0, 0, 0, 0};
+    if (pass == MRI3D_PASS_FWD) {
+        p.ws_bytes = (size_t)27 * g.co * sizeof(float);   // the repacked weights [tap][co]
+        return p;
+    }
+    p.part_floats = (size_t)kCin1Shares * 27 * g.co, p.bias_floats = (size_t)kCin1Shares * g.co;
+    p.alpha_doubles = (size_t)kCin1Shares * g.co;
+    p.ws_bytes = (p.part_floats + p.bias_floats) * sizeof(float) + p.alpha_doubles * sizeof(double);   // (the floats: a multiple of 8 bytes)
+    return p;
+}
+
+size_t conv_cin1_act_workspace_bytes(const Mri3dConvGeom& g, int pass) { return cin1_act_plan(g, pass).ws_bytes; }
+
+bool conv_cin1_act_route_name(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, int pass, int align, char* name, size_t name_bytes) {
+    const int len = conv_cin1_act_supported(g, a_ld, act, alpha_n, pass, align)
+                        ? snprintf(name, name_bytes, "cin1 act %s co%d", pass == MRI3D_PASS_FWD ? "fwd" : "bwd", g.co)
+                        : snprintf(name, name_bytes, "none");
+    return len > 0 && (size_t)len < name_bytes;
+}
+
+int conv_cin1_act_fwd(const Mri3dConvGeom& g, int a_ld, int act, int alpha_n, float slope, const float* x, const float* w,
+                      const float* bias, const float* alpha, float* z, float* a, void* ws, size_t ws_bytes, hipStream_t s) {
+    MRI3D_REQUIRE(conv_cin1_act_supported(g, a_ld, act, alpha_n, MRI3D_PASS_FWD, ptr_align(z, a, ws)), MRI3D_ENOTSUP,
+                  "conv_cin1_act_fwd: geometry / activation / alignment not served (query mri3d_conv_cin1_act_supported)");
+    const Cin1ActPlan p = cin1_act_plan(g, MRI3D_PASS_FWD);
+    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, MRI3D_EWORKSPACE, "conv_cin1_act_fwd: workspace %zu < %zu", ws_bytes, p.ws_bytes);
+    float* wp = static_cast<float*>(ws);
+    hipLaunchKernelGGL(repack_w_kernel, dim3(1), dim3(256), 0, s, w, wp, g.co, 1, 27, g.co, 0);
+    const C1Tiles t = cin1_tiles(g);
+    const int grid = std::min((int)t.ntiles, 256 * 8);
+    const Cin1Act pa{alpha, alpha_n, act, slope};
+    if (g.co == 8)
+        hipLaunchKernelGGL(conv_cin1_act_fwd_kernel<8>, dim3(grid), dim3(256), 0, s, g, x, wp, bias, pa, z, a, a_ld, t.tilesD, t.tilesH,
+                           t.tilesW, (int)t.ntiles);
+    else
+        hipLaunchKernelGGL(conv_cin1_act_fwd_kernel<16>, dim3(grid), dim3(256), 0, s, g, x, wp, bias, pa, z, a, a_ld, t.tilesD, t.tilesH,
+                           t.tilesW, (int)t.ntiles);
+    return check_launch("conv_cin1_act_fwd");
+}
+
+int conv_cin1_act_bwd(const Mri3dConvGeom& g, int da_ld, int act, int alpha_n, float slope, const float* x, const float* z,
+                      const float* da, const float* alpha, float* dw, float* dbias, float* dalpha, void* ws, size_t ws_bytes,
+                      hipStream_t s) {
+    MRI3D_REQUIRE(conv_cin1_act_supported(g, da_ld, act, alpha_n, MRI3D_PASS_WGRAD, ptr_align(z, da, ws)), MRI3D_ENOTSUP,
+                  "conv_cin1_act_bwd: geometry / activation / alignment not served (query mri3d_conv_cin1_act_supported)");
+    const Cin1ActPlan p = cin1_act_plan(g, MRI3D_PASS_WGRAD);
+    MRI3D_REQUIRE(ws != nullptr && ws_bytes >= p.ws_bytes, MRI3D_EWORKSPACE, "conv_cin1_act_bwd: workspace %zu < %zu", ws_bytes, p.ws_bytes);
+    float* part = static_cast<float*>(ws);
+    float* bias_part = dbias ? part + p.part_floats : nullptr;
+    double* alpha_part = (dalpha && act == MRI3D_ACT_PRELU) ? reinterpret_cast<double*>(part + p.part_floats + p.bias_floats) : nullptr;
+    const C1Tiles t = cin1_tiles(g);
+    const Cin1Act pa{alpha, alpha_n, act, slope};
+    // every workgroup writes its slots, also when its share of the tiles is empty (zeros)
+    hipLaunchKernelGGL(conv_cin1_act_bwd_kernel<8>, dim3(kCin1Shares), dim3(768), 0, s, g, x, z, da, da_ld, pa, part, bias_part,
+                       alpha_part, t.tilesD, t.tilesH, t.tilesW, (int)t.ntiles, kCin1Shares);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(cdiv(g.co * 27 + g.co, 8)), dim3(256), 0, s, part, bias_part, dw, dbias, kCin1Shares,
+                       27, 1, g.co, 1, g.co);
+    if (alpha_part)
+        hipLaunchKernelGGL(cin1_act_dalpha_kernel, dim3(1), dim3(256), 0, s, alpha_part, kCin1Shares, g.co, alpha_n, dalpha);
+    return check_launch("conv_cin1_act_bwd");
 }
 
 }  // namespace mri3d

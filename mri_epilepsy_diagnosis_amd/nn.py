@@ -200,15 +200,35 @@ def fused_norm_act_pool(norm, act, x, pool):
                        (x,))
 
 
-def conv_norm_act(conv, norm, act, x, out=None, head=None, pool=None):
+def fused_conv_act(conv, act, x):
+    """act(conv(x)) as ONE operator (ops.conv3d_act) where that is served: `conv` a plain 3x3x3 Conv3d of one input channel with
+    stride 1, padding 1 and dilation 1, `act` a PReLU, LeakyReLU or ReLU, x an fp32 device tensor nobody wants a gradient of, and the
+    native predicate's yes.  Returns None — with nothing run — where it is not: the caller keeps the two operators."""
+    if not (isinstance(conv, Conv3d) and conv.padding_mode == "zeros" and conv.groups == 1 and not isinstance(conv.padding, str)
+            and tuple(conv.kernel_size) == (3, 3, 3) and tuple(conv.stride) == (1, 1, 1) and tuple(conv.padding) == (1, 1, 1)
+            and tuple(conv.dilation) == (1, 1, 1) and torch.is_tensor(x)):
+        return None
+    kind, alpha, slope = _act_spec(act)
+    if kind is None or not ops.conv3d_act_supported(x, conv.weight, kind, alpha):
+        return None
+    return ops.conv3d_act(x, conv.weight, conv.bias, alpha, kind, slope)
+
+
+def conv_norm_act(conv, norm, act, x, out=None, head=None, pool=None, fused_first=True):
     """act(norm(conv(x))) for a Conv3d module followed by a normalisation (`unet.UNet`'s ConvolutionalBlock, the conv -> BN ->
     ReLU stems of cnn_model.py).  When `norm` is a BatchNorm3d that will use BATCH statistics (training mode, local statistics)
     the convolution is asked to accumulate them in its epilogue, which saves the statistics pass over its output.
     head: a Conv3d module applied to the result (`unet.UNet`'s 1x1x1 classifier); the return value is then head(act(norm(conv(x)))),
     computed without storing the activation where `fused_norm_act_head` serves the case.
     pool: a MaxPool3d module applied to the result, which is also kept (`unet.UNet`'s encoder levels); the return value is then
-    (pool(a), a) for a = act(norm(conv(x))), from one operator where `fused_norm_act_pool` serves the case."""
-    wants = (isinstance(norm, tnn.modules.batchnorm._BatchNorm) and (norm.training or norm.running_mean is None)
+    (pool(a), a) for a = act(norm(conv(x))), from one operator where `fused_norm_act_pool` serves the case.
+    fused_first: without a normalisation, out, head or pool, the convolution and its activation run as one operator where
+    `fused_conv_act` serves the case (`unet.UNet`'s first layer)."""
+    if fused_first and norm is None and out is None and head is None and pool is None:
+        a = fused_conv_act(conv, act, x)
+        if a is not None:
+            return a
+    wants =(isinstance(norm, tnn.modules.batchnorm._BatchNorm) and (norm.training or norm.running_mean is None)
              and ops.sync_batchnorm_reducer() is None and isinstance(conv, Conv3d) and conv.padding_mode == "zeros"
              and conv.groups == 1 and not isinstance(conv.padding, str))
     if isinstance(x, (tuple, list)):

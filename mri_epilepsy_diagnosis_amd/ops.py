@@ -6,6 +6,7 @@ eager-PyTorch fallback (a CPU tensor raises), so a green GPU test always means t
 
 Reference operators replaced (file:line in /root/reference):
   conv3d               nn.Conv3d            unet.UNet via segmentation/routine.py:346-356; AE_model.py:9-26; cnn_model.py:14
+  conv3d_act           nn.Conv3d(1, 8|16, 3, padding=1) + PReLU/LeakyReLU/ReLU, the U-Net's first layer, as one operator
   conv_transpose3d     nn.ConvTranspose3d   AE_model.py:62-68,159
   norm_act             nn.BatchNorm3d / nn.InstanceNorm3d + PReLU/LeakyReLU/ReLU   AE_model.py:30-36; modified_3dunet.py:20-94
   max_pool3d           nn.MaxPool3d         AE_model.py:27; cnn_model.py:115-148,221
@@ -824,6 +825,132 @@ def conv3d(x, weight, bias=None, stride=1, padding=0, dilation=1, bn_stats=False
     """bn_stats=True: the caller applies a batch-statistics BatchNorm to the result next (nn.conv_norm_act); where the MFMA
     forward kernel serves the geometry its epilogue accumulates the statistics, and `norm_act` picks them up from the result."""
     return _apply_with_bn_stats(_Conv3dFn, bn_stats, _autocast_in(x), weight, bias, _triple(stride), _triple(padding), _triple(dilation))
+
+
+# ----------------------------------------------------------------------------------------------- first layer + activation
+# unet.UNet's first ConvolutionalBlock: Conv3d(1, 8, 3, padding=1) + PReLU, nothing in between.  One autograd node on two kernels
+# (mri3d_conv_cin1_act_fwd / _bwd) instead of conv, activation, activation backward and weight gradient: the pre-activation z is
+# stored once and its gradient never.
+
+
+def conv_cin1_act_route(g, a_ld, act_code, alpha_n, pass_, align=16):
+    """Name of the kernel mri3d_conv_cin1_act_fwd (PASS_FWD) / _bwd (PASS_WGRAD) launches for the convolution g, "none" where the
+    native predicate declines: host only, nothing is launched and no device is needed."""
+    name = ctypes.create_string_buffer(64)
+    check(_lib.lib().mri3d_conv_cin1_act_route(ctypes.byref(g), a_ld, act_code, alpha_n, pass_, align, name, 64), "conv_cin1_act_route")
+    return name.value.decode()
+
+
+def _cin1_act_alpha_n(act_code, alpha):
+    return 1 if act_code != ACT_PRELU else (alpha.numel() if alpha is not None else 0)
+
+
+def conv3d_act_supported(x, weight, act, alpha=None, out=None):
+    """True when `conv3d_act` serves act(conv3d(x, weight, bias, padding=1)) as one operator: what only the caller can see (an fp32
+    tensor outside an autocast region whose own gradient nobody wants, an NDHWC layout, an activation with a slope), then the
+    native predicate on the geometry.  Host only: it answers for host tensors too."""
+    if not (torch.is_tensor(x) and x.dim() == 5 and x.dtype == torch.float32 and not x.requires_grad):
+        return False
+    if _autocast_dtype is not None or act not in ("relu", "leaky_relu", "prelu"):
+        return False
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3) or weight.shape[1] != x.shape[1] or weight.dtype != torch.float32:
+        return False
+    if act == "prelu" and (alpha is None or alpha.dtype != torch.float32):
+        return False
+    x_ld = _pitch_of(x)
+    g = _conv_geom(x.shape, weight.shape, _ONE, _ONE, _ONE, x_ld=x.shape[1] if x_ld is None else x_ld)
+    act_code = _ACT_CODES[act]
+    z_ld = a_ld = g.co
+    if out is not None:
+        z_ld, a_ld = _pitch_of(out[0]), _pitch_of(out[1])
+        if z_ld is None or a_ld is None:
+            return False
+        g.y_ld = z_ld
+    align = 16 if out is None else _ptr_align(*out)
+    return bool(_lib.lib().mri3d_conv_cin1_act_supported(ctypes.byref(g), a_ld, act_code, _cin1_act_alpha_n(act_code, alpha), PASS_FWD, align))
+
+
+def _cin1_act_tag(kind, g):
+    return "conv3d_act_%s 1->%d @%dx%dx%d n%d" % (kind, g.co, g.dout, g.ho, g.wo, g.n)
+
+
+class _Conv3dActFn(torch.autograd.Function):
+    """a = act(z), z = conv3d(x, weight, bias, padding=1), for one input channel.  Saves x and z; the backward forms the gradient of
+    z in registers.  out: None, or (z, a) to write into (logical (N, Co, D, H, W) tensors of NDHWC memory, any pitch)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, alpha, act, slope, out):
+        _require_device(x)
+        _require_param(weight, bias, alpha)
+        L = _lib.lib()
+        x, x_ld = _nd(x)
+        w = weight.contiguous()
+        g = _conv_geom(x.shape, w.shape, _ONE, _ONE, _ONE, x_ld=x_ld)
+        shape = (g.n, g.co, g.dout, g.ho, g.wo)
+        z, a = (_new(shape, x), _new(shape, x)) if out is None else out
+        if tuple(z.shape) != shape or tuple(a.shape) != shape or z.dtype != x.dtype or a.dtype != x.dtype:
+            raise RuntimeError("conv3d_act(out=): two float32 tensors of shape %s expected" % (shape,))
+        g.y_ld, a_ld = _pitch_of(z), _pitch_of(a)
+        if g.y_ld is None or a_ld is None:
+            raise RuntimeError("conv3d_act(out=): the output tensors must be NDHWC in memory")
+        act_code = _ACT_CODES[act]
+        prelu = act_code == ACT_PRELU
+        alpha_n = _cin1_act_alpha_n(act_code, alpha)
+        _launch(L.mri3d_conv_cin1_act_fwd, lambda: _cin1_act_tag("fwd", g),
+                lambda: {"flops": _conv_work(g, "fwd")["flops"], "bytes": 4.0 * (x.numel() + 2 * z.numel())},
+                L.mri3d_conv_cin1_act_workspace_bytes(ctypes.byref(g), PASS_FWD), x.device,
+                g, a_ld, act_code, alpha_n, float(slope), x, w, bias, alpha if prelu else None, z, a)
+        ctx.save_for_backward(x, w, z, alpha if prelu else None)
+        ctx.geom, ctx.act, ctx.slope = g, (act_code, alpha_n), float(slope)
+        ctx.params, ctx.has_bias = (weight, bias, alpha if prelu else None), bias is not None
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        L = _lib.lib()
+        x, w, z, alpha = ctx.saved_tensors
+        g0 = ctx.geom
+        act_code, alpha_n = ctx.act
+        if da.dtype != z.dtype:
+            raise RuntimeError("conv3d_act backward: gradient dtype %s does not match activation dtype %s" % (da.dtype, z.dtype))
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("conv3d_act: no data gradient (ops.conv3d_act_supported declines an input that requires one)")
+        weight, bias, alpha_p = ctx.params
+        if not any(p is not None and ctx.needs_input_grad[1 + i] for i, p in enumerate(ctx.params)):
+            return None, None, None, None, None, None, None
+        da, da_ld = _nd(da)
+        csinks, cgrads = _grad_slots(ctx, (w, bias), 1, (weight, bias), all_written=True)
+        asinks, agrads = _grad_slots(ctx, (alpha,), 3, (alpha_p,))
+        dw, db = cgrads
+        dalpha = agrads[0]
+        g = _repitched(g0, g0.x_ld, g0.y_ld)
+        if L.mri3d_conv_cin1_act_supported(ctypes.byref(g), da_ld, act_code, alpha_n, PASS_WGRAD, _ptr_align(z, da)):
+            _launch(L.mri3d_conv_cin1_act_bwd, lambda: _cin1_act_tag("bwd", g),
+                    lambda: {"flops": _conv_work(g, "wgrad")["flops"], "bytes": 4.0 * (x.numel() + 2 * z.numel())},
+                    L.mri3d_conv_cin1_act_workspace_bytes(ctypes.byref(g), PASS_WGRAD), x.device,
+                    g, da_ld, act_code, alpha_n, ctx.slope, x, z, da, alpha, dw, db, dalpha)
+        else:
+            # where the backward kernel is not offered (sixteen output channels: the layer's weight gradient is an MFMA kernel
+            # with its own summation order): the activation's backward and the plain weight gradient, as without the fold
+            zd = z if g0.y_ld == g0.co else z.contiguous(memory_format=CL3D)
+            dz = _new(zd.shape, zd)
+            ng = NormGeom(g0.n, g0.dout * g0.ho * g0.wo, g0.co, g0.co, da_ld, 0, act_code, alpha_n, ctx.slope, 0.0, 0, F32)
+            ws = _workspace(L.mri3d_norm_workspace_bytes(ctypes.byref(ng)), x.device)
+            with _timed(lambda: "norm_act_bwd c%d vox%d n%d" % (ng.c, ng.vox, ng.n), lambda: {"flops": 0.0, "bytes": 20.0 * zd.numel()}):
+                check(L.mri3d_norm_act_bwd(ctypes.byref(ng), 0, _ptr(zd), _ptr(da), None, None, None, None, _ptr(alpha), _ptr(dz), None,
+                                           None, _ptr(dalpha), _ptr(ws), ws.numel(), _stream()), "norm_act_bwd")
+            _conv_wgrad(_repitched(g0, g0.x_ld, g0.co), x, dz, w, db is not None, dw, db)
+        return (None, *_grad_slots_done(ctx, cgrads, csinks, 1, (weight, bias)), *_grad_slots_done(ctx, agrads, asinks, 3, (alpha_p,)),
+                None, None, None)
+
+
+def conv3d_act(x, weight, bias=None, alpha=None, act="prelu", slope=0.01, out=None):
+    """act(conv3d(x, weight, bias, padding=1)) for a 3x3x3 kernel over ONE input channel and act = "prelu" (alpha: one slope or one
+    per channel), "leaky_relu" (slope) or "relu", as one operator — where `conv3d_act_supported`; a RuntimeError elsewhere (the
+    caller keeps ops.conv3d + ops.norm_act).  out = (z, a): tensors to write the pre-activation and the result into."""
+    if not conv3d_act_supported(x, weight, act, alpha, out):
+        raise RuntimeError("conv3d_act: not served for this input, kernel or activation (ask conv3d_act_supported)")
+    return _Conv3dActFn.apply(x, weight, bias, alpha, act, slope, out)
 
 
 # ----------------------------------------------------------------------------------------------- BayesConv3d

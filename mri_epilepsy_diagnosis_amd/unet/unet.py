@@ -49,10 +49,11 @@ class ConvolutionalBlock(tnn.Module):
         self.dropout_layer = None
         self.block = tnn.Sequential(*[m for m in (conv, norm, act) if m is not None])
 
-    def forward(self, x, out=None, head=None, pool=None):
+    def forward(self, x, out=None, head=None, pool=None, fused_first=True):
         # head: the classifier's 1x1x1 Conv3d, applied to this block's result (mnn.conv_norm_act)
         # pool: the encoder level's MaxPool3d; the result is then (pooled, this block's result)
-        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out, head, pool)
+        # fused_first: a block without normalisation may run its convolution and activation as one operator
+        return mnn.conv_norm_act(self.conv_layer, self.norm_layer, self.activation_layer, x, out, head, pool, fused_first)
 
 
 class EncodingBlock(tnn.Module):
@@ -74,14 +75,14 @@ class EncodingBlock(tnn.Module):
                 raise NotImplementedError("only max pooling is used by the reference")
             self.downsample = mnn.MaxPool3d(kernel_size=2)
 
-    def forward(self, x, skip_out=None, head=None, fused_pool=True):
+    def forward(self, x, skip_out=None, head=None, fused_pool=True, fused_first=True):
         # skip_out = (concat buffer, 0): the block's output is written straight into the decoder's concat buffer
         if self.downsample is None:
-            return self.conv2(self.conv1(x), skip_out, head)
+            return self.conv2(self.conv1(x, fused_first=fused_first), skip_out, head)
         if fused_pool and skip_out is None and isinstance(self.downsample, mnn.MaxPool3d):
             # (pooled, skip) from conv2's BatchNorm + activation pass itself where ops.norm_act_pool serves the level
-            return self.conv2(self.conv1(x), pool=self.downsample)
-        x = self.conv2(self.conv1(x), skip_out)
+            return self.conv2(self.conv1(x, fused_first=fused_first), pool=self.downsample)
+        x = self.conv2(self.conv1(x, fused_first=fused_first), skip_out)
         # (pooled, skip) from one autograd node: the two gradients of x are summed inside the pool-backward kernel
         return self.downsample.forward_with_skip(x)
 
@@ -107,10 +108,10 @@ class Encoder(tnn.Module):
             if self.dilation is not None:
                 self.dilation *= 2
 
-    def forward(self, x, cat_bufs=None, fused_pool=True):
+    def forward(self, x, cat_bufs=None, fused_pool=True, fused_first=True):
         skips = []
         for i, blk in enumerate(self.encoding_blocks):
-            x, skip = blk(x, None if cat_bufs is None else (cat_bufs[i], 0), fused_pool=fused_pool)
+            x, skip = blk(x, None if cat_bufs is None else (cat_bufs[i], 0), fused_pool=fused_pool, fused_first=fused_first)
             skips.append(skip)
         return skips, x
 
@@ -208,6 +209,10 @@ class UNet(tnn.Module):
         # the reference's API): same tensors and gradients bit for bit in fp32, without re-reading the activation or storing the
         # summed gradient of the skip connection and the pool
         self.fused_pool = True
+        # the first layer (Conv3d(1, c0, 3, padding=1) + activation, no normalisation) runs as one operator on two kernels (A/B
+        # switch; not part of the reference's API): same tensors and gradients bit for bit in fp32, without a pass of its own for
+        # the activation or a stored gradient of the pre-activation
+        self.fused_first = True
         self.classifier = ConvolutionalBlock(dimensions, 2 * out_channels_first_layer, out_classes, kernel_size=1,
                                              activation=None)
 
@@ -232,9 +237,9 @@ class UNet(tnn.Module):
         mc = mc if (mc is not None and mc.training and mc.p > 0) else None
         head = clf.conv_layer if (self.fused_head and mc is None and x.is_cuda and clf.norm_layer is None
                                   and clf.activation_layer is None and clf.dropout_layer is None) else None
-        skips, enc = self.encoder(x, cat_bufs, self.fused_pool)
+        skips, enc = self.encoder(x, cat_bufs, self.fused_pool, self.fused_first)
         if not skips:
-            x = self.bottom_block(enc, head=head)
+            x = self.bottom_block(enc, head=head, fused_first=self.fused_first)
         else:
             x = self.decoder(skips, self.bottom_block(enc), cat_bufs, head)
         if head is not None:
