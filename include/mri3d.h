@@ -599,6 +599,46 @@ int mri3d_surface_elements(const uint8_t* gt, const uint8_t* pred, int32_t d, in
                            void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Connected components of a mask or a class map (components.hip): what scipy.ndimage.label, np.bincount and a
+ * cluster filter give on the host, for the lesion-wise scores of a detector and the usual mask clean-up.  One (d,h,w) uint8
+ * volume in C order, d*h*w < 2^31 (else MRI3D_ENOTSUP); a 2-D map is a volume with d = 1.  All integer: the same bits every run.
+ * No allocation, no synchronisation; no kernel waits for another workgroup.
+ *
+ * mri3d_components_label: connectivity 6, 18 or 26 (faces; faces and edges; faces, edges and corners; anything else
+ *   MRI3D_EINVAL).  by_value == 0: foreground is mask != 0.  by_value != 0: two voxels connect only when their values are equal
+ *   and non-zero (the components of every class of a class map in one call).  labels: int32 (d,h,w), 0 = background, component ids
+ *   1..K in the order of each component's first voxel in C-order scan (scipy.ndimage.label's numbering); count[0] = K (device
+ *   int32).  Workspace: mri3d_components_workspace_bytes (0 for a volume the entry point refuses), 4-byte aligned.
+ * mri3d_components_stats: per component id 1..capacity (a row per id, row id-1; components above `capacity` are dropped)
+ *   stats[capacity][8] (device int64) = voxel count, count of voxels with other != 0 (0 without `other`), dmin, dmax, hmin, hmax,
+ *     wmin, wmax (inclusive; a row no voxel reaches: 0, 0, d, -1, h, -1, w, -1);
+ *   peak[capacity] (device float32) = max of `score` over the component (-inf for a row no voxel reaches); score and peak are
+ *     both given or both NULL; scores are finite (-0 orders below +0);
+ *   hit[capacity_other] (device uint8) = 1 where component j+1 of `other_labels`, a second int32 label volume, shares a voxel
+ *     with any foreground voxel (label > 0) of `labels`, else 0; other_labels, hit and capacity_other > 0 are given together or
+ *     all NULL / 0.  `other` (uint8 mask) and `other_labels` are independent of each other.
+ * mri3d_components_select: out[i] = keep[labels[i]] over nvox voxels; keep is a uint8 table of keep_len entries (count + 1, with
+ *   keep[0] = 0 for the background); a label outside the table selects 0.
+ * mri3d_components_plan_query: host only; what the launches of mri3d_components_label go by: tile extents, tiles per axis, the
+ *   grid of each of its six launches (tile union-find, boundary merge, root count, scan, rank, relabel), scan_blocks = block
+ *   counts the scan walks, offsets = backward neighbours per voxel (3, 9, 13), static LDS bytes of the tile kernel and the
+ *   workspace.  -1 for NULL, non-positive extents or a connectivity the entry point calls invalid, -2 for a volume it refuses. */
+typedef struct Mri3dComponentsPlanInfo {
+    int32_t td, th, tw, tiles_d, tiles_h, tiles_w, grid_local, grid_merge, grid_roots, grid_scan, grid_rank, grid_relabel,
+        scan_blocks, offsets;
+    int64_t lds_bytes, ws_bytes;
+} Mri3dComponentsPlanInfo;
+size_t mri3d_components_workspace_bytes(int32_t d, int32_t h, int32_t w);
+int32_t mri3d_components_plan_query(int32_t d, int32_t h, int32_t w, int32_t connectivity, Mri3dComponentsPlanInfo* out);
+int mri3d_components_label(const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t connectivity, int32_t by_value,
+                           int32_t* labels, int32_t* count, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_components_stats(const int32_t* labels, int32_t d, int32_t h, int32_t w, int32_t capacity, const uint8_t* other,
+                           const float* score, int64_t* stats, float* peak, const int32_t* other_labels, int32_t capacity_other,
+                           uint8_t* hit, mri3d_stream_t stream);
+int mri3d_components_select(const int32_t* labels, int64_t nvox, const uint8_t* keep, int32_t keep_len, uint8_t* out,
+                            mri3d_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Patch pipeline: the windows TorchIO cuts for patch training and grid inference
  * (torchio.Queue + torchio.sampler.ImageSampler, segmentation/routine.py:150-178 and pretraining_3d_unet.ipynb cell 24;
  * torchio.inference.GridSampler / GridAggregator.add_batch(labels, locations), pretraining_3d_unet.ipynb cell 26).

@@ -50,6 +50,12 @@ class MarchPlanInfo(Structure):
                                        "whole_chunks", "dispatcher")] + [("smem_bytes", c_int64), ("wp_bytes", c_int64)]
 
 
+class ComponentsPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("td", "th", "tw", "tiles_d", "tiles_h", "tiles_w", "grid_local", "grid_merge", "grid_roots",
+                                       "grid_scan", "grid_rank", "grid_relabel", "scan_blocks", "offsets")] + \
+               [("lds_bytes", c_int64), ("ws_bytes", c_int64)]
+
+
 class PoolGeom(Structure):
     _fields_ = [(n, c_int32) for n in (
         "n", "di", "hi", "wi", "dout", "ho", "wo", "c", "kd", "kh", "kw", "sd", "sh", "sw", "pd", "ph", "pw",
@@ -162,6 +168,11 @@ SIGNATURES = {
     "mri3d_surface_distance_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mri3d_surface_distance": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_elements": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P]),
+    "mri3d_components_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "mri3d_components_plan_query": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(ComponentsPlanInfo)]),
+    "mri3d_components_label": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
+    "mri3d_components_stats": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _FP, _P, _FP, _P, c_int32, _P, _P]),
+    "mri3d_components_select": (c_int32, [_P, c_int64, _P, c_int32, _P, _P]),
     "mri3d_extract_patches": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32,
                                         c_int32, _P, _P]),
     "mri3d_aggregate_patches_u8": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P,

@@ -105,6 +105,25 @@ class FCDMaskGenerator:
         n_and, n_or = (int(v) for v in ops.mask_overlap_counts(pred_mask, true_mask)[3:].tolist())
         return n_and / n_or if n_or else float("nan")
 
+    def lesion_report(self, pred_mask, true_mask, connectivity=26):
+        """Lesion-wise scores of a predicted mask against `true_mask > 0` (segmentation.components.lesion_scores): lesions hit
+        and missed, true and false clusters, their sizes; the voxel-wise counterpart is `get_iou`."""
+        from ..segmentation.components import lesion_scores
+        if pred_mask.shape != true_mask.shape:
+            raise RuntimeError("lesion_report: wrong shape of masks, %s vs %s" % (tuple(pred_mask.shape), tuple(true_mask.shape)))
+        return lesion_scores(pred_mask, (true_mask > 0).to(torch.uint8), connectivity)
+
+    def clusters(self, pred_mask, top_k=None, connectivity=26):
+        """The connected clusters of a predicted mask, largest first (then by id): a dict of device tensors "ids" (int64, 1-based,
+        numbered by first voxel in C order), "sizes" (int64) and "boxes" (int64 [K, 6]: inclusive min and max per axis), the first
+        `top_k` of them."""
+        from ..segmentation.components import components
+        c = components(pred_mask, connectivity)
+        order = torch.sort(c.sizes, descending=True, stable=True).indices
+        if top_k is not None:
+            order = order[:int(top_k)]
+        return {"ids": order + 1, "sizes": c.sizes[order], "boxes": c.boxes[order]}
+
     def inference_pipeline(self, volume, mask=None):
         """model_utils.py:234-246 without the NIfTI reading and writing: (predicted uint8 mask, IoU against `mask > 0` or None)."""
         pred = self.get_mask(min_max_normalize(volume.to(torch.float32)))

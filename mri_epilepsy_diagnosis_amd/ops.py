@@ -18,7 +18,8 @@ Reference operators replaced (file:line in /root/reference):
   softmax_dice_index_loss   the same loss against a uint8 class map (2..32 classes)   segmentation/routine.py:272-274
   gaussian_kde / intensity_moments   scipy.stats.gaussian_kde over a volume's voxels   full_sample_classification.ipynb cell 9
 Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd);
-confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask.
+confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask; label_components / component_stats /
+select_components, the connected components of a mask (scipy.ndimage.label's numbering), their tables and the masks they select.
 """
 import collections
 import ctypes
@@ -2146,6 +2147,144 @@ def class_scores_from_confusion(conf):
             dice[k] = 2 * tp / (sg + sp)
             iou[k] = float(np.float32(tp)) / np.float32(sg + sp - tp)
     return dice, iou
+
+
+# ----------------------------------------------------------------------------------------------- connected components (csrc/components.hip)
+COMPONENTS_PLAN_FIELDS = tuple(f for f, _ in _lib.ComponentsPlanInfo._fields_)
+COMPONENT_STATS_COLUMNS = ("count", "overlap", "dmin", "dmax", "hmin", "hmax", "wmin", "wmax")
+_CONNECTIVITY = {1: 6, 2: 18, 3: 26, 6: 6, 18: 18, 26: 26}
+
+
+def _connectivity(who, connectivity):
+    if connectivity not in _CONNECTIVITY:
+        raise ValueError("%s: connectivity must be 6, 18 or 26 (or scipy's 1, 2, 3), got %r" % (who, connectivity))
+    return _CONNECTIVITY[connectivity]
+
+
+def _dhw(who, t):
+    """A (d, h, w) volume or an (h, w) map (d = 1) as its three extents."""
+    if t.dim() not in (2, 3):
+        raise RuntimeError("%s: expected a (d, h, w) volume or an (h, w) map, got shape %s" % (who, tuple(t.shape)))
+    return (1,) * (3 - t.dim()) + tuple(int(s) for s in t.shape)
+
+
+def _volume_like(who, what, t, dtype, like):
+    """An optional companion volume of `like`'s shape and device, contiguous, of the given dtype (bool counts as uint8)."""
+    if t is None:
+        return None
+    _require_labels(who, t)
+    if t.dtype == torch.bool and dtype == torch.uint8:
+        t = t.view(torch.uint8)
+    if t.dtype != dtype or t.shape != like.shape or t.device != like.device:
+        raise RuntimeError("%s: %s must be a %s tensor of shape %s on %s, got %s %s on %s"
+                           % (who, what, dtype, tuple(like.shape), like.device, t.dtype, tuple(t.shape), t.device))
+    return t.contiguous()
+
+
+def components_plan(shape, connectivity):
+    """What the launches of `label_components` go by for a (d, h, w) or (h, w) shape: COMPONENTS_PLAN_FIELDS as a dict (host only)."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3):
+        raise RuntimeError("components_plan: expected (d, h, w) or (h, w), got %s" % (shape,))
+    d, h, w = (1,) * (3 - len(shape)) + shape
+    info = _lib.ComponentsPlanInfo()
+    rc = _lib.lib().mri3d_components_plan_query(d, h, w, _connectivity("components_plan", connectivity), ctypes.byref(info))
+    if rc != 0:
+        raise RuntimeError("components_plan: the library refuses shape %s (rc=%d)" % (shape, rc))
+    return {f: getattr(info, f) for f in COMPONENTS_PLAN_FIELDS}
+
+
+def label_components(mask, connectivity=6, by_value=False, out=None):
+    """Connected components of a uint8 / bool device mask (d, h, w) or (h, w) -> (labels, count): int32 labels of the mask's
+    shape, 0 for background and 1..K numbered by each component's first voxel in C order (scipy.ndimage.label's numbering, the
+    same bits every run), and K as an int32 device scalar.  connectivity 6 / 18 / 26 (or scipy's 1 / 2 / 3); by_value: voxels
+    connect only when their values are equal and non-zero (the components of every class of a class map)."""
+    who = "label_components"
+    _require_labels(who, mask)
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8:
+        raise RuntimeError("%s: the mask must be uint8 or bool, got %s" % (who, mask.dtype))
+    conn = _connectivity(who, connectivity)
+    d, h, w = _dhw(who, mask)
+    mask = mask.contiguous()
+    if out is None:
+        out = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+    elif out.dtype != torch.int32 or out.shape != mask.shape or out.device != mask.device or not out.is_contiguous():
+        raise RuntimeError("%s: out must be a contiguous int32 tensor of the mask's shape and device" % who)
+    count = torch.zeros((), dtype=torch.int32, device=mask.device)
+    if mask.numel():
+        L = _lib.lib()
+        ws = _workspace(L.mri3d_components_workspace_bytes(d, h, w), mask.device)
+        check(L.mri3d_components_label(_ptr(mask), d, h, w, conn, int(bool(by_value)), _ptr(out), _ptr(count), _ptr(ws), ws.numel(),
+                                       _stream()), "components_label")
+    return out, count
+
+
+def component_stats(labels, capacity, other=None, other_labels=None, score=None, other_capacity=None, out=None):
+    """Per-component tables of an int32 label volume, ids 1..capacity (row id - 1; ids above are dropped), as device tensors:
+      "stats"  int64 (capacity, 8), columns COMPONENT_STATS_COLUMNS: voxels, voxels with other != 0 (`other`: a uint8 / bool mask),
+               and the inclusive bounding box; a row no voxel reaches holds 0, 0, d, -1, h, -1, w, -1
+      "peak"   float32 (capacity,), the maximum of the float32 volume `score` over the component (with `score`; finite scores)
+      "hit"    uint8 (other_capacity,), 1 where component j + 1 of the int32 volume `other_labels` shares a voxel with any labelled
+               voxel of `labels` (with `other_labels`; other_capacity is then required)
+    out: a dict of preallocated contiguous tensors for any of the three."""
+    who = "component_stats"
+    _require_labels(who, labels)
+    if labels.dtype != torch.int32:
+        raise RuntimeError("%s: labels must be int32, got %s" % (who, labels.dtype))
+    d, h, w = _dhw(who, labels)
+    labels = labels.contiguous()
+    capacity = int(capacity)
+    if capacity <= 0:
+        raise ValueError("%s: capacity must be positive, got %d" % (who, capacity))
+    other = _volume_like(who, "other", other, torch.uint8, labels)
+    score = _volume_like(who, "score", score, torch.float32, labels)
+    other_labels = _volume_like(who, "other_labels", other_labels, torch.int32, labels)
+    if (other_labels is None) != (other_capacity is None) or (other_capacity is not None and int(other_capacity) <= 0):
+        raise ValueError("%s: other_labels and a positive other_capacity are given together" % who)
+    out = {} if out is None else out
+    want = {"stats": ((capacity, 8), torch.int64)}
+    if score is not None:
+        want["peak"] = ((capacity,), torch.float32)
+    if other_labels is not None:
+        want["hit"] = ((int(other_capacity),), torch.uint8)
+    res = {}
+    for k, (shape, dtype) in want.items():
+        t = out.get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=labels.device)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != labels.device or not t.is_contiguous():
+            raise RuntimeError("%s: out[%r] must be a contiguous %s tensor of shape %s on the labels' device" % (who, k, dtype, shape))
+        res[k] = t
+    if labels.numel() == 0:
+        raise RuntimeError("%s: empty volume" % who)
+    check(_lib.lib().mri3d_components_stats(_ptr(labels), d, h, w, capacity, _ptr(other), _ptr(score), _ptr(res["stats"]),
+                                            _ptr(res.get("peak")), _ptr(other_labels), int(other_capacity or 0), _ptr(res.get("hit")),
+                                            _stream()), "components_stats")
+    return res
+
+
+def select_components(labels, keep, out=None):
+    """out[i] = keep[labels[i]]: the uint8 mask of the components a uint8 device table keeps (count + 1 entries, keep[0] = 0 for
+    the background; a label beyond the table selects 0).  One streaming pass."""
+    who = "select_components"
+    _require_labels(who, labels, keep)
+    if labels.dtype != torch.int32:
+        raise RuntimeError("%s: labels must be int32, got %s" % (who, labels.dtype))
+    if keep.dtype == torch.bool:
+        keep = keep.view(torch.uint8)
+    if keep.dtype != torch.uint8 or keep.dim() != 1 or keep.numel() == 0 or keep.device != labels.device:
+        raise RuntimeError("%s: keep must be a non-empty 1-D uint8 / bool tensor on the labels' device" % who)
+    labels, keep = labels.contiguous(), keep.contiguous()
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    elif out.dtype != torch.uint8 or out.shape != labels.shape or out.device != labels.device or not out.is_contiguous():
+        raise RuntimeError("%s: out must be a contiguous uint8 tensor of the labels' shape and device" % who)
+    if labels.numel():
+        check(_lib.lib().mri3d_components_select(_ptr(labels), labels.numel(), _ptr(keep), keep.numel(), _ptr(out), _stream()),
+              "components_select")
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- intensity statistics (csrc/intensity.hip)

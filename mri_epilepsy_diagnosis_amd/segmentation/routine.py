@@ -188,6 +188,25 @@ def validate_classes(model, loader, label_map, prepare=None):
     return dice, iou
 
 
+def validate_lesions(model, loader, connectivity=26, min_voxels=0, prepare=None):
+    """Lesion-wise scores per volume: for the first volume of every batch (as `validate_dsc_asd`), components.lesion_scores of the
+    arg-max mask against the target, both on the device: a lesion is a connected component of the target, a cluster one of the
+    prediction (clusters under `min_voxels` voxels are dropped first).  Returns the list of score dicts; only their small tables
+    cross to the host.  prepare(batch, device) -> (inputs, targets) defaults to `prepare_batch`."""
+    from . import components
+    scores = []
+    prepare = prepare_batch if prepare is None else prepare
+    model.eval()
+    for batch in loader:
+        inputs, targets = prepare(batch, device)
+        with torch.no_grad():
+            logits = forward(model, inputs)
+        labels = ops.argmax_mask(logits)
+        gt = (targets[0][0] != 0).to(torch.uint8).to(labels.device)
+        scores.append(components.lesion_scores(labels[0], gt, connectivity, min_voxels))
+    return scores
+
+
 def get_dice_score(output, target, SPATIAL_DIMENSIONS=(2, 3, 4), epsilon=1e-9):
     """Tensor-formula helper kept for API compatibility; the training loop uses the fused HIP loss instead."""
     p0, g0 = output, target
