@@ -829,6 +829,58 @@ int mri3d_adam_step(float* p, const float* g, float* m, float* v, int64_t n, flo
                     float eps, float weight_decay, int32_t step, float grad_scale, int32_t decoupled,
                     mri3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Affine registration to a template (register.hip): the device pieces of an intensity-based registration, the counterpart of
+ * the FLIRT call in the reference's detection/preprocessing_utils.py:11-73.  Volumes are dense (d, h, w); the "fixed" volume is
+ * the template's grid, the "moving" one the subject's.  An affine is 12 fp32 numbers, a row-major (3, 4) matrix that maps a
+ * fixed voxel index o = (d, h, w) to a moving voxel index, warp3d's convention.  The file is compiled without contraction and
+ * writes no fused multiply-add: every * and + below is one fp32 rounding, in the order written (tests/register_ref.py restates it).
+ *
+ *   coordinates   r_a = (A[a][0]*d + A[a][1]*h) + A[a][3]          s_a = A[a][2]*w + r_a                  a = 0, 1, 2
+ *   inside        -0.5 <= s_a <= N_a - 0.5 on all three axes (N the moving extents); a NaN coordinate is outside
+ *   trilinear     q_a = min(max(s_a, -1), N_a)   e_a = floor(q_a)   f_a = q_a - e_a (exact)   indices e_a, e_a + 1 clamped to
+ *                 [0, N_a - 1];  along w: x = v0 + f_2*(v1 - v0) for the four (d, h) corner pairs, then along h:
+ *                 y = x0 + f_1*(x1 - x0), then along d: v = y0 + f_0*(y1 - y0)
+ *   nearest       index clamp(floor(q_a + 0.5), 0, N_a - 1)
+ *
+ * mri3d_quantize_u8: out[i] = clamp(floor((x[i] - lo) * scale), 0, bins - 1) as a byte; 255 ("skip") where the mask byte is 0
+ *   (mask may be NULL) or x[i] is not finite.  2 <= bins <= 64, scale finite.
+ * mri3d_joint_hist: for candidate c of k (1..64), every fixed voxel o whose byte bf = fixed_bins[o] is not 255 and whose sample
+ *   under affines[c] is inside adds 1 to hist[c][bf][bm], bm = clamp(floor((v - m_lo) * m_scale), 0, bins - 1) (a NaN v goes to
+ *   bin 0).  A fixed byte in bins..254 is treated as skip.  hist: DEVICE int64 (k, bins, bins), fully written.  affines: DEVICE
+ *   (k, 3, 4) fp32.  Counts are integers summed with integer atomics: the same inputs give the same bits whatever the workspace
+ *   held.  workspace: mri3d_joint_hist_workspace_bytes(df, hf, wf, k, bins) bytes (0 for invalid arguments), 4-byte aligned.
+ *   Every volume has fewer than 2^31 voxels (else MRI3D_ENOTSUP).
+ * mri3d_joint_hist_plan (host only): out = {blocks per candidate group, candidate groups, candidates that share one block's
+ *   fixed loads, fixed rows per block and trip (one per wave), trips of a block's row loop, LDS bytes, reduction stages, fixed
+ *   voxels per wave step}.
+ * mri3d_hist_costs: out[c] = {cost, n}, DEVICE float64 (k, 2), n the counted samples of hist[c], one block per candidate, float64
+ *   in a fixed order.  With p = hist / n, p_i its row sums (fixed), p_j its column sums (moving), y_j = j + 0.5:
+ *     kind 0  correlation ratio   sum_i p_i Var_i(y) / Var(y),  Var_i(y) = sum_j p_ij (y_j - mean_i)^2 / p_i
+ *     kind 1  -MI = -(H_f + H_m - H_fm),  H = -sum p log p (natural logarithm)
+ *     kind 2  -(H_f + H_m) / H_fm
+ *   +inf when n < min_count, n == 0 or the denominator (Var(y), H_fm) is 0.
+ * mri3d_resample_affine: image_out[o] = trilinear sample of `image`, pad_value outside; label_out[o] = the raw bits of the
+ *   nearest element of `label` (label_bytes 1, 2 or 4), zero bits outside.  One pass writes both; either pair may be NULL, not
+ *   both.  `affine`: DEVICE, 12 floats.  No destination may overlap a source or the affine.
+ * mri3d_downsample2_mean_f32: y (ceil(d/2), ceil(h/2), ceil(w/2)); y[o] = (sum of the voxels of x in the cell 2o .. 2o + 1 that
+ *   exist, added in (d, h, w) order to a sum that starts at the first) * (1 / their number); the number is 1, 2, 4 or 8.
+ * No entry allocates or synchronises; arguments are validated on the host before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+int mri3d_quantize_u8(const float* x, const uint8_t* mask, int64_t n, float lo, float scale, int32_t bins, uint8_t* out,
+                      mri3d_stream_t stream);
+size_t mri3d_joint_hist_workspace_bytes(int32_t df, int32_t hf, int32_t wf, int32_t k, int32_t bins);
+int mri3d_joint_hist_plan(int32_t df, int32_t hf, int32_t wf, int32_t k, int32_t bins, int32_t out[8]);
+int mri3d_joint_hist(const uint8_t* fixed_bins, int32_t df, int32_t hf, int32_t wf, const float* moving, int32_t dm, int32_t hm,
+                     int32_t wm, const float* affines, int32_t k, float m_lo, float m_scale, int32_t bins, int64_t* hist,
+                     void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_hist_costs(const int64_t* hist, int32_t k, int32_t bins, int32_t kind, double min_count, double* out,
+                     mri3d_stream_t stream);
+int mri3d_resample_affine(const float* image, float* image_out, const void* label, void* label_out, int32_t label_bytes,
+                          int32_t dm, int32_t hm, int32_t wm, int32_t df, int32_t hf, int32_t wf, const float* affine,
+                          float pad_value, mri3d_stream_t stream);
+int mri3d_downsample2_mean_f32(const float* x, int32_t d, int32_t h, int32_t w, float* y, mri3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2359,6 +2359,133 @@ def gaussian_kde(x, num_positions=100, positions=None, bw_method=None, mask=None
     return pos_out, density
 
 
+# ----------------------------------------------------------------------------------------------- registration (csrc/register.hip)
+JOINT_HIST_PLAN_FIELDS = ("blocks", "groups", "group_candidates", "rows_per_trip", "trips", "lds_bytes", "stages", "wave_step")
+HIST_COST_KINDS = {"corratio": 0, "mi": 1, "nmi": 2}
+_RESAMPLE_LABEL_DTYPES = (torch.uint8, torch.int8, torch.bool, torch.int16, torch.int32)
+
+
+def _volume(who, what, t, dtypes):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype not in dtypes:
+        raise RuntimeError("%s: %s must be a %s ROCm device tensor (got %s on %s); there is no CPU fallback"
+                           % (who, what, "/".join(str(d) for d in dtypes), getattr(t, "dtype", type(t)), getattr(t, "device", "host")))
+    if t.dim() != 3 or t.numel() == 0:
+        raise RuntimeError("%s: %s must be a non-empty (d, h, w) volume, got shape %s" % (who, what, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _affines(who, affines, device):
+    """(k, 3, 4) fixed-voxel -> moving-voxel matrices as a contiguous fp32 device tensor (host arrays and float64 are converted)."""
+    a = torch.as_tensor(affines)
+    if a.dim() == 2:
+        a = a[None]
+    if a.dim() != 3 or tuple(a.shape[1:]) != (3, 4) or a.shape[0] == 0:
+        raise RuntimeError("%s: affines must be (k, 3, 4) or (3, 4), got shape %s" % (who, tuple(a.shape)))
+    return a.to(device=device, dtype=torch.float32).contiguous()
+
+
+def quantize_bins(x, lo, scale, bins, mask=None):
+    """Histogram bin of every voxel of a float32 device tensor as uint8: clamp(floor((x - lo) * scale), 0, bins - 1), and 255
+    ("skip") where `mask` (bool / uint8, same shape) is zero or x is not finite.  2 <= bins <= 64."""
+    if not x.is_cuda or x.dtype != torch.float32:
+        raise RuntimeError("quantize_bins: needs a float32 ROCm device tensor (got %s on %s); there is no CPU fallback" % (x.dtype, x.device))
+    x = x.contiguous()
+    if mask is not None:
+        if not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tuple(x.shape):
+            raise RuntimeError("quantize_bins: the mask must be a bool / uint8 device tensor of shape %s (got %s %s on %s)"
+                               % (tuple(x.shape), tuple(mask.shape), mask.dtype, mask.device))
+        mask = mask.contiguous().view(torch.uint8)
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    check(_lib.lib().mri3d_quantize_u8(_ptr(x), _ptr(mask), x.numel(), float(lo), float(scale), int(bins), _ptr(out), _stream()),
+          "quantize_u8")
+    return out
+
+
+def joint_hist_plan(fixed_shape, k, bins):
+    """What one `joint_histogram` launch is built from, as a dict over JOINT_HIST_PLAN_FIELDS (host only)."""
+    d, h, w = (int(s) for s in fixed_shape)
+    out = (ctypes.c_int32 * 8)()
+    check(_lib.lib().mri3d_joint_hist_plan(d, h, w, int(k), int(bins), out), "joint_hist_plan")
+    return dict(zip(JOINT_HIST_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def joint_histogram(fixed_bins, moving, affines, m_lo, m_scale, bins, out=None):
+    """Joint histograms of a quantised fixed volume (uint8 from `quantize_bins`, 255 = skip) and a float32 moving volume sampled
+    trilinearly under each of k <= 64 candidate affines ((k, 3, 4), fixed voxel index -> moving voxel index): an int64 (k, bins, bins)
+    device tensor, hist[c][fixed bin][moving bin].  Samples outside the moving volume are not counted."""
+    fixed_bins = _volume("joint_histogram", "fixed_bins", fixed_bins, (torch.uint8,))
+    moving = _volume("joint_histogram", "moving", moving, (torch.float32,))
+    affines = _affines("joint_histogram", affines, moving.device)
+    k, bins = affines.shape[0], int(bins)
+    if out is None:
+        out = torch.empty((k, max(bins, 0), max(bins, 0)), dtype=torch.int64, device=moving.device)
+    elif tuple(out.shape) != (k, bins, bins) or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError("joint_histogram: out must be a contiguous (%d, %d, %d) int64 device tensor" % (k, bins, bins))
+    L = _lib.lib()
+    df, hf, wf = fixed_bins.shape
+    dm, hm, wm = moving.shape
+    ws = _workspace(L.mri3d_joint_hist_workspace_bytes(df, hf, wf, k, bins), moving.device)
+    check(L.mri3d_joint_hist(_ptr(fixed_bins), df, hf, wf, _ptr(moving), dm, hm, wm, _ptr(affines), k, float(m_lo), float(m_scale), bins,
+                             _ptr(out), _ptr(ws), ws.numel(), _stream()), "joint_hist")
+    return out
+
+
+def histogram_costs(hist, kind="corratio", min_count=0):
+    """Similarity costs of (k, bins, bins) int64 joint histograms on the device: a (k, 2) float64 tensor of {cost, counted samples}.
+    kind: 'corratio' (FLIRT's default), 'mi' (minus the mutual information) or 'nmi' (minus (H_f + H_m) / H_fm), or 0, 1, 2.
+    The cost is +inf below `min_count` samples or where the measure's denominator vanishes."""
+    if not hist.is_cuda or hist.dtype != torch.int64 or hist.dim() != 3 or hist.shape[1] != hist.shape[2] or hist.shape[0] == 0:
+        raise RuntimeError("histogram_costs: needs a (k, bins, bins) int64 ROCm device tensor (got %s %s on %s); there is no CPU fallback"
+                           % (tuple(hist.shape), hist.dtype, hist.device))
+    if isinstance(kind, str):
+        if kind not in HIST_COST_KINDS:
+            raise ValueError("histogram_costs: kind must be one of %s, got %r" % (sorted(HIST_COST_KINDS), kind))
+        kind = HIST_COST_KINDS[kind]
+    hist = hist.contiguous()
+    out = torch.empty((hist.shape[0], 2), dtype=torch.float64, device=hist.device)
+    check(_lib.lib().mri3d_hist_costs(_ptr(hist), hist.shape[0], hist.shape[1], int(kind), float(min_count), _ptr(out), _stream()),
+          "hist_costs")
+    return out
+
+
+def resample_affine(image=None, label=None, affine=None, out_shape=None, pad=0.0):
+    """Resample a (d, h, w) float32 image (trilinear) and / or a label map (nearest; uint8, int8, bool, int16 or int32) onto a grid of
+    `out_shape` under one (3, 4) affine from a destination voxel index to a source voxel index.  Outside the source the image gets
+    `pad` and the label 0.  Returns (image_out, label_out), None where no input was given."""
+    if image is None and label is None:
+        raise RuntimeError("resample_affine: neither an image nor a label map given")
+    if out_shape is None or len(tuple(out_shape)) != 3:
+        raise RuntimeError("resample_affine: out_shape must be (d, h, w), got %r" % (out_shape,))
+    df, hf, wf = (int(s) for s in out_shape)
+    if image is not None:
+        image = _volume("resample_affine", "image", image, (torch.float32,))
+    if label is not None:
+        label = _volume("resample_affine", "label", label, _RESAMPLE_LABEL_DTYPES)
+        if image is not None and (tuple(label.shape) != tuple(image.shape) or label.device != image.device):
+            raise RuntimeError("resample_affine: image %s and label %s differ in shape or device" % (tuple(image.shape), tuple(label.shape)))
+    src = image if image is not None else label
+    affine = _affines("resample_affine", affine, src.device)
+    if affine.shape[0] != 1:
+        raise RuntimeError("resample_affine: one (3, 4) affine expected, got %d" % affine.shape[0])
+    dm, hm, wm = src.shape
+    image_out = torch.empty((max(df, 0), max(hf, 0), max(wf, 0)), dtype=torch.float32, device=src.device) if image is not None else None
+    label_out = torch.empty((max(df, 0), max(hf, 0), max(wf, 0)), dtype=label.dtype, device=src.device) if label is not None else None
+    check(_lib.lib().mri3d_resample_affine(_ptr(image), _ptr(image_out), _ptr(label), _ptr(label_out),
+                                           label.element_size() if label is not None else 0, dm, hm, wm, df, hf, wf, _ptr(affine),
+                                           float(pad), _stream()), "resample_affine")
+    return image_out, label_out
+
+
+def downsample2(x):
+    """One level of the image pyramid: a (ceil(d/2), ceil(h/2), ceil(w/2)) float32 volume, each voxel the mean of the 1-8 voxels of
+    its 2x2x2 cell of `x` that exist."""
+    x = _volume("downsample2", "x", x, (torch.float32,))
+    d, h, w = x.shape
+    y = torch.empty(((d + 1) // 2, (h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=x.device)
+    check(_lib.lib().mri3d_downsample2_mean_f32(_ptr(x), d, h, w, _ptr(y), _stream()), "downsample2_mean")
+    return y
+
+
 # ----------------------------------------------------------------------------------------------- cat / add
 
 
