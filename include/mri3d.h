@@ -881,6 +881,47 @@ int mri3d_resample_affine(const float* image, float* image_out, const void* labe
                           float pad_value, mri3d_stream_t stream);
 int mri3d_downsample2_mean_f32(const float* x, int32_t d, int32_t h, int32_t w, float* y, mri3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Bias-field estimation over tissue classes (tissue.hip): the device passes of an EM for a K-class Gaussian mixture on
+ * log-intensity with a smooth multiplicative field, the model behind the `_restore` image that the reference takes from FSL FAST
+ * (detection/preprocessing_utils.py:11-53).  No MRF prior, no partial volumes, no spline field.  x: DEVICE fp32 (d, h, w), fewer
+ * than 2^31 voxels (else MRI3D_ENOTSUP); mask: DEVICE uint8 of the same shape or NULL.  All arithmetic is float64.
+ *
+ *   selected      mask byte != 0 (no mask: always), x finite and > 0;   y = log(x)
+ *   coordinates   (xh, yh, zh) = the voxel's (d, h, w) mapped to np.linspace(-1, 1, N) per axis (0 when N == 1), as bias_field
+ *   field         b = sum_n c_n xh^i yh^j zh^k, the terms in bias_field's nesting (i, then j, then k, i + j + k <= order),
+ *                 M = (order + 1)(order + 2)(order + 3) / 6 of them;  r = y - b
+ *   posteriors    p_k proportional to pi_k v_k^-1/2 exp(-(r - mu_k)^2 / (2 v_k)), normalised through the largest log term
+ *
+ * params_host: HOST array of 3K + M doubles (pi[K], mu[K], v[K], c[M]), read before the call returns.  2 <= classes <= 4,
+ * 0 <= order <= 3 (MRI3D_ENOTSUP above 3); pi finite and >= 0 with one > 0, mu and c finite, v finite and > 0 (else MRI3D_EINVAL).
+ *
+ * mri3d_tissue_em_pass: one pass with the parameters fixed.  sums: DEVICE float64, 2 + 3K + N2 + M numbers, fully written:
+ *     [0] n, the selected voxels           [1] LL = sum log sum_k pi_k N(r; mu_k, v_k), the -1/2 log 2 pi included
+ *     [2 + k] S0_k = sum p_k               [2 + K + k] S1_k = sum p_k r            [2 + 2K + k] S2_k = sum p_k r^2
+ *     [2 + 3K + m]      Mw[a][b][c] = sum w xh^a yh^b zh^c,  w = sum_k p_k / v_k,  the N2 = (2 order + 1)(2 order + 2)(2 order + 3) / 6
+ *                       exponent triples with a + b + c <= 2 order enumerated a, then b, then c (c fastest), m their running number
+ *     [2 + 3K + N2 + m] Mt[a][b][c] = sum t xh^a yh^b zh^c,  t = sum_k p_k (y - mu_k) / v_k,  a + b + c <= order, same enumeration
+ *   Two stages without float atomics: a wave sums one (d, h) row into 2 + 3K + (2 order + 1) + (order + 1) numbers in the
+ *   workspace, then one block per table entry adds the rows, times xh^a yh^b, in a fixed order.  The same inputs give the same
+ *   bits whatever the workspace held.  workspace: mri3d_tissue_em_workspace_bytes(d, h, w, classes, order) bytes (0 for invalid
+ *   arguments), 8-byte aligned; neither it nor sums may overlap x or the mask.
+ * mri3d_tissue_em_plan (host only): out = {stage-1 blocks, rows per block and trip (one per wave), trips of a block's row loop,
+ *   wave steps of 64 voxels per row, sums per row, table entries (= stage-2 blocks), stage-2 threads per entry, rows d * h}.
+ *   The workspace is out[4] * out[7] doubles.
+ * mri3d_tissue_apply: the final pass over EVERY voxel: restored = x exp(-b) and, unless NULL, field = exp(b), each rounded once
+ *   to fp32; labels (uint8) = 0 where the voxel is not selected, else 1 + the rank, by ascending mu (equal means in the caller's
+ *   order), of the class with the largest log pi_k - 1/2 log v_k - (r - mu_k)^2 / (2 v_k), the first of equal maxima in that
+ *   rank order.  restored == x (in place) is allowed; any other overlap among the buffers is MRI3D_EINVAL.
+ * No entry allocates or synchronises; arguments are validated on the host before any launch.
+ * ---------------------------------------------------------------------------------------------- */
+size_t mri3d_tissue_em_workspace_bytes(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order);
+int mri3d_tissue_em_plan(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order, int32_t out[8]);
+int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                         const double* params_host, double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                       const double* params_host, float* restored, uint8_t* labels, float* field, mri3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

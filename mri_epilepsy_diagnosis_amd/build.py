@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libmri3d_hip.so")
-SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip"]
+SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip", "tissue.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file additions.  conv_march.hip keeps its accumulators in v160..v255 BY NAME (inline asm), above the v0..v159 that
@@ -25,8 +25,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-u
 # tests/intensity_ref.py restates operation by operation: no contraction there either.
 # register.hip documents the fp32 order of its coordinates and interpolation, one rounding per * and +, and
 # tests/register_ref.py emulates it: no contraction.
+# tissue.hip is float64 throughout and tests/tissue_ref.py restates its expressions as written: no contraction.
 EXTRA_FLAGS = {"conv_march.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mc_stats.hip": ["-ffp-contract=off"],
-               "intensity.hip": ["-ffp-contract=off"], "register.hip": ["-ffp-contract=off"]}
+               "intensity.hip": ["-ffp-contract=off"], "register.hip": ["-ffp-contract=off"], "tissue.hip": ["-ffp-contract=off"]}
 
 
 def _digest(path):

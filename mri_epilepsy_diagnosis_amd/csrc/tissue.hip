@@ -1,0 +1,382 @@
+// tissue.hip — the device passes of a bias-field estimator over tissue classes: a K-class Gaussian mixture on log-intensity with
+// a smooth multiplicative field, exp(b), b a polynomial of order <= 3 in the voxel's normalised coordinates (the field family
+// of mri3d_bias_field_f32, same coordinates, same nesting of the coefficients).  Reference: get_registered_img_and_mask
+// (detection/preprocessing_utils.py:11-53) calls FSL FAST for its bias-corrected `_restore` image; this is the model FAST's
+// correction rests on (Wells / Van Leemput), not a clone of it.  The host loop that drives these passes is
+// mri_epilepsy_diagnosis_amd/tissue/.
+//
+// All arithmetic is float64, log and exp included; the input is fp32 and the outputs of the final pass are rounded once.  The
+// file is compiled with -ffp-contract=off.
+//
+// mri3d_tissue_em_pass, two stages, no float atomics:
+//   rows   one wave per (d, h) row, 4 rows per block and trip; lanes stride along w, 64 voxels per wave step (a wave step whose
+//          voxels are all unselected costs its loads and one ballot).  The (xh, yh) part of the polynomial is hoisted out of the
+//          w loop: b = ((q3 zh + q2) zh + q1) zh + q0.  A lane keeps R = 2 + 3K + (2 order + 1) + (order + 1) sums: n, LL,
+//          S0/S1/S2 per class, sum w zh^q, sum t zh^q; they are reduced over the wave in a fixed tree (tis_wave_sum) and lane 0 stores the
+//          row's R numbers at part[slot][row] of the workspace.  Every row writes every slot: what the workspace held before
+//          never reaches a result.
+//   fold   one block of 1024 threads per entry of the table: thread t adds the rows t, t + 1024, ... of the entry's slot times
+//          xh^a yh^b in ascending order, and the 1024 sums meet in a fixed tree in LDS.  Same inputs, same bits.
+// 4-byte loads per lane on purpose: the pass is bound by its float64 arithmetic, and at the template's W = 182 a wave step of
+// 64 voxels keeps 182 / 192 of the lanes busy where a 16-byte step of 256 voxels would keep 182 / 256.
+#include "common.h"
+#include <math.h>
+
+namespace mri3d {
+
+constexpr int kTisWaves = 4;            // rows per block and trip
+constexpr int kTisMaxBlocks = 8192;     // stage-1 grid cap: blocks beyond the resident ones back-fill as others finish
+constexpr int kTisFoldThreads = 1024;
+constexpr int kTisMaxK = 4;
+constexpr int kTisCoef = 20;            // order-3 nesting
+constexpr int kTisMaxEntries = 128;     // >= 2 + 3*4 + 84 + 20
+
+struct TisParams {
+    double a[kTisMaxK];      // log pi - 0.5 log v (- 0.5 log 2 pi in the EM pass)
+    double mu[kTisMaxK];
+    double inv_v[kTisMaxK];  // 1 / v
+    double hiv[kTisMaxK];    // 1 / (2 v)
+    double c[kTisCoef];      // order-3 layout; terms above the caller's order are zero
+    double d0, h0, w0, step_d, step_h, step_w;   // coordinate of index i along an axis: x0 + i * step
+};
+
+struct TisFold { uint8_t slot[kTisMaxEntries], a[kTisMaxEntries], b[kTisMaxEntries]; };
+
+// b at (xh, yh) as a cubic in zh: q[k] = sum_{i + j <= 3 - k} c_ijk xh^i yh^j
+__device__ __forceinline__ void tis_row(const double* c, double xh, double yh, double q[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0.0;
+    int n = 0;
+    double xi = 1.0;
+#pragma unroll
+    for (int i = 0; i <= 3; ++i) {
+        double yj = xi;
+#pragma unroll
+        for (int j = 0; j <= 3 - i; ++j) {
+#pragma unroll
+            for (int k = 0; k <= 3 - i - j; ++k) q[k] = q[k] + c[n++] * yj;
+            yj = yj * yh;
+        }
+        xi = xi * xh;
+    }
+}
+
+// The sum of v over the wave, the same bits in every lane.  The four levels inside a row of 16 lanes are DPP moves (VALU, no LDS):
+// lanes 1 apart, 2 apart (quad permutes), then the other quad of an 8 (half mirror) and the other 8 of the row (mirror); a level's
+// partners hold equal sums, so a mirror pairs as well as an xor.  The two levels across rows are shuffles.  22 sums a row through six
+// shuffle levels each kept the CU's one LDS pipe busier than its four SIMDs.
+template <int CTRL>
+__device__ __forceinline__ double tis_dpp(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double tis_wave_sum(double v) {
+    v = v + tis_dpp<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+    v = v + tis_dpp<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+    v = v + tis_dpp<0x141>(v);   // row_half_mirror
+    v = v + tis_dpp<0x140>(v);   // row_mirror
+    v = v + __shfl_xor(v, 16, 64);
+    v = v + __shfl_xor(v, 32, 64);
+    return v;
+}
+
+__device__ __forceinline__ bool tis_selected(const uint8_t* mr, int w, float xv) {
+    return (mr ? mr[w] != 0 : true) && isfinite(xv) && xv > 0.f;
+}
+
+// ------------------------------------------------------------------ EM pass, stage 1: per-row sums
+template <int K, int ORDER>
+__global__ void __launch_bounds__(64 * kTisWaves)
+tissue_em_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p,
+                      double* __restrict__ part) {
+    constexpr int NW = 2 * ORDER + 1, NT = ORDER + 1, R = 2 + 3 * K + NW + NT;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rows = D * H;   // < 2^31, checked by the host
+    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
+        const int d = row / H, h = row - d * H;
+        double q[4];
+        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
+        double acc[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) acc[i] = 0.0;
+        const float* xr = x + (size_t)row * W;
+        const uint8_t* mr = mask ? mask + (size_t)row * W : nullptr;
+        for (int w0 = 0; w0 < W; w0 += 64) {
+            const int w = w0 + lane;
+            float xv = 0.f;
+            bool sel = false;
+            if (w < W) {
+                xv = xr[w];
+                sel = tis_selected(mr, w, xv);
+            }
+            if (__ballot(sel) == 0ull) continue;   // wave-uniform: background
+            if (sel) {
+                const double y = log((double)xv);
+                const double zh = p.w0 + (double)w * p.step_w;
+                const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
+                const double r = y - b;
+                double l[K], lmax = -(double)INFINITY;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double dk = r - p.mu[k];
+                    l[k] = p.a[k] - (dk * dk) * p.hiv[k];
+                    lmax = fmax(lmax, l[k]);
+                }
+                double s = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    l[k] = exp(l[k] - lmax);
+                    s = s + l[k];
+                }
+                const double inv_s = 1.0 / s;
+                acc[0] = acc[0] + 1.0;
+                acc[1] = acc[1] + (lmax + log(s));
+                double wv = 0.0, tv = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double pk = l[k] * inv_s;
+                    acc[2 + k] = acc[2 + k] + pk;
+                    acc[2 + K + k] = acc[2 + K + k] + pk * r;
+                    acc[2 + 2 * K + k] = acc[2 + 2 * K + k] + pk * (r * r);
+                    wv = wv + pk * p.inv_v[k];
+                    tv = tv + pk * ((y - p.mu[k]) * p.inv_v[k]);
+                }
+                double zq = 1.0;
+#pragma unroll
+                for (int i = 0; i < NW; ++i) {
+                    acc[2 + 3 * K + i] = acc[2 + 3 * K + i] + wv * zq;
+                    if (i < NT) acc[2 + 3 * K + NW + i] = acc[2 + 3 * K + NW + i] + tv * zq;
+                    zq = zq * zh;
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) acc[i] = tis_wave_sum(acc[i]);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) part[(size_t)i * rows + row] = acc[i];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ EM pass, stage 2: rows -> table
+__global__ void __launch_bounds__(kTisFoldThreads)
+tissue_em_fold_kernel(const double* __restrict__ part, int D, int H, TisFold f, double d0, double step_d, double h0, double step_h,
+                      double* __restrict__ sums) {
+    __shared__ double sh[kTisFoldThreads];
+    const int e = blockIdx.x, t = threadIdx.x;
+    const int rows = D * H;
+    const int a = f.a[e], b = f.b[e];
+    const double* src = part + (size_t)f.slot[e] * rows;
+    double acc = 0.0;
+    for (int row = t; row < rows; row += kTisFoldThreads) {
+        const int d = row / H, h = row - d * H;
+        const double xh = d0 + (double)d * step_d, yh = h0 + (double)h * step_h;
+        double wgt = 1.0;
+        for (int i = 0; i < a; ++i) wgt = wgt * xh;
+        for (int j = 0; j < b; ++j) wgt = wgt * yh;
+        acc = acc + src[row] * wgt;
+    }
+    sh[t] = acc;
+    __syncthreads();
+    for (int s = kTisFoldThreads / 2; s > 0; s >>= 1) {
+        if (t < s) sh[t] = sh[t] + sh[t + s];
+        __syncthreads();
+    }
+    if (t == 0) sums[e] = sh[0];
+}
+
+// ------------------------------------------------------------------ final pass
+// x and restored may be the same buffer (a voxel is read and written by one lane): no __restrict__ on the two
+template <int K>
+__global__ void __launch_bounds__(64 * kTisWaves)
+tissue_apply_kernel(const float* x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p, float* restored,
+                    uint8_t* __restrict__ labels, float* __restrict__ field) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rows = D * H;
+    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
+        const int d = row / H, h = row - d * H;
+        double q[4];
+        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
+        const size_t base = (size_t)row * W;
+        const uint8_t* mr = mask ? mask + base : nullptr;
+        for (int w = lane; w < W; w += 64) {
+            const float xv = x[base + w];
+            const double zh = p.w0 + (double)w * p.step_w;
+            const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
+            int lab = 0;
+            if (tis_selected(mr, w, xv)) {
+                const double r = log((double)xv) - b;
+                double best = -(double)INFINITY;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double dk = r - p.mu[k];
+                    const double lk = p.a[k] - (dk * dk) * p.hiv[k];
+                    if (k == 0 || lk > best) best = lk, lab = k + 1;   // the first of equal maxima
+                }
+            }
+            restored[base + w] = (float)((double)xv * exp(-b));
+            labels[base + w] = (uint8_t)lab;
+            if (field) field[base + w] = (float)exp(b);
+        }
+    }
+}
+
+static int tis_ncoef(int order) { return (order + 1) * (order + 2) * (order + 3) / 6; }
+static int tis_row_sums(int classes, int order) { return 2 + 3 * classes + (2 * order + 1) + (order + 1); }
+static int tis_entries(int classes, int order) { return 2 + 3 * classes + tis_ncoef(2 * order) + tis_ncoef(order); }
+static int tis_blocks(int64_t rows) { return (int)std::min<int64_t>(cdiv64(rows, kTisWaves), kTisMaxBlocks); }
+
+// the checks every entry shares; `who` starts the error string
+static int tis_check_dims(const char* who, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order) {
+    MRI3D_REQUIRE(d > 0 && h > 0 && w > 0, MRI3D_EINVAL, "%s: extents %d,%d,%d", who, d, h, w);
+    MRI3D_REQUIRE((int64_t)d * h * w < 0x7fffffffLL, MRI3D_ENOTSUP, "%s: volume too large", who);
+    MRI3D_REQUIRE(classes >= 2 && classes <= kTisMaxK, MRI3D_EINVAL, "%s: classes = %d outside 2..%d", who, classes, kTisMaxK);
+    MRI3D_REQUIRE(order >= 0, MRI3D_EINVAL, "%s: negative order %d", who, order);
+    MRI3D_REQUIRE(order <= 3, MRI3D_ENOTSUP, "%s: order %d (at most 3)", who, order);
+    return MRI3D_OK;
+}
+
+// params_host = (pi[K], mu[K], v[K], c[M]) -> the kernels' constants.  Classes go to the kernel in ascending order of mu when
+// `sort` is set (a stable order: equal means keep the caller's).
+static int tis_params(const char* who, const double* ph, int K, int order, int d, int h, int w, bool with_2pi, bool sort, TisParams& p) {
+    const int M = tis_ncoef(order);
+    bool any_pi = false;
+    for (int k = 0; k < K; ++k) {
+        const double pi = ph[k], mu = ph[K + k], v = ph[2 * K + k];
+        MRI3D_REQUIRE(isfinite(pi) && pi >= 0.0, MRI3D_EINVAL, "%s: pi[%d] = %g must be finite and >= 0", who, k, pi);
+        MRI3D_REQUIRE(isfinite(mu), MRI3D_EINVAL, "%s: mu[%d] = %g must be finite", who, k, mu);
+        MRI3D_REQUIRE(isfinite(v) && v > 0.0, MRI3D_EINVAL, "%s: v[%d] = %g must be finite and > 0", who, k, v);
+        any_pi = any_pi || pi > 0.0;
+    }
+    MRI3D_REQUIRE(any_pi, MRI3D_EINVAL, "%s: every pi is 0", who);
+    for (int n = 0; n < M; ++n) MRI3D_REQUIRE(isfinite(ph[3 * K + n]), MRI3D_EINVAL, "%s: c[%d] = %g must be finite", who, n, ph[3 * K + n]);
+    int idx[kTisMaxK];
+    for (int k = 0; k < K; ++k) idx[k] = k;
+    if (sort) std::stable_sort(idx, idx + K, [&](int i, int j) { return ph[K + i] < ph[K + j]; });
+    for (int k = 0; k < kTisMaxK; ++k) {
+        const int s = idx[std::min(k, K - 1)];
+        const double pi = ph[s], mu = ph[K + s], v = ph[2 * K + s];
+        p.a[k] = (log(pi) - 0.5 * log(v)) - (with_2pi ? 0.5 * log(2.0 * M_PI) : 0.0);
+        p.mu[k] = mu, p.inv_v[k] = 1.0 / v, p.hiv[k] = 1.0 / (2.0 * v);
+    }
+    // where term n of the caller's nesting (i, j, k up to `order`) sits in the kernel's order-3 nesting
+    for (int n = 0; n < kTisCoef; ++n) p.c[n] = 0.0;
+    int n = 0, n3 = 0;
+    for (int i = 0; i <= 3; ++i)
+        for (int j = 0; j <= 3 - i; ++j)
+            for (int k = 0; k <= 3 - i - j; ++k, ++n3)
+                if (i + j + k <= order) p.c[n3] = ph[3 * K + n++];
+    auto step = [](int len) { return len > 1 ? 2.0 / (double)(len - 1) : 0.0; };
+    auto start = [](int len) { return len > 1 ? -1.0 : 0.0; };
+    p.d0 = start(d), p.h0 = start(h), p.w0 = start(w), p.step_d = step(d), p.step_h = step(h), p.step_w = step(w);
+    return MRI3D_OK;
+}
+
+}  // namespace mri3d
+
+using namespace mri3d;
+
+extern "C" size_t mri3d_tissue_em_workspace_bytes(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order) {
+    if (d <= 0 || h <= 0 || w <= 0 || (int64_t)d * h * w >= 0x7fffffffLL || classes < 2 || classes > kTisMaxK || order < 0 || order > 3) return 0;
+    return (size_t)tis_row_sums(classes, order) * (size_t)d * (size_t)h * sizeof(double);
+}
+
+extern "C" int mri3d_tissue_em_plan(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order, int32_t out[8]) {
+    MRI3D_REQUIRE(out != nullptr, MRI3D_EINVAL, "tissue_em_plan: null output");
+    if (int rc = tis_check_dims("tissue_em_plan", d, h, w, classes, order)) return rc;
+    const int64_t rows = (int64_t)d * h;
+    const int blocks = tis_blocks(rows);
+    out[0] = blocks;
+    out[1] = kTisWaves;
+    out[2] = (int32_t)cdiv64(cdiv64(rows, kTisWaves), blocks);
+    out[3] = cdiv(w, 64);
+    out[4] = tis_row_sums(classes, order);
+    out[5] = tis_entries(classes, order);
+    out[6] = kTisFoldThreads;
+    out[7] = (int32_t)rows;
+    return MRI3D_OK;
+}
+
+extern "C" int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                                    const double* params_host, double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(x && params_host && sums, MRI3D_EINVAL, "tissue_em_pass: null pointer (x %p, params %p, sums %p)", (const void*)x,
+                  (const void*)params_host, (void*)sums);
+    if (int rc = tis_check_dims("tissue_em_pass", d, h, w, classes, order)) return rc;
+    TisParams p;
+    if (int rc = tis_params("tissue_em_pass", params_host, classes, order, d, h, w, true, false, p)) return rc;
+    MRI3D_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0, MRI3D_EINVAL,
+                  "tissue_em_pass: a pointer is not aligned to its element");
+    const size_t need = mri3d_tissue_em_workspace_bytes(d, h, w, classes, order);
+    if (int rc = ws_check8("tissue_em_pass", workspace, ws_bytes, need)) return rc;
+    const size_t nvox = (size_t)d * h * w;
+    const int entries = tis_entries(classes, order);
+    const size_t sums_bytes = (size_t)entries * sizeof(double);
+    MRI3D_REQUIRE(!overlaps(sums, sums_bytes, workspace, need) && !overlaps(sums, sums_bytes, x, nvox * 4) &&
+                      !overlaps(sums, sums_bytes, mask, nvox) && !overlaps(workspace, need, x, nvox * 4) &&
+                      !overlaps(workspace, need, mask, nvox),
+                  MRI3D_EINVAL, "tissue_em_pass: the sums or the workspace overlap another buffer");
+    // the table: n, LL, S0[K], S1[K], S2[K], Mw[a][b][c] (a + b + c <= 2 order, c fastest), Mt[a][b][c] (a + b + c <= order)
+    const int K = classes, nw = 2 * order + 1;
+    TisFold f;
+    int e = 0;
+    for (; e < 2 + 3 * K; ++e) f.slot[e] = (uint8_t)e, f.a[e] = 0, f.b[e] = 0;
+    for (int a = 0; a <= 2 * order; ++a)
+        for (int b = 0; b <= 2 * order - a; ++b)
+            for (int c = 0; c <= 2 * order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
+    for (int a = 0; a <= order; ++a)
+        for (int b = 0; b <= order - a; ++b)
+            for (int c = 0; c <= order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + nw + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
+    for (int i = e; i < kTisMaxEntries; ++i) f.slot[i] = 0, f.a[i] = 0, f.b[i] = 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
+#define TIS_EM(KK, OO) hipLaunchKernelGGL((tissue_em_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, p, part)
+#define TIS_EM_K(KK)                 \
+    switch (order) {                 \
+        case 0: TIS_EM(KK, 0); break; \
+        case 1: TIS_EM(KK, 1); break; \
+        case 2: TIS_EM(KK, 2); break; \
+        default: TIS_EM(KK, 3); break; \
+    }
+    switch (K) {
+        case 2: TIS_EM_K(2); break;
+        case 3: TIS_EM_K(3); break;
+        default: TIS_EM_K(4); break;
+    }
+#undef TIS_EM_K
+#undef TIS_EM
+    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(entries), dim3(kTisFoldThreads), 0, st, part, d, h, f, p.d0, p.step_d, p.h0, p.step_h, sums);
+    return check_launch("tissue_em_pass");
+}
+
+extern "C" int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                                  const double* params_host, float* restored, uint8_t* labels, float* field, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(x && params_host && restored && labels, MRI3D_EINVAL, "tissue_apply: null pointer (x %p, params %p, restored %p, labels %p)",
+                  (const void*)x, (const void*)params_host, (void*)restored, (void*)labels);
+    if (int rc = tis_check_dims("tissue_apply", d, h, w, classes, order)) return rc;
+    TisParams p;
+    if (int rc = tis_params("tissue_apply", params_host, classes, order, d, h, w, false, true, p)) return rc;
+    MRI3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(restored) | reinterpret_cast<uintptr_t>(field)) & 3) == 0,
+                  MRI3D_EINVAL, "tissue_apply: pointers not aligned to float");
+    const size_t nvox = (size_t)d * h * w;
+    // in place (restored == x) is allowed; any other overlap is not
+    MRI3D_REQUIRE((x == restored || !overlaps(x, nvox * 4, restored, nvox * 4)) && !overlaps(restored, nvox * 4, mask, nvox) &&
+                      !overlaps(restored, nvox * 4, labels, nvox) && !overlaps(restored, nvox * 4, field, nvox * 4) &&
+                      !overlaps(labels, nvox, x, nvox * 4) && !overlaps(labels, nvox, mask, nvox) && !overlaps(labels, nvox, field, nvox * 4) &&
+                      !overlaps(field, nvox * 4, x, nvox * 4) && !overlaps(field, nvox * 4, mask, nvox),
+                  MRI3D_EINVAL, "tissue_apply: an output overlaps another buffer (only restored == x is allowed)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
+#define TIS_APPLY(KK) hipLaunchKernelGGL((tissue_apply_kernel<KK>), grid, block, 0, st, x, mask, d, h, w, p, restored, labels, field)
+    switch (classes) {
+        case 2: TIS_APPLY(2); break;
+        case 3: TIS_APPLY(3); break;
+        default: TIS_APPLY(4); break;
+    }
+#undef TIS_APPLY
+    return check_launch("tissue_apply");
+}

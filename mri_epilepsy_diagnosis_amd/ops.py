@@ -2486,6 +2486,78 @@ def downsample2(x):
     return y
 
 
+# ----------------------------------------------------------------------------------------------- tissue classes (csrc/tissue.hip)
+TISSUE_EM_PLAN_FIELDS = ("blocks", "rows_per_trip", "trips", "wave_steps", "row_sums", "entries", "fold_threads", "rows")
+
+
+def tissue_coefficients(order):
+    """Terms of a polynomial field of `order`: (order + 1)(order + 2)(order + 3) / 6."""
+    return (order + 1) * (order + 2) * (order + 3) // 6
+
+
+def tissue_table_size(classes, order):
+    """Entries of the sums table of one EM pass: n, LL, S0/S1/S2 per class, the moments of w up to 2 * order and of t up to order."""
+    return 2 + 3 * classes + tissue_coefficients(2 * order) + tissue_coefficients(order)
+
+
+def _tissue_args(who, x, mask, classes, order, params):
+    import numpy as np
+    x = _volume(who, "x", x, (torch.float32,))
+    if mask is not None:
+        mask = _volume(who, "mask", mask, (torch.uint8, torch.bool))
+        if tuple(mask.shape) != tuple(x.shape) or mask.device != x.device:
+            raise RuntimeError("%s: x %s and mask %s differ in shape or device" % (who, tuple(x.shape), tuple(mask.shape)))
+        mask = mask.view(torch.uint8)
+    classes, order = int(classes), int(order)
+    p = np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(-1))
+    if 2 <= classes <= 4 and 0 <= order <= 3 and p.size != 3 * classes + tissue_coefficients(order):
+        raise ValueError("%s: %d classes and order %d take %d parameters (pi, mu, v, c), got %d"
+                         % (who, classes, order, 3 * classes + tissue_coefficients(order), p.size))
+    return x, mask, classes, order, p
+
+
+def tissue_em_plan(shape, classes, order):
+    """What one `tissue_em_pass` launch is built from, as a dict over TISSUE_EM_PLAN_FIELDS (host only)."""
+    d, h, w = (int(s) for s in shape)
+    out = (ctypes.c_int32 * 8)()
+    check(_lib.lib().mri3d_tissue_em_plan(d, h, w, int(classes), int(order), out), "tissue_em_plan")
+    return dict(zip(TISSUE_EM_PLAN_FIELDS, (int(v) for v in out)))
+
+
+def tissue_em_pass(x, mask, classes, order, params, out=None):
+    """One EM pass of the tissue-class bias-field model over a float32 (d, h, w) device volume with the parameters fixed: the
+    float64 device table (n, LL, S0[K], S1[K], S2[K], Mw, Mt) that include/mri3d.h documents.  mask: uint8 / bool device volume
+    or None; params: 3K + M host doubles (pi, mu, v, c)."""
+    x, mask, classes, order, p = _tissue_args("tissue_em_pass", x, mask, classes, order, params)
+    size = tissue_table_size(classes, order) if 2 <= classes <= 4 and 0 <= order <= 3 else 1
+    if out is None:
+        out = torch.empty(size, dtype=torch.float64, device=x.device)
+    elif tuple(out.shape) != (size,) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError("tissue_em_pass: out must be a contiguous (%d,) float64 device tensor" % size)
+    L = _lib.lib()
+    d, h, w = x.shape
+    ws = _workspace(L.mri3d_tissue_em_workspace_bytes(d, h, w, classes, order), x.device)
+    check(L.mri3d_tissue_em_pass(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), _ptr(out), _ptr(ws),
+                                 ws.numel(), _stream()), "tissue_em_pass")
+    return out
+
+
+def tissue_apply(x, mask, classes, order, params, want_field=False, restored=None):
+    """The final pass: (restored = x exp(-b), labels uint8, field = exp(b) or None) over every voxel; labels are 0 where the voxel
+    is not selected and else 1 + the rank by ascending mean of its most probable class.  `restored` may be `x` itself."""
+    x, mask, classes, order, p = _tissue_args("tissue_apply", x, mask, classes, order, params)
+    if restored is None:
+        restored = torch.empty_like(x)
+    elif tuple(restored.shape) != tuple(x.shape) or restored.dtype != torch.float32 or not restored.is_cuda or not restored.is_contiguous():
+        raise RuntimeError("tissue_apply: restored must be a contiguous %s float32 device tensor" % (tuple(x.shape),))
+    labels = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    field = torch.empty_like(x) if want_field else None
+    d, h, w = x.shape
+    check(_lib.lib().mri3d_tissue_apply(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), _ptr(restored),
+                                        _ptr(labels), _ptr(field), _stream()), "tissue_apply")
+    return restored, labels, field
+
+
 # ----------------------------------------------------------------------------------------------- cat / add
 
 
