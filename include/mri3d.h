@@ -197,6 +197,39 @@ typedef struct Mri3dMarchPlanInfo {
 } Mri3dMarchPlanInfo;
 int32_t mri3d_conv3d_march_plan_query(const Mri3dConvGeom* g, int32_t pass, int32_t stats, Mri3dMarchPlanInfo* out);
 
+/* THE NUMBERS OF THE LAUNCH PLAN of the 3x3x3 MFMA kernels of csrc/conv_mfma.hip and csrc/conv_mfma_wgrad.hip, for the call
+ * mri3d_conv3d_route names with the same arguments (mri3d_conv3d_fwd / _fwd_stats / _dgrad / _wgrad, split > 0: the *_cat entry
+ * points).  Host only: no device is needed, nothing is launched, nothing is allocated; the numbers are read from the plan objects
+ * the launch reads.  Returns MRI3D_ENOTSUP, and leaves *out alone, exactly where mri3d_conv3d_route names a kernel of another file
+ * ("generic ...", "pointwise ...", "march ...") or "none"; MRI3D_EINVAL as mri3d_conv3d_route, and for a NULL out.
+ * Kc = input channels of the pass (forward ci, data gradient co), Nc = its output channels.
+ *   kernel        MRI3D_MFMA_*: the first word(s) of the route name
+ *   ck, chunks, partial_chunk   channels per K chunk, chunks = ceil(Kc / ck), 1 where the last chunk is not full (weight gradient:
+ *                 ck = input channels per ci-tile, chunks = cit)
+ *   nt, ntt, gy   tiled / direct: 16-channel N-tiles per wave, N-tiles = ceil(Nc / 16), N-blocks = ntt / nt
+ *   tile_d, tile_h, tile_w      output tile in voxels (direct: 1 x 1 x 16, an M-tile of 16 voxels; bf16t: tile_d = segl)
+ *   tiles_d, tiles_h, tiles_w, ntiles   tiles per axis, and in all samples (direct: ntiles = M-tiles; bf16t: tasks)
+ *   units         work units the grid shares: tiled ntiles * gy, direct M-tiles * gy, weight gradient ntiles
+ *   grid          workgroups of the launch (weight gradient: p * cit * cob)
+ *   mode, split, wbn   direct: strided data gradient, a unit's taps spread over the workgroup's four waves, 16-voxel blocks per row
+ *                 residue (mode 1)
+ *   cit, cob, tg, p, ci8, co8, segl   weight gradient: ci-tiles, 16-channel output blocks, tap groups (accumulators without the
+ *                 one of dbias), workgroups per (ci-tile, output block), the eight-channel forms of wgrad6, planes per bf16t task
+ *   max_tasks, min_tasks   most / fewest units (tiled, weight gradient) one persistent workgroup takes (direct: 1, 1)
+ *   chain         weight gradient: the longest fp32 accumulation chain of one accumulator element of one wave, in products:
+ *                 max_tasks * tile_d * tile_h * tile_w / 4 (a wave owns a quarter of every tile's voxels)
+ *   stats_blocks  statistics partials the forward writes (= grid with stats, else 0)
+ *   workspace_bytes   what the launch requires of the workspace: packed-weight image / weight-gradient partials */
+enum { MRI3D_MFMA_TILED = 1, MRI3D_MFMA_TILED_N8 = 2, MRI3D_MFMA_DIRECT = 3, MRI3D_MFMA_CIN1 = 4, MRI3D_MFMA_WGRAD3 = 5,
+       MRI3D_MFMA_WGRAD4 = 6, MRI3D_MFMA_BF16 = 7, MRI3D_MFMA_BF16T = 8, MRI3D_MFMA_WGRAD6 = 9 };
+typedef struct Mri3dConvMfmaPlanInfo {
+    int32_t kernel, ck, chunks, partial_chunk, nt, ntt, gy, tile_d, tile_h, tile_w, tiles_d, tiles_h, tiles_w, ntiles, units, grid,
+        mode, split, wbn, cit, cob, tg, p, ci8, co8, segl, max_tasks, min_tasks, chain, stats_blocks;
+    int64_t workspace_bytes;
+} Mri3dConvMfmaPlanInfo;
+int32_t mri3d_conv3d_mfma_plan_query(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t bias, int32_t split, int32_t second_ld,
+                                     int32_t align_x, int32_t align_y, Mri3dConvMfmaPlanInfo* out);
+
 /* Conv3d over a nearest-neighbour upsampled input that is never formed (csrc/upconv.hip):
  *     y = conv3d(upsample_nearest(x, scale_factor = scale), w, bias, stride 1, padding g->p*)
  * replaces nn.Upsample(scale_factor=4, mode='nearest') followed by the block's first nn.Conv3d in UpBlock

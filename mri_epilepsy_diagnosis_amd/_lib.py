@@ -50,6 +50,13 @@ class MarchPlanInfo(Structure):
                                        "whole_chunks", "dispatcher")] + [("smem_bytes", c_int64), ("wp_bytes", c_int64)]
 
 
+class ConvMfmaPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("kernel", "ck", "chunks", "partial_chunk", "nt", "ntt", "gy", "tile_d", "tile_h", "tile_w",
+                                       "tiles_d", "tiles_h", "tiles_w", "ntiles", "units", "grid", "mode", "split", "wbn", "cit", "cob",
+                                       "tg", "p", "ci8", "co8", "segl", "max_tasks", "min_tasks", "chain", "stats_blocks")] + \
+               [("workspace_bytes", c_int64)]
+
+
 class ComponentsPlanInfo(Structure):
     _fields_ = [(n, c_int32) for n in ("td", "th", "tw", "tiles_d", "tiles_h", "tiles_w", "grid_local", "grid_merge", "grid_roots",
                                        "grid_scan", "grid_rank", "grid_relabel", "scan_blocks", "offsets")] + \
@@ -104,6 +111,8 @@ SIGNATURES = {
     "mri3d_conv3d_march_supported": (c_int32, [POINTER(ConvGeom), c_int32]),
     "mri3d_conv3d_march_stats_blocks": (c_int32, [POINTER(ConvGeom)]),
     "mri3d_conv3d_march_plan_query": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, POINTER(MarchPlanInfo)]),
+    "mri3d_conv3d_mfma_plan_query": (c_int32, [POINTER(ConvGeom), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                               POINTER(ConvMfmaPlanInfo)]),
     "mri3d_conv3d_fwd_march": (c_int32, [POINTER(ConvGeom), _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_conv3d_dgrad_march": (c_int32, [POINTER(ConvGeom), _P, _P, _P, _P, c_int32, c_int32, _P, c_size_t, _P]),
     "mri3d_upconv3d_supported": (c_int32, [POINTER(ConvGeom), c_int32]),

@@ -320,3 +320,21 @@ extern "C" int mri3d_conv3d_route(const Mri3dConvGeom* g, int32_t pass, int32_t 
     }
     return MRI3D_OK;
 }
+
+// ---- the numbers of that launch where the 3x3x3 MFMA files serve it (host only): the same backend decision, then their plan.
+// `bias` is part of the call the query describes (as in mri3d_conv3d_route); no plan number of these kernels depends on it.
+extern "C" int32_t mri3d_conv3d_mfma_plan_query(const Mri3dConvGeom* g, int32_t pass, int32_t stats, int32_t /* bias */, int32_t split,
+                                                int32_t second_ld, int32_t align_x, int32_t align_y, Mri3dConvMfmaPlanInfo* out) {
+    int rc = conv_check(g, "conv3d_mfma_plan_query", split > 0 ? split : -1);
+    if (rc) return rc;
+    MRI3D_REQUIRE(out != nullptr, MRI3D_EINVAL, "conv3d_mfma_plan_query: null pointer");
+    MRI3D_REQUIRE(pass == MRI3D_PASS_FWD || pass == MRI3D_PASS_DGRAD || pass == MRI3D_PASS_WGRAD, MRI3D_EINVAL, "conv3d_mfma_plan_query: unknown pass %d", pass);
+    MRI3D_REQUIRE(split >= 0 && (!stats || pass == MRI3D_PASS_FWD), MRI3D_EINVAL, "conv3d_mfma_plan_query: negative split, or statistics outside the forward");
+    MRI3D_REQUIRE(conv_backend(*g, pass, stats != 0, split, second_ld, align_x < align_y ? align_x : align_y, align_x) == ConvBackend::mfma,
+                  MRI3D_ENOTSUP, "conv3d_mfma_plan_query: the call is not served by the MFMA files (see mri3d_conv3d_route)");
+    Mri3dConvMfmaPlanInfo info;
+    MRI3D_REQUIRE(conv_mfma_plan_info(*g, pass, stats != 0, ConvSplit{nullptr, split, second_ld}, info), MRI3D_ENOTSUP,
+                  "conv3d_mfma_plan_query: served by the marching kernel (see mri3d_conv3d_march_plan_query)");
+    *out = info;
+    return MRI3D_OK;
+}

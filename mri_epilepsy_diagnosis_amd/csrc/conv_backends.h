@@ -53,12 +53,42 @@ int conv_mfma_fwd_stats(const Mri3dConvGeom& g, const void* x, const float* w, c
 // name of the kernel instantiation the pass launches (mri3d_conv3d_route; the vocabulary is in include/mri3d.h), written from the
 // same fwd_route answer (weight gradient: the same plan, below) the launch reads.  false: the pass is not served.
 bool conv_mfma_route_name(const Mri3dConvGeom& g, int pass, bool stats, bool bias, const ConvSplit& sp, char* name, size_t name_bytes);
+// the numbers of that launch (mri3d_conv3d_mfma_plan_query), filled from the same fwd_route answer / weight-gradient plan.  false,
+// and `out` untouched: the pass is not served, or by the marching kernel (conv_march.hip has its own query)
+bool conv_mfma_plan_info(const Mri3dConvGeom& g, int pass, bool stats, const ConvSplit& sp, Mri3dConvMfmaPlanInfo& out);
+
+// Most and fewest units one persistent workgroup takes.  A HOST restatement, for the plan queries only, of the unit -> workgroup
+// map the kernels compute from gridDim / blockIdx: conv_mfma_fwd2_kernel's (rows = 1) and tile_walk's of conv_mfma_wgrad.hip
+// (P = gridDim.x, rows = gridDim.y * gridDim.z; the map of a row is that of row 0 rotated by P * row mod min(P, 8)).  Workgroups
+// that share an XCD group (block id mod 8) take the units of the group's contiguous range round-robin.  (One __host__ __device__
+// function called from both sides was tried: hipcc then allocates the scalar registers of every weight-gradient kernel's prologue
+// differently, and those kernels are kept instruction for instruction.  tests/mfma_emu.py restates the walk once more and asserts
+// that its longest sequence is the query's `chain`.)
+struct WalkCounts { int max_tasks, min_tasks; };
+inline WalkCounts xcd_walk_counts(int P, int rows, int units) {
+    const int NX = P < 8 ? P : 8;
+    WalkCounts c{0, units};
+    for (int row = 0; row < rows && row < 8; ++row) {
+        const int off = (int)(((int64_t)P * row) % NX);
+        for (int bx = 0; bx < P; ++bx) {
+            const int grp = (bx + off) % NX, p0 = (grp - off + NX) % NX;
+            const int slot = (bx - p0) / NX, members = (P - p0 + NX - 1) / NX;
+            const int r_lo = (int)(((int64_t)units * grp) / NX), r_hi = (int)(((int64_t)units * (grp + 1)) / NX);
+            const int first = r_lo + slot;
+            const int count = first < r_hi ? (r_hi - first + members - 1) / members : 0;
+            c.max_tasks = count > c.max_tasks ? count : c.max_tasks;
+            c.min_tasks = count < c.min_tasks ? count : c.min_tasks;
+        }
+    }
+    return c;
+}
 
 // conv_mfma_wgrad.hip: the weight gradient of the 3x3x3 MFMA path.  The three queries are what conv_mfma.hip's queries over all
 // passes answer with for MRI3D_PASS_WGRAD; all read the one plan the launch reads.
 bool conv_mfma_wgrad_supported(const Mri3dConvGeom& g, int split = 0, int second_ld = 0);   // split > 0: ... with that split operand
 size_t conv_mfma_wgrad_workspace_bytes(const Mri3dConvGeom& g);                             // 0: not served
 bool conv_mfma_wgrad_route_name(const Mri3dConvGeom& g, char* name, size_t name_bytes);     // false: not served
+bool conv_mfma_wgrad_plan_info(const Mri3dConvGeom& g, Mri3dConvMfmaPlanInfo& out);         // false, `out` untouched: not served
 int conv_mfma_wgrad(const Mri3dConvGeom& g, const void* x, const void* dy, float* dw, float* dbias, void* ws,
                     size_t ws_bytes, hipStream_t s);
 int conv_mfma_wgrad_cat(const Mri3dConvGeom& g, const void* x, const void* x2, int split, int x2_ld, const void* dy, float* dw,

@@ -1255,6 +1255,43 @@ bool conv_mfma_route_name(const Mri3dConvGeom& g, int pass, bool stats, bool bia
     return true;
 }
 
+// The numbers run_mfma_fwd launches by (mri3d_conv3d_mfma_plan_query), from the same fwd_route answer; the weight gradient's come
+// from its own plan.  The marching kernel is not of this file: false.
+bool conv_mfma_plan_info(const Mri3dConvGeom& g, int pass, bool stats, const ConvSplit& sp, Mri3dConvMfmaPlanInfo& out) {
+    if (pass == MRI3D_PASS_WGRAD) return conv_mfma_wgrad_plan_info(g, out);
+    if (pass != MRI3D_PASS_FWD && pass != MRI3D_PASS_DGRAD) return false;
+    const bool dgrad = pass == MRI3D_PASS_DGRAD;
+    const FwdRoute r = fwd_route(g, dgrad, stats, sp);
+    if (r.kernel == FwdKernel::none || r.kernel == FwdKernel::march) return false;
+    const int Kc = dgrad ? g.co : g.ci;
+    Mri3dConvMfmaPlanInfo o{};
+    o.grid = r.grid;
+    o.workspace_bytes = (int64_t)r.wp_bytes;
+    o.stats_blocks = stats ? r.grid : 0;
+    if (r.kernel == FwdKernel::direct) {
+        const DirectPlan& d = r.direct;
+        o.kernel = MRI3D_MFMA_DIRECT;
+        o.ck = 16, o.chunks = cdiv(Kc, 16), o.partial_chunk = Kc % 16 != 0;
+        o.nt = d.nt, o.ntt = d.q.NTT, o.gy = d.q.gy;
+        o.tile_d = o.tile_h = 1, o.tile_w = 16;
+        o.ntiles = d.q.nmt, o.units = d.units;
+        o.mode = d.mode, o.split = d.split, o.wbn = d.q.wbn;
+        o.max_tasks = o.min_tasks = 1;
+    } else {
+        const MfmaFwdPlan& p = r.tiled;
+        o.kernel = r.kernel == FwdKernel::tiled_n8 ? MRI3D_MFMA_TILED_N8 : MRI3D_MFMA_TILED;
+        o.ck = p.CK, o.chunks = p.nchunks, o.partial_chunk = Kc % p.CK != 0;
+        o.nt = p.NT, o.ntt = p.NTT, o.gy = p.gy;
+        o.tile_d = TD, o.tile_h = TH, o.tile_w = TW;
+        o.tiles_d = p.tilesD, o.tiles_h = p.tilesH, o.tiles_w = p.tilesW, o.ntiles = p.ntiles;
+        o.units = p.ntiles * p.gy;
+        const WalkCounts wc = xcd_walk_counts(r.grid, 1, o.units);
+        o.max_tasks = wc.max_tasks, o.min_tasks = wc.min_tasks;
+    }
+    out = o;
+    return true;
+}
+
 // Forward / data gradient: the caller asks before it knows whether statistics or a split operand will be requested, and
 // mri3d_conv3d_{fwd,dgrad}_march is documented to size its workspace with this query too.  So the answer is not the need of one
 // route but the maximum over the kernel families that accept the geometry at all: the tiled kernel's image where mfma_fwd_plan

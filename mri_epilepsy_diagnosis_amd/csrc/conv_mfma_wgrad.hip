@@ -1353,6 +1353,7 @@ struct MfmaWgradPlan {
     WgradKernel kernel;
     bool ci8, co8;   // wgrad6 with eight-channel operands: rows / columns 8..15 of a tile repeat the channels for another tap
     int CK, CIT, COB, TG, P, tilesD, tilesH, tilesW, ntiles, segl;
+    int td, th, tw;   // the output tile (tasks of bf16t: td = segl planes of a column)
     size_t part_floats, smem;
     // the transposed-tile kernels are the only ones with a second operand; wgrad6 needs whole 16-channel chunks in it (the bf16
     // kernels' 8 follow from Cin % 8 == 0 and split % 16 == 0)
@@ -1438,6 +1439,7 @@ static bool mfma_wgrad_plan(const Mri3dConvGeom& g, MfmaWgradPlan& p) {
     if (p.CK >= 4 && g.x_ld % 4 != 0) return false;
     p.CIT = cdiv(g.ci, p.CK);
     p.COB = cdiv(g.co, 16);
+    p.td = td, p.th = th, p.tw = tw;
     p.tilesD = cdiv(g.di, td);
     p.tilesH = cdiv(g.hi, th);
     p.tilesW = cdiv(g.wi, tw);
@@ -1480,6 +1482,42 @@ bool conv_mfma_wgrad_route_name(const Mri3dConvGeom& g, char* name, size_t name_
     case WgradKernel::wgrad6: snprintf(name, name_bytes, "wgrad6%s%s", q.ci8 ? " ci8" : "", q.co8 ? " co8" : ""); break;
     case WgradKernel::bf16t: snprintf(name, name_bytes, "bf16t"); break;
     }
+    return true;
+}
+
+// the numbers of the launch (mri3d_conv3d_mfma_plan_query), from the plan the launch reads
+bool conv_mfma_wgrad_plan_info(const Mri3dConvGeom& g, Mri3dConvMfmaPlanInfo& out) {
+    MfmaWgradPlan q;
+    if (!mfma_wgrad_plan(g, q)) return false;
+    Mri3dConvMfmaPlanInfo o{};
+    switch (q.kernel) {
+    case WgradKernel::cin1: o.kernel = MRI3D_MFMA_CIN1; break;
+    case WgradKernel::wgrad3: o.kernel = MRI3D_MFMA_WGRAD3; break;
+    case WgradKernel::wgrad4: o.kernel = MRI3D_MFMA_WGRAD4; break;
+    case WgradKernel::bf16: o.kernel = MRI3D_MFMA_BF16; break;
+    case WgradKernel::wgrad6: o.kernel = MRI3D_MFMA_WGRAD6; break;
+    case WgradKernel::bf16t: o.kernel = MRI3D_MFMA_BF16T; break;
+    }
+    o.ck = q.CK, o.chunks = q.CIT, o.partial_chunk = g.ci % q.CK != 0;
+    o.tile_d = q.td, o.tile_h = q.th, o.tile_w = q.tw;
+    o.tiles_d = q.tilesD, o.tiles_h = q.tilesH, o.tiles_w = q.tilesW, o.ntiles = q.ntiles, o.units = q.ntiles;
+    o.cit = q.CIT, o.cob = q.COB, o.tg = q.TG, o.p = q.P, o.ci8 = q.ci8, o.co8 = q.co8, o.segl = q.segl;
+    o.grid = q.P * q.CIT * q.COB;
+    if (q.kernel == WgradKernel::cin1) {   // contiguous ranges [ntiles * b / P, ntiles * (b + 1) / P), not tile_walk
+        o.max_tasks = 0, o.min_tasks = q.ntiles;
+        for (int b = 0; b < q.P; ++b) {
+            const int n = (int)(((int64_t)q.ntiles * (b + 1)) / q.P) - (int)(((int64_t)q.ntiles * b) / q.P);
+            o.max_tasks = std::max(o.max_tasks, n), o.min_tasks = std::min(o.min_tasks, n);
+        }
+    } else {
+        const WalkCounts wc = xcd_walk_counts(q.P, q.CIT * q.COB, q.ntiles);
+        o.max_tasks = wc.max_tasks, o.min_tasks = wc.min_tasks;
+    }
+    // every wave owns a quarter of a tile's voxels (cin1, wgrad3, wgrad4: one of 2 x 2 (d, h) halves; the others: a quarter of the
+    // rows), each one product of every accumulator element, padding included
+    o.chain = (int)std::min<int64_t>((int64_t)o.max_tasks * q.td * q.th * q.tw / 4, 0x7fffffff);
+    o.workspace_bytes = (int64_t)(q.part_floats * sizeof(float));
+    out = o;
     return true;
 }
 

@@ -445,6 +445,23 @@ def conv_march_plan(g, pass_, stats=False):
     return {f: int(getattr(info, f)) for f in MARCH_PLAN_FIELDS}
 
 
+MFMA_PLAN_FIELDS = tuple(f for f, _ in _lib.ConvMfmaPlanInfo._fields_)
+MFMA_KERNELS = {1: "tiled", 2: "tiled_n8", 3: "direct", 4: "cin1", 5: "wgrad3", 6: "wgrad4", 7: "bf16", 8: "bf16t", 9: "wgrad6"}
+
+
+def conv_mfma_plan(g, pass_, stats=False, bias=False, split=0, second_ld=0, align=16, x_align=None, y_align=None):
+    """Numbers of the launch plan whose kernel `conv_route` names (same arguments, host only) where the 3x3x3 MFMA kernels of
+    csrc/conv_mfma.hip / conv_mfma_wgrad.hip serve the call: a dict of the fields of Mri3dConvMfmaPlanInfo (include/mri3d.h), `kernel`
+    as the first word of the route name.  Raises Mri3dError (MRI3D_ENOTSUP) where `conv_route` names another file's kernel or "none"."""
+    info = _lib.ConvMfmaPlanInfo()
+    xa, ya = align if x_align is None else x_align, align if y_align is None else y_align
+    check(_lib.lib().mri3d_conv3d_mfma_plan_query(ctypes.byref(g), pass_, int(bool(stats)), int(bool(bias)), split, second_ld, xa, ya,
+                                                  ctypes.byref(info)), "conv3d_mfma_plan_query")
+    out = {f: int(getattr(info, f)) for f in MFMA_PLAN_FIELDS}
+    out["kernel"] = MFMA_KERNELS[out["kernel"]]
+    return out
+
+
 def norm_plan(g, pass_, align=16):
     """Launch plan of the norm-activation family for geometry `g` (a NormGeom) in pass `pass_` (NORM_PASS_STATS / _FWD / _BWD): the
     tuple (vec, CL, VT, cy, nblk, groups, gvox) documented at mri3d_norm_plan_query in include/mri3d.h.  Host only: nothing is

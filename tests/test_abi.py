@@ -49,7 +49,8 @@ def test_struct_layouts_match_header(tmp_path):
     """Compile the public header with gcc and compare sizeof/offsetof with the ctypes mirrors."""
     structs = {"Mri3dConvGeom": _lib.ConvGeom, "Mri3dNormGeom": _lib.NormGeom, "Mri3dPoolGeom": _lib.PoolGeom,
                "Mri3dUpGeom": _lib.UpGeom, "Mri3dDiceGeom": _lib.DiceGeom, "Mri3dNormPlanInfo": _lib.NormPlanInfo,
-               "Mri3dResamplePlanInfo": _lib.ResamplePlanInfo, "Mri3dMarchPlanInfo": _lib.MarchPlanInfo}
+               "Mri3dResamplePlanInfo": _lib.ResamplePlanInfo, "Mri3dMarchPlanInfo": _lib.MarchPlanInfo,
+               "Mri3dConvMfmaPlanInfo": _lib.ConvMfmaPlanInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "mri3d.h"', 'int main(void){']
     for cname, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
@@ -203,6 +204,40 @@ def test_march_plan_query_is_declared_bound_and_host_only():
     assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_WGRAD, 0, ctypes.byref(info)) == -1
     assert L.mri3d_conv3d_march_plan_query(None, _lib.PASS_FWD, 0, ctypes.byref(info)) == -1
     assert L.mri3d_conv3d_march_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, None) == -1
+
+
+def test_mfma_plan_query_is_declared_bound_and_host_only():
+    from mri_epilepsy_diagnosis_amd import ops
+    assert "mri3d_conv3d_mfma_plan_query" in _declared() and "mri3d_conv3d_mfma_plan_query" in _lib.SIGNATURES
+    fields = ["kernel", "ck", "chunks", "partial_chunk", "nt", "ntt", "gy", "tile_d", "tile_h", "tile_w", "tiles_d", "tiles_h", "tiles_w", "ntiles",
+              "units", "grid", "mode", "split", "wbn", "cit", "cob", "tg", "p", "ci8", "co8", "segl", "max_tasks", "min_tasks", "chain", "stats_blocks",
+              "workspace_bytes"]
+    assert [f for f, _ in _lib.ConvMfmaPlanInfo._fields_] == fields == list(ops.MFMA_PLAN_FIELDS)      # (layout: test_struct_layouts_match_header)
+    src = open(HEADER).read()
+    for value, name in ops.MFMA_KERNELS.items():
+        assert re.search(r"MRI3D_MFMA_%s\s*=\s*%d\b" % (name.upper(), value), src), name
+    L = _lib.lib()
+    info = _lib.ConvMfmaPlanInfo()
+    # the U-Net's 48 -> 16 decoder layer in fp32 at 2 x 160x192x160: 19200 tiles of 4 x 8 x 16 on the persistent grid of 512, six chunks
+    g = _lib.ConvGeom(2, 160, 192, 160, 48, 160, 192, 160, 16, 3, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 48, 16, _lib.F32)
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_FWD, 1, 1, 0, 0, 16, 16, ctypes.byref(info)) == 0
+    got = {f: getattr(info, f) for f in fields}
+    assert got == dict(kernel=1, ck=8, chunks=6, partial_chunk=0, nt=1, ntt=1, gy=1, tile_d=4, tile_h=8, tile_w=16, tiles_d=40, tiles_h=24, tiles_w=10,
+                       ntiles=19200, units=19200, grid=512, mode=0, split=0, wbn=0, cit=0, cob=0, tg=0, p=0, ci8=0, co8=0, segl=0, max_tasks=38,
+                       min_tasks=37, chain=0, stats_blocks=512, workspace_bytes=6 * 14 * 1024), got
+    assert got["stats_blocks"] == L.mri3d_conv3d_fwd_stats_blocks(ctypes.byref(g))
+    assert ops.conv_mfma_plan(g, _lib.PASS_FWD, stats=True) == dict(got, kernel="tiled")
+    # its weight gradient: wgrad6, three ci-tiles of 170 workgroups (21 or 22 per XCD group) walking 290 to 305 of the 51200 tiles of 2 x 6 x 16: chains of 305 x 48 products
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_WGRAD, 0, 0, 0, 0, 16, 16, ctypes.byref(info)) == 0
+    assert (info.kernel, info.cit, info.cob, info.tg, info.p, info.ntiles, info.max_tasks, info.min_tasks, info.chain, info.workspace_bytes) == \
+        (9, 3, 1, 27, 170, 51200, 305, 290, 305 * 48, 170 * 3 * 28 * 1024)
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, 0, 0, 0, 8, 16, ctypes.byref(info)) == -2      # a generic kernel's
+    g.dtype = _lib.BF16                                                                                                  # the marching kernel's
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, 0, 0, 0, 16, 16, ctypes.byref(info)) == -2
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_DGRAD, 1, 0, 0, 0, 16, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), 3, 0, 0, 0, 0, 16, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_mfma_plan_query(None, _lib.PASS_FWD, 0, 0, 0, 0, 16, 16, ctypes.byref(info)) == -1
+    assert L.mri3d_conv3d_mfma_plan_query(ctypes.byref(g), _lib.PASS_FWD, 0, 0, 0, 0, 16, 16, None) == -1
 
 
 def test_host_code_is_clean_under_address_and_ub_sanitizers():
