@@ -544,6 +544,49 @@ int mri3d_softmax_dice_index_fwd(const Mri3dDiceIndexGeom* g, const void* logits
 int mri3d_softmax_dice_index_bwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels,
                                  const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream);
 
+/* Voxel-wise cross-entropy / focal loss against a class map, alone or fused with the softmax-Dice above (ce_loss.hip).  Inputs
+ * as mri3d_softmax_dice_index_*: logits (n, vox, x_ld >= c) fp32 or bf16, labels dense uint8 (n, vox), 2 <= c <= 32 (else
+ * MRI3D_ENOTSUP), a label >= c marks an ignored voxel.  weight: c class weights, float32 on the device, or NULL for all ones.
+ *     logp_y = z_y - max z - log sum_j exp(z_j - max z),  pt = softmax(z)_y
+ *     l_v    = -w_y (1 - pt)^gamma logp_y                                (0 for an ignored voxel)
+ *     CE     = sum_v l_v / sum_v w_y     over the non-ignored voxels of the whole batch; when no voxel counts (sum_v w_y == 0) CE is
+ *              0 and its gradient exactly 0, where torch's cross_entropy gives NaN
+ *     loss   = dice_weight * Dice_index + ce_weight * CE
+ * gamma = 0 is F.cross_entropy(weight, ignore_index, reduction = "mean"); gamma in [1, 8] the focal loss; anything else, a negative
+ * or non-finite loss weight, or both loss weights zero: MRI3D_EINVAL.  dice_weight == 0 runs the CE-only kernels, which carry no
+ * Dice sums.  stats: 4 + n*c*3 floats = {CE, 1 / sum_w (0 when nothing counts), sum_v l_v, Dice_index}, then (with dice_weight > 0)
+ * the (tp, sum_p, sum_g) triples of mri3d_softmax_dice_index_fwd.  The backward reads them and dloss on the device and writes
+ * dlogits = dloss * d(loss)/d(logits) with one store per element (bf16: rounded once).  Sums are taken in double in a fixed order:
+ * same inputs, same bits.  Bytes per voxel: forward c * esz + 1, backward 2 * c * esz + 1, with or without the Dice part.
+ * mri3d_softmax_ce_index_plan_query (host only) reports what a pass launches by, for pass = MRI3D_PASS_FWD or MRI3D_PASS_DGRAD
+ * (the backward) and the alignments of the logits (with the backward: of logits and dlogits together) and of the labels, each the
+ * largest power of two <= 16 dividing the address: the class bucket (2, 4, 8, 16, 32), the read mode (0: element by element, 1: a
+ * voxel's classes in 4-element vectors, 2: two dense classes, 4 voxels per lane), whether the Dice part is compiled in, blocks per
+ * sample, lanes per sample (256 a block), and the work items of sample 0 (voxels; mode 2: 4-voxel groups and the single voxels
+ * behind them) as whole trips of all lanes and a remainder. */
+typedef struct Mri3dCeIndexGeom {
+    int32_t n;
+    int64_t vox;
+    int32_t c;
+    int32_t x_ld;
+    float eps;
+    int32_t dtype;
+    float gamma;
+    float dice_weight;
+    float ce_weight;
+} Mri3dCeIndexGeom;
+typedef struct Mri3dCeIndexPlanInfo {
+    int32_t bucket, mode, dice, blocks, lanes, whole_trips, remainder;
+    int64_t items;
+} Mri3dCeIndexPlanInfo;
+size_t mri3d_softmax_ce_index_workspace_bytes(const Mri3dCeIndexGeom* g);
+int mri3d_softmax_ce_index_plan_query(const Mri3dCeIndexGeom* g, int32_t pass, int32_t align_logits, int32_t align_labels,
+                                      Mri3dCeIndexPlanInfo* out);
+int mri3d_softmax_ce_index_fwd(const Mri3dCeIndexGeom* g, const void* logits, const uint8_t* labels, const float* weight,
+                               float* loss, float* stats, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_softmax_ce_index_bwd(const Mri3dCeIndexGeom* g, const void* logits, const uint8_t* labels, const float* weight,
+                               const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream);
+
 /* Confusion counts of two class maps — the per-class form of validate_dsc_asd's Dice / IoU (segmentation/routine.py:198-235,
  * metrics.py:312-329), exact integers.  pred, gt: nvox uint8 each, 2 <= c <= 32 (else MRI3D_ENOTSUP).
  *   counts[g*c + p] = #(gt == g and pred == p)      counts[c*c] = #(gt >= c or pred >= c)        (int64[c*c + 1])

@@ -84,6 +84,15 @@ class DiceIndexGeom(Structure):
     _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("x_ld", c_int32), ("eps", c_float), ("dtype", c_int32)]
 
 
+class CeIndexGeom(Structure):
+    _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("x_ld", c_int32), ("eps", c_float), ("dtype", c_int32),
+                ("gamma", c_float), ("dice_weight", c_float), ("ce_weight", c_float)]
+
+
+class CeIndexPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("bucket", "mode", "dice", "blocks", "lanes", "whole_trips", "remainder")] + [("items", c_int64)]
+
+
 _P = c_void_p
 _FP = c_void_p  # float* passed as raw address
 
@@ -162,6 +171,10 @@ SIGNATURES = {
     "mri3d_softmax_dice_index_workspace_bytes": (c_size_t, [POINTER(DiceIndexGeom)]),
     "mri3d_softmax_dice_index_fwd": (c_int32, [POINTER(DiceIndexGeom), _P, _P, _FP, _FP, _P, c_size_t, _P]),
     "mri3d_softmax_dice_index_bwd": (c_int32, [POINTER(DiceIndexGeom), _P, _P, _FP, _FP, _P, _P]),
+    "mri3d_softmax_ce_index_workspace_bytes": (c_size_t, [POINTER(CeIndexGeom)]),
+    "mri3d_softmax_ce_index_plan_query": (c_int32, [POINTER(CeIndexGeom), c_int32, c_int32, c_int32, POINTER(CeIndexPlanInfo)]),
+    "mri3d_softmax_ce_index_fwd": (c_int32, [POINTER(CeIndexGeom), _P, _P, _FP, _FP, _FP, _P, c_size_t, _P]),
+    "mri3d_softmax_ce_index_bwd": (c_int32, [POINTER(CeIndexGeom), _P, _P, _FP, _FP, _FP, _P, _P]),
     "mri3d_confusion_workspace_bytes": (c_size_t, [c_int32]),
     "mri3d_confusion_counts": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
     "mri3d_order_stats_workspace_bytes": (c_size_t, []),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libmri3d_hip.so")
-SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip", "tissue.hip"]
+SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "ce_loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip", "tissue.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file additions.  conv_march.hip keeps its accumulators in v160..v255 BY NAME (inline asm), above the v0..v159 that
@@ -32,7 +32,8 @@ EXTRA_FLAGS = {"conv_march.hip": ["-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"], "mc
 
 def _digest(path):
     h = hashlib.sha256()
-    for dep in [path, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_backends.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(HERE, "..", "include", "mri3d.h")]:
+    for dep in [path, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_backends.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "loss_index.h"),
+                os.path.join(HERE, "..", "include", "mri3d.h")]:
         with open(dep, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS + EXTRA_FLAGS.get(os.path.basename(path), [])).encode())
@@ -116,7 +117,7 @@ def build_host_sanitizer(verbose=True):
     flags = ["--offload-arch=gfx950", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
              "-O1", "-g", "-std=c++17", "-w", "-I", os.path.join(root, "include")]
     h = hashlib.sha256(" ".join(flags).encode())
-    inputs = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_backends.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(root, "include", "mri3d.h"), driver]
+    inputs = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_backends.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "loss_index.h"), os.path.join(root, "include", "mri3d.h"), driver]
     for f in inputs:
         with open(f, "rb") as fh:
             h.update(fh.read())

@@ -19,7 +19,9 @@ Reference operators replaced (file:line in /root/reference):
   gaussian_kde / intensity_moments   scipy.stats.gaussian_kde over a volume's voxels   full_sample_classification.ipynb cell 9
 Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo read-out of its stochastic models (no autograd);
 confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask; label_components / component_stats /
-select_components, the connected components of a mask (scipy.ndimage.label's numbering), their tables and the masks they select.
+select_components, the connected components of a mask (scipy.ndimage.label's numbering), their tables and the masks they select;
+softmax_ce_index_loss / softmax_dice_ce_index_loss, cross-entropy and focal loss against a class map, alone or fused with the index
+Dice (the reference trains on Dice alone).
 """
 import collections
 import ctypes
@@ -2133,6 +2135,97 @@ def softmax_dice_index_loss(logits, labels, eps=1e-9):
     voxel is ignored by every class's numerator and target sum).  One byte of target per voxel instead of 4*C."""
     return _SoftmaxDiceFn.apply(logits, labels, eps, (_dice_index_geometry, "mri3d_softmax_dice_index_workspace_bytes",
                                                       "mri3d_softmax_dice_index_fwd", "mri3d_softmax_dice_index_bwd"))
+
+
+# ----------------------------------------------------------------------------------------------- cross-entropy / focal (csrc/ce_loss.hip)
+CE_PLAN_FIELDS = tuple(f for f, _ in _lib.CeIndexPlanInfo._fields_)
+CE_READ_MODES = {0: "scalar", 1: "rows4", 2: "vox4"}
+
+
+def _ce_settings(who, gamma, dice_weight, ce_weight):
+    """The scalar settings of the CE family as floats; what the library would refuse is refused here by name."""
+    gamma, dice_weight, ce_weight = float(gamma), float(dice_weight), float(ce_weight)
+    if not (gamma == 0.0 or 1.0 <= gamma <= 8.0):
+        raise RuntimeError("%s: gamma must be 0 or in [1, 8], got %r" % (who, gamma))
+    if not (0.0 <= dice_weight < float("inf") and 0.0 <= ce_weight < float("inf")) or dice_weight + ce_weight == 0.0:
+        raise RuntimeError("%s: dice_weight and ce_weight must be finite, not negative and not both zero, got %r and %r"
+                           % (who, dice_weight, ce_weight))
+    return gamma, dice_weight, ce_weight
+
+
+def ce_index_plan(n, vox, c, dtype=torch.float32, pass_=_lib.PASS_FWD, x_ld=None, dice_weight=0.0, ce_weight=1.0, gamma=0.0,
+                  align_logits=16, align_labels=16):
+    """What `softmax_ce_index_loss` / `softmax_dice_ce_index_loss` launch by for `n` samples of `vox` voxels and `c` classes, host
+    only: a dict of CE_PLAN_FIELDS (Mri3dCeIndexPlanInfo, include/mri3d.h) with the read mode by name.  pass_: _lib.PASS_FWD or
+    _lib.PASS_DGRAD (the backward); align_*: the largest power of two <= 16 dividing the addresses."""
+    g = _lib.CeIndexGeom(int(n), int(vox), int(c), int(c if x_ld is None else x_ld), 1e-9, BF16 if dtype == torch.bfloat16 else F32,
+                         float(gamma), float(dice_weight), float(ce_weight))
+    info = _lib.CeIndexPlanInfo()
+    check(_lib.lib().mri3d_softmax_ce_index_plan_query(ctypes.byref(g), int(pass_), int(align_logits), int(align_labels),
+                                                       ctypes.byref(info)), "softmax_ce_index_plan_query")
+    out = {f: getattr(info, f) for f in CE_PLAN_FIELDS}
+    out["mode"] = CE_READ_MODES[out["mode"]]
+    return out
+
+
+class _SoftmaxCeFn(torch.autograd.Function):
+    """dice_weight * Dice_index + ce_weight * CE in one forward and one backward pass (dice_weight == 0: the CE-only kernels)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, weight, gamma, dice_weight, ce_weight, eps, who):
+        _require_device(logits)
+        _require_labels(who, labels)
+        if labels.dtype != torch.uint8:
+            raise RuntimeError("%s: labels must be a uint8 class map, got %s" % (who, labels.dtype))
+        logits = _cl(logits)
+        n, c, d, h, w = logits.shape
+        if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
+            raise RuntimeError("%s: labels shape %s incompatible with logits %s" % (who, tuple(labels.shape), tuple(logits.shape)))
+        gamma, dice_weight, ce_weight = _ce_settings(who, gamma, dice_weight, ce_weight)
+        if weight is not None:
+            if not torch.is_tensor(weight) or weight.device != logits.device or weight.dtype != torch.float32 \
+                    or tuple(weight.shape) != (c,):
+                raise RuntimeError("%s: weight must be a float32 tensor of %d entries on %s, got %s"
+                                   % (who, c, logits.device, "%s %s on %s" % (weight.dtype, tuple(weight.shape), weight.device)
+                                      if torch.is_tensor(weight) else type(weight).__name__))
+            weight = weight.detach().contiguous()
+        labels = labels.contiguous()
+        g = _lib.CeIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits), gamma, dice_weight, ce_weight)
+        L = _lib.lib()
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        stats = torch.empty(4 + n * c * 3, dtype=torch.float32, device=logits.device)
+        ws = _workspace(L.mri3d_softmax_ce_index_workspace_bytes(ctypes.byref(g)), logits.device)
+        check(L.mri3d_softmax_ce_index_fwd(ctypes.byref(g), _ptr(logits), _ptr(labels), _ptr(weight), _ptr(loss), _ptr(stats), _ptr(ws),
+                                           ws.numel(), _stream()), "softmax_ce_index_fwd")
+        ctx.save_for_backward(logits, labels, stats)
+        ctx.geom, ctx.weight = g, weight
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, labels, stats = ctx.saved_tensors
+        dloss = dloss.to(torch.float32).contiguous()
+        dlogits = _new(logits.shape, logits)
+        check(_lib.lib().mri3d_softmax_ce_index_bwd(ctypes.byref(ctx.geom), _ptr(logits), _ptr(labels), _ptr(ctx.weight), _ptr(stats),
+                                                    _ptr(dloss), _ptr(dlogits), _stream()), "softmax_ce_index_bwd")
+        return (dlogits,) + (None,) * 7
+
+
+def softmax_ce_index_loss(logits, labels, weight=None, gamma=0.0):
+    """Voxel-wise cross-entropy (gamma = 0) or focal loss (gamma in [1, 8]) of softmax(logits) against a uint8 class map
+    (N, 1, D, H, W) or (N, D, H, W), 2..32 classes:  sum_v -w_y (1 - p_y)^gamma log p_y / sum_v w_y over the voxels of the whole batch
+    whose label is a class; a label >= C marks an ignored voxel.  `weight`: float32 device tensor of C class weights, or None for
+    ones.  gamma = 0 is F.cross_entropy(logits, labels, weight, ignore_index, reduction="mean") — except that when no voxel counts
+    (everything ignored, or every class that occurs has weight 0) the loss is 0 and its gradient exactly 0 where torch gives NaN:
+    a patch outside the labelled region must not poison a run.  Device tensors only; there is no CPU fallback."""
+    return _SoftmaxCeFn.apply(logits, labels, weight, gamma, 0.0, 1.0, 1e-9, "softmax_ce_index_loss")
+
+
+def softmax_dice_ce_index_loss(logits, labels, dice_weight=1.0, ce_weight=1.0, weight=None, gamma=0.0, eps=1e-9):
+    """dice_weight * softmax_dice_index_loss(logits, labels, eps) + ce_weight * softmax_ce_index_loss(logits, labels, weight, gamma),
+    each pass reading the logits once: the bytes of the index Dice alone.  The CE term is 0 with a zero gradient when no voxel
+    counts (see softmax_ce_index_loss); the class weights apply to the CE term only."""
+    return _SoftmaxCeFn.apply(logits, labels, weight, gamma, dice_weight, ce_weight, eps, "softmax_dice_ce_index_loss")
 
 
 def confusion_counts(pred, gt, classes):
