@@ -998,6 +998,70 @@ int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t
 int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
                        const double* params_host, float* restored, uint8_t* labels, float* field, mri3d_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Distance maps (distance.hip): the exact squared Euclidean distance transform of a batch of n dense (d,h,w) uint8
+ * volumes in C order, ball morphology as a threshold of it, the signed map of a class map, and the boundary loss that reads it.
+ *   sq[v] = squared distance in voxels from v to the nearest zero voxel of the same volume (int32; 0 at a zero voxel).
+ *   value == -1: a voxel is zero when its byte is 0; 0 <= value <= 255: when its byte differs from `value` (a class of a class map;
+ *     value = 0 measures the distance to the non-zero voxels).  Anything else: MRI3D_EINVAL.
+ *   outside_zero == 0: only real voxels count (scipy.ndimage.distance_transform_edt); a volume without a zero voxel saturates to
+ *     MRI3D_EDT_INF everywhere.  outside_zero != 0: the volume is surrounded by zero voxels (scipy's border_value = 0 erosion).
+ *   d^2 + h^2 + w^2 >= MRI3D_EDT_INF or d*h*w >= 2^31: MRI3D_ENOTSUP.  A 2-D map is d = 1.  Integers only, no atomics: the same bits
+ *   every run.  No allocation, no synchronisation.
+ * mri3d_edt_sq_u8: out = sq (int32).
+ * mri3d_edt_threshold_u8: out (uint8) = sq <= r2 (greater == 0) or sq > r2 (greater != 0), 0 <= r2 < MRI3D_EDT_INF (else
+ *   MRI3D_EINVAL); the int32 map is never written.  With the ball of radius r and r2 = floor(r^2): value = 0, outside_zero = 0,
+ *   greater = 0 is binary_dilation; value = -1, greater = 1 is binary_erosion with border_value = !outside_zero.
+ * mri3d_signed_sqdist_u8: labels is a class map, `classes` in [2, 32] (else MRI3D_ENOTSUP), ids a HOST array of k class ids, 1 <= k
+ *   <= 32 and every id < classes (else MRI3D_EINVAL).  out: int32 (n, k, d, h, w).  For plane i (class c = ids[i]) and a voxel of label y:
+ *     y >= classes: INT32_MIN (the voxel is ignored);  class c absent from the volume, or no counted voxel of it of another class: 0;
+ *     y != c: +(squared distance to the nearest voxel of class c);  y == c: -(squared distance to the nearest voxel not of class c,
+ *     ignored voxels included).
+ *   Absence and fullness are decided on the device (a class mask per volume): nothing comes to the host.
+ * Workspace of all three: mri3d_edt_workspace_bytes(n, d, h, w) bytes (0 for a shape they refuse), 8-byte aligned.
+ * mri3d_edt_plan (host only): what the three passes launch by.  The w pass stages rows_w consecutive rows per workgroup (partial_w:
+ *   rows of the last workgroup when it is not whole, else 0); the h and d passes stage tiles of all len values of tx_h / tx_d
+ *   neighbouring lines (partial_*: lines of the last tile of a slice when it is not whole).  staged_* = 0: the line is longer than
+ *   the tile, lanes read global memory (rows_w = 1, tx = 64).  batch = n; grid_*: workgroups; lds_bytes: static LDS of a pass.
+ *
+ * Boundary loss (Kervadec et al., MIDL 2019) of logits NDHWC with voxel pitch x_ld >= c, fp32 or bf16, 2 <= c <= 32 (else
+ * MRI3D_ENOTSUP), against map = the (n, k, vox) int32 signed map of the k distinct class ids (k outside [1, 32], an id >= c or given
+ * twice: MRI3D_EINVAL):
+ *   loss = (1 / cnt) sum over (n, i, v) with s != INT32_MIN of softmax(z)[n, ids[i], v] * phi(s[n, i, v]),  cnt = number of terms,
+ *   phi(s) = sqrt(s) for s > 0, -(sqrt(-s) - 1) for s < 0, 0 for s = 0;  cnt == 0: loss 0 and a zero gradient.
+ *   dlogits_j = dloss / cnt * p_j (phi_j [j among ids] - sum_i p_ids[i] phi_i), the softmax recomputed; dlogits has the logits'
+ *   layout with its own voxel pitch dx_ld >= c (else MRI3D_EINVAL).
+ * stats: 4 floats the forward leaves for the backward {loss, 1 / cnt, cnt, sum}.  Sums are double block partials folded in a fixed
+ * order: the same bits every run.  Workspace of the forward: mri3d_softmax_boundary_workspace_bytes(), 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define MRI3D_EDT_INF 0x3f000000
+typedef struct Mri3dEdtPlanInfo {
+    int32_t rows_w, staged_w, partial_w, tx_h, staged_h, partial_h, tx_d, staged_d, partial_d, batch;
+    int64_t grid_w, grid_h, grid_d, lds_bytes, ws_bytes;
+} Mri3dEdtPlanInfo;
+typedef struct Mri3dBoundaryGeom {
+    int32_t n;
+    int64_t vox;
+    int32_t c;
+    int32_t x_ld;
+    int32_t dtype;
+    int32_t k;
+    int32_t ids[32];
+} Mri3dBoundaryGeom;
+size_t mri3d_edt_workspace_bytes(int32_t n, int32_t d, int32_t h, int32_t w);
+int mri3d_edt_plan(int32_t n, int32_t d, int32_t h, int32_t w, Mri3dEdtPlanInfo* out);
+int mri3d_edt_sq_u8(const uint8_t* in, int32_t n, int32_t d, int32_t h, int32_t w, int32_t value, int32_t outside_zero, int32_t* out,
+                    void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_edt_threshold_u8(const uint8_t* in, int32_t n, int32_t d, int32_t h, int32_t w, int32_t value, int32_t outside_zero,
+                           int32_t r2, int32_t greater, uint8_t* out, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_signed_sqdist_u8(const uint8_t* labels, int32_t n, int32_t d, int32_t h, int32_t w, int32_t classes, const int32_t* ids,
+                           int32_t k, int32_t* out, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+size_t mri3d_softmax_boundary_workspace_bytes(void);
+int mri3d_softmax_boundary_fwd(const Mri3dBoundaryGeom* g, const void* logits, const int32_t* map, float* loss, float* stats,
+                               void* workspace, size_t ws_bytes, mri3d_stream_t stream);
+int mri3d_softmax_boundary_bwd(const Mri3dBoundaryGeom* g, const void* logits, const int32_t* map, const float* stats,
+                               const float* dloss, void* dlogits, int32_t dx_ld, mri3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,18 @@ class CeIndexPlanInfo(Structure):
     _fields_ = [(n, c_int32) for n in ("bucket", "mode", "dice", "blocks", "lanes", "whole_trips", "remainder")] + [("items", c_int64)]
 
 
+class EdtPlanInfo(Structure):
+    _fields_ = [(n, c_int32) for n in ("rows_w", "staged_w", "partial_w", "tx_h", "staged_h", "partial_h", "tx_d", "staged_d", "partial_d",
+                                       "batch")] + [(n, c_int64) for n in ("grid_w", "grid_h", "grid_d", "lds_bytes", "ws_bytes")]
+
+
+class BoundaryGeom(Structure):
+    _fields_ = [("n", c_int32), ("vox", c_int64), ("c", c_int32), ("x_ld", c_int32), ("dtype", c_int32), ("k", c_int32),
+                ("ids", c_int32 * 32)]
+
+
+EDT_INF = 0x3f000000
+
 _P = c_void_p
 _FP = c_void_p  # float* passed as raw address
 
@@ -202,6 +214,16 @@ SIGNATURES = {
     "mri3d_surface_distance_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mri3d_surface_distance": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_elements": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P]),
+    "mri3d_edt_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "mri3d_edt_plan": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(EdtPlanInfo)]),
+    "mri3d_edt_sq_u8": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
+    "mri3d_edt_threshold_u8": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, c_size_t,
+                                         _P]),
+    "mri3d_signed_sqdist_u8": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), c_int32, _P, _P, c_size_t,
+                                         _P]),
+    "mri3d_softmax_boundary_workspace_bytes": (c_size_t, []),
+    "mri3d_softmax_boundary_fwd": (c_int32, [POINTER(BoundaryGeom), _P, _P, _FP, _FP, _P, c_size_t, _P]),
+    "mri3d_softmax_boundary_bwd": (c_int32, [POINTER(BoundaryGeom), _P, _P, _FP, _FP, _P, c_int32, _P]),
     "mri3d_components_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mri3d_components_plan_query": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(ComponentsPlanInfo)]),
     "mri3d_components_label": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "build")
 LIB = os.path.join(HERE, "libmri3d_hip.so")
-SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "ce_loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip", "tissue.hip"]
+SOURCES = ["api.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_wgrad.hip", "conv_march.hip", "conv_pointwise.hip", "upconv.hip", "sepconv.hip", "norm.hip", "resample.hip", "loss.hip", "ce_loss.hip", "labels.hip", "elementwise.hip", "bayes.hip", "mc_stats.hip", "preprocess.hip", "intensity.hip", "surface.hip", "distance.hip", "components.hip", "patches.hip", "detection.hip", "augment.hip", "kspace.hip", "register.hip", "tissue.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 # per-file additions.  conv_march.hip keeps its accumulators in v160..v255 BY NAME (inline asm), above the v0..v159 that

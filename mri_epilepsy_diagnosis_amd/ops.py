@@ -21,7 +21,9 @@ Beyond the reference: mc_state / mc_accumulate / mc_finalize, the Monte-Carlo re
 confusion_counts / class_scores_from_confusion, per-class Dice and IoU of a multi-class mask; label_components / component_stats /
 select_components, the connected components of a mask (scipy.ndimage.label's numbering), their tables and the masks they select;
 softmax_ce_index_loss / softmax_dice_ce_index_loss, cross-entropy and focal loss against a class map, alone or fused with the index
-Dice (the reference trains on Dice alone).
+Dice (the reference trains on Dice alone); edt_sq / edt_threshold / signed_sqdist / softmax_boundary_loss, the exact squared
+Euclidean distance transform of a mask, ball morphology as its thresholds, the signed distance maps of a class map and the
+boundary loss that reads them.
 """
 import collections
 import ctypes
@@ -2395,6 +2397,166 @@ def select_components(labels, keep, out=None):
         check(_lib.lib().mri3d_components_select(_ptr(labels), labels.numel(), _ptr(keep), keep.numel(), _ptr(out), _stream()),
               "components_select")
     return out
+
+
+# ----------------------------------------------------------------------------------------------- distance maps (csrc/distance.hip)
+EDT_PLAN_FIELDS = tuple(f for f, _ in _lib.EdtPlanInfo._fields_)
+EDT_INF = _lib.EDT_INF
+INT32_MIN = -2 ** 31
+
+
+def _batch_dhw(who, t):
+    """A (d, h, w) volume, an (h, w) map (d = 1) or a batch (n, d, h, w) as (n, d, h, w)."""
+    if t.dim() not in (2, 3, 4):
+        raise RuntimeError("%s: expected (h, w), (d, h, w) or (n, d, h, w), got shape %s" % (who, tuple(t.shape)))
+    return (1,) * (4 - t.dim()) + tuple(int(s) for s in t.shape)
+
+
+def _u8_volume(who, t):
+    _require_labels(who, t)
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    if t.dtype != torch.uint8:
+        raise RuntimeError("%s: expected a uint8 or bool tensor, got %s" % (who, t.dtype))
+    if t.numel() == 0:
+        raise RuntimeError("%s: empty volume" % who)
+    return t.contiguous()
+
+
+def _out_like(who, out, shape, dtype, like):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != like.device or not out.is_contiguous():
+        raise RuntimeError("%s: out must be a contiguous %s tensor of shape %s on the input's device" % (who, dtype, tuple(shape)))
+    return out
+
+
+def _edt_value(who, value):
+    if value is None:
+        return -1
+    if not 0 <= int(value) <= 255:
+        raise ValueError("%s: value must be None or a byte, got %r" % (who, value))
+    return int(value)
+
+
+def edt_plan(shape):
+    """What the three passes of the distance transform launch by for an (n, d, h, w), (d, h, w) or (h, w) shape: EDT_PLAN_FIELDS as
+    a dict (Mri3dEdtPlanInfo, include/mri3d.h).  Host only."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (2, 3, 4):
+        raise RuntimeError("edt_plan: expected (h, w), (d, h, w) or (n, d, h, w), got %s" % (shape,))
+    n, d, h, w = (1,) * (4 - len(shape)) + shape
+    info = _lib.EdtPlanInfo()
+    rc = _lib.lib().mri3d_edt_plan(n, d, h, w, ctypes.byref(info))
+    if rc != 0:
+        raise RuntimeError("edt_plan: the library refuses shape %s (rc=%d)" % (shape, rc))
+    return {f: getattr(info, f) for f in EDT_PLAN_FIELDS}
+
+
+def edt_sq(mask, value=None, outside_zero=False, out=None):
+    """Exact squared Euclidean distance transform of a uint8 / bool device tensor (h, w), (d, h, w) or a batch (n, d, h, w): int32
+    of the same shape, the squared distance in voxels to the nearest zero voxel of the same volume (scipy's
+    distance_transform_edt, squared, bit for bit).  value: a voxel is inside when it equals `value` instead of when it is non-zero.
+    outside_zero: the volume is surrounded by zeros.  A volume without a zero voxel gives EDT_INF everywhere."""
+    who = "edt_sq"
+    mask = _u8_volume(who, mask)
+    n, d, h, w = _batch_dhw(who, mask)
+    out = _out_like(who, out, mask.shape, torch.int32, mask)
+    L = _lib.lib()
+    ws = _workspace(L.mri3d_edt_workspace_bytes(n, d, h, w), mask.device)
+    check(L.mri3d_edt_sq_u8(_ptr(mask), n, d, h, w, _edt_value(who, value), int(bool(outside_zero)), _ptr(out), _ptr(ws), ws.numel(),
+                            _stream()), "edt_sq_u8")
+    return out
+
+
+def edt_threshold(mask, r2, greater=False, value=None, outside_zero=False, out=None):
+    """uint8 (edt_sq(mask, value, outside_zero) <= r2), or (> r2) with greater, in the transform's last pass: the int32 map is never
+    written.  r2 is an integer >= 0 (above EDT_INF - 1 it is EDT_INF - 1: a saturated volume is further than any radius)."""
+    who = "edt_threshold"
+    mask = _u8_volume(who, mask)
+    n, d, h, w = _batch_dhw(who, mask)
+    out = _out_like(who, out, mask.shape, torch.uint8, mask)
+    if int(r2) < 0:
+        raise ValueError("%s: r2 must not be negative, got %r" % (who, r2))
+    L = _lib.lib()
+    ws = _workspace(L.mri3d_edt_workspace_bytes(n, d, h, w), mask.device)
+    check(L.mri3d_edt_threshold_u8(_ptr(mask), n, d, h, w, _edt_value(who, value), int(bool(outside_zero)), min(int(r2), EDT_INF - 1),
+                                   int(bool(greater)), _ptr(out), _ptr(ws), ws.numel(), _stream()), "edt_threshold_u8")
+    return out
+
+
+def _class_ids(who, classes, ids):
+    classes, ids = int(classes), tuple(int(i) for i in ids)
+    if not 2 <= classes <= 32:
+        raise ValueError("%s: classes must be in [2, 32], got %d" % (who, classes))
+    if not 1 <= len(ids) <= 32 or any(not 0 <= i < classes for i in ids) or len(set(ids)) != len(ids):
+        raise ValueError("%s: ids are 1 to 32 distinct classes below %d, got %r" % (who, classes, ids))
+    return classes, ids
+
+
+def signed_sqdist(class_map, classes, ids, out=None):
+    """Signed squared-distance maps of a uint8 device class map (n, d, h, w) or (n, 1, d, h, w): int32 (n, K, d, h, w), one plane per
+    class id.  INT32_MIN at a voxel whose label is >= classes; 0 everywhere in a volume the class is absent from or fills; + the
+    squared distance to the class outside it; - the squared distance to what is not the class inside it.  Nothing comes to the host:
+    the call can stand inside a captured step."""
+    who = "signed_sqdist"
+    classes, ids = _class_ids(who, classes, ids)
+    class_map = _u8_volume(who, class_map)
+    if class_map.dim() == 5 and class_map.shape[1] == 1:
+        class_map = class_map[:, 0]
+    if class_map.dim() != 4:
+        raise RuntimeError("%s: expected a class map (n, d, h, w) or (n, 1, d, h, w), got shape %s" % (who, tuple(class_map.shape)))
+    n, d, h, w = (int(s) for s in class_map.shape)
+    out = _out_like(who, out, (n, len(ids), d, h, w), torch.int32, class_map)
+    L = _lib.lib()
+    ws = _workspace(L.mri3d_edt_workspace_bytes(n, d, h, w), class_map.device)
+    check(L.mri3d_signed_sqdist_u8(_ptr(class_map), n, d, h, w, classes, (ctypes.c_int32 * len(ids))(*ids), len(ids), _ptr(out), _ptr(ws),
+                                   ws.numel(), _stream()), "signed_sqdist_u8")
+    return out
+
+
+class _SoftmaxBoundaryFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, signed_map, ids):
+        who = "softmax_boundary_loss"
+        _require_device(logits)
+        _require_labels(who, signed_map)
+        logits, x_ld = _nd(logits)                    # the logits keep their voxel pitch; the gradient is dense
+        n, c, d, h, w = logits.shape
+        _, ids = _class_ids(who, c, ids)
+        if signed_map.dtype != torch.int32 or tuple(signed_map.shape) != (n, len(ids), d, h, w) or signed_map.device != logits.device:
+            raise RuntimeError("%s: the map must be int32 of shape %s on %s, got %s %s on %s"
+                               % (who, (n, len(ids), d, h, w), logits.device, signed_map.dtype, tuple(signed_map.shape),
+                                  signed_map.device))
+        signed_map = signed_map.contiguous()
+        g = _lib.BoundaryGeom(n, d * h * w, c, x_ld, _dt(logits), len(ids), (ctypes.c_int32 * 32)(*ids))
+        L = _lib.lib()
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        stats = torch.empty(4, dtype=torch.float32, device=logits.device)
+        ws = _workspace(L.mri3d_softmax_boundary_workspace_bytes(), logits.device)
+        check(L.mri3d_softmax_boundary_fwd(ctypes.byref(g), _ptr(logits), _ptr(signed_map), _ptr(loss), _ptr(stats), _ptr(ws), ws.numel(),
+                                           _stream()), "softmax_boundary_fwd")
+        ctx.save_for_backward(logits, signed_map, stats)
+        ctx.geom = g
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, signed_map, stats = ctx.saved_tensors
+        g = ctx.geom
+        dloss = dloss.to(torch.float32).contiguous()
+        dlogits = _new(logits.shape, logits)
+        check(_lib.lib().mri3d_softmax_boundary_bwd(ctypes.byref(g), _ptr(logits), _ptr(signed_map), _ptr(stats), _ptr(dloss),
+                                                    _ptr(dlogits), g.c, _stream()), "softmax_boundary_bwd")
+        return dlogits, None, None
+
+
+def softmax_boundary_loss(logits, signed_map, ids):
+    """Boundary loss (Kervadec et al., MIDL 2019): the mean over classes `ids` and voxels of softmax(logits)[:, id] * phi(s), with s
+    the int32 map of `signed_sqdist(class_map, C, ids)` and phi(s) = sqrt(s), -(sqrt(-s) - 1) or 0 for s > 0, < 0, = 0.  Terms with
+    s == INT32_MIN (ignored voxels) are left out of the sum and of the count; with none left the loss is 0 and its gradient zero.
+    logits: fp32 / bf16 (n, C, d, h, w), NDHWC with any voxel pitch, 2..32 classes.  No gradient flows into the map."""
+    return _SoftmaxBoundaryFn.apply(logits, signed_map, tuple(ids))
 
 
 # ----------------------------------------------------------------------------------------------- intensity statistics (csrc/intensity.hip)

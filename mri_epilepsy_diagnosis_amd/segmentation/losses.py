@@ -9,6 +9,9 @@ All three run csrc/ce_loss.hip (ops.softmax_ce_index_loss / ops.softmax_dice_ce_
 backward, whatever the combination.  The class weights are host numbers held by the loss; they go to a device once, the first
 time that device is seen, in a table shared by every loss with the same weights — never inside a captured training step.  Two
 losses built with equal settings are equal and hash alike, so `parallel.StepCache` replays the step it captured for the first.
+
+BoundaryLoss and DiceBoundaryLoss (csrc/distance.hip) add the boundary term of Kervadec et al.: the signed distance maps of the
+class map are computed on the device inside every step.
 """
 import numpy as np
 import torch
@@ -93,6 +96,57 @@ class DiceCELoss(_IndexLoss):
 
     def __init__(self, dice_weight=1.0, ce_weight=1.0, weight=None, gamma=0.0):
         super().__init__(dice_weight, ce_weight, weight, gamma)
+
+
+class _BoundaryLoss:
+    """dice_weight * index Dice + boundary_weight * boundary term; equality and hash go by the settings."""
+
+    def __init__(self, dice_weight, boundary_weight, ids, classes):
+        self.dice_weight, self.boundary_weight = float(dice_weight), float(boundary_weight)
+        self.classes, self.ids = ops._class_ids(type(self).__name__, classes, ids)
+        if not (0.0 <= self.dice_weight < float("inf") and 0.0 < self.boundary_weight < float("inf")):
+            raise ValueError("%s: dice_weight must be finite and >= 0, boundary_weight finite and > 0, got %r and %r"
+                             % (type(self).__name__, dice_weight, boundary_weight))
+
+    def _key(self):
+        return (self.dice_weight, self.boundary_weight, self.ids, self.classes)
+
+    def __eq__(self, other):
+        return isinstance(other, _BoundaryLoss) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "%s(dice_weight=%g, boundary_weight=%g, ids=%s, classes=%d)" % ((type(self).__name__,) + self._key())
+
+    def __call__(self, logits, class_map):
+        if logits.shape[1] != self.classes:
+            raise RuntimeError("%s: built for %d classes, the logits have %d" % (type(self).__name__, self.classes, logits.shape[1]))
+        maps = ops.signed_sqdist(class_map, self.classes, self.ids)       # per step: the targets change with the augmentation
+        loss = self.boundary_weight * ops.softmax_boundary_loss(logits, maps, self.ids)
+        if self.dice_weight > 0.0:
+            loss = loss + self.dice_weight * ops.softmax_dice_index_loss(logits, class_map)
+        return loss
+
+
+class BoundaryLoss(_BoundaryLoss):
+    """Boundary loss of Kervadec et al. (MIDL 2019) for the classes `ids` of a `classes`-class map: the mean of softmax(logits)[id]
+    times the signed distance to the class's boundary (negative inside), whose gradient does not vanish when prediction and lesion
+    do not overlap.  The signed maps are made on the device inside the step (csrc/distance.hip), with no host synchronisation."""
+
+    def __init__(self, ids=(1,), classes=2):
+        super().__init__(0.0, 1.0, ids, classes)
+
+
+class DiceBoundaryLoss(_BoundaryLoss):
+    """dice_weight * softmax-Dice (ops.softmax_dice_index_loss) + boundary_weight * BoundaryLoss, two operators on the same logits.
+    Two losses with equal settings are equal and hash alike, so `parallel.StepCache` replays the step it captured for the first;
+    the weights are part of the settings, so a re-weighted schedule (the paper's rebalancing of the two terms over the epochs)
+    costs one new capture per distinct (dice_weight, boundary_weight) pair: step the weights a few times a run, not every epoch."""
+
+    def __init__(self, dice_weight=1.0, boundary_weight=1.0, ids=(1,), classes=2):
+        super().__init__(dice_weight, boundary_weight, ids, classes)
 
 
 def weights_from_counts(counts, rule):
