@@ -21,8 +21,10 @@
 //
 // Boundary loss: L = (1 / cnt) sum over (n, k, v) with s != INT32_MIN of softmax(z)[n, c_k, v] * phi(s[n, k, v]),
 //   phi(s) = sqrt(s) for s > 0, -(sqrt(-s) - 1) for s < 0, 0 for s = 0;  dL/dz_j = g / cnt * p_j (phi_j [j in ids] - sum_k p_ck phi_k).
-// One streaming pass each way over the plan of the class-map losses (loss_index.h: class buckets, scalar or 4-element reads);
-// float products, double sums per lane, block partials folded in a fixed order.
+// One streaming pass each way over loss_index.h's row reads and row store (class buckets, scalar or 4-element accesses), launched
+// by its idx_plan with no label bytes, so without a 4-voxel path.  The two row loops stand here: they index a map by voxel where
+// the class-map walk hands its body a label.  Float products, double sums per lane, block partials folded in a fixed order by the
+// pair-sum helpers that the cross-entropy uses too.
 #include "loss_index.h"
 #include <limits.h>
 
@@ -242,15 +244,14 @@ template <typename T, int CB>
 __global__ void __launch_bounds__(256)
 boundary_fwd_kernel(const T* __restrict__ logits, const int* __restrict__ map, double* __restrict__ part, int64_t vox, int C, int K,
                     int x_ld, int mode, BdSlots slots) {
-    __shared__ double red[4][2];
     __shared__ int8_t sslot[kIdxMaxC];
     if (threadIdx.x < kIdxMaxC) sslot[threadIdx.x] = (int)threadIdx.x < CB ? slots.slot[threadIdx.x] : (int8_t)-1;
     __syncthreads();
     const int n = blockIdx.y;
-    const T* zn = logits + (int64_t)n * vox * x_ld;
     const int* mn = map + (int64_t)n * K * vox;
     double sum = 0.0;
     unsigned cnt = 0;
+    const T* zn = logits + (int64_t)n * vox * x_ld;
 #pragma unroll 1
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < vox; v += (int64_t)gridDim.x * 256) {
         float z[CB], phi[CB], s;
@@ -264,24 +265,15 @@ boundary_fwd_kernel(const T* __restrict__ logits, const int* __restrict__ map, d
     sum = wave_sum_d(sum);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = sum; red[threadIdx.x >> 6][1] = (double)cnt; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        part[((size_t)n * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    pair_block_row(sum, (double)cnt, n, part);
 }
 
 // stats = {loss, 1 / cnt (0 when nothing counts), cnt, sum}
 __global__ void __launch_bounds__(256)
 boundary_finalize_kernel(const double* __restrict__ part, int rows, float* __restrict__ stats, float* __restrict__ loss) {
-    __shared__ double r0[256], r1[256];
-    double a = 0.0, b = 0.0;
-    for (int q = threadIdx.x; q < rows; q += 256) { a += part[(size_t)q * 2]; b += part[(size_t)q * 2 + 1]; }
-    r0[threadIdx.x] = a, r1[threadIdx.x] = b;
-    __syncthreads();
+    double num, den;
+    pair_finalize_sum(part, rows, num, den);
     if (threadIdx.x == 0) {
-        double num = 0.0, den = 0.0;
-        for (int k = 0; k < 256; ++k) { num += r0[k]; den += r1[k]; }
         const float l = den > 0.0 ? (float)(num / den) : 0.f;
         stats[0] = l;
         stats[1] = den > 0.0 ? (float)(1.0 / den) : 0.f;
@@ -300,10 +292,10 @@ boundary_bwd_kernel(const T* __restrict__ logits, const int* __restrict__ map, c
     if (threadIdx.x < kIdxMaxC) sslot[threadIdx.x] = (int)threadIdx.x < CB ? slots.slot[threadIdx.x] : (int8_t)-1;
     __syncthreads();
     const int n = blockIdx.y;
-    const T* zn = logits + (int64_t)n * vox * x_ld;
-    T* dn = dlogits + (int64_t)n * vox * dx_ld;
     const int* mn = map + (int64_t)n * K * vox;
     const float kc = dloss[0] * stats[1];
+    const T* zn = logits + (int64_t)n * vox * x_ld;
+    T* dn = dlogits + (int64_t)n * vox * dx_ld;
 #pragma unroll 1
     for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < vox; v += (int64_t)gridDim.x * 256) {
         float z[CB], phi[CB], s;
@@ -318,21 +310,7 @@ boundary_bwd_kernel(const T* __restrict__ logits, const int* __restrict__ map, c
         }
 #pragma unroll
         for (int j = 0; j < CB; ++j) z[j] = kc * z[j] * (phi[j] - dot);
-        T* d = dn + v * dx_ld;
-        bool stored = false;
-        if constexpr (CB >= 4) {
-            if (mode == kIdxRows4) {
-#pragma unroll
-                for (int j = 0; j < CB; j += 4)
-                    if (j < C) stf4(d + j, make_float4(z[j], z[j + 1], z[j + 2], z[j + 3]));
-                stored = true;
-            }
-        }
-        if (!stored) {
-#pragma unroll
-            for (int j = 0; j < CB; ++j)
-                if (j < C) stf(d + j, z[j]);
-        }
+        idx_store_row<T, CB>(dn + v * dx_ld, C, mode, z);       // the gradient has its own pitch
     }
 }
 
@@ -418,17 +396,10 @@ static int edt_common(const char* who, const void* in, int n, int d, int h, int 
     return ws_check8(who, workspace, ws_bytes, edt_ws_bytes(n, d, h, w));
 }
 
-struct BdPlan { int bucket, mode, blocks; };
-
 static int bd_check(const Mri3dBoundaryGeom* g, const char* who, BdSlots* slots) {
-    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
-    MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
-    MRI3D_REQUIRE(g->n > 0 && g->vox > 0, MRI3D_EINVAL, "%s: empty tensor", who);
-    MRI3D_REQUIRE(g->c >= kIdxMinC && g->c <= kIdxMaxC, MRI3D_ENOTSUP, "%s: classes must be in [%d,%d], got %d", who, kIdxMinC,
-                  kIdxMaxC, g->c);
-    MRI3D_REQUIRE(g->x_ld >= g->c, MRI3D_EINVAL, "%s: pitch %d < classes %d", who, g->x_ld, g->c);
+    int rc = idx_check(g, who, kIdxMaxC, kIdxMaxBlocks);
+    if (rc) return rc;
     MRI3D_REQUIRE(g->k >= 1 && g->k <= kIdxMaxC, MRI3D_EINVAL, "%s: 1 to %d class ids, got %d", who, kIdxMaxC, g->k);
-    MRI3D_REQUIRE(g->n <= kIdxMaxBlocks, MRI3D_ENOTSUP, "%s: at most %d samples, got %d", who, kIdxMaxBlocks, g->n);
     BdSlots sl;
     for (int j = 0; j < kIdxMaxC; ++j) sl.slot[j] = -1;
     for (int k = 0; k < g->k; ++k) {
@@ -439,14 +410,6 @@ static int bd_check(const Mri3dBoundaryGeom* g, const char* who, BdSlots* slots)
     }
     if (slots) *slots = sl;
     return MRI3D_OK;
-}
-
-static BdPlan bd_plan(const Mri3dBoundaryGeom& g, bool bwd, int align_logits, int dx_ld = 0) {
-    BdPlan p;
-    p.bucket = g.c <= 2 ? 2 : g.c <= 4 ? 4 : g.c <= 8 ? 8 : g.c <= 16 ? 16 : 32;
-    p.mode = g.c % 4 == 0 && g.x_ld % 4 == 0 && dx_ld % 4 == 0 && align_vec4(g.dtype, align_logits) ? kIdxRows4 : kIdxScalar;
-    p.blocks = bwd ? dice_bwd_blocks(g.vox, g.n) : dice_fwd_blocks(g.vox, g.n, kIdxMaxBlocks);
-    return p;
 }
 
 }  // namespace mri3d
@@ -532,17 +495,6 @@ extern "C" int mri3d_signed_sqdist_u8(const uint8_t* labels, int32_t n, int32_t 
     return MRI3D_OK;
 }
 
-#define BD_DISPATCH(CALL)                   \
-    do {                                    \
-        switch (plan.bucket) {              \
-            case 2: CALL(2); break;         \
-            case 4: CALL(4); break;         \
-            case 8: CALL(8); break;         \
-            case 16: CALL(16); break;       \
-            default: CALL(32); break;       \
-        }                                   \
-    } while (0)
-
 extern "C" size_t mri3d_softmax_boundary_workspace_bytes(void) { return (size_t)kIdxMaxBlocks * 2 * sizeof(double); }
 
 extern "C" int mri3d_softmax_boundary_fwd(const Mri3dBoundaryGeom* g, const void* logits, const int32_t* map, float* loss, float* stats,
@@ -554,12 +506,12 @@ extern "C" int mri3d_softmax_boundary_fwd(const Mri3dBoundaryGeom* g, const void
     rc = ws_check8("softmax_boundary_fwd", workspace, ws_bytes, mri3d_softmax_boundary_workspace_bytes());
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const BdPlan plan = bd_plan(*g, false, ptr_align(logits));
+    const IdxPlan plan = idx_plan(g->dtype, g->n, g->vox, g->c, g->x_ld, g->x_ld, false, ptr_align(logits), 0);
     double* part = static_cast<double*>(workspace);
 #define CALL(CB)                                                                                                                 \
     hipLaunchKernelGGL((boundary_fwd_kernel<T, CB>), dim3(plan.blocks, g->n), dim3(256), 0, s, (const T*)logits, (const int*)map, part, \
                        g->vox, g->c, g->k, g->x_ld, plan.mode, slots)
-    MRI3D_DISPATCH_DTYPE(g->dtype, T, { BD_DISPATCH(CALL); });
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(plan.bucket, CALL); });
 #undef CALL
     rc = check_launch("softmax_boundary_fwd");
     if (rc) return rc;
@@ -575,11 +527,11 @@ extern "C" int mri3d_softmax_boundary_bwd(const Mri3dBoundaryGeom* g, const void
     MRI3D_REQUIRE(dx_ld >= g->c, MRI3D_EINVAL, "softmax_boundary_bwd: gradient pitch %d < classes %d", dx_ld, g->c);
     MRI3D_REQUIRE(logits && map && stats && dloss && dlogits, MRI3D_EINVAL, "softmax_boundary_bwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const BdPlan plan = bd_plan(*g, true, ptr_align(logits, dlogits), dx_ld);
+    const IdxPlan plan = idx_plan(g->dtype, g->n, g->vox, g->c, g->x_ld, dx_ld, true, ptr_align(logits, dlogits), 0);
 #define CALL(CB)                                                                                                                 \
     hipLaunchKernelGGL((boundary_bwd_kernel<T, CB>), dim3(plan.blocks, g->n), dim3(256), 0, s, (const T*)logits, (const int*)map, stats, \
                        dloss, (T*)dlogits, g->vox, g->c, g->k, g->x_ld, dx_ld, plan.mode, slots)
-    MRI3D_DISPATCH_DTYPE(g->dtype, T, { BD_DISPATCH(CALL); });
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(plan.bucket, CALL); });
 #undef CALL
     return check_launch("softmax_boundary_bwd");
 }

@@ -10,12 +10,12 @@
 // Appendix C.1); ct == 1 reproduces that broadcast, ct == c is the per-class form.  Class map: g_c = [label == c], a label >= C
 // belongs to no class.
 //
-// The two forms have their own forward and backward loops (the class map's 4-voxel path, class buckets and integer sum_g have no
-// float-target counterpart) and share what stands around them: the softmax, the block's row of partial sums, the finalize kernel,
-// the gradient's coefficients, the grid rules and the host checks.
+// The float form has its own forward and backward loops; the class-map form is a body inside loss_index.h's voxel walk (4-voxel
+// path, class buckets, integer sum_g) and launches by its idx_plan.  Both share what stands around them: the softmax, the block's
+// row of partial sums, the finalize, the gradient's coefficients, the grid rules and the head of the host checks.
 //
 // HBM-bound.  Bytes per voxel: forward C * esz + target, backward 2 * C * esz + target; target = 4 * ct (float) or 1 (class map).
-#include "loss_index.h"   // what the class-map form shares with ce_loss.hip, moved there word for word
+#include "loss_index.h"
 
 namespace mri3d {
 
@@ -38,46 +38,12 @@ template <int K> __device__ __forceinline__ void softmax_inplace(float (&z)[K]) 
     for (int j = 0; j < K; ++j) z[j] *= inv;
 }
 
-// part -> stats[n][c][3] and the mean loss: the float-target and the class-index loss are one expression of the three sums.
-// One block of 256 threads: (n, c) pairs are handled 8 at a time by 32 partial lanes each (fixed-order double sums)
+// part -> stats[n][c][3] and the mean loss, one block of 256 threads
 __global__ void __launch_bounds__(256)
 dice_finalize_kernel(const double* __restrict__ part, float* __restrict__ stats, float* __restrict__ loss, int N, int C,
                      int nblk, float eps) {
-    __shared__ double r0[256], r1[256], r2[256];
-    __shared__ double acc_loss;
-    const int el = threadIdx.x >> 5, ql = threadIdx.x & 31;
-    if (threadIdx.x == 0) acc_loss = 0.0;
-    __syncthreads();
-    for (int base = 0; base < N * C; base += 8) {
-        const int i = base + el;
-        double tp = 0.0, sp = 0.0, sg = 0.0;
-        if (i < N * C) {
-            const int n = i / C, c = i - n * C;
-            const double* p = part + ((size_t)n * nblk * C + c) * 3;
-            for (int q = ql; q < nblk; q += 32) {
-                tp += p[(size_t)q * C * 3];
-                sp += p[(size_t)q * C * 3 + 1];
-                sg += p[(size_t)q * C * 3 + 2];
-            }
-        }
-        r0[threadIdx.x] = tp; r1[threadIdx.x] = sp; r2[threadIdx.x] = sg;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int e = 0; e < 8 && base + e < N * C; ++e) {
-                double a = 0.0, b = 0.0, d = 0.0;
-                for (int k = 0; k < 32; ++k) { a += r0[e * 32 + k]; b += r1[e * 32 + k]; d += r2[e * 32 + k]; }
-                const int i2 = base + e;
-                stats[i2 * 3] = (float)a;
-                stats[i2 * 3 + 1] = (float)b;
-                stats[i2 * 3 + 2] = (float)d;
-                // float arithmetic from here mirrors the reference's fp32 tensors
-                const float ftp = (float)a, den = 2.f * ftp + ((float)b - ftp) + ((float)d - ftp) + eps;
-                acc_loss += 1.0 - (double)(2.f * ftp / den);
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = (float)(acc_loss / (double)(N * C));
+    const float dv = dice_finalize_rows(part, stats, N, C, nblk, eps);
+    if (threadIdx.x == 0) loss[0] = dv;
 }
 
 // ------------------------------------------------------------------ float target
@@ -144,46 +110,14 @@ __global__ void __launch_bounds__(256)
 dice_index_fwd_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ labels, double* __restrict__ part, int64_t vox,
                       int C, int x_ld, int mode) {
     __shared__ double red[4][CB * 3];
-    const int n = blockIdx.y;
-    const T* zn = logits + (int64_t)n * vox * x_ld;
-    const uint8_t* ln = labels + (int64_t)n * vox;
     IdxAcc<CB> a;
 #pragma unroll
     for (int j = 0; j < CB; ++j) { a.tp[j] = 0.0; a.sp[j] = 0.0; a.sg[j] = 0u; }
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    if (CB == 2 && mode == kIdxVox4) {
-        if constexpr (CB == 2) {
-            const IdxVox4Plan plan(n, vox);
-            for (int64_t i = tid; i < plan.items; i += nth) {
-                if (i < plan.groups) {
-                    const int64_t v0 = plan.head + i * 4;
-                    float z[8];
-                    idx_ld8(zn + v0 * 2, z);
-                    const uint32_t lw = *reinterpret_cast<const uint32_t*>(ln + v0);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        float p[2] = {z[2 * k], z[2 * k + 1]};
-                        softmax_inplace<2>(p);
-                        a.add(p, (lw >> (8 * k)) & 0xffu);
-                    }
-                } else {
-                    const int64_t v = plan.single(i);
-                    float p[2] = {ldf(zn + v * 2), ldf(zn + v * 2 + 1)};
-                    softmax_inplace<2>(p);
-                    a.add(p, ln[v]);
-                }
-            }
-        }
-    } else {
-#pragma unroll 1
-        for (int64_t v = tid; v < vox; v += nth) {
-            float p[CB];
-            idx_load_row<T, CB>(zn + v * x_ld, C, mode, p);
-            softmax_inplace<CB>(p);
-            a.add(p, ln[v]);
-        }
-    }
-    dice_block_row<CB>(a.tp, a.sp, a.sg, C, n, red, part);
+    idx_walk<false, T, CB>(logits, labels, (T*)nullptr, vox, C, x_ld, mode, [&](float (&p)[CB], unsigned lab, int) {
+        softmax_inplace<CB>(p);
+        a.add(p, lab);
+    });
+    dice_block_row<CB>(a.tp, a.sp, a.sg, C, blockIdx.y, red, part);
 }
 
 // ka * [label == c] + kb (dice_bwd_kernel's fmaf(ka, g, kb) at g = 1 and g = 0), then the softmax Jacobian
@@ -205,9 +139,6 @@ dice_index_bwd_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ 
                       const float* __restrict__ dloss, T* __restrict__ dlogits, int64_t vox, int N, int C, int x_ld, int mode,
                       float eps) {
     const int n = blockIdx.y;
-    const T* zn = logits + (int64_t)n * vox * x_ld;
-    const uint8_t* ln = labels + (int64_t)n * vox;
-    T* dn = dlogits + (int64_t)n * vox * x_ld;
     // the two coefficients of every class, one class per lane, then to every lane's registers through LDS
     __shared__ float ska[CB], skb[CB];
     if (threadIdx.x < CB) {
@@ -220,58 +151,10 @@ dice_index_bwd_kernel(const T* __restrict__ logits, const uint8_t* __restrict__ 
     float ka[CB], kb[CB];
 #pragma unroll
     for (int j = 0; j < CB; ++j) ka[j] = ska[j], kb[j] = skb[j];
-    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
-    if (CB == 2 && mode == kIdxVox4) {
-        if constexpr (CB == 2) {
-            const IdxVox4Plan plan(n, vox);
-            for (int64_t i = tid; i < plan.items; i += nth) {
-                if (i < plan.groups) {
-                    const int64_t v0 = plan.head + i * 4;
-                    float z[8];
-                    idx_ld8(zn + v0 * 2, z);
-                    const uint32_t lw = *reinterpret_cast<const uint32_t*>(ln + v0);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        float p[2] = {z[2 * k], z[2 * k + 1]};
-                        softmax_inplace<2>(p);
-                        idx_grad<2>(p, (lw >> (8 * k)) & 0xffu, ka, kb);
-                        z[2 * k] = p[0], z[2 * k + 1] = p[1];
-                    }
-                    idx_st8(dn + v0 * 2, z);
-                } else {
-                    const int64_t v = plan.single(i);
-                    float p[2] = {ldf(zn + v * 2), ldf(zn + v * 2 + 1)};
-                    softmax_inplace<2>(p);
-                    idx_grad<2>(p, ln[v], ka, kb);
-                    stf(dn + v * 2, p[0]);
-                    stf(dn + v * 2 + 1, p[1]);
-                }
-            }
-        }
-        return;
-    }
-#pragma unroll 1      // one voxel's CB registers at a time: unrolled, the 32-class body does not fit the register file
-    for (int64_t v = tid; v < vox; v += nth) {
-        float p[CB];
-        idx_load_row<T, CB>(zn + v * x_ld, C, mode, p);
+    idx_walk<true, T, CB>(logits, labels, dlogits, vox, C, x_ld, mode, [&](float (&p)[CB], unsigned lab, int) {
         softmax_inplace<CB>(p);
-        idx_grad<CB>(p, ln[v], ka, kb);
-        T* d = dn + v * x_ld;
-        bool stored = false;
-        if constexpr (CB >= 4) {
-            if (mode == kIdxRows4) {
-#pragma unroll
-                for (int j = 0; j < CB; j += 4)
-                    if (j < C) stf4(d + j, make_float4(p[j], p[j + 1], p[j + 2], p[j + 3]));
-                stored = true;
-            }
-        }
-        if (!stored) {
-#pragma unroll
-            for (int j = 0; j < CB; ++j)
-                if (j < C) stf(d + j, p[j]);
-        }
-    }
+        idx_grad<CB>(p, lab, ka, kb);
+    });
 }
 
 // ------------------------------------------------------------------ arg-max
@@ -294,18 +177,8 @@ argmax_u8_kernel(const T* __restrict__ logits, uint8_t* __restrict__ out, int64_
 // ------------------------------------------------------------------ host side of both Dice forms
 static size_t dice_ws_bytes(int cap, int n, int c) { return ((size_t)cap + (size_t)n) * c * 3 * sizeof(double); }
 
-// what the two geometries have in common: Geom is Mri3dDiceGeom or Mri3dDiceIndexGeom
-template <typename Geom> static int dice_check(const Geom* g, const char* who, int cmax) {
-    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
-    MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
-    MRI3D_REQUIRE(g->n > 0 && g->vox > 0, MRI3D_EINVAL, "%s: empty tensor", who);
-    MRI3D_REQUIRE(g->c >= kIdxMinC && g->c <= cmax, MRI3D_ENOTSUP, "%s: classes must be in [%d,%d], got %d", who, kIdxMinC, cmax, g->c);
-    MRI3D_REQUIRE(g->x_ld >= g->c, MRI3D_EINVAL, "%s: pitch %d < classes %d", who, g->x_ld, g->c);
-    return MRI3D_OK;
-}
-
 static int dice_float_check(const Mri3dDiceGeom* g, const char* who) {
-    int rc = dice_check(g, who, kDiceMaxC);
+    int rc = idx_check(g, who, kDiceMaxC, 0);
     if (rc) return rc;
     MRI3D_REQUIRE(g->ct == 1 || g->ct == g->c, MRI3D_EINVAL, "%s: target channels %d must be 1 or %d", who, g->ct, g->c);
     MRI3D_REQUIRE(g->t_ld >= g->ct, MRI3D_EINVAL, "%s: target pitch %d < target channels %d", who, g->t_ld, g->ct);
@@ -317,14 +190,6 @@ static int dice_finalize(const char* who, const double* part, float* stats, floa
     hipLaunchKernelGGL(dice_finalize_kernel, dim3(1), dim3(256), 0, s, part, stats, loss, n, c, nblk, eps);
     return check_launch(who);
 }
-
-static int idx_mode(const Mri3dDiceIndexGeom& g, const void* logits, const void* labels, const void* dlogits = nullptr) {
-    if (g.c == 2 && g.x_ld == 2 && aligned16(logits, dlogits) && (reinterpret_cast<uintptr_t>(labels) & 3) == 0) return kIdxVox4;
-    if (g.c % 4 == 0 && g.x_ld % 4 == 0 && aligned_vec4(g.dtype, logits, dlogits)) return kIdxRows4;
-    return kIdxScalar;
-}
-// work items of one sample: voxels, or the 4-voxel path's groups and (at most 6) single voxels
-static int64_t idx_items(const Mri3dDiceIndexGeom& g, int mode) { return mode == kIdxVox4 ? g.vox / 4 + 6 : g.vox; }
 
 }  // namespace mri3d
 
@@ -340,15 +205,6 @@ using namespace mri3d;
         case 7: CALL(7); break;             \
         default: CALL(8); break;            \
     }
-
-#define IDX_DISPATCH(CALL)           \
-    do {                             \
-        if (g->c <= 2) CALL(2);      \
-        else if (g->c <= 4) CALL(4); \
-        else if (g->c <= 8) CALL(8); \
-        else if (g->c <= 16) CALL(16); \
-        else CALL(32);               \
-    } while (0)
 
 extern "C" size_t mri3d_softmax_dice_workspace_bytes(const Mri3dDiceGeom* g) {
     return g ? dice_ws_bytes(kDiceMaxBlocks, g->n, g->c) : 0;
@@ -395,35 +251,33 @@ extern "C" size_t mri3d_softmax_dice_index_workspace_bytes(const Mri3dDiceIndexG
 
 extern "C" int mri3d_softmax_dice_index_fwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels, float* loss,
                                             float* stats, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
-    int rc = dice_check(g, "softmax_dice_index_fwd", kIdxMaxC);
+    int rc = idx_check(g, "softmax_dice_index_fwd", kIdxMaxC, 0);
     if (rc) return rc;
     MRI3D_REQUIRE(logits && labels && loss && stats, MRI3D_EINVAL, "softmax_dice_index_fwd: null pointer");
     rc = ws_check8("softmax_dice_index_fwd", workspace, ws_bytes, mri3d_softmax_dice_index_workspace_bytes(g));
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int mode = idx_mode(*g, logits, labels);
-    const int nblk = dice_fwd_blocks(idx_items(*g, mode), g->n, kIdxMaxBlocks);
+    const IdxPlan plan = idx_plan(g->dtype, g->n, g->vox, g->c, g->x_ld, g->x_ld, false, ptr_align(logits), ptr_align(labels));
     double* part = static_cast<double*>(workspace);
 #define CALL(CB)                                                                                                    \
-    hipLaunchKernelGGL((dice_index_fwd_kernel<T, CB>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits, labels, \
-                       part, g->vox, g->c, g->x_ld, mode)
-    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(CALL); });
+    hipLaunchKernelGGL((dice_index_fwd_kernel<T, CB>), dim3(plan.blocks, g->n), dim3(256), 0, s, (const T*)logits, labels, \
+                       part, g->vox, g->c, g->x_ld, plan.mode)
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(plan.bucket, CALL); });
 #undef CALL
-    return dice_finalize("softmax_dice_index_fwd", part, stats, loss, g->n, g->c, nblk, g->eps, s);
+    return dice_finalize("softmax_dice_index_fwd", part, stats, loss, g->n, g->c, plan.blocks, g->eps, s);
 }
 
 extern "C" int mri3d_softmax_dice_index_bwd(const Mri3dDiceIndexGeom* g, const void* logits, const uint8_t* labels,
                                             const float* stats, const float* dloss, void* dlogits, mri3d_stream_t stream) {
-    int rc = dice_check(g, "softmax_dice_index_bwd", kIdxMaxC);
+    int rc = idx_check(g, "softmax_dice_index_bwd", kIdxMaxC, 0);
     if (rc) return rc;
     MRI3D_REQUIRE(logits && labels && stats && dloss && dlogits, MRI3D_EINVAL, "softmax_dice_index_bwd: null pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const int mode = idx_mode(*g, logits, labels, dlogits);
-    const int nblk = dice_bwd_blocks(idx_items(*g, mode), g->n);
+    const IdxPlan plan = idx_plan(g->dtype, g->n, g->vox, g->c, g->x_ld, g->x_ld, true, ptr_align(logits, dlogits), ptr_align(labels));
 #define CALL(CB)                                                                                                    \
-    hipLaunchKernelGGL((dice_index_bwd_kernel<T, CB>), dim3(nblk, g->n), dim3(256), 0, s, (const T*)logits, labels, \
-                       stats, dloss, (T*)dlogits, g->vox, g->n, g->c, g->x_ld, mode, g->eps)
-    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(CALL); });
+    hipLaunchKernelGGL((dice_index_bwd_kernel<T, CB>), dim3(plan.blocks, g->n), dim3(256), 0, s, (const T*)logits, labels, \
+                       stats, dloss, (T*)dlogits, g->vox, g->n, g->c, g->x_ld, plan.mode, g->eps)
+    MRI3D_DISPATCH_DTYPE(g->dtype, T, { IDX_DISPATCH(plan.bucket, CALL); });
 #undef CALL
     return check_launch("softmax_dice_index_bwd");
 }

@@ -1,6 +1,15 @@
-// loss_index.h — what the class-map losses share: loss.hip (softmax-Dice) and ce_loss.hip (cross-entropy / focal, alone or fused
-// with that Dice).  The device helpers stand here word for word as loss.hip had them: its kernels' code generation is sensitive to
-// how they are written (tests/golden/loss_family_bits.json records their bits), so change nothing here without recomputing it.
+// loss_index.h — what the class-map losses are made of: loss.hip (softmax-Dice), ce_loss.hip (cross-entropy / focal, alone or
+// fused with that Dice) and the boundary loss of distance.hip.  Every one of them reads softmax(logits) against a per-voxel target
+// and is written as prologue + per-voxel body + epilogue around the pieces that stand here once:
+//   device  idx_walk (the 4-voxel path with its head and tail singles, the row loop over idx_load_row and, in a backward, the
+//           write-back through idx_store_row), dice_block_row / pair_block_row (a block's row of partials), dice_finalize_rows /
+//           pair_finalize_sum (the single-block folds, every sum in a fixed order);
+//   host    idx_check (the common head of the geometry checks), idx_plan (bucket, read mode, blocks, lanes, items, trips: the six
+//           launches and mri3d_softmax_ce_index_plan_query all go by it), IDX_DISPATCH (the bucket -> instantiation switch).
+// A class-map kernel supplies only its body: one voxel's logits in place plus its label.  The boundary kernels index a map by
+// voxel and keep their two row loops, around the same idx_load_row and idx_store_row.  The bodies keep their arithmetic expression
+// for expression: tests/golden/loss_family_bits.json records the bits of the whole family, and tests/test_loss_codegen.py holds
+// every instantiation to 0 bytes of scratch and to the occupancy recorded before the walk was shared.
 #pragma once
 #include "common.h"
 #include <math.h>
@@ -127,8 +136,144 @@ template <int CB> struct IdxAcc {
     }
 };
 
-// ------------------------------------------------------------------ grid rules of the class-map kernels (host)
-// forward: a lane takes about 4 items, and all samples together at most `cap` blocks
+// p -> one voxel's C classes at d: 4-element vectors (rows-of-4 mode) or one element at a time
+template <typename T, int CB>
+__device__ __forceinline__ void idx_store_row(T* d, int C, int mode, const float (&p)[CB]) {
+    if constexpr (CB >= 4) {
+        if (mode == kIdxRows4) {
+#pragma unroll
+            for (int j = 0; j < CB; j += 4)
+                if (j < C) stf4(d + j, make_float4(p[j], p[j + 1], p[j + 2], p[j + 3]));
+            return;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < CB; ++j)
+        if (j < C) stf(d + j, p[j]);
+}
+
+// The voxels of sample blockIdx.y of a class-map loss: body(p, label, classes) gets one voxel's logits (classes >= C: -inf) and
+// leaves in p what STORE writes to the gradient (which has the logits' pitch).  In the 4-voxel mode (two dense classes) a lane takes 8 logits and a 4-byte label word at a time, the head
+// and tail as singles.
+template <bool STORE, typename T, int CB, typename Body>
+__device__ __forceinline__ void idx_walk(const T* logits, const uint8_t* labels, T* dlogits, int64_t vox, int C, int x_ld, int mode,
+                                         Body&& body) {
+    const int n = blockIdx.y;
+    const T* zn = logits + (int64_t)n * vox * x_ld;
+    const uint8_t* ln = labels + (int64_t)n * vox;
+    T* dn = STORE ? dlogits + (int64_t)n * vox * x_ld : nullptr;
+    if (CB == 2 && mode == kIdxVox4) {
+        if constexpr (CB == 2) {
+            const IdxVox4Plan plan(n, vox);
+            for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < plan.items; i += (int64_t)gridDim.x * 256) {
+                if (i < plan.groups) {
+                    const int64_t v0 = plan.head + i * 4;
+                    float z[8];
+                    idx_ld8(zn + v0 * 2, z);
+                    const uint32_t lw = *reinterpret_cast<const uint32_t*>(ln + v0);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        float p[2] = {z[2 * k], z[2 * k + 1]};
+                        body(p, (lw >> (8 * k)) & 0xffu, 2);
+                        if constexpr (STORE) z[2 * k] = p[0], z[2 * k + 1] = p[1];
+                    }
+                    if constexpr (STORE) idx_st8(dn + v0 * 2, z);
+                } else {
+                    const int64_t v = plan.single(i);
+                    float p[2] = {ldf(zn + v * 2), ldf(zn + v * 2 + 1)};
+                    body(p, ln[v], 2);
+                    if constexpr (STORE) { stf(dn + v * 2, p[0]); stf(dn + v * 2 + 1, p[1]); }
+                }
+            }
+        }
+        return;
+    }
+#pragma unroll 1      // one voxel's CB registers at a time: unrolled, the 32-class bodies do not fit the register file
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < vox; v += (int64_t)gridDim.x * 256) {
+        float p[CB];
+        idx_load_row<T, CB>(zn + v * x_ld, C, mode, p);
+        body(p, ln[v], C);
+        if constexpr (STORE) idx_store_row<T, CB>(dn + v * x_ld, C, mode, p);
+    }
+}
+
+// Two wave-reduced double sums of a block -> part[(n * gridDim.x + blockIdx.x) * 2]: the four waves through LDS in a fixed order
+__device__ __forceinline__ void pair_block_row(double a, double b, int n, double* __restrict__ part) {
+    __shared__ double red[4][2];
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = a; red[threadIdx.x >> 6][1] = b; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        part[((size_t)n * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// `rows` such rows -> (num, den), valid in thread 0 of a block of 256: lane t adds rows t, t + 256, ...; lane 0 adds the 256
+// lane sums in order
+__device__ __forceinline__ void pair_finalize_sum(const double* __restrict__ part, int rows, double& num, double& den) {
+    __shared__ double r0[256], r1[256];
+    double a = 0.0, b = 0.0;
+    for (int q = threadIdx.x; q < rows; q += 256) { a += part[(size_t)q * 2]; b += part[(size_t)q * 2 + 1]; }
+    r0[threadIdx.x] = a; r1[threadIdx.x] = b;
+    __syncthreads();
+    num = 0.0, den = 0.0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 256; ++k) { num += r0[k]; den += r1[k]; }
+}
+
+// dice_block_row's rows -> stats[n][c][3] = (tp, sum_p, sum_g) and the mean over (n, c) of 1 - dice, valid in thread 0 of a block
+// of 256: the pairs are handled 8 at a time by 32 partial lanes each (fixed-order double sums).  The float-target and the
+// class-map loss are one expression of the three sums.
+__device__ __forceinline__ float dice_finalize_rows(const double* __restrict__ part, float* __restrict__ stats, int N, int C, int nblk,
+                                                    float eps) {
+    __shared__ double r0[256], r1[256], r2[256];
+    const int el = threadIdx.x >> 5, ql = threadIdx.x & 31;
+    double acc_loss = 0.0;
+    for (int base = 0; base < N * C; base += 8) {
+        const int i = base + el;
+        double tp = 0.0, sp = 0.0, sg = 0.0;
+        if (i < N * C) {
+            const int n = i / C, c = i - n * C;
+            const double* p = part + ((size_t)n * nblk * C + c) * 3;
+            for (int q = ql; q < nblk; q += 32) {
+                tp += p[(size_t)q * C * 3];
+                sp += p[(size_t)q * C * 3 + 1];
+                sg += p[(size_t)q * C * 3 + 2];
+            }
+        }
+        r0[threadIdx.x] = tp; r1[threadIdx.x] = sp; r2[threadIdx.x] = sg;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int e = 0; e < 8 && base + e < N * C; ++e) {
+                double a = 0.0, b = 0.0, d = 0.0;
+                for (int k = 0; k < 32; ++k) { a += r0[e * 32 + k]; b += r1[e * 32 + k]; d += r2[e * 32 + k]; }
+                const int i2 = base + e;
+                stats[i2 * 3] = (float)a;
+                stats[i2 * 3 + 1] = (float)b;
+                stats[i2 * 3 + 2] = (float)d;
+                // float arithmetic from here mirrors the reference's fp32 tensors
+                const float ftp = (float)a, den = 2.f * ftp + ((float)b - ftp) + ((float)d - ftp) + eps;
+                acc_loss += 1.0 - (double)(2.f * ftp / den);
+            }
+        }
+        __syncthreads();
+    }
+    return (float)(acc_loss / (double)(N * C));
+}
+
+// ------------------------------------------------------------------ host side of the class-map kernels
+// The common head of every geometry check of the family (Geom: any of the loss geometries of mri3d.h); nmax: the most samples,
+// 0 for none.  An operator adds its own clauses behind it.
+template <typename Geom> static int idx_check(const Geom* g, const char* who, int cmax, int nmax) {
+    MRI3D_REQUIRE(g != nullptr, MRI3D_EINVAL, "%s: null geometry", who);
+    MRI3D_REQUIRE(g->dtype == MRI3D_F32 || g->dtype == MRI3D_BF16, MRI3D_ENOTSUP, "%s: unknown dtype %d", who, g->dtype);
+    MRI3D_REQUIRE(g->n > 0 && g->vox > 0, MRI3D_EINVAL, "%s: empty tensor", who);
+    MRI3D_REQUIRE(g->c >= kIdxMinC && g->c <= cmax, MRI3D_ENOTSUP, "%s: classes must be in [%d,%d], got %d", who, kIdxMinC, cmax, g->c);
+    MRI3D_REQUIRE(g->x_ld >= g->c, MRI3D_EINVAL, "%s: pitch %d < classes %d", who, g->x_ld, g->c);
+    MRI3D_REQUIRE(nmax == 0 || g->n <= nmax, MRI3D_ENOTSUP, "%s: at most %d samples, got %d", who, nmax, g->n);
+    return MRI3D_OK;
+}
+
+// grid rules (blocks of 256).  Forward: a lane takes about 4 items, and all samples together at most `cap` blocks
 static int dice_fwd_blocks(int64_t items, int n, int cap) {
     const int64_t want = cdiv64(items, 256 * 4);
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, cap / n));
@@ -141,4 +286,38 @@ static int dice_bwd_blocks(int64_t items, int n) {
     return (int)b;
 }
 
+// One decision per pass: the plan query reports it, every launch of the family goes by it.  dx_ld: the gradient's pitch (the
+// logits' where there is none); align_logits: ptr_align of the logits (and, in a backward, of their gradient); align_labels:
+// ptr_align of the class map, or 0 for an operator that reads no label bytes and so has no 4-voxel path (boundary).
+struct IdxPlan { int bucket, mode, blocks, lanes, whole_trips, remainder; int64_t items; };
+
+static IdxPlan idx_plan(int dtype, int n, int64_t vox, int c, int x_ld, int dx_ld, bool bwd, int align_logits, int align_labels) {
+    IdxPlan p;
+    p.bucket = c <= 2 ? 2 : c <= 4 ? 4 : c <= 8 ? 8 : c <= 16 ? 16 : 32;
+    if (c == 2 && x_ld == 2 && dx_ld == 2 && align16(align_logits) && align_labels >= 4) p.mode = kIdxVox4;
+    else if (c % 4 == 0 && x_ld % 4 == 0 && dx_ld % 4 == 0 && align_vec4(dtype, align_logits)) p.mode = kIdxRows4;
+    else p.mode = kIdxScalar;
+    // the grid is sized by the most items a sample can have (4-voxel path: groups and at most 6 single voxels)
+    const int64_t grid_items = p.mode == kIdxVox4 ? vox / 4 + 6 : vox;
+    p.blocks = bwd ? dice_bwd_blocks(grid_items, n) : dice_fwd_blocks(grid_items, n, kIdxMaxBlocks);
+    p.lanes = p.blocks * 256;
+    // the trips are those of sample 0, which starts aligned: groups of 4 and the voxels behind them
+    p.items = p.mode == kIdxVox4 ? vox / 4 + vox % 4 : vox;
+    p.whole_trips = (int)(p.items / p.lanes);
+    p.remainder = (int)(p.items % p.lanes);
+    return p;
+}
+
 }  // namespace mri3d
+
+// CALL(CB) for the plan's class bucket
+#define IDX_DISPATCH(BUCKET, CALL)          \
+    do {                                    \
+        switch (BUCKET) {                   \
+            case 2: CALL(2); break;         \
+            case 4: CALL(4); break;         \
+            case 8: CALL(8); break;         \
+            case 16: CALL(16); break;       \
+            default: CALL(32); break;       \
+        }                                   \
+    } while (0)

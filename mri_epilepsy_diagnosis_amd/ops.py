@@ -1921,51 +1921,55 @@ def upsample_conv3d(x, scale, weight, bias=None, padding=0):
 # ----------------------------------------------------------------------------------------------- loss
 
 
-class _SoftmaxDiceFn(torch.autograd.Function):
-    """Both softmax-Dice forms.  `form` = (geometry, query, fwd, bwd): geometry(logits, target, eps) checks the pair and returns it
-    as the kernels read it, with the C geometry; the other three name the workspace query and the two passes."""
+# What a public loss function hands to `_ScalarLossFn`: the checked logits as the kernels read them (detached: the caller's tensor
+# owns the gradient) and the C geometry, the length of `stats` and the workspace bytes, the fwd / bwd entry names, the pointer
+# arguments between the logits and the loss (target, labels, weights, a map: tensors or None) and what the backward passes
+# after the gradient (a pitch).
+_LossRecord = collections.namedtuple("_LossRecord", "logits geom stats_len ws_bytes fwd bwd extra bwd_tail", defaults=((),))
+
+
+class _ScalarLossFn(torch.autograd.Function):
+    """A scalar loss of logits: fwd(g, logits, *extra, loss, stats, workspace, bytes, stream) leaves the loss and the `stats` that
+    bwd(g, logits, *extra, stats, dloss, dlogits, *bwd_tail, stream) turns into the dense gradient.  `logits` is the caller's
+    tensor (the gradient's owner); the kernels read rec.logits."""
 
     @staticmethod
-    def forward(ctx, logits, target, eps, form):
-        geometry, query, fwd, bwd = form
-        logits, target, g = geometry(logits, target, eps)
-        L = _lib.lib()
-        n, c = logits.shape[:2]
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        stats = torch.empty(n * c * 3, dtype=torch.float32, device=logits.device)
-        ws = _workspace(getattr(L, query)(ctypes.byref(g)), logits.device)
-        check(getattr(L, fwd)(ctypes.byref(g), _ptr(logits), _ptr(target), _ptr(loss), _ptr(stats), _ptr(ws), ws.numel(), _stream()),
-              fwd[len("mri3d_"):])
-        ctx.save_for_backward(logits, target, stats)
-        ctx.geom, ctx.bwd = g, bwd
+    def forward(ctx, logits, rec):
+        x = rec.logits
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        stats = torch.empty(rec.stats_len, dtype=torch.float32, device=x.device)
+        ws = _workspace(rec.ws_bytes, x.device)
+        check(getattr(_lib.lib(), rec.fwd)(ctypes.byref(rec.geom), _ptr(x), *map(_ptr, rec.extra), _ptr(loss), _ptr(stats), _ptr(ws),
+                                           ws.numel(), _stream()), rec.fwd[len("mri3d_"):])
+        ctx.save_for_backward(x, stats, *rec.extra)
+        ctx.rec = rec
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, target, stats = ctx.saved_tensors
+        x, stats, *extra = ctx.saved_tensors
+        rec = ctx.rec
         dloss = dloss.to(torch.float32).contiguous()
-        dlogits = _new(logits.shape, logits)
-        check(getattr(_lib.lib(), ctx.bwd)(ctypes.byref(ctx.geom), _ptr(logits), _ptr(target), _ptr(stats), _ptr(dloss), _ptr(dlogits),
-                                           _stream()), ctx.bwd[len("mri3d_"):])
-        return dlogits, None, None, None
-
-
-def _dice_float_geometry(logits, target, eps):
-    _require_device(logits)
-    _require_param(target)
-    logits, target = _cl(logits), _cl(target)
-    n, c, d, h, w = logits.shape
-    ct = target.shape[1]
-    if tuple(target.shape) != (n, ct, d, h, w) or ct not in (1, c):
-        raise RuntimeError("softmax_dice_loss: target shape %s incompatible with logits %s"
-                           % (tuple(target.shape), tuple(logits.shape)))
-    return logits, target, DiceGeom(n, d * h * w, c, ct, c, ct, float(eps), _dt(logits))
+        dlogits = _new(x.shape, x)
+        check(getattr(_lib.lib(), rec.bwd)(ctypes.byref(rec.geom), _ptr(x), *map(_ptr, extra), _ptr(stats), _ptr(dloss), _ptr(dlogits),
+                                           *rec.bwd_tail, _stream()), rec.bwd[len("mri3d_"):])
+        return dlogits, None
 
 
 def softmax_dice_loss(logits, target, eps=1e-9):
     """mean over (n, c) of 1 - dice(softmax(logits)[:, c], target) — segmentation/routine.py:272-274 in one kernel."""
-    return _SoftmaxDiceFn.apply(logits, target.to(torch.float32), eps, (_dice_float_geometry, "mri3d_softmax_dice_workspace_bytes",
-                                                                        "mri3d_softmax_dice_fwd", "mri3d_softmax_dice_bwd"))
+    target = target.to(torch.float32)
+    _require_device(logits)
+    _require_param(target)
+    x, target = _cl(logits.detach()), _cl(target.detach())
+    n, c, d, h, w = x.shape
+    ct = target.shape[1]
+    if tuple(target.shape) != (n, ct, d, h, w) or ct not in (1, c):
+        raise RuntimeError("softmax_dice_loss: target shape %s incompatible with logits %s"
+                           % (tuple(target.shape), tuple(x.shape)))
+    g = DiceGeom(n, d * h * w, c, ct, c, ct, float(eps), _dt(x))
+    return _ScalarLossFn.apply(logits, _LossRecord(x, g, n * c * 3, _lib.lib().mri3d_softmax_dice_workspace_bytes(ctypes.byref(g)),
+                                            "mri3d_softmax_dice_fwd", "mri3d_softmax_dice_bwd", (target,)))
 
 
 def argmax_mask(logits):
@@ -2118,25 +2122,29 @@ def remap_labels(labels, lut, above=0, other=0, out_dtype=torch.uint8, out=None)
     return out
 
 
-def _dice_index_geometry(logits, labels, eps):
+def _class_map(who, logits, labels):
+    """The uint8 class map `labels` (N, 1, D, H, W) or (N, D, H, W) of `logits`, checked: (dense NDHWC logits, contiguous labels, n,
+    voxels of a sample, classes)."""
     _require_device(logits)
-    _require_labels("softmax_dice_index_loss", labels)
+    _require_labels(who, labels)
     if labels.dtype != torch.uint8:
-        raise RuntimeError("softmax_dice_index_loss: labels must be a uint8 class map, got %s" % labels.dtype)
-    logits = _cl(logits)
-    n, c, d, h, w = logits.shape
+        raise RuntimeError("%s: labels must be a uint8 class map, got %s" % (who, labels.dtype))
+    x = _cl(logits.detach())
+    n, c, d, h, w = x.shape
     if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
-        raise RuntimeError("softmax_dice_index_loss: labels shape %s incompatible with logits %s"
-                           % (tuple(labels.shape), tuple(logits.shape)))
-    return logits, labels.contiguous(), _lib.DiceIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits))
+        raise RuntimeError("%s: labels shape %s incompatible with logits %s" % (who, tuple(labels.shape), tuple(x.shape)))
+    return x, labels.contiguous(), n, d * h * w, c
 
 
 def softmax_dice_index_loss(logits, labels, eps=1e-9):
     """`softmax_dice_loss` with the target as a uint8 class map (N, 1, D, H, W) or (N, D, H, W) instead of float one-hot channels:
     mean over (n, c) of 1 - dice(softmax(logits)[:, c], labels == c), for 2..32 classes.  A label >= C belongs to no class (the
-    voxel is ignored by every class's numerator and target sum).  One byte of target per voxel instead of 4*C."""
-    return _SoftmaxDiceFn.apply(logits, labels, eps, (_dice_index_geometry, "mri3d_softmax_dice_index_workspace_bytes",
-                                                      "mri3d_softmax_dice_index_fwd", "mri3d_softmax_dice_index_bwd"))
+    voxel is ignored by every class's numerator and target sum).  One byte of target per voxel instead of 4*C.  It launches by the
+    plan that `ce_index_plan` reports: one function of the library decides for the whole class-map family."""
+    x, labels, n, vox, c = _class_map("softmax_dice_index_loss", logits, labels)
+    g = _lib.DiceIndexGeom(n, vox, c, c, float(eps), _dt(x))
+    return _ScalarLossFn.apply(logits, _LossRecord(x, g, n * c * 3, _lib.lib().mri3d_softmax_dice_index_workspace_bytes(ctypes.byref(g)),
+                                            "mri3d_softmax_dice_index_fwd", "mri3d_softmax_dice_index_bwd", (labels,)))
 
 
 # ----------------------------------------------------------------------------------------------- cross-entropy / focal (csrc/ce_loss.hip)
@@ -2157,7 +2165,7 @@ def _ce_settings(who, gamma, dice_weight, ce_weight):
 
 def ce_index_plan(n, vox, c, dtype=torch.float32, pass_=_lib.PASS_FWD, x_ld=None, dice_weight=0.0, ce_weight=1.0, gamma=0.0,
                   align_logits=16, align_labels=16):
-    """What `softmax_ce_index_loss` / `softmax_dice_ce_index_loss` launch by for `n` samples of `vox` voxels and `c` classes, host
+    """What `softmax_ce_index_loss` / `softmax_dice_ce_index_loss` and `softmax_dice_index_loss` launch by for `n` samples of `vox` voxels and `c` classes, host
     only: a dict of CE_PLAN_FIELDS (Mri3dCeIndexPlanInfo, include/mri3d.h) with the read mode by name.  pass_: _lib.PASS_FWD or
     _lib.PASS_DGRAD (the backward); align_*: the largest power of two <= 16 dividing the addresses."""
     g = _lib.CeIndexGeom(int(n), int(vox), int(c), int(c if x_ld is None else x_ld), 1e-9, BF16 if dtype == torch.bfloat16 else F32,
@@ -2170,47 +2178,20 @@ def ce_index_plan(n, vox, c, dtype=torch.float32, pass_=_lib.PASS_FWD, x_ld=None
     return out
 
 
-class _SoftmaxCeFn(torch.autograd.Function):
+def _ce_loss(who, logits, labels, weight, gamma, dice_weight, ce_weight, eps):
     """dice_weight * Dice_index + ce_weight * CE in one forward and one backward pass (dice_weight == 0: the CE-only kernels)."""
-
-    @staticmethod
-    def forward(ctx, logits, labels, weight, gamma, dice_weight, ce_weight, eps, who):
-        _require_device(logits)
-        _require_labels(who, labels)
-        if labels.dtype != torch.uint8:
-            raise RuntimeError("%s: labels must be a uint8 class map, got %s" % (who, labels.dtype))
-        logits = _cl(logits)
-        n, c, d, h, w = logits.shape
-        if tuple(labels.shape) not in ((n, 1, d, h, w), (n, d, h, w)):
-            raise RuntimeError("%s: labels shape %s incompatible with logits %s" % (who, tuple(labels.shape), tuple(logits.shape)))
-        gamma, dice_weight, ce_weight = _ce_settings(who, gamma, dice_weight, ce_weight)
-        if weight is not None:
-            if not torch.is_tensor(weight) or weight.device != logits.device or weight.dtype != torch.float32 \
-                    or tuple(weight.shape) != (c,):
-                raise RuntimeError("%s: weight must be a float32 tensor of %d entries on %s, got %s"
-                                   % (who, c, logits.device, "%s %s on %s" % (weight.dtype, tuple(weight.shape), weight.device)
-                                      if torch.is_tensor(weight) else type(weight).__name__))
-            weight = weight.detach().contiguous()
-        labels = labels.contiguous()
-        g = _lib.CeIndexGeom(n, d * h * w, c, c, float(eps), _dt(logits), gamma, dice_weight, ce_weight)
-        L = _lib.lib()
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        stats = torch.empty(4 + n * c * 3, dtype=torch.float32, device=logits.device)
-        ws = _workspace(L.mri3d_softmax_ce_index_workspace_bytes(ctypes.byref(g)), logits.device)
-        check(L.mri3d_softmax_ce_index_fwd(ctypes.byref(g), _ptr(logits), _ptr(labels), _ptr(weight), _ptr(loss), _ptr(stats), _ptr(ws),
-                                           ws.numel(), _stream()), "softmax_ce_index_fwd")
-        ctx.save_for_backward(logits, labels, stats)
-        ctx.geom, ctx.weight = g, weight
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, labels, stats = ctx.saved_tensors
-        dloss = dloss.to(torch.float32).contiguous()
-        dlogits = _new(logits.shape, logits)
-        check(_lib.lib().mri3d_softmax_ce_index_bwd(ctypes.byref(ctx.geom), _ptr(logits), _ptr(labels), _ptr(ctx.weight), _ptr(stats),
-                                                    _ptr(dloss), _ptr(dlogits), _stream()), "softmax_ce_index_bwd")
-        return (dlogits,) + (None,) * 7
+    x, labels, n, vox, c = _class_map(who, logits, labels)
+    gamma, dice_weight, ce_weight = _ce_settings(who, gamma, dice_weight, ce_weight)
+    if weight is not None:
+        if not torch.is_tensor(weight) or weight.device != x.device or weight.dtype != torch.float32 \
+                or tuple(weight.shape) != (c,):
+            raise RuntimeError("%s: weight must be a float32 tensor of %d entries on %s, got %s"
+                               % (who, c, x.device, "%s %s on %s" % (weight.dtype, tuple(weight.shape), weight.device)
+                                  if torch.is_tensor(weight) else type(weight).__name__))
+        weight = weight.detach().contiguous()
+    g = _lib.CeIndexGeom(n, vox, c, c, float(eps), _dt(x), gamma, dice_weight, ce_weight)
+    return _ScalarLossFn.apply(logits, _LossRecord(x, g, 4 + n * c * 3, _lib.lib().mri3d_softmax_ce_index_workspace_bytes(ctypes.byref(g)),
+                                            "mri3d_softmax_ce_index_fwd", "mri3d_softmax_ce_index_bwd", (labels, weight)))
 
 
 def softmax_ce_index_loss(logits, labels, weight=None, gamma=0.0):
@@ -2220,14 +2201,14 @@ def softmax_ce_index_loss(logits, labels, weight=None, gamma=0.0):
     ones.  gamma = 0 is F.cross_entropy(logits, labels, weight, ignore_index, reduction="mean") — except that when no voxel counts
     (everything ignored, or every class that occurs has weight 0) the loss is 0 and its gradient exactly 0 where torch gives NaN:
     a patch outside the labelled region must not poison a run.  Device tensors only; there is no CPU fallback."""
-    return _SoftmaxCeFn.apply(logits, labels, weight, gamma, 0.0, 1.0, 1e-9, "softmax_ce_index_loss")
+    return _ce_loss("softmax_ce_index_loss", logits, labels, weight, gamma, 0.0, 1.0, 1e-9)
 
 
 def softmax_dice_ce_index_loss(logits, labels, dice_weight=1.0, ce_weight=1.0, weight=None, gamma=0.0, eps=1e-9):
     """dice_weight * softmax_dice_index_loss(logits, labels, eps) + ce_weight * softmax_ce_index_loss(logits, labels, weight, gamma),
     each pass reading the logits once: the bytes of the index Dice alone.  The CE term is 0 with a zero gradient when no voxel
     counts (see softmax_ce_index_loss); the class weights apply to the CE term only."""
-    return _SoftmaxCeFn.apply(logits, labels, weight, gamma, dice_weight, ce_weight, eps, "softmax_dice_ce_index_loss")
+    return _ce_loss("softmax_dice_ce_index_loss", logits, labels, weight, gamma, dice_weight, ce_weight, eps)
 
 
 def confusion_counts(pred, gt, classes):
@@ -2515,48 +2496,23 @@ def signed_sqdist(class_map, classes, ids, out=None):
     return out
 
 
-class _SoftmaxBoundaryFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, signed_map, ids):
-        who = "softmax_boundary_loss"
-        _require_device(logits)
-        _require_labels(who, signed_map)
-        logits, x_ld = _nd(logits)                    # the logits keep their voxel pitch; the gradient is dense
-        n, c, d, h, w = logits.shape
-        _, ids = _class_ids(who, c, ids)
-        if signed_map.dtype != torch.int32 or tuple(signed_map.shape) != (n, len(ids), d, h, w) or signed_map.device != logits.device:
-            raise RuntimeError("%s: the map must be int32 of shape %s on %s, got %s %s on %s"
-                               % (who, (n, len(ids), d, h, w), logits.device, signed_map.dtype, tuple(signed_map.shape),
-                                  signed_map.device))
-        signed_map = signed_map.contiguous()
-        g = _lib.BoundaryGeom(n, d * h * w, c, x_ld, _dt(logits), len(ids), (ctypes.c_int32 * 32)(*ids))
-        L = _lib.lib()
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        stats = torch.empty(4, dtype=torch.float32, device=logits.device)
-        ws = _workspace(L.mri3d_softmax_boundary_workspace_bytes(), logits.device)
-        check(L.mri3d_softmax_boundary_fwd(ctypes.byref(g), _ptr(logits), _ptr(signed_map), _ptr(loss), _ptr(stats), _ptr(ws), ws.numel(),
-                                           _stream()), "softmax_boundary_fwd")
-        ctx.save_for_backward(logits, signed_map, stats)
-        ctx.geom = g
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        logits, signed_map, stats = ctx.saved_tensors
-        g = ctx.geom
-        dloss = dloss.to(torch.float32).contiguous()
-        dlogits = _new(logits.shape, logits)
-        check(_lib.lib().mri3d_softmax_boundary_bwd(ctypes.byref(g), _ptr(logits), _ptr(signed_map), _ptr(stats), _ptr(dloss),
-                                                    _ptr(dlogits), g.c, _stream()), "softmax_boundary_bwd")
-        return dlogits, None, None
-
-
 def softmax_boundary_loss(logits, signed_map, ids):
     """Boundary loss (Kervadec et al., MIDL 2019): the mean over classes `ids` and voxels of softmax(logits)[:, id] * phi(s), with s
     the int32 map of `signed_sqdist(class_map, C, ids)` and phi(s) = sqrt(s), -(sqrt(-s) - 1) or 0 for s > 0, < 0, = 0.  Terms with
     s == INT32_MIN (ignored voxels) are left out of the sum and of the count; with none left the loss is 0 and its gradient zero.
     logits: fp32 / bf16 (n, C, d, h, w), NDHWC with any voxel pitch, 2..32 classes.  No gradient flows into the map."""
-    return _SoftmaxBoundaryFn.apply(logits, signed_map, tuple(ids))
+    who = "softmax_boundary_loss"
+    _require_device(logits)
+    _require_labels(who, signed_map)
+    x, x_ld = _nd(logits.detach())                # the logits keep their voxel pitch; the gradient is dense
+    n, c, d, h, w = x.shape
+    _, ids = _class_ids(who, c, ids)
+    if signed_map.dtype != torch.int32 or tuple(signed_map.shape) != (n, len(ids), d, h, w) or signed_map.device != x.device:
+        raise RuntimeError("%s: the map must be int32 of shape %s on %s, got %s %s on %s"
+                           % (who, (n, len(ids), d, h, w), x.device, signed_map.dtype, tuple(signed_map.shape), signed_map.device))
+    g = _lib.BoundaryGeom(n, d * h * w, c, x_ld, _dt(x), len(ids), (ctypes.c_int32 * 32)(*ids))
+    return _ScalarLossFn.apply(logits, _LossRecord(x, g, 4, _lib.lib().mri3d_softmax_boundary_workspace_bytes(), "mri3d_softmax_boundary_fwd",
+                                            "mri3d_softmax_boundary_bwd", (signed_map.detach().contiguous(),), (c,)))
 
 
 # ----------------------------------------------------------------------------------------------- intensity statistics (csrc/intensity.hip)

@@ -158,15 +158,15 @@ def test_float_dice_same_bits_run_to_run(C, ct, dtype):
 
 
 def test_both_forms_keep_their_recorded_bits():
-    """tests/golden/loss_family_bits.json (tools/record_loss_bits.py): loss bits and gradient digest of both target forms, as one
-    toolchain compiled them.  A change of the sources that is meant to keep the arithmetic keeps every case."""
+    """tests/golden/loss_family_bits.json (tools/record_loss_bits.py): loss bits and gradient digest of both Dice target forms, of CE / focal alone
+    and fused with the class-map Dice, and of the boundary loss, as one toolchain compiled them.  A change of the sources that is meant to keep the arithmetic keeps every case."""
     with open(BITS_FILE) as f:
         want = json.load(f)["cases"]
     cases = loss_cases.bit_cases()
     assert sorted(want) == sorted(c[0] for c in cases)
     bad = []
-    for name, form, z, t in cases:
-        got = loss_cases.device_bits(ops, form, z, t)
+    for name, form, z, t, kw in cases:
+        got = loss_cases.device_bits(ops, form, z, t, **kw)
         if got != want[name]:
             bad.append((name, got, want[name]))
     assert not bad, bad

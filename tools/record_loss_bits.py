@@ -1,12 +1,12 @@
-"""Record the bits of the softmax-Dice family into tests/golden/loss_family_bits.json (on a machine with the GPU, from the repository
+"""Record the bits of the loss family into tests/golden/loss_family_bits.json (on a machine with the GPU, from the repository
 root, after building the library):
 
     python tools/record_loss_bits.py [--out FILE]
 
-For every case of tests/loss_cases.py: bit_cases() (the float-target form and the class-index form, both storage types, inputs from
-the seeded CPU generators of the test suites) the file holds the loss as its int32 bit pattern and the sha256 of the gradient's bytes
-in NDHWC order.  tests/test_dice_gpu.py recomputes every case and asserts equality, which is how a change of csrc/loss.hip or
-csrc/labels.hip that means to keep the arithmetic is held to it.
+For every case of tests/loss_cases.py: bit_cases() (the float-target Dice, the class-map Dice, CE / focal alone and fused with that Dice, and the
+boundary loss; both storage types, inputs from the seeded CPU generators of the test suites) the file holds the loss as its int32 bit pattern and the sha256 of the gradient's bytes
+in NDHWC order.  tests/test_dice_gpu.py recomputes every case and asserts equality, which is how a change of csrc/loss_index.h, loss.hip,
+ce_loss.hip or the boundary part of distance.hip that means to keep the arithmetic is held to it.
 
 The file is valid for one toolchain: both sources are compiled with the default contraction mode, so another compiler may fuse other
 multiply-adds and legitimately give other bits.  Re-recording is legitimate only then (or after a deliberate change of the
@@ -29,7 +29,7 @@ def main():
     if "--out" in sys.argv:
         out = sys.argv[sys.argv.index("--out") + 1]
     assert torch.cuda.is_available(), "recording needs the device"
-    cases = {name: loss_cases.device_bits(ops, form, z, t) for name, form, z, t in loss_cases.bit_cases()}
+    cases = {name: loss_cases.device_bits(ops, form, z, t, **kw) for name, form, z, t, kw in loss_cases.bit_cases()}
     with open(out, "w") as f:
         json.dump({"cases": cases}, f, indent=1, sort_keys=True)
         f.write("\n")
