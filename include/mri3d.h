@@ -960,7 +960,8 @@ int mri3d_downsample2_mean_f32(const float* x, int32_t d, int32_t h, int32_t w, 
 /* ------------------------------------------------------------------------------------------------
  * Bias-field estimation over tissue classes (tissue.hip): the device passes of an EM for a K-class Gaussian mixture on
  * log-intensity with a smooth multiplicative field, the model behind the `_restore` image that the reference takes from FSL FAST
- * (detection/preprocessing_utils.py:11-53).  No MRF prior, no partial volumes, no spline field.  x: DEVICE fp32 (d, h, w), fewer
+ * (detection/preprocessing_utils.py:11-53), with an optional Potts prior on the labels (mri3d_tissue_mrf_pass).  No 26-neighbourhood,
+ * no anisotropic beta, no mean-field (soft) neighbours, no partial volumes, no spline field.  x: DEVICE fp32 (d, h, w), fewer
  * than 2^31 voxels (else MRI3D_ENOTSUP); mask: DEVICE uint8 of the same shape or NULL.  All arithmetic is float64.
  *
  *   selected      mask byte != 0 (no mask: always), x finite and > 0;   y = log(x)
@@ -989,6 +990,21 @@ int mri3d_downsample2_mean_f32(const float* x, int32_t d, int32_t h, int32_t w, 
  *   to fp32; labels (uint8) = 0 where the voxel is not selected, else 1 + the rank, by ascending mu (equal means in the caller's
  *   order), of the class with the largest log pi_k - 1/2 log v_k - (r - mu_k)^2 / (2 v_k), the first of equal maxima in that
  *   rank order.  restored == x (in place) is allowed; any other overlap among the buffers is MRI3D_EINVAL.
+ * mri3d_tissue_mrf_pass: mri3d_tissue_em_pass with a Markov random field (Potts) prior on a label volume, one half-sweep of
+ *   red-black ICM: hidden-MRF EM.  Labels are uint8 (d, h, w): 0 where a voxel is not selected, else 1 + its class in the order
+ *   of params_host (not by ascending mu).  n_k = how many of the voxel's up to six face neighbours inside the volume hold k + 1
+ *   in labels_in; any other byte (0, or one above K) counts for no class.  Per selected voxel
+ *       logt_k = log pi_k - 1/2 log v_k - 1/2 log 2 pi - (r - mu_k)^2 / (2 v_k) + beta n_k,   p_k = softmax_k logt_k,
+ *       new = 1 + argmax_k logt_k, the first of equal maxima;
+ *   sums has mri3d_tissue_em_pass's layout and definitions with these p_k, [1] the pseudo-log-likelihood
+ *   sum [logsumexp_k logt_k - log sum_k pi_k exp(beta n_k)]; with beta = 0 the table is the plain pass's whatever the labels.
+ *   mode 0 or 1: labels_out = new where the voxel is selected and (d + h + w) & 1 == mode, labels_in where it is selected and of
+ *   the other colour, 0 where it is not selected.  mode 2, the start: no neighbour term, labels_in is not read and may be NULL,
+ *   every selected voxel gets new.  labels_out is fully written.  labels_in and labels_out are two buffers: a resting voxel still
+ *   contributes its posterior, read from active neighbours, so a pass in place would depend on the launch order; with two buffers
+ *   every voxel reads labels_in only, there are no atomics and the same inputs give the same bits.  0 <= beta <= 8 and finite,
+ *   mode 0..2, labels_in NULL only in mode 2, no overlap among labels_in, labels_out, x, mask, sums and the workspace (else
+ *   MRI3D_EINVAL).  The plan and the workspace are mri3d_tissue_em_pass's (mri3d_tissue_em_plan, mri3d_tissue_em_workspace_bytes).
  * No entry allocates or synchronises; arguments are validated on the host before any launch.
  * ---------------------------------------------------------------------------------------------- */
 size_t mri3d_tissue_em_workspace_bytes(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order);
@@ -997,6 +1013,9 @@ int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t
                          const double* params_host, double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
                        const double* params_host, float* restored, uint8_t* labels, float* field, mri3d_stream_t stream);
+int mri3d_tissue_mrf_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                          const double* params_host, double beta, int32_t mode, const uint8_t* labels_in, uint8_t* labels_out,
+                          double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Distance maps (distance.hip): the exact squared Euclidean distance transform of a batch of n dense (d,h,w) uint8

@@ -211,6 +211,7 @@ SIGNATURES = {
     "mri3d_tissue_em_plan": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, _P]),
     "mri3d_tissue_em_pass": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "mri3d_tissue_apply": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
+    "mri3d_tissue_mrf_pass": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, c_double, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_distance_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "mri3d_surface_distance": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "mri3d_surface_elements": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int64, _P, _P, c_size_t, _P]),

@@ -17,6 +17,8 @@
 //          never reaches a result.
 //   fold   one block of 1024 threads per entry of the table: thread t adds the rows t, t + 1024, ... of the entry's slot times
 //          xh^a yh^b in ascending order, and the 1024 sums meet in a fixed tree in LDS.  Same inputs, same bits.
+// mri3d_tissue_mrf_pass is the same two stages with a Potts prior on a label volume (hidden-MRF EM, red-black ICM): its row kernel
+// adds beta n_k to a voxel's log-terms from the six face neighbours' labels and writes the voxel's new label; the fold is shared.
 // 4-byte loads per lane on purpose: the pass is bound by its float64 arithmetic, and at the template's W = 182 a wave step of
 // 64 voxels keeps 182 / 192 of the lanes busy where a 16-byte step of 256 voxels would keep 182 / 256.
 #include "common.h"
@@ -30,6 +32,7 @@ constexpr int kTisFoldThreads = 1024;
 constexpr int kTisMaxK = 4;
 constexpr int kTisCoef = 20;            // order-3 nesting
 constexpr int kTisMaxEntries = 128;     // >= 2 + 3*4 + 84 + 20
+constexpr double kTisMaxBeta = 8.0;     // of the label prior: exp(6 beta) stays far inside float64
 
 struct TisParams {
     double a[kTisMaxK];      // log pi - 0.5 log v (- 0.5 log 2 pi in the EM pass)
@@ -85,6 +88,42 @@ __device__ __forceinline__ bool tis_selected(const uint8_t* mr, int w, float xv)
     return (mr ? mr[w] != 0 : true) && isfinite(xv) && xv > 0.f;
 }
 
+// One selected voxel's terms of the row sums, from its K log-terms l (consumed): the posteriors p_k = softmax_k l_k into S0/S1/S2 and
+// the moments of w and t; acc[1] is the caller's.  Returns logsumexp_k l_k.  Both row kernels go through here, operation for operation.
+template <int K, int ORDER>
+__device__ __forceinline__ double tis_voxel_sums(const TisParams& p, double l[K], double y, double r, double zh, double* acc) {
+    constexpr int NW = 2 * ORDER + 1, NT = ORDER + 1;
+    double lmax = -(double)INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) lmax = fmax(lmax, l[k]);
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        l[k] = exp(l[k] - lmax);
+        s = s + l[k];
+    }
+    const double inv_s = 1.0 / s;
+    acc[0] = acc[0] + 1.0;
+    double wv = 0.0, tv = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double pk = l[k] * inv_s;
+        acc[2 + k] = acc[2 + k] + pk;
+        acc[2 + K + k] = acc[2 + K + k] + pk * r;
+        acc[2 + 2 * K + k] = acc[2 + 2 * K + k] + pk * (r * r);
+        wv = wv + pk * p.inv_v[k];
+        tv = tv + pk * ((y - p.mu[k]) * p.inv_v[k]);
+    }
+    double zq = 1.0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        acc[2 + 3 * K + i] = acc[2 + 3 * K + i] + wv * zq;
+        if (i < NT) acc[2 + 3 * K + NW + i] = acc[2 + 3 * K + NW + i] + tv * zq;
+        zq = zq * zh;
+    }
+    return lmax + log(s);
+}
+
 // ------------------------------------------------------------------ EM pass, stage 1: per-row sums
 template <int K, int ORDER>
 __global__ void __launch_bounds__(64 * kTisWaves)
@@ -117,40 +156,108 @@ tissue_em_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ m
                 const double zh = p.w0 + (double)w * p.step_w;
                 const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
                 const double r = y - b;
-                double l[K], lmax = -(double)INFINITY;
+                double l[K];
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     const double dk = r - p.mu[k];
                     l[k] = p.a[k] - (dk * dk) * p.hiv[k];
-                    lmax = fmax(lmax, l[k]);
                 }
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    l[k] = exp(l[k] - lmax);
-                    s = s + l[k];
-                }
-                const double inv_s = 1.0 / s;
-                acc[0] = acc[0] + 1.0;
-                acc[1] = acc[1] + (lmax + log(s));
-                double wv = 0.0, tv = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double pk = l[k] * inv_s;
-                    acc[2 + k] = acc[2 + k] + pk;
-                    acc[2 + K + k] = acc[2 + K + k] + pk * r;
-                    acc[2 + 2 * K + k] = acc[2 + 2 * K + k] + pk * (r * r);
-                    wv = wv + pk * p.inv_v[k];
-                    tv = tv + pk * ((y - p.mu[k]) * p.inv_v[k]);
-                }
-                double zq = 1.0;
-#pragma unroll
-                for (int i = 0; i < NW; ++i) {
-                    acc[2 + 3 * K + i] = acc[2 + 3 * K + i] + wv * zq;
-                    if (i < NT) acc[2 + 3 * K + NW + i] = acc[2 + 3 * K + NW + i] + tv * zq;
-                    zq = zq * zh;
-                }
+                acc[1] = acc[1] + tis_voxel_sums<K, ORDER>(p, l, y, r, zh, acc);
             }
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) acc[i] = tis_wave_sum(acc[i]);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < R; ++i) part[(size_t)i * rows + row] = acc[i];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ MRF pass, stage 1: per-row sums and the labels
+// The EM row kernel with a Potts prior on a label volume: l_k gains beta n_k, n_k the face neighbours inside the volume whose
+// byte of `lin` is k + 1, and LL becomes the pseudo-log-likelihood (logsumexp_k l_k - log sum_k pi_k e^{beta n_k}); e^{beta n} for
+// n = 0..6 comes from the host.  Every voxel reads `lin` only and writes its own byte of `lout`: two buffers, no atomics, the same
+// bits whatever the launch order.  The row's own bytes at w - 1 and w + 1 are second byte loads, like the four rows around it.
+struct TisMrf {
+    double pi[kTisMaxK];
+    double beta;
+    double e[7];     // exp(beta n)
+    int mode;        // 0, 1: that colour of (d + h + w) & 1 takes its new label, the other keeps lin's; 2: no neighbours, lin unread
+};
+
+template <int K, int ORDER>
+__global__ void __launch_bounds__(64 * kTisWaves)
+tissue_mrf_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p, TisMrf m,
+                       const uint8_t* __restrict__ lin, uint8_t* __restrict__ lout, double* __restrict__ part) {
+    constexpr int NW = 2 * ORDER + 1, NT = ORDER + 1, R = 2 + 3 * K + NW + NT;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rows = D * H;   // < 2^31, checked by the host
+    const bool prior = m.mode != 2;
+    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
+        const int d = row / H, h = row - d * H;
+        double q[4];
+        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
+        double acc[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) acc[i] = 0.0;
+        const size_t base = (size_t)row * W;
+        const float* xr = x + base;
+        const uint8_t* mr = mask ? mask + base : nullptr;
+        uint8_t* lo = lout + base;
+        // the row itself and the four rows around it, null where there is none
+        const uint8_t* l0 = prior ? lin + base : nullptr;
+        const uint8_t* ld0 = prior && d > 0 ? l0 - (size_t)H * W : nullptr;
+        const uint8_t* ld1 = prior && d < D - 1 ? l0 + (size_t)H * W : nullptr;
+        const uint8_t* lh0 = prior && h > 0 ? l0 - W : nullptr;
+        const uint8_t* lh1 = prior && h < H - 1 ? l0 + W : nullptr;
+        for (int w0 = 0; w0 < W; w0 += 64) {
+            const int w = w0 + lane;
+            float xv = 0.f;
+            bool sel = false;
+            if (w < W) {
+                xv = xr[w];
+                sel = tis_selected(mr, w, xv);
+            }
+            if (__ballot(sel) == 0ull) {           // wave-uniform: background still gets its zeros
+                if (w < W) lo[w] = 0;
+                continue;
+            }
+            int lab = 0;
+            if (sel) {
+                const double y = log((double)xv);
+                const double zh = p.w0 + (double)w * p.step_w;
+                const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
+                const double r = y - b;
+                int own = 0, nb[6] = {0, 0, 0, 0, 0, 0};
+                if (prior) {
+                    own = l0[w];
+                    if (ld0) nb[0] = ld0[w];
+                    if (ld1) nb[1] = ld1[w];
+                    if (lh0) nb[2] = lh0[w];
+                    if (lh1) nb[3] = lh1[w];
+                    if (w > 0) nb[4] = l0[w - 1];
+                    if (w < W - 1) nb[5] = l0[w + 1];
+                }
+                double l[K], z = 0.0, best = -(double)INFINITY;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    int n = 0;
+#pragma unroll
+                    for (int j = 0; j < 6; ++j) n += nb[j] == k + 1;
+                    double en = m.e[0];
+#pragma unroll
+                    for (int j = 1; j <= 6; ++j) en = n == j ? m.e[j] : en;
+                    const double dk = r - p.mu[k];
+                    l[k] = (p.a[k] - (dk * dk) * p.hiv[k]) + m.beta * (double)n;
+                    z = z + m.pi[k] * en;
+                    if (k == 0 || l[k] > best) best = l[k], lab = k + 1;   // the first of equal maxima
+                }
+                if (prior && ((d + h + w) & 1) != m.mode) lab = own;
+                acc[1] = acc[1] + (tis_voxel_sums<K, ORDER>(p, l, y, r, zh, acc) - log(z));
+            }
+            if (w < W) lo[w] = (uint8_t)lab;
         }
 #pragma unroll
         for (int i = 0; i < R; ++i) acc[i] = tis_wave_sum(acc[i]);
@@ -276,6 +383,35 @@ static int tis_params(const char* who, const double* ph, int K, int order, int d
     return MRI3D_OK;
 }
 
+// the table: n, LL, S0[K], S1[K], S2[K], Mw[a][b][c] (a + b + c <= 2 order, c fastest), Mt[a][b][c] (a + b + c <= order)
+static void tis_fold_table(int K, int order, TisFold& f) {
+    const int nw = 2 * order + 1;
+    int e = 0;
+    for (; e < 2 + 3 * K; ++e) f.slot[e] = (uint8_t)e, f.a[e] = 0, f.b[e] = 0;
+    for (int a = 0; a <= 2 * order; ++a)
+        for (int b = 0; b <= 2 * order - a; ++b)
+            for (int c = 0; c <= 2 * order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
+    for (int a = 0; a <= order; ++a)
+        for (int b = 0; b <= order - a; ++b)
+            for (int c = 0; c <= order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + nw + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
+    for (int i = e; i < kTisMaxEntries; ++i) f.slot[i] = 0, f.a[i] = 0, f.b[i] = 0;
+}
+
+// LAUNCH(K, ORDER) for the row kernel instance of (classes, order), both already checked
+#define TIS_ROWS_ORDER(LAUNCH, KK, order) \
+    switch (order) {                      \
+        case 0: LAUNCH(KK, 0); break;     \
+        case 1: LAUNCH(KK, 1); break;     \
+        case 2: LAUNCH(KK, 2); break;     \
+        default: LAUNCH(KK, 3); break;    \
+    }
+#define TIS_ROWS_DISPATCH(LAUNCH, classes, order)          \
+    switch (classes) {                                     \
+        case 2: TIS_ROWS_ORDER(LAUNCH, 2, order); break;   \
+        case 3: TIS_ROWS_ORDER(LAUNCH, 3, order); break;   \
+        default: TIS_ROWS_ORDER(LAUNCH, 4, order); break;  \
+    }
+
 }  // namespace mri3d
 
 using namespace mri3d;
@@ -301,56 +437,82 @@ extern "C" int mri3d_tissue_em_plan(int32_t d, int32_t h, int32_t w, int32_t cla
     return MRI3D_OK;
 }
 
+// What the two passes share, in the order the checks are made: pointers, extents, parameters -> the kernels' constants, alignment,
+// the workspace, the buffers the pass writes against the ones it reads, and the fold table.  `who` starts the error string.
+struct TisPass {
+    TisParams p;
+    TisFold f;
+    size_t need, sums_bytes, nvox;
+    int entries;
+};
+
+static int tis_pass_setup(const char* who, const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                          const double* params_host, double* sums, void* workspace, size_t ws_bytes, TisPass& t) {
+    MRI3D_REQUIRE(x && params_host && sums, MRI3D_EINVAL, "%s: null pointer (x %p, params %p, sums %p)", who, (const void*)x,
+                  (const void*)params_host, (void*)sums);
+    if (int rc = tis_check_dims(who, d, h, w, classes, order)) return rc;
+    if (int rc = tis_params(who, params_host, classes, order, d, h, w, true, false, t.p)) return rc;
+    MRI3D_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0, MRI3D_EINVAL,
+                  "%s: a pointer is not aligned to its element", who);
+    t.need = mri3d_tissue_em_workspace_bytes(d, h, w, classes, order);
+    if (int rc = ws_check8(who, workspace, ws_bytes, t.need)) return rc;
+    t.nvox = (size_t)d * h * w;
+    t.entries = tis_entries(classes, order);
+    t.sums_bytes = (size_t)t.entries * sizeof(double);
+    MRI3D_REQUIRE(!overlaps(sums, t.sums_bytes, workspace, t.need) && !overlaps(sums, t.sums_bytes, x, t.nvox * 4) &&
+                      !overlaps(sums, t.sums_bytes, mask, t.nvox) && !overlaps(workspace, t.need, x, t.nvox * 4) &&
+                      !overlaps(workspace, t.need, mask, t.nvox),
+                  MRI3D_EINVAL, "%s: the sums or the workspace overlap another buffer", who);
+    tis_fold_table(classes, order, t.f);
+    return MRI3D_OK;
+}
+
 extern "C" int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
                                     const double* params_host, double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
-    MRI3D_REQUIRE(x && params_host && sums, MRI3D_EINVAL, "tissue_em_pass: null pointer (x %p, params %p, sums %p)", (const void*)x,
-                  (const void*)params_host, (void*)sums);
-    if (int rc = tis_check_dims("tissue_em_pass", d, h, w, classes, order)) return rc;
-    TisParams p;
-    if (int rc = tis_params("tissue_em_pass", params_host, classes, order, d, h, w, true, false, p)) return rc;
-    MRI3D_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(sums) & 7) == 0, MRI3D_EINVAL,
-                  "tissue_em_pass: a pointer is not aligned to its element");
-    const size_t need = mri3d_tissue_em_workspace_bytes(d, h, w, classes, order);
-    if (int rc = ws_check8("tissue_em_pass", workspace, ws_bytes, need)) return rc;
-    const size_t nvox = (size_t)d * h * w;
-    const int entries = tis_entries(classes, order);
-    const size_t sums_bytes = (size_t)entries * sizeof(double);
-    MRI3D_REQUIRE(!overlaps(sums, sums_bytes, workspace, need) && !overlaps(sums, sums_bytes, x, nvox * 4) &&
-                      !overlaps(sums, sums_bytes, mask, nvox) && !overlaps(workspace, need, x, nvox * 4) &&
-                      !overlaps(workspace, need, mask, nvox),
-                  MRI3D_EINVAL, "tissue_em_pass: the sums or the workspace overlap another buffer");
-    // the table: n, LL, S0[K], S1[K], S2[K], Mw[a][b][c] (a + b + c <= 2 order, c fastest), Mt[a][b][c] (a + b + c <= order)
-    const int K = classes, nw = 2 * order + 1;
-    TisFold f;
-    int e = 0;
-    for (; e < 2 + 3 * K; ++e) f.slot[e] = (uint8_t)e, f.a[e] = 0, f.b[e] = 0;
-    for (int a = 0; a <= 2 * order; ++a)
-        for (int b = 0; b <= 2 * order - a; ++b)
-            for (int c = 0; c <= 2 * order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
-    for (int a = 0; a <= order; ++a)
-        for (int b = 0; b <= order - a; ++b)
-            for (int c = 0; c <= order - a - b; ++c, ++e) f.slot[e] = (uint8_t)(2 + 3 * K + nw + c), f.a[e] = (uint8_t)a, f.b[e] = (uint8_t)b;
-    for (int i = e; i < kTisMaxEntries; ++i) f.slot[i] = 0, f.a[i] = 0, f.b[i] = 0;
+    TisPass t;
+    if (int rc = tis_pass_setup("tissue_em_pass", x, mask, d, h, w, classes, order, params_host, sums, workspace, ws_bytes, t)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(workspace);
     const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
-#define TIS_EM(KK, OO) hipLaunchKernelGGL((tissue_em_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, p, part)
-#define TIS_EM_K(KK)                 \
-    switch (order) {                 \
-        case 0: TIS_EM(KK, 0); break; \
-        case 1: TIS_EM(KK, 1); break; \
-        case 2: TIS_EM(KK, 2); break; \
-        default: TIS_EM(KK, 3); break; \
-    }
-    switch (K) {
-        case 2: TIS_EM_K(2); break;
-        case 3: TIS_EM_K(3); break;
-        default: TIS_EM_K(4); break;
-    }
-#undef TIS_EM_K
+#define TIS_EM(KK, OO) hipLaunchKernelGGL((tissue_em_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, t.p, part)
+    TIS_ROWS_DISPATCH(TIS_EM, classes, order);
 #undef TIS_EM
-    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(entries), dim3(kTisFoldThreads), 0, st, part, d, h, f, p.d0, p.step_d, p.h0, p.step_h, sums);
+    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(t.entries), dim3(kTisFoldThreads), 0, st, part, d, h, t.f, t.p.d0, t.p.step_d, t.p.h0, t.p.step_h,
+                       sums);
     return check_launch("tissue_em_pass");
+}
+
+extern "C" int mri3d_tissue_mrf_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
+                                     const double* params_host, double beta, int32_t mode, const uint8_t* labels_in, uint8_t* labels_out,
+                                     double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
+    MRI3D_REQUIRE(labels_out, MRI3D_EINVAL, "tissue_mrf_pass: null pointer (labels_out)");
+    TisPass t;
+    if (int rc = tis_pass_setup("tissue_mrf_pass", x, mask, d, h, w, classes, order, params_host, sums, workspace, ws_bytes, t)) return rc;
+    MRI3D_REQUIRE(isfinite(beta) && beta >= 0.0 && beta <= kTisMaxBeta, MRI3D_EINVAL, "tissue_mrf_pass: beta = %g must be finite and in 0..%g", beta,
+                  kTisMaxBeta);
+    MRI3D_REQUIRE(mode >= 0 && mode <= 2, MRI3D_EINVAL, "tissue_mrf_pass: mode = %d outside 0..2", mode);
+    MRI3D_REQUIRE(labels_in || mode == 2, MRI3D_EINVAL, "tissue_mrf_pass: labels_in is null in mode %d (only the start pass, mode 2, reads none)", mode);
+    // two label buffers: a pass in place would let the table depend on the launch order
+    MRI3D_REQUIRE(!overlaps(labels_out, t.nvox, labels_in, t.nvox), MRI3D_EINVAL,
+                  "tissue_mrf_pass: labels_in and labels_out overlap (a pass reads one buffer and writes another)");
+    MRI3D_REQUIRE(!overlaps(labels_out, t.nvox, x, t.nvox * 4) && !overlaps(labels_out, t.nvox, mask, t.nvox) &&
+                      !overlaps(labels_out, t.nvox, sums, t.sums_bytes) && !overlaps(labels_out, t.nvox, workspace, t.need) &&
+                      !overlaps(labels_in, t.nvox, sums, t.sums_bytes) && !overlaps(labels_in, t.nvox, workspace, t.need),
+                  MRI3D_EINVAL, "tissue_mrf_pass: a label buffer overlaps x, the mask, the sums or the workspace");
+    TisMrf m;
+    for (int k = 0; k < kTisMaxK; ++k) m.pi[k] = params_host[std::min(k, classes - 1)];
+    m.beta = beta, m.mode = mode;
+    for (int n = 0; n <= 6; ++n) m.e[n] = exp(beta * (double)n);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
+#define TIS_MRF(KK, OO) \
+    hipLaunchKernelGGL((tissue_mrf_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, t.p, m, labels_in, labels_out, part)
+    TIS_ROWS_DISPATCH(TIS_MRF, classes, order);
+#undef TIS_MRF
+    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(t.entries), dim3(kTisFoldThreads), 0, st, part, d, h, t.f, t.p.d0, t.p.step_d, t.p.h0, t.p.step_h,
+                       sums);
+    return check_launch("tissue_mrf_pass");
 }
 
 extern "C" int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,

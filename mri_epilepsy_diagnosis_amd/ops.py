@@ -2770,6 +2770,31 @@ def tissue_em_pass(x, mask, classes, order, params, out=None):
     return out
 
 
+def tissue_mrf_pass(x, mask, classes, order, params, beta, mode, labels_in, labels_out=None, out=None):
+    """`tissue_em_pass` with a Potts prior of strength `beta` on a uint8 label volume (0: not selected, else 1 + the class in the
+    order of `params`), one half-sweep of red-black ICM: (sums, labels_out).  mode 0 / 1: the voxels of that colour of
+    (d + h + w) & 1 take their new label, the others keep `labels_in`'s; mode 2, the start: no neighbour term, `labels_in` may be
+    None.  `labels_out` is another buffer than `labels_in` (include/mri3d.h says why)."""
+    x, mask, classes, order, p = _tissue_args("tissue_mrf_pass", x, mask, classes, order, params)
+    size = tissue_table_size(classes, order) if 2 <= classes <= 4 and 0 <= order <= 3 else 1
+    if out is None:
+        out = torch.empty(size, dtype=torch.float64, device=x.device)
+    elif tuple(out.shape) != (size,) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise RuntimeError("tissue_mrf_pass: out must be a contiguous (%d,) float64 device tensor" % size)
+    if labels_out is None:
+        labels_out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    for name, t in (("labels_in", labels_in), ("labels_out", labels_out)):
+        if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != tuple(x.shape) or t.dtype != torch.uint8 or t.device != x.device
+                              or not t.is_contiguous()):
+            raise RuntimeError("tissue_mrf_pass: %s must be a contiguous %s uint8 tensor on x's device" % (name, tuple(x.shape)))
+    L = _lib.lib()
+    d, h, w = x.shape
+    ws = _workspace(L.mri3d_tissue_em_workspace_bytes(d, h, w, classes, order), x.device)
+    check(L.mri3d_tissue_mrf_pass(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), float(beta), int(mode),
+                                  _ptr(labels_in), _ptr(labels_out), _ptr(out), _ptr(ws), ws.numel(), _stream()), "tissue_mrf_pass")
+    return out, labels_out
+
+
 def tissue_apply(x, mask, classes, order, params, want_field=False, restored=None):
     """The final pass: (restored = x exp(-b), labels uint8, field = exp(b) or None) over every voxel; labels are 0 where the voxel
     is not selected and else 1 + the rank by ascending mean of its most probable class.  `restored` may be `x` itself."""

@@ -1,7 +1,8 @@
 """The host loop of the tissue-class bias-field estimator: an EM whose every iteration is one streaming pass of
-csrc/tissue.hip over the volume (`ops.tissue_em_pass`) and a few float64 operations on the table it returns.  The device
-counterpart of the FAST call in the reference's detection/preprocessing_utils.py:11-53 (`_restore`, the bias-corrected image);
-no Markov random field, no partial volumes, no spline field.  tests/tissue_ref.py restates the algorithm in float64 numpy."""
+csrc/tissue.hip over the volume (`ops.tissue_em_pass`, or `ops.tissue_mrf_pass` with the Potts prior on the labels, beta > 0) and a few float64 operations on the
+table it returns.  The device counterpart of the FAST call in the reference's detection/preprocessing_utils.py:11-53 (`_restore`,
+the bias-corrected image); no partial volumes, no spline field.  tests/tissue_ref.py and tests/tissue_mrf_ref.py restate the
+algorithm in float64 numpy."""
 import collections
 
 import numpy as np
@@ -42,7 +43,7 @@ def _update(params, sums, classes, order, v_floor):
     return np.concatenate([pi, mu, v, c])
 
 
-def segment(volume, mask=None, classes=3, order=3, iterations=60):
+def segment(volume, mask=None, classes=3, order=3, iterations=60, beta=0.0, warmup=20):
     """Estimate tissue classes and the bias field of a (d, h, w) device volume: a TissueSegmentation with
         restored        volume * exp(-b), float32, every voxel
         labels          uint8: 0 where the voxel is not selected, else 1..classes by ascending class mean
@@ -51,15 +52,23 @@ def segment(volume, mask=None, classes=3, order=3, iterations=60):
         coefficients    of b, np.linspace(-1, 1, N) coordinates, `ops`' bias-field nesting (what `transforms.bias_field` takes)
         log_likelihood  one value per iteration, of the parameters that iteration started from
         selected        the voxels that counted: mask non-zero (no mask: all), finite and > 0
-    classes 2..4, order 0..3.  Only the sums table of a pass crosses to the host per iteration."""
+    classes 2..4, order 0..3.  Only the sums table of a pass crosses to the host per iteration.
+    beta > 0 (at most 8) puts a Markov random field prior on the labels, beta per face neighbour of the same class (hidden-MRF EM with
+    red-black ICM): iterations t < warmup are plain passes, iteration `warmup` starts the label volume, later ones
+    update the colour t & 1 of it, and two closing half-sweeps with the final parameters give `labels`.  The warm-up is needed:
+    the prior from the first iteration merges classes.  0 <= warmup < iterations.  beta = 0 is the plain mixture and ignores warmup."""
     if not torch.is_tensor(volume) or not volume.is_cuda or volume.dim() != 3:
         raise RuntimeError("tissue.segment: volume must be a (d, h, w) ROCm device tensor (got %s); there is no CPU fallback"
                            % (getattr(volume, "device", type(volume)),))
     if mask is not None and (not torch.is_tensor(mask) or not mask.is_cuda or tuple(mask.shape) != tuple(volume.shape)):
         raise RuntimeError("tissue.segment: mask must be a device tensor of the volume's shape %s" % (tuple(volume.shape),))
-    K, order, iterations = int(classes), int(order), int(iterations)
+    K, order, iterations, beta, warmup = int(classes), int(order), int(iterations), float(beta), int(warmup)
     if not 2 <= K <= 4 or not 0 <= order <= 3:
         raise ValueError("tissue.segment: classes must be 2..4 and order 0..3, got %d and %d" % (K, order))
+    if not 0.0 <= beta <= 8.0:
+        raise ValueError("tissue.segment: beta must be in 0..8, got %g" % beta)
+    if beta > 0 and not 0 <= warmup < iterations:      # without the prior the warm-up is the whole run, whatever it says
+        raise ValueError("tissue.segment: warmup must be in 0..iterations - 1 = %d, got %d" % (iterations - 1, warmup))
     x = volume.to(torch.float32).contiguous()
     if mask is not None:
         mask = (mask != 0).contiguous()
@@ -78,10 +87,21 @@ def segment(volume, mask=None, classes=3, order=3, iterations=60):
     params = np.concatenate([np.full(K, 1.0 / K), pct[2:], np.full(K, v0), np.zeros(M)])
     sums_dev = torch.empty(ops.tissue_table_size(K, order), dtype=torch.float64, device=x.device)
     log_likelihood = []
-    for _ in range(iterations):
-        sums = ops.tissue_em_pass(x, mask, K, order, params, out=sums_dev).cpu().numpy()
+    prior = beta > 0
+    cur, nxt = (torch.empty(x.shape, dtype=torch.uint8, device=x.device) for _ in range(2)) if prior else (None, None)
+    for t in range(iterations):
+        if not prior or t < warmup:
+            ops.tissue_em_pass(x, mask, K, order, params, out=sums_dev)
+        else:   # the start pass, then one colour per iteration; `cur` holds the labels the next pass reads
+            ops.tissue_mrf_pass(x, mask, K, order, params, beta, 2 if t == warmup else t & 1, None if t == warmup else cur, nxt, out=sums_dev)
+            cur, nxt = nxt, cur
+        sums = sums_dev.cpu().numpy()
         log_likelihood.append(float(sums[1]))
         params = _update(params, sums, K, order, VARIANCE_FLOOR * v0)
+    if prior:   # both colours once more with the parameters the last M-step left
+        for mode in (0, 1):
+            ops.tissue_mrf_pass(x, mask, K, order, params, beta, mode, cur, nxt, out=sums_dev)
+            cur, nxt = nxt, cur
     # the field's mean over the selected voxels from the moments of 1: a pass with every v = 1 has w = sum_k p_k = 1
     ones = np.concatenate([params[:2 * K], np.ones(K), np.zeros(M)])
     m1 = ops.tissue_em_pass(x, mask, K, order, ones, out=sums_dev).cpu().numpy()[2 + 3 * K:]
@@ -92,6 +112,10 @@ def segment(volume, mask=None, classes=3, order=3, iterations=60):
     idx = np.argsort(params[K:2 * K], kind="stable")
     pi, mu, v = params[:K][idx], params[K:2 * K][idx] + mean_b, params[2 * K:3 * K][idx]
     restored, labels, field = ops.tissue_apply(x, mask, K, order, np.concatenate([pi, mu, v, c]), want_field=True)
+    if prior:   # the prior's labels, in the order of `params`, renumbered by ascending mean
+        lut = np.zeros(K + 1, dtype=np.uint8)
+        lut[1 + idx] = 1 + np.arange(K)
+        labels = ops.remap_labels(cur, torch.from_numpy(lut).to(x.device), out=cur)
     return TissueSegmentation(restored, labels, field, mu, v, pi, c, log_likelihood, n_sel)
 
 
