@@ -19,6 +19,8 @@
 //          xh^a yh^b in ascending order, and the 1024 sums meet in a fixed tree in LDS.  Same inputs, same bits.
 // mri3d_tissue_mrf_pass is the same two stages with a Potts prior on a label volume (hidden-MRF EM, red-black ICM): its row kernel
 // adds beta n_k to a voxel's log-terms from the six face neighbours' labels and writes the voxel's new label; the fold is shared.
+// The two row kernels and the final pass are one row walk (tis_walk) around each kernel's per-voxel body; tests/test_tissue_codegen.py
+// holds what the compiler makes of that to the registers of the kernels written out one by one.
 // 4-byte loads per lane on purpose: the pass is bound by its float64 arithmetic, and at the template's W = 182 a wave step of
 // 64 voxels keeps 182 / 192 of the lanes busy where a 16-byte step of 256 voxels would keep 182 / 256.
 #include "common.h"
@@ -124,61 +126,90 @@ __device__ __forceinline__ double tis_voxel_sums(const TisParams& p, double l[K]
     return lmax + log(s);
 }
 
+// zh of voxel w of a row and b there, from the row's cubic
+__device__ __forceinline__ double tis_field(const TisParams& p, const double q[4], int w, double& zh) {
+    zh = p.w0 + (double)w * p.step_w;
+    return ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
+}
+
+// the Gaussian log-term of class k at the residual r = y - b
+__device__ __forceinline__ double tis_log_term(const TisParams& p, int k, double r) {
+    const double dk = r - p.mu[k];
+    return p.a[k] - (dk * dk) * p.hiv[k];
+}
+
+// the running argmax over k = 0, 1, ...: the first of equal maxima, as label k + 1
+__device__ __forceinline__ void tis_argmax(int k, double lk, double& best, int& lab) {
+    if (k == 0 || lk > best) best = lk, lab = k + 1;
+}
+
+// ------------------------------------------------------------------ the row walk of the three kernels
+// Block and wave -> rows, a row -> (d, h) and its cubic q, then wave steps of 64 voxels along w: voxel(acc, q, at, xv, sel) runs in
+// every lane that has a voxel, selected or not, and a sums kernel (R > 0) ends a row with its R sums at part[slot][row].  What a
+// wave step without a selected voxel does is the kernel's choice:
+enum class TisIdle {
+    unknown,      // no ballot is taken: the step is like any other
+    skipped,      // the step ends at its ballot (for a body that does nothing for an unselected voxel)
+    unselected,   // the body runs with sel = false, a constant
+};
+
+struct TisAt { int d, h, w; size_t row0; };   // row0: the index in the volume of the row's first voxel (wave-uniform)
+
+template <int R, TisIdle IDLE, class Voxel>
+__device__ __forceinline__ void tis_walk(const float* x, const uint8_t* mask, int D, int H, int W, const TisParams& p, double* part,
+                                         Voxel&& voxel) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int rows = D * H;   // < 2^31, checked by the host
+    double acc[R > 0 ? R : 1] = {};
+    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
+        const int d = row / H, h = row - d * H;
+        double q[4];
+        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
+        const size_t base = (size_t)row * W;
+        const float* xr = x + base;
+        const uint8_t* mr = mask ? mask + base : nullptr;
+        for (int w = lane; w < W; w += 64) {   // lanes past the row's end leave: a ballot is over the ones that have a voxel
+            const TisAt at = {d, h, w, base};
+            const float xv = xr[w];
+            const bool sel = tis_selected(mr, w, xv);
+            if (IDLE != TisIdle::unknown && __ballot(sel) == 0ull) {   // wave-uniform: background
+                if (IDLE == TisIdle::unselected) voxel(acc, q, at, xv, false);
+                continue;
+            }
+            voxel(acc, q, at, xv, sel);
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {   // the end of a row: the sums meet over the wave, lane 0 stores them, the next row starts from zero
+            const double v = tis_wave_sum(acc[i]);
+            if (lane == 0) part[(size_t)i * rows + row] = v;
+            acc[i] = 0.0;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ EM pass, stage 1: per-row sums
 template <int K, int ORDER>
 __global__ void __launch_bounds__(64 * kTisWaves)
 tissue_em_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p,
                       double* __restrict__ part) {
-    constexpr int NW = 2 * ORDER + 1, NT = ORDER + 1, R = 2 + 3 * K + NW + NT;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rows = D * H;   // < 2^31, checked by the host
-    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
-        const int d = row / H, h = row - d * H;
-        double q[4];
-        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
-        double acc[R];
+    tis_walk<2 + 3 * K + (2 * ORDER + 1) + (ORDER + 1), TisIdle::skipped>(
+        x, mask, D, H, W, p, part, [&](double* acc, const double* q, const TisAt& at, float xv, bool sel) {
+            if (!sel) return;
+            const double y = log((double)xv);
+            double zh, l[K];
+            const double r = y - tis_field(p, q, at.w, zh);
 #pragma unroll
-        for (int i = 0; i < R; ++i) acc[i] = 0.0;
-        const float* xr = x + (size_t)row * W;
-        const uint8_t* mr = mask ? mask + (size_t)row * W : nullptr;
-        for (int w0 = 0; w0 < W; w0 += 64) {
-            const int w = w0 + lane;
-            float xv = 0.f;
-            bool sel = false;
-            if (w < W) {
-                xv = xr[w];
-                sel = tis_selected(mr, w, xv);
-            }
-            if (__ballot(sel) == 0ull) continue;   // wave-uniform: background
-            if (sel) {
-                const double y = log((double)xv);
-                const double zh = p.w0 + (double)w * p.step_w;
-                const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
-                const double r = y - b;
-                double l[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double dk = r - p.mu[k];
-                    l[k] = p.a[k] - (dk * dk) * p.hiv[k];
-                }
-                acc[1] = acc[1] + tis_voxel_sums<K, ORDER>(p, l, y, r, zh, acc);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < R; ++i) acc[i] = tis_wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) part[(size_t)i * rows + row] = acc[i];
-        }
-    }
+            for (int k = 0; k < K; ++k) l[k] = tis_log_term(p, k, r);
+            acc[1] = acc[1] + tis_voxel_sums<K, ORDER>(p, l, y, r, zh, acc);
+        });
 }
 
 // ------------------------------------------------------------------ MRF pass, stage 1: per-row sums and the labels
 // The EM row kernel with a Potts prior on a label volume: l_k gains beta n_k, n_k the face neighbours inside the volume whose
 // byte of `lin` is k + 1, and LL becomes the pseudo-log-likelihood (logsumexp_k l_k - log sum_k pi_k e^{beta n_k}); e^{beta n} for
-// n = 0..6 comes from the host.  Every voxel reads `lin` only and writes its own byte of `lout`: two buffers, no atomics, the same
-// bits whatever the launch order.  The row's own bytes at w - 1 and w + 1 are second byte loads, like the four rows around it.
+// n = 0..6 comes from the host.  Every voxel reads `lin` only and writes its own byte of `lout`, a 0 where it is not selected (a
+// wave step of background included): two buffers, no atomics, the same bits whatever the launch order.
 struct TisMrf {
     double pi[kTisMaxK];
     double beta;
@@ -190,55 +221,25 @@ template <int K, int ORDER>
 __global__ void __launch_bounds__(64 * kTisWaves)
 tissue_mrf_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p, TisMrf m,
                        const uint8_t* __restrict__ lin, uint8_t* __restrict__ lout, double* __restrict__ part) {
-    constexpr int NW = 2 * ORDER + 1, NT = ORDER + 1, R = 2 + 3 * K + NW + NT;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rows = D * H;   // < 2^31, checked by the host
     const bool prior = m.mode != 2;
-    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
-        const int d = row / H, h = row - d * H;
-        double q[4];
-        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
-        double acc[R];
-#pragma unroll
-        for (int i = 0; i < R; ++i) acc[i] = 0.0;
-        const size_t base = (size_t)row * W;
-        const float* xr = x + base;
-        const uint8_t* mr = mask ? mask + base : nullptr;
-        uint8_t* lo = lout + base;
-        // the row itself and the four rows around it, null where there is none
-        const uint8_t* l0 = prior ? lin + base : nullptr;
-        const uint8_t* ld0 = prior && d > 0 ? l0 - (size_t)H * W : nullptr;
-        const uint8_t* ld1 = prior && d < D - 1 ? l0 + (size_t)H * W : nullptr;
-        const uint8_t* lh0 = prior && h > 0 ? l0 - W : nullptr;
-        const uint8_t* lh1 = prior && h < H - 1 ? l0 + W : nullptr;
-        for (int w0 = 0; w0 < W; w0 += 64) {
-            const int w = w0 + lane;
-            float xv = 0.f;
-            bool sel = false;
-            if (w < W) {
-                xv = xr[w];
-                sel = tis_selected(mr, w, xv);
-            }
-            if (__ballot(sel) == 0ull) {           // wave-uniform: background still gets its zeros
-                if (w < W) lo[w] = 0;
-                continue;
-            }
+    const size_t plane = (size_t)H * W;
+    tis_walk<2 + 3 * K + (2 * ORDER + 1) + (ORDER + 1), TisIdle::unselected>(
+        x, mask, D, H, W, p, part, [&](double* acc, const double* q, const TisAt& at, float xv, bool sel) {
             int lab = 0;
             if (sel) {
                 const double y = log((double)xv);
-                const double zh = p.w0 + (double)w * p.step_w;
-                const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
-                const double r = y - b;
+                double zh;
+                const double r = y - tis_field(p, q, at.w, zh);
                 int own = 0, nb[6] = {0, 0, 0, 0, 0, 0};
                 if (prior) {
-                    own = l0[w];
-                    if (ld0) nb[0] = ld0[w];
-                    if (ld1) nb[1] = ld1[w];
-                    if (lh0) nb[2] = lh0[w];
-                    if (lh1) nb[3] = lh1[w];
-                    if (w > 0) nb[4] = l0[w - 1];
-                    if (w < W - 1) nb[5] = l0[w + 1];
+                    const uint8_t* l0 = lin + at.row0;   // the row itself; the four rows around it where there is one
+                    own = l0[at.w];
+                    if (at.d > 0) nb[0] = (l0 - plane)[at.w];
+                    if (at.d < D - 1) nb[1] = (l0 + plane)[at.w];
+                    if (at.h > 0) nb[2] = (l0 - W)[at.w];
+                    if (at.h < H - 1) nb[3] = (l0 + W)[at.w];
+                    if (at.w > 0) nb[4] = l0[at.w - 1];
+                    if (at.w < W - 1) nb[5] = l0[at.w + 1];
                 }
                 double l[K], z = 0.0, best = -(double)INFINITY;
 #pragma unroll
@@ -249,23 +250,15 @@ tissue_mrf_rows_kernel(const float* __restrict__ x, const uint8_t* __restrict__ 
                     double en = m.e[0];
 #pragma unroll
                     for (int j = 1; j <= 6; ++j) en = n == j ? m.e[j] : en;
-                    const double dk = r - p.mu[k];
-                    l[k] = (p.a[k] - (dk * dk) * p.hiv[k]) + m.beta * (double)n;
+                    l[k] = tis_log_term(p, k, r) + m.beta * (double)n;
                     z = z + m.pi[k] * en;
-                    if (k == 0 || l[k] > best) best = l[k], lab = k + 1;   // the first of equal maxima
+                    tis_argmax(k, l[k], best, lab);
                 }
-                if (prior && ((d + h + w) & 1) != m.mode) lab = own;
+                if (prior && ((at.d + at.h + at.w) & 1) != m.mode) lab = own;
                 acc[1] = acc[1] + (tis_voxel_sums<K, ORDER>(p, l, y, r, zh, acc) - log(z));
             }
-            if (w < W) lo[w] = (uint8_t)lab;
-        }
-#pragma unroll
-        for (int i = 0; i < R; ++i) acc[i] = tis_wave_sum(acc[i]);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < R; ++i) part[(size_t)i * rows + row] = acc[i];
-        }
-    }
+            (lout + at.row0)[at.w] = (uint8_t)lab;
+        });
 }
 
 // ------------------------------------------------------------------ EM pass, stage 2: rows -> table
@@ -301,35 +294,20 @@ template <int K>
 __global__ void __launch_bounds__(64 * kTisWaves)
 tissue_apply_kernel(const float* x, const uint8_t* __restrict__ mask, int D, int H, int W, TisParams p, float* restored,
                     uint8_t* __restrict__ labels, float* __restrict__ field) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rows = D * H;
-    for (int row = blockIdx.x * kTisWaves + wave; row < rows; row += gridDim.x * kTisWaves) {
-        const int d = row / H, h = row - d * H;
-        double q[4];
-        tis_row(p.c, p.d0 + (double)d * p.step_d, p.h0 + (double)h * p.step_h, q);
-        const size_t base = (size_t)row * W;
-        const uint8_t* mr = mask ? mask + base : nullptr;
-        for (int w = lane; w < W; w += 64) {
-            const float xv = x[base + w];
-            const double zh = p.w0 + (double)w * p.step_w;
-            const double b = ((q[3] * zh + q[2]) * zh + q[1]) * zh + q[0];
-            int lab = 0;
-            if (tis_selected(mr, w, xv)) {
-                const double r = log((double)xv) - b;
-                double best = -(double)INFINITY;
+    tis_walk<0, TisIdle::unknown>(x, mask, D, H, W, p, nullptr, [&](double*, const double* q, const TisAt& at, float xv, bool sel) {
+        double zh;
+        const double b = tis_field(p, q, at.w, zh);
+        int lab = 0;
+        if (sel) {
+            const double r = log((double)xv) - b;
+            double best = -(double)INFINITY;
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double dk = r - p.mu[k];
-                    const double lk = p.a[k] - (dk * dk) * p.hiv[k];
-                    if (k == 0 || lk > best) best = lk, lab = k + 1;   // the first of equal maxima
-                }
-            }
-            restored[base + w] = (float)((double)xv * exp(-b));
-            labels[base + w] = (uint8_t)lab;
-            if (field) field[base + w] = (float)exp(b);
+            for (int k = 0; k < K; ++k) tis_argmax(k, tis_log_term(p, k, r), best, lab);
         }
-    }
+        (restored + at.row0)[at.w] = (float)((double)xv * exp(-b));
+        (labels + at.row0)[at.w] = (uint8_t)lab;
+        if (field) (field + at.row0)[at.w] = (float)exp(b);
+    });
 }
 
 static int tis_ncoef(int order) { return (order + 1) * (order + 2) * (order + 3) / 6; }
@@ -397,27 +375,47 @@ static void tis_fold_table(int K, int order, TisFold& f) {
     for (int i = e; i < kTisMaxEntries; ++i) f.slot[i] = 0, f.a[i] = 0, f.b[i] = 0;
 }
 
-// LAUNCH(K, ORDER) for the row kernel instance of (classes, order), both already checked
-#define TIS_ROWS_ORDER(LAUNCH, KK, order) \
-    switch (order) {                      \
-        case 0: LAUNCH(KK, 0); break;     \
-        case 1: LAUNCH(KK, 1); break;     \
-        case 2: LAUNCH(KK, 2); break;     \
-        default: LAUNCH(KK, 3); break;    \
+// f(K) and f(K, ORDER) with (classes, order), both already checked, as compile-time constants: the kernels' instances
+template <int N> using TisInt = std::integral_constant<int, N>;
+
+template <class F>
+static void tis_for_classes(int classes, F&& f) {
+    switch (classes) {
+        case 2: f(TisInt<2>{}); break;
+        case 3: f(TisInt<3>{}); break;
+        default: f(TisInt<4>{}); break;
     }
-#define TIS_ROWS_DISPATCH(LAUNCH, classes, order)          \
-    switch (classes) {                                     \
-        case 2: TIS_ROWS_ORDER(LAUNCH, 2, order); break;   \
-        case 3: TIS_ROWS_ORDER(LAUNCH, 3, order); break;   \
-        default: TIS_ROWS_ORDER(LAUNCH, 4, order); break;  \
-    }
+}
+
+template <class F>
+static void tis_for_instance(int classes, int order, F&& f) {
+    tis_for_classes(classes, [&](auto k) {
+        switch (order) {
+            case 0: f(k, TisInt<0>{}); break;
+            case 1: f(k, TisInt<1>{}); break;
+            case 2: f(k, TisInt<2>{}); break;
+            default: f(k, TisInt<3>{}); break;
+        }
+    });
+}
+
+// Whether a buffer that a call writes shares a byte with another buffer of the list; two that are only read may overlap, and a
+// null pointer overlaps nothing.
+struct TisBuf { const void* p; size_t bytes; bool written; };
+
+static bool tis_clash(std::initializer_list<TisBuf> bufs) {
+    for (const TisBuf* a = bufs.begin(); a != bufs.end(); ++a)
+        for (const TisBuf* b = a + 1; b != bufs.end(); ++b)
+            if ((a->written || b->written) && overlaps(a->p, a->bytes, b->p, b->bytes)) return true;
+    return false;
+}
 
 }  // namespace mri3d
 
 using namespace mri3d;
 
 extern "C" size_t mri3d_tissue_em_workspace_bytes(int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order) {
-    if (d <= 0 || h <= 0 || w <= 0 || (int64_t)d * h * w >= 0x7fffffffLL || classes < 2 || classes > kTisMaxK || order < 0 || order > 3) return 0;
+    if (tis_check_dims("tissue_em_workspace_bytes", d, h, w, classes, order)) return 0;   // the query's 0 comes with the reason as the error string
     return (size_t)tis_row_sums(classes, order) * (size_t)d * (size_t)h * sizeof(double);
 }
 
@@ -459,27 +457,32 @@ static int tis_pass_setup(const char* who, const float* x, const uint8_t* mask, 
     t.nvox = (size_t)d * h * w;
     t.entries = tis_entries(classes, order);
     t.sums_bytes = (size_t)t.entries * sizeof(double);
-    MRI3D_REQUIRE(!overlaps(sums, t.sums_bytes, workspace, t.need) && !overlaps(sums, t.sums_bytes, x, t.nvox * 4) &&
-                      !overlaps(sums, t.sums_bytes, mask, t.nvox) && !overlaps(workspace, t.need, x, t.nvox * 4) &&
-                      !overlaps(workspace, t.need, mask, t.nvox),
-                  MRI3D_EINVAL, "%s: the sums or the workspace overlap another buffer", who);
+    MRI3D_REQUIRE(!tis_clash({{sums, t.sums_bytes, true}, {workspace, t.need, true}, {x, t.nvox * 4, false}, {mask, t.nvox, false}}), MRI3D_EINVAL,
+                  "%s: the sums or the workspace overlap another buffer", who);
     tis_fold_table(classes, order, t.f);
     return MRI3D_OK;
+}
+
+// The launches of a pass that tis_pass_setup accepted: the row kernel instance that pick(K, ORDER) returns, on the arguments every
+// row kernel starts with, then `extra`, then the workspace; and the fold.
+template <class Pick, class... Extra>
+static int tis_pass_launch(const char* who, const TisPass& t, const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes,
+                           int32_t order, double* sums, void* workspace, mri3d_stream_t stream, Pick&& pick, Extra... extra) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(workspace);
+    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
+    tis_for_instance(classes, order, [&](auto k, auto o) { hipLaunchKernelGGL(pick(k, o), grid, block, 0, st, x, mask, d, h, w, t.p, extra..., part); });
+    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(t.entries), dim3(kTisFoldThreads), 0, st, part, d, h, t.f, t.p.d0, t.p.step_d, t.p.h0, t.p.step_h,
+                       sums);
+    return check_launch(who);
 }
 
 extern "C" int mri3d_tissue_em_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
                                     const double* params_host, double* sums, void* workspace, size_t ws_bytes, mri3d_stream_t stream) {
     TisPass t;
     if (int rc = tis_pass_setup("tissue_em_pass", x, mask, d, h, w, classes, order, params_host, sums, workspace, ws_bytes, t)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = static_cast<double*>(workspace);
-    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
-#define TIS_EM(KK, OO) hipLaunchKernelGGL((tissue_em_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, t.p, part)
-    TIS_ROWS_DISPATCH(TIS_EM, classes, order);
-#undef TIS_EM
-    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(t.entries), dim3(kTisFoldThreads), 0, st, part, d, h, t.f, t.p.d0, t.p.step_d, t.p.h0, t.p.step_h,
-                       sums);
-    return check_launch("tissue_em_pass");
+    return tis_pass_launch("tissue_em_pass", t, x, mask, d, h, w, classes, order, sums, workspace, stream,
+                           [](auto k, auto o) { return tissue_em_rows_kernel<decltype(k)::value, decltype(o)::value>; });
 }
 
 extern "C" int mri3d_tissue_mrf_pass(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
@@ -495,24 +498,16 @@ extern "C" int mri3d_tissue_mrf_pass(const float* x, const uint8_t* mask, int32_
     // two label buffers: a pass in place would let the table depend on the launch order
     MRI3D_REQUIRE(!overlaps(labels_out, t.nvox, labels_in, t.nvox), MRI3D_EINVAL,
                   "tissue_mrf_pass: labels_in and labels_out overlap (a pass reads one buffer and writes another)");
-    MRI3D_REQUIRE(!overlaps(labels_out, t.nvox, x, t.nvox * 4) && !overlaps(labels_out, t.nvox, mask, t.nvox) &&
-                      !overlaps(labels_out, t.nvox, sums, t.sums_bytes) && !overlaps(labels_out, t.nvox, workspace, t.need) &&
-                      !overlaps(labels_in, t.nvox, sums, t.sums_bytes) && !overlaps(labels_in, t.nvox, workspace, t.need),
+    // the sums and the workspace count as written here too: labels_in may lie on x or the mask, not on them
+    MRI3D_REQUIRE(!tis_clash({{labels_out, t.nvox, true}, {labels_in, t.nvox, false}, {x, t.nvox * 4, false}, {mask, t.nvox, false},
+                              {sums, t.sums_bytes, true}, {workspace, t.need, true}}),
                   MRI3D_EINVAL, "tissue_mrf_pass: a label buffer overlaps x, the mask, the sums or the workspace");
     TisMrf m;
     for (int k = 0; k < kTisMaxK; ++k) m.pi[k] = params_host[std::min(k, classes - 1)];
     m.beta = beta, m.mode = mode;
     for (int n = 0; n <= 6; ++n) m.e[n] = exp(beta * (double)n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = static_cast<double*>(workspace);
-    const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
-#define TIS_MRF(KK, OO) \
-    hipLaunchKernelGGL((tissue_mrf_rows_kernel<KK, OO>), grid, block, 0, st, x, mask, d, h, w, t.p, m, labels_in, labels_out, part)
-    TIS_ROWS_DISPATCH(TIS_MRF, classes, order);
-#undef TIS_MRF
-    hipLaunchKernelGGL(tissue_em_fold_kernel, dim3(t.entries), dim3(kTisFoldThreads), 0, st, part, d, h, t.f, t.p.d0, t.p.step_d, t.p.h0, t.p.step_h,
-                       sums);
-    return check_launch("tissue_mrf_pass");
+    return tis_pass_launch("tissue_mrf_pass", t, x, mask, d, h, w, classes, order, sums, workspace, stream,
+                           [](auto k, auto o) { return tissue_mrf_rows_kernel<decltype(k)::value, decltype(o)::value>; }, m, labels_in, labels_out);
 }
 
 extern "C" int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d, int32_t h, int32_t w, int32_t classes, int32_t order,
@@ -525,20 +520,14 @@ extern "C" int mri3d_tissue_apply(const float* x, const uint8_t* mask, int32_t d
     MRI3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(restored) | reinterpret_cast<uintptr_t>(field)) & 3) == 0,
                   MRI3D_EINVAL, "tissue_apply: pointers not aligned to float");
     const size_t nvox = (size_t)d * h * w;
-    // in place (restored == x) is allowed; any other overlap is not
-    MRI3D_REQUIRE((x == restored || !overlaps(x, nvox * 4, restored, nvox * 4)) && !overlaps(restored, nvox * 4, mask, nvox) &&
-                      !overlaps(restored, nvox * 4, labels, nvox) && !overlaps(restored, nvox * 4, field, nvox * 4) &&
-                      !overlaps(labels, nvox, x, nvox * 4) && !overlaps(labels, nvox, mask, nvox) && !overlaps(labels, nvox, field, nvox * 4) &&
-                      !overlaps(field, nvox * 4, x, nvox * 4) && !overlaps(field, nvox * 4, mask, nvox),
+    // in place (restored == x) is allowed, and x then is restored's entry of the list; any other overlap is not
+    MRI3D_REQUIRE(!tis_clash({{x == restored ? nullptr : x, nvox * 4, false}, {mask, nvox, false}, {restored, nvox * 4, true}, {labels, nvox, true},
+                              {field, nvox * 4, true}}),
                   MRI3D_EINVAL, "tissue_apply: an output overlaps another buffer (only restored == x is allowed)");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(tis_blocks((int64_t)d * h)), block(64 * kTisWaves);
-#define TIS_APPLY(KK) hipLaunchKernelGGL((tissue_apply_kernel<KK>), grid, block, 0, st, x, mask, d, h, w, p, restored, labels, field)
-    switch (classes) {
-        case 2: TIS_APPLY(2); break;
-        case 3: TIS_APPLY(3); break;
-        default: TIS_APPLY(4); break;
-    }
-#undef TIS_APPLY
+    tis_for_classes(classes, [&](auto k) {
+        hipLaunchKernelGGL((tissue_apply_kernel<decltype(k)::value>), grid, block, 0, st, x, mask, d, h, w, p, restored, labels, field);
+    });
     return check_launch("tissue_apply");
 }

@@ -2729,6 +2729,8 @@ def tissue_table_size(classes, order):
 
 
 def _tissue_args(who, x, mask, classes, order, params):
+    """The checked volume and mask (the caller holds them over its launch), and the eight arguments every C entry of the family starts
+    with: x, mask, d, h, w, classes, order, params."""
     import numpy as np
     x = _volume(who, "x", x, (torch.float32,))
     if mask is not None:
@@ -2741,7 +2743,7 @@ def _tissue_args(who, x, mask, classes, order, params):
     if 2 <= classes <= 4 and 0 <= order <= 3 and p.size != 3 * classes + tissue_coefficients(order):
         raise ValueError("%s: %d classes and order %d take %d parameters (pi, mu, v, c), got %d"
                          % (who, classes, order, 3 * classes + tissue_coefficients(order), p.size))
-    return x, mask, classes, order, p
+    return x, mask, (_ptr(x), _ptr(mask), *x.shape, classes, order, p.ctypes.data_as(ctypes.c_void_p))     # the pointer keeps p alive
 
 
 def tissue_em_plan(shape, classes, order):
@@ -2752,21 +2754,21 @@ def tissue_em_plan(shape, classes, order):
     return dict(zip(TISSUE_EM_PLAN_FIELDS, (int(v) for v in out)))
 
 
+def _tissue_pass_args(who, x, mask, classes, order, params, out):
+    """What the two sums passes share: `_tissue_args`, then the sums tensor and the workspace."""
+    x, mask, head = _tissue_args(who, x, mask, classes, order, params)
+    d, h, w, classes, order = head[2:7]
+    size = tissue_table_size(classes, order) if 2 <= classes <= 4 and 0 <= order <= 3 else 1
+    out = _out_like(who, out, (size,), torch.float64, x)
+    return x, mask, head, out, _workspace(_lib.lib().mri3d_tissue_em_workspace_bytes(d, h, w, classes, order), x.device)
+
+
 def tissue_em_pass(x, mask, classes, order, params, out=None):
     """One EM pass of the tissue-class bias-field model over a float32 (d, h, w) device volume with the parameters fixed: the
     float64 device table (n, LL, S0[K], S1[K], S2[K], Mw, Mt) that include/mri3d.h documents.  mask: uint8 / bool device volume
     or None; params: 3K + M host doubles (pi, mu, v, c)."""
-    x, mask, classes, order, p = _tissue_args("tissue_em_pass", x, mask, classes, order, params)
-    size = tissue_table_size(classes, order) if 2 <= classes <= 4 and 0 <= order <= 3 else 1
-    if out is None:
-        out = torch.empty(size, dtype=torch.float64, device=x.device)
-    elif tuple(out.shape) != (size,) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
-        raise RuntimeError("tissue_em_pass: out must be a contiguous (%d,) float64 device tensor" % size)
-    L = _lib.lib()
-    d, h, w = x.shape
-    ws = _workspace(L.mri3d_tissue_em_workspace_bytes(d, h, w, classes, order), x.device)
-    check(L.mri3d_tissue_em_pass(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), _ptr(out), _ptr(ws),
-                                 ws.numel(), _stream()), "tissue_em_pass")
+    x, mask, head, out, ws = _tissue_pass_args("tissue_em_pass", x, mask, classes, order, params, out)
+    check(_lib.lib().mri3d_tissue_em_pass(*head, _ptr(out), _ptr(ws), ws.numel(), _stream()), "tissue_em_pass")
     return out
 
 
@@ -2775,39 +2777,29 @@ def tissue_mrf_pass(x, mask, classes, order, params, beta, mode, labels_in, labe
     order of `params`), one half-sweep of red-black ICM: (sums, labels_out).  mode 0 / 1: the voxels of that colour of
     (d + h + w) & 1 take their new label, the others keep `labels_in`'s; mode 2, the start: no neighbour term, `labels_in` may be
     None.  `labels_out` is another buffer than `labels_in` (include/mri3d.h says why)."""
-    x, mask, classes, order, p = _tissue_args("tissue_mrf_pass", x, mask, classes, order, params)
-    size = tissue_table_size(classes, order) if 2 <= classes <= 4 and 0 <= order <= 3 else 1
-    if out is None:
-        out = torch.empty(size, dtype=torch.float64, device=x.device)
-    elif tuple(out.shape) != (size,) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
-        raise RuntimeError("tissue_mrf_pass: out must be a contiguous (%d,) float64 device tensor" % size)
+    x, mask, head, out, ws = _tissue_pass_args("tissue_mrf_pass", x, mask, classes, order, params, out)
     if labels_out is None:
         labels_out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     for name, t in (("labels_in", labels_in), ("labels_out", labels_out)):
         if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != tuple(x.shape) or t.dtype != torch.uint8 or t.device != x.device
                               or not t.is_contiguous()):
             raise RuntimeError("tissue_mrf_pass: %s must be a contiguous %s uint8 tensor on x's device" % (name, tuple(x.shape)))
-    L = _lib.lib()
-    d, h, w = x.shape
-    ws = _workspace(L.mri3d_tissue_em_workspace_bytes(d, h, w, classes, order), x.device)
-    check(L.mri3d_tissue_mrf_pass(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), float(beta), int(mode),
-                                  _ptr(labels_in), _ptr(labels_out), _ptr(out), _ptr(ws), ws.numel(), _stream()), "tissue_mrf_pass")
+    check(_lib.lib().mri3d_tissue_mrf_pass(*head, float(beta), int(mode), _ptr(labels_in), _ptr(labels_out), _ptr(out), _ptr(ws), ws.numel(),
+                                           _stream()), "tissue_mrf_pass")
     return out, labels_out
 
 
 def tissue_apply(x, mask, classes, order, params, want_field=False, restored=None):
     """The final pass: (restored = x exp(-b), labels uint8, field = exp(b) or None) over every voxel; labels are 0 where the voxel
     is not selected and else 1 + the rank by ascending mean of its most probable class.  `restored` may be `x` itself."""
-    x, mask, classes, order, p = _tissue_args("tissue_apply", x, mask, classes, order, params)
+    x, mask, head = _tissue_args("tissue_apply", x, mask, classes, order, params)
     if restored is None:
         restored = torch.empty_like(x)
     elif tuple(restored.shape) != tuple(x.shape) or restored.dtype != torch.float32 or not restored.is_cuda or not restored.is_contiguous():
         raise RuntimeError("tissue_apply: restored must be a contiguous %s float32 device tensor" % (tuple(x.shape),))
     labels = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
     field = torch.empty_like(x) if want_field else None
-    d, h, w = x.shape
-    check(_lib.lib().mri3d_tissue_apply(_ptr(x), _ptr(mask), d, h, w, classes, order, p.ctypes.data_as(ctypes.c_void_p), _ptr(restored),
-                                        _ptr(labels), _ptr(field), _stream()), "tissue_apply")
+    check(_lib.lib().mri3d_tissue_apply(*head, _ptr(restored), _ptr(labels), _ptr(field), _stream()), "tissue_apply")
     return restored, labels, field
 
 

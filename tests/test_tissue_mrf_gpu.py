@@ -5,18 +5,22 @@ mrf_pass: per entry of the table |device - reference| <= tissue_mrf_ref.bound, t
 the roundings of beta n_k and of the normaliser counted the same way; labels_out exact except where the reference's two best
 logt lie within 2^-30 max|logt| of each other; at beta = 0 the table is within the family's bound of `ops.tissue_em_pass` on the
 same inputs.  labels_out, sums and the workspace lie between guard bands, the workspace and labels_out start as 0xA5, and every
-pass runs twice to equal bits.
+pass runs twice to equal bits.  The whole family (`em_pass`, `mrf_pass`, `apply`) reproduces the digests of
+tests/golden/tissue_family_bits.json, entry for entry.
 
 End to end (phantom (40, 48, 36) with noise 0.10, classes 3, order 3, 60 iterations, warmup 20, beta 1): label agreement >= 0.98,
 field rms error <= 0.007, isolated voxels <= 100; the three figures equal the reference's to four decimals and the labels differ
 from the reference's on at most 10^-4 of the selected voxels."""
 import ctypes
 import functools
+import json
+import os
 
 import numpy as np
 import pytest
 import torch
 
+import tissue_bits
 import tissue_cases as TC
 import tissue_mrf_cases as MC
 import tissue_mrf_ref as M
@@ -29,6 +33,7 @@ pytestmark = pytest.mark.gpu
 
 AGREE_MIN, RMS_MAX, ISOLATED_MAX = 0.98, 0.007, 100
 LABEL_SHARE_MAX = 1e-4
+BITS_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tissue_family_bits.json")
 
 
 def _dev(a):
@@ -120,6 +125,18 @@ def test_overlapping_label_buffers_are_refused_and_leave_the_output_untouched():
     torch.cuda.synchronize()
     assert torch.equal(both.region, before)
     both.assert_guards_intact("refused labels")
+
+
+def test_the_family_reproduces_its_recorded_bits():
+    """tests/golden/tissue_family_bits.json (tools/record_tissue_bits.py): the sha256 of every output of `em_pass`, `mrf_pass` and `apply` on
+    the parity cases and on a sweep over all 12 (classes, order) instances, as the toolchain the file names compiled them.  A change of
+    csrc/tissue.hip that is meant to keep the arithmetic keeps every entry."""
+    with open(BITS_FILE) as f:
+        want = json.load(f)["entries"]
+    got = tissue_bits.device_bits(ops)
+    assert sorted(got) == sorted(want)
+    bad = sorted(name for name in want if got[name] != want[name])
+    assert not bad, (len(bad), bad[:20])
 
 
 # ---------------------------------------------------------------------------------------------- end to end
